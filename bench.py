@@ -8,6 +8,10 @@ input, batch-sharded over N MI355X with one RCCL all-reduce of the summed log-li
 
 A "step" = one pass of the hot path over the GLOBAL batch (fixed as N grows: strong scaling, as
 BASELINE.json's north_star asks).  Prints ONE JSON line on rank 0.
+
+A plain run measures the headline only.  `--full` adds the CPU baselines and the secondary lines (the other
+workloads, batch sizes, training, specialist and sampling configurations) to the same JSON line.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see write_outputs).
 """
 import argparse
 import json
@@ -51,12 +55,19 @@ def parse():
     ap.add_argument("--workload", default="cifar10", choices=["cifar10", "mnist", "smap", "atm"])
     ap.add_argument("--global-batch", type=int, default=2097152)
     ap.add_argument("--chunk", type=int, default=262144, help="samples per kernel launch sequence on one rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the mnist / smap / small-batch lines (N = 1 only)")
+    ap.add_argument("--full", action="store_true", help="also measure the CPU baselines and the secondary lines (N = 1 only); "
+                    "a plain run times the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the mnist / smap / small-batch lines (N = 1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed as "
+                    "DIR/<name>.npy (float32 / float64, a fixed seeded sample of the rows of a large output)")
     ap.add_argument("--train", action="store_true", help="time the data-parallel TRAINING step (SURVEY 8(f)1) instead of the forward: "
                     "one captured HIP graph per rank with the gradient all-reduces inside, weak scaling")
     ap.add_argument("--train-batch", type=int, default=16384, help="samples per rank and training step (--train)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def synth(name, n, dev, seed):
@@ -71,6 +82,29 @@ def synth(name, n, dev, seed):
         else:
             out[i:i + m] = torch.randint(0, 256, (m, C, H, W), device=dev, generator=g).float()
     return out
+
+
+DUMP_ROWS, DUMP_Z_ROWS, DUMP_BYTES = 65536, 1024, 64 << 20
+
+
+def dump_rows(n, seed=2024):
+    """--dump-outputs: the fixed, seeded sample of a step's n output rows that is written: up to DUMP_ROWS rows of log p
+    (B, M) and the first DUMP_Z_ROWS of them for z (sorted row indices; all rows when n is that small)."""
+    perm = torch.randperm(n, generator=torch.Generator().manual_seed(seed))
+    return perm[:DUMP_ROWS].sort().values, perm[:DUMP_Z_ROWS].sort().values
+
+
+def write_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy, float32 or float64, at most DUMP_BYTES in all."""
+    import numpy as np
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_BYTES, "outputs of %d bytes exceed the %d-byte budget" % (total, DUMP_BYTES)
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
 
 
 def host_cores():
@@ -644,6 +678,9 @@ def train_main(a, model, cfg, name, dev, rank, local_rank, world, rehearsal, sin
         loss = step(x, gt)
     fence()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:        # the step's loss and the parameters its optimizer step left
+        write_outputs(a.dump_outputs, {"loss": loss.detach().double().reshape(1),
+                                       "params": torch.cat([p.detach().float().reshape(-1) for p in model.parameters()])})
     table = torch.zeros(world, 3, dtype=torch.float64, device=dev)
     table[rank] = torch.tensor([dt, float(loss), float(local_rank)], dtype=torch.float64, device=dev)
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -728,14 +765,22 @@ def main():
     x = synth(name, hi - lo, dev, seed=1000 + rank)
     nll_acc = torch.zeros(1, dtype=torch.float64, device=dev)
     ar_events = []                                      # (start, end) HIP events around the all-reduce of every timed step
+    sel = []                                            # --dump-outputs: per chunk, the sampled rows of log p and z on the device
+    if a.dump_outputs:
+        rows, zrows = dump_rows(hi - lo)
+        for c0 in range(0, hi - lo, a.chunk):
+            c1 = min(c0 + a.chunk, hi - lo)
+            sel.append(tuple((r[(r >= c0) & (r < c1)] - c0).to(dev) for r in (rows, zrows)))
 
     @torch.no_grad()                                   # density evaluation (experiment_cl.py:163-185 runs it under no_grad):
-    def step(timed):                                   # no autograd tape, no W^-1 for the backward
+    def step(timed, keep=None):                        # no autograd tape, no W^-1 for the backward
         nll_acc.zero_()
-        for c0 in range(0, hi - lo, a.chunk):
+        for i, c0 in enumerate(range(0, hi - lo, a.chunk)):
             xb = x[c0:c0 + a.chunk]
-            _, logp = model(xb)
+            z, logp = model(xb)
             _hip.call("cf_nll_sum", _hip.p(logp), _hip.p(nll_acc), logp.shape[0], logp.shape[1], _hip.stream())
+            if keep is not None:
+                keep.append((logp.index_select(0, sel[i][0]), z.index_select(0, sel[i][1])))
         if timed:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -754,10 +799,11 @@ def main():
     for _ in range(a.warmup):
         red = step(False)
     events = kernel_events(model, name)
+    keep = [] if a.dump_outputs else None
     fence()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
-        red = step(True)
+    for i in range(a.steps):
+        red = step(True, keep if i == a.steps - 1 else None)
     fence()
     dt = time.perf_counter() - t0
     torch.cuda.synchronize()
@@ -783,6 +829,9 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
     bpd = cdist.mean_bits_per_dim(red.cpu(), DIMS[name])
+    if a.dump_outputs and rank == 0:        # rank 0's shard: sampled rows of log p (B, M) and z, the reduced [sum log p, count]
+        write_outputs(a.dump_outputs, {"logp": torch.cat([k[0] for k in keep]), "z": torch.cat([k[1] for k in keep]), "nll": red,
+                                       "bits_per_dim": torch.tensor([bpd], dtype=torch.float64)})
     roof = roofline(events, name, dt)
     walls, kerns, ars = [p["wall_s"] for p in per_rank], [p["kernel_s"] for p in per_rank], [p["allreduce_s"] for p in per_rank]
     comm = {"backend": dist.get_backend() if dist.is_initialized() else None, "world_size": world,
@@ -804,10 +853,10 @@ def main():
                           "global_batch": G, "per_gpu_batch": hi - lo, "chunk": a.chunk, "parallelism": "dp%d" % world,
                           "collective": "all_reduce(sum log p, count) fp64 x2 per step"},
                "bits_per_dim": round(bpd, 6), "roofline": roof, "comm": comm}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(name)
             out["gpu_over_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
-        if world == 1 and not a.no_secondary and name == "cifar10":
+        if a.full and world == 1 and not a.no_secondary and name == "cifar10":
             # the other single-GPU configs of BASELINE.json and the batch sizes of SURVEY.md 8(d); the headline fields above
             # are unaffected (measured first, their buffers released)
             del model, x

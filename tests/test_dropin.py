@@ -6,8 +6,10 @@
   directory) hold another `layers` package - the situation in the reference tree (contextflow/model.py:14-15);
 * nothing else of contextflow_amd becomes a top-level name;
 * the reference's UNMODIFIED `create_model` (model.py:95-163), imported through the launcher, builds the mnist /
-  cifar10 / smap generalists and a specialist out of this repo's classes with the reference's state_dict layout.
-  That half needs /root/reference (build container only; skipped elsewhere - the reference never travels)."""
+  cifar10 / smap generalists and specialists out of this repo's classes with the reference's state_dict layout.
+  The reference is not part of this repo: tests/golden/dropin_reference.json records what its model.py takes from
+  `layers` and the layout of every model its `create_model` built on the drop-in (tests/golden/make_dropin_fixture.py);
+  the tests below replay both against the launcher and `create_model` here."""
 import os
 import subprocess
 import sys
@@ -16,7 +18,7 @@ import textwrap
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_SCRIPT = "/root/reference/contextflow/model.py"
+FIXTURE = os.path.join(ROOT, "tests", "golden", "dropin_reference.json")
 
 
 def _run(args, cwd, timeout=600):
@@ -73,85 +75,90 @@ def test_launcher_refuses_a_foreign_layers(tmp_path):
 
 
 DRIVER = r"""
-import os, sys, types
-import torch.nn as nn
-sys.dont_write_bytecode = True                      # the reference tree is read-only
-
-def stub(name, **attrs):                            # third-party / dataset modules absent from this image; none is on
-    m = types.ModuleType(name); m.__path__ = []     # the density path (SURVEY.md Appendix C)
-    for k, v in attrs.items():
-        setattr(m, k, v)
-    sys.modules[name] = m
-
-class InputDropout(nn.Module):
-    def __init__(self, *a, **k): super().__init__()
-    def forward(self, x): return x
-
-stub("datasets"); stub("datasets.ts", InputDropout=InputDropout, load_data_ts=None)
-stub("datasets.mnist", load_data=None); stub("datasets.cifar10", load_data=None)
-stub("datasets.mtad_dataloader", mtad_entities={})
-stub("torchinfo", summary=None); stub("ood_metrics", auroc=None, aupr=None, fpr_at_95_tpr=None)
-
+import json, os, sys
+sys.dont_write_bytecode = True
+fx = json.load(open(sys.argv[1]))
+from layers.rtdl.nn._embeddings import *            # model.py:14-15, as the reference script imports them
+from layers import *
 from contextflow_amd import run
-M = run.load(sys.argv[1])                           # the reference's model.py, unmodified, as module `model`
 import layers, contextflow_amd as cfa
 assert layers.__file__.startswith(run.DROPIN), layers.__file__
-assert M.__file__ == sys.argv[1]
-assert M.Coupling is cfa.layers.Coupling and M.FlowSequential is cfa.layers.FlowSequential
-assert M.OneHotEncoder is cfa.layers.OneHotEncoder and M.CatEmbeddings is cfa.layers.CatEmbeddings
-from layers.rtdl.nn._embeddings import *            # model.py:14
+g = globals()
+missing = [n for n in fx["layers_names"] if n not in g]
+assert not missing, missing                         # every name the reference's model.py takes from `layers`
+for n in fx["layers_names"]:
+    assert g[n].__module__.startswith("contextflow_amd."), (n, g[n].__module__)
+assert Coupling is cfa.layers.Coupling and FlowSequential is cfa.layers.FlowSequential
+assert OneHotEncoder is cfa.layers.OneHotEncoder and CatEmbeddings is cfa.layers.CatEmbeddings
 from oracle import flow_oracle as fo, params as op
 
-def ref_build(name, generalist=True, contexts=None, enc_emb="onehot", enc_type="uniform", contextflow=False):
+for rec in fx["models"]:
+    name = rec["name"]
     preset, data_size, mixtures = cfa.preset_config(name)
-    M.c = types.SimpleNamespace(dataset=name)       # create_model reads this module global (model.py:113,125)
-    cfg = dict(preset, generalist=generalist, enc_emb=enc_emb, enc_type=enc_type, contextflow=contextflow)
-    return M.create_model(cfg, data_size=data_size, mixtures=mixtures, contexts=contexts), cfg, data_size, mixtures
-
-for name, contexts in (("mnist", [-1]), ("cifar10", [-1, -1]), ("smap", [55])):
-    flow, cfg, data_size, mixtures = ref_build(name, contexts=contexts)
-    assert type(flow).__module__ == "contextflow_amd.layers.flowsequential", type(flow).__module__
+    cfg = dict(preset, generalist=rec["generalist"], enc_emb=rec["enc_emb"], enc_type=rec["enc_type"], contextflow=rec["contextflow"])
+    flow = cfa.create_model(cfg, data_size, mixtures, rec["contexts"])
+    assert type(flow).__module__ + "." + type(flow).__qualname__ == rec["flow_class"], type(flow)
     for m in flow.modules():
         assert type(m).__module__.startswith(("contextflow_amd.", "torch.")), type(m)
-    ops, prior, M2 = fo.program(name)
-    spec = op.param_spec(ops, prior, M2)            # == the reference's own state_dict (asserted in make_golden.py)
     sd = flow.state_dict()
-    assert list(sd) == list(spec), set(sd) ^ set(spec)
-    assert all(tuple(sd[k].shape) == tuple(spec[k][0]) for k in sd)
-    print("generalist", name, len(sd), sum(v.numel() for v in flow.parameters()))
-
-for name, contexts, emb, enc, cf in (("cifar10", [15, 5], "onehot", "uniform", True), ("smap", [55], "eye", "uniform", False),
-                                     ("mnist", [64], "embed", "probsample", True)):
-    flow, cfg, data_size, mixtures = ref_build(name, False, contexts, emb, enc, cf)
-    assert type(flow).__module__ == "contextflow_amd.layers.flowsequential"
-    # model.ContextEncoder (model.py:30-90) is the script's own nn.Sequential; everything inside it is ours
-    foreign = {type(m).__qualname__ for m in flow.modules() if not type(m).__module__.startswith(("contextflow_amd.", "torch."))}
-    assert foreign == {"ContextEncoder"}, foreign
-    ours = cfa.create_model(cfg, data_size, mixtures, contexts)
-    a, b = flow.state_dict(), ours.state_dict()
-    assert list(a) == list(b) and all(a[k].shape == b[k].shape for k in a), set(a) ^ set(b)
-    print("specialist", name, emb, enc, cf, len(a))
+    ref = [(k, tuple(s)) for k, s in rec["state_dict"]]
+    assert list(sd) == [k for k, _ in ref], set(sd) ^ {k for k, _ in ref}
+    assert [tuple(v.shape) for v in sd.values()] == [s for _, s in ref], name
+    if rec["generalist"]:
+        ops, prior, M2 = fo.program(name)
+        spec = op.param_spec(ops, prior, M2)        # == the reference's own state_dict (asserted in make_golden.py)
+        assert list(sd) == list(spec) and all(tuple(sd[k].shape) == tuple(spec[k][0]) for k in sd), name
+        print("generalist", name, len(sd), sum(v.numel() for v in flow.parameters()))
+    else:
+        # the reference builds ContextEncoder itself (model.py:30-90, an nn.Sequential); everything else is this repo's
+        assert rec["foreign_classes"] == ["ContextEncoder"], rec["foreign_classes"]
+        print("specialist", name, rec["enc_emb"], rec["enc_type"], rec["contextflow"], len(sd))
 print("DROPIN OK")
 """
 
 
-@pytest.mark.skipif(not os.path.isfile(REF_SCRIPT), reason="needs the reference tree (build container only)")
-def test_reference_create_model_builds_on_the_dropin():
-    """cwd = the reference's own source directory, the hardest case: its `layers`, `model`, `config` ... are all importable
-    from '' and from the script directory."""
-    r = _run(["-c", DRIVER, REF_SCRIPT], cwd=os.path.dirname(REF_SCRIPT))
+def _reference_like_tree(d):
+    """A script directory laid out as the reference's (contextflow/): its own `layers` package, which must not be the one
+    imported, and its own `config.py`, which must be."""
+    (d / "layers").mkdir()
+    (d / "layers" / "__init__.py").write_text("raise ImportError('the script directory\'s own layers package was imported')\n")
+    (d / "config.py").write_text(textwrap.dedent("""
+        import argparse
+        def get_args():
+            p = argparse.ArgumentParser(description="reference-like script")
+            p.add_argument("--dataset", default="mnist")
+            return p.parse_args()
+    """))
+
+
+def test_reference_create_model_builds_on_the_dropin(tmp_path):
+    """cwd = a directory laid out as the reference's own source directory, the hardest case: its `layers` and `config`
+    are importable from '' and from the script directory.  Through the launcher, every name the reference's model.py
+    takes from `layers` is bound to this repo's classes, and create_model gives the state_dict layout that the reference's
+    create_model built on the drop-in (tests/golden/dropin_reference.json)."""
+    _reference_like_tree(tmp_path)
+    (tmp_path / "driver.py").write_text(DRIVER)
+    r = _run(["-m", "contextflow_amd.run", str(tmp_path / "driver.py"), FIXTURE], cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert "DROPIN OK" in r.stdout
     assert r.stdout.count("generalist") == 3 and r.stdout.count("specialist") == 3, r.stdout
 
 
-@pytest.mark.skipif(not os.path.isfile(REF_SCRIPT), reason="needs the reference tree (build container only)")
-def test_documented_command_reaches_the_reference_script():
-    """`python -m contextflow_amd.run .../model.py --help` as INTEGRATION.md writes it.  In this image the script stops at
-    its first import of a package that is not installed (torchvision / skimage / torchinfo ...): that must be the ONLY
-    way it fails here - i.e. it got past `from layers import *` on our package - or it prints its argparse help."""
-    r = _run(["-m", "contextflow_amd.run", REF_SCRIPT, "--help"], cwd=os.path.dirname(REF_SCRIPT))
-    if r.returncode == 0:
-        assert "--dataset" in r.stdout
-    else:
-        assert "ModuleNotFoundError" in r.stderr and "contextflow_amd" not in r.stderr.split("ModuleNotFoundError")[-1], r.stderr[-2000:]
+def test_documented_command_reaches_the_reference_script(tmp_path):
+    """`python -m contextflow_amd.run .../model.py --help` as INTEGRATION.md writes it, on a script with the reference's
+    `layers` imports (model.py:14-15) in a directory laid out as the reference's: the script gets past
+    `from layers import *` on our package, with every name the reference takes from it, and prints its argparse help."""
+    import json
+    names = json.load(open(FIXTURE))["layers_names"]
+    _reference_like_tree(tmp_path)
+    (tmp_path / "model.py").write_text(textwrap.dedent("""
+        from config import get_args
+        from layers.rtdl.nn._embeddings import *
+        from layers import *
+        missing = [n for n in %r if n not in globals()]
+        assert not missing, missing
+        args = get_args()
+    """ % (names,)))
+    r = _run(["-m", "contextflow_amd.run", str(tmp_path / "model.py"), "--help"], cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "--dataset" in r.stdout, r.stdout
