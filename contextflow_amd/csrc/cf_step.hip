@@ -36,6 +36,7 @@ struct StepPackBatch {
         *w3[kPrepBatch], *b3[kPrepBatch];
     float* ws[kPrepBatch];
     int pieces;                          // also the bf16 pieces of the Winograd-domain weights (CONTEXTFLOW_BF16_SPLIT=1)
+    int w24;                             // also the F(2x4, 3x3) Winograd-domain weights of the 4x4 level (unless CONTEXTFLOW_WINO24=0)
 };
 template <class G>
 __global__ __launch_bounds__(256) void k_step_pack(const StepPackBatch pb) {
@@ -138,6 +139,24 @@ __global__ __launch_bounds__(256) void k_step_pack(const StepPackBatch pb) {
                 for (int pz = 0; pz < 3; ++pz)
                     wb[((((int64_t)(tap * G::RT16 + rt16) * G::KB32 + kb) * 3 + pz) * 64 + ln) * 8 + j] = (unsigned short)(pc[pz] >> 16);
             }
+        }
+    }
+    if (G::H == 4 && G::W == 4 && pb.w24) {
+        // Winograd-domain weights of the F(2x4, 3x3) form (winograd24_phase2): U[xi][nu] = G2 w G4^T (fp64, rounded once), G2 as above,
+        // G4 = the F(4, 3) Toom-Cook rows on the points {0, 1, -1, 1/2, -1/2, inf}
+        constexpr int HID = G::HID;
+        const double G2[4][3] = {{1, 0, 0}, {.5, .5, .5}, {.5, -.5, .5}, {0, 0, 1}};
+        const double G4[6][3] = {{4, 0, 0}, {2. / 3, 2. / 3, 2. / 3}, {2. / 3, -2. / 3, 2. / 3}, {-8. / 3, -4. / 3, -2. / 3},
+                                 {-8. / 3, 4. / 3, -2. / 3}, {0, 0, 1}};
+        for (int e = gtid; e < 24 * HID * HID; e += gsz) {
+            const int jj = e & 3, ln = (e >> 2) & 63, q = e >> 8;
+            const int kg = q % G::KG4, rt16 = (q / G::KG4) % G::RT16, pos = q / (G::KG4 * G::RT16);
+            const int co = rt16 * 16 + (ln & 15), ci = 4 * (4 * kg + jj) + (ln >> 4), xi = pos / 6, nu = pos % 6;
+            const float* wk = w2 + ((int64_t)co * HID + ci) * 9;
+            double u = 0.0;
+            for (int a = 0; a < 3; ++a)
+                for (int b = 0; b < 3; ++b) u += G2[xi][a] * G4[nu][b] * (double)wk[a * 3 + b];
+            ws[G::OFF_AW24 + e] = (float)u;
         }
     }
     if constexpr (G::RS16) {
@@ -1351,6 +1370,11 @@ static bool direct_conv_only() {
     static const bool v = [] { const char* e = getenv("CONTEXTFLOW_DIRECT_CONV"); return e && e[0] == '1'; }();
     return v;
 }
+// the 4x4 level's evaluation forward in the Winograd F(2x4, 3x3) form (G64w24) unless CONTEXTFLOW_WINO24=0 (A/B: F(2x2, 3x3), G64w2)
+static bool wino24_enabled() {
+    static const bool v = [] { const char* e = getenv("CONTEXTFLOW_WINO24"); return !(e && e[0] == '0'); }();
+    return v;
+}
 
 extern "C" {
 
@@ -1378,6 +1402,8 @@ int cf_flow_step_prepare_batch(int n, const float* const* Wm, const float* const
         const int m = n - i0 < kPrepBatch ? n - i0 : kPrepBatch;
         StepPackBatch pb{};
         pb.pieces = bf16_split_enabled() ? 1 : 0;
+        // (the training tables too: they are bitwise those of the evaluation forward - test_prepare_train_equals_prepare_plus_inverse)
+        pb.w24 = (wino24_enabled() && !direct_conv_only()) ? 1 : 0;
         for (int i = 0; i < m; ++i) {
             const int j = i0 + i;
             CF_REQUIRE(Wm[j] && t[j] && logs[j] && w1[j] && b1[j] && w2[j] && b2[j] && w3[j] && b3[j] && ws[j] &&
@@ -1531,6 +1557,7 @@ int cf_flow_step_fwd_debug(const float* x, float* z, float* ldj_acc, const void*
         case 20: CF_STEP(G32w); break;
         case 28: CF_STEP(G64w); break;
         case 29: CF_STEP(G64w2); break;           // variant 5: row-split Winograd at 128 pixels per workgroup
+        case 30: CF_STEP(G64w24); break;          // variant 6: ... in the F(2x4, 3x3) form, the rows split over all four waves
         default: cf_set_error("cf_flow_step_fwd: shape (%d,%d,%d) variant %d unsupported", C, H, W, variant); return CF_ERR_UNSUPPORTED;
     }
 #undef CF_STEP
@@ -1599,7 +1626,8 @@ int cf_flow_step_fwd(const float* x, float* z, float* ldj_acc, const void* ws, i
     // CONTEXTFLOW_DIRECT_CONV=1 keeps the direct form (A/B measurements, tools/step_bench.py).
     const bool direct_only = direct_conv_only();
     if (!direct_only && (sid == 0 || sid == 1 || (sid == 2 && B >= 256 * G32::SPW))) flags = 4 << 16;
-    if (!direct_only && sid == 3 && B >= 256 * G64w2::SPW) flags = 5 << 16;      // 4x4: 8 samples per workgroup, rows split over wave pairs
+    // 4x4: 8 samples per workgroup, rows split over wave pairs (F(2x2)) / over all four waves (F(2x4), 24 instead of 32 products per 8 pixels)
+    if (!direct_only && sid == 3 && B >= 256 * G64w2::SPW) flags = (wino24_enabled() ? 6 : 5) << 16;
     // CONTEXTFLOW_BF16_SPLIT=1 (off by default): the 16x16 level's Winograd-domain products as bf16-piece MFMAs (G16wb)
     // (mode 2, the direct bf16-piece form: from 1024 samples per launch - below that the chained launches of the fp32 form run)
     if (!direct_only && sid == 1 && bf16_split_mode() == 1) flags = 6 << 16;
@@ -1629,13 +1657,15 @@ int cf_flow_step_fwd(const float* x, float* z, float* ldj_acc, const void* ws, i
 // pass 0 = cf_flow_step_fwd, 1 = cf_flow_step_fwd_taped, 2 = cf_flow_step_bwd_taped (direct transposed 3x3), 3 = cf_flow_step_inv
 // (the forward's conditioner + W^-1 instead of W: the same count; Winograd form at every level).  The direct
 // form runs C^2 (Conv1x1) + C^2 + 36 C^2 + 2 C^2 = 40 C^2 per pixel; the Winograd form of the 3x3 runs 16 instead of 36
-// C^2.  The conditions below restate the dispatch of the two entry points above / below - change them together.
+// C^2 (F(2x2, 3x3)) or 12 C^2 (F(2x4, 3x3): the 4x4 level's evaluation forward).  The conditions below restate the dispatch of
+// the two entry points above / below - change them together.
 int64_t cf_flow_step_macs(int B, int C, int H, int W, int pass) {
     const int sid = shape_id(C, H, W);
     if (sid < 0 || pass < 0 || pass > 3) return 0;
-    const int64_t direct = 40ll * C * C * H * W, wino = 20ll * C * C * H * W;
+    const int64_t direct = 40ll * C * C * H * W, wino = 20ll * C * C * H * W, wino24 = 16ll * C * C * H * W;
     if (pass == 2 || direct_conv_only()) return direct;
     if (pass == 3) return wino;
+    if (sid == 3 && pass == 0 && wino24_enabled() && B >= 256 * G64w2::SPW) return wino24;
     bool w;
     if (sid == 0) w = pass == 0;                                  // mnist's C = 8 level: evaluation only
     else if (sid == 1) w = true;                                  // 16x16, C = 16: every batch size

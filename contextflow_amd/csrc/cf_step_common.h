@@ -60,7 +60,9 @@ struct Geo {
     static constexpr int OFF_SA2 = OFF_SA1 + (HID16 ? SG1 * 256 : 0);
     // Winograd F(2x2,3x3) form of the 3x3 (PIPE == 3, winograd_phase2 below): U = G w G^T for the 16 positions, packed as
     // 16x16x4 A fragments: [position][16-row tile][group of 4 k-steps][lane][4]
-    static constexpr bool WINO = (PIPE_ == 3 || PIPE_ == 4);
+    // PIPE == 6: Winograd F(2x4, 3x3) on the 4x4 level (winograd24_phase2): 24 products per 2x4 output tile instead of 2 x 16
+    static constexpr bool W24 = (PIPE_ == 6);
+    static constexpr bool WINO = (PIPE_ == 3 || PIPE_ == 4 || W24);
     // PIPE == 4: the Winograd-domain products on the bf16 matrix cores - every fp32 operand as three bf16 pieces, the six piece
     // products with i + j <= 2 accumulated in fp32 (winograd_phase2; tools/micro/bf16_split_gemm.hip: the error of the f32 MFMA)
     static constexpr bool BF16S = (PIPE_ == 4);
@@ -86,7 +88,10 @@ struct Geo {
     // bf16 pieces of the direct 3x3 taps (DBF): [tap][16-row tile][32-channel block][piece][lane] 16 bytes = 8 bf16: element j of
     // lane l = piece of NN.2[16 rt + (l & 15)][32 kb + 8 (l >> 4) + j][tap] (the hardware's own k order)
     static constexpr int OFF_ADB = WS_END0 + 16 * RT16 * KB32 * 3 * 256;
-    static constexpr int WS_FLOATS = OFF_ADB + 9 * RT16 * KB32 * 3 * 256;
+    // Winograd-domain weights of the F(2x4, 3x3) form (4x4 images only): U = G2 w G4^T for the 4 x 6 positions, packed as the
+    // 16 positions of the F(2x2) form: [position xi * 6 + nu][16-row tile][group of 4 k-steps][lane][4]
+    static constexpr int OFF_AW24 = OFF_ADB + 9 * RT16 * KB32 * 3 * 256;
+    static constexpr int WS_FLOATS = OFF_AW24 + ((H == 4 && W == 4) ? 24 * HID * HID : 0);
     static constexpr int PP = 2 * W + 2 * H + 4;      // fold slots per sample: 2 patched rows, 2 patched columns, 4 corners
     static constexpr int RS = PATCH ? ((PIX + SPW * PP + 1 + 3) & ~3) : PIX;
     // C = 8 (HID = 16) in the Winograd form: all 16 Winograd-domain weight matrices are 16 KB - staged into LDS once per workgroup
@@ -101,6 +106,7 @@ struct Geo {
     // waves per SIMD the register allocator must leave room for = workgroups per CU the LDS footprint admits
     static constexpr int MINW = (160 * 1024) / (LDS_FLOATS * 4) >= 4 ? 4 : ((160 * 1024) / (LDS_FLOATS * 4) >= 2 ? 2 : 1);
     static_assert(PIX % 128 == 0 && PTW >= 1, "workgroup must own a multiple of 128 pixels");
+    static_assert(!W24 || (H == 4 && W == 4 && SPW == 8), "F(2x4, 3x3): 4x4 images, 8 samples = one column tile of 16 output tiles");
     static_assert(HID % 8 == 0 && C % 4 == 0, "channel counts must fill whole k-steps");
     static_assert((HW & (HW - 1)) == 0 && (W & (W - 1)) == 0, "power-of-two images");
 };
@@ -886,6 +892,177 @@ __device__ __forceinline__ void winograd_phase2(float* __restrict__ lds, const f
     else cf_wave_sync();
 }
 
+// ---- Winograd F(2x4, 3x3) form of the reflect-padded 3x3 on the 4x4 level (phase 2 of PIPE == 6 geometries) -------------
+// F(2, 3) down the rows and F(4, 3) along the columns: per 2x4 output tile and channel pair 24 products instead of the 2 x 16 of
+// two F(2x2) tiles, so the 3x3 runs 12 instead of 16 C^2 multiply-adds per pixel (a step 16 instead of 20):
+//     Y = A2^T [ sum_ci U[ci] (.) (B2^T d[ci] B4) ] A4,     U = G2 w G4^T (packed once, fp64 -> fp32, k_step_pack),
+// d = the 4x6 input patch of the tile (reflect-padded).  F(4, 3) is the Toom-Cook form on the points {0, 1, -1, 1/2, -1/2, inf}:
+// every entry of B4^T ({0, +-1/4, +-1/2, +-1, -5/4}) and A4^T ({0, +-1, +-1/2, 1/4, +-1/8}) is exact in fp32, the 1/f_k of the
+// construction (4, 2/3, -8/3) lives in the packed weights.  The integer points {0, +-1, +-2, inf} cost twice the error on the cifar10
+// "extreme" fixture (9.2e-6 bits/dim against a 1e-5 bar); the half points keep F(2x2)'s 4.6e-6 (tests/test_winograd24.py).
+// Mapping: 8 samples x 2 tiles = the 16 lanes of ONE 16x16x4 column tile per workgroup; the four waves split the output ROWS
+// (RTW = RT16 / 4 row tiles each) and each forms the Winograd-domain operands of all 16 tiles itself.  Per vertical index xi and
+// group of 4 k-steps the lane sums its two patch rows once per patch column (A[c] = d[r1][c] + sigma d[r2][c], six values) and
+// the six horizontal positions come from those with constant FMAs; the six position products accumulate in M[nu] over all k,
+// and the output transform runs once per xi (Z = M A4, Y[i] += A2^T[i][xi] Z).
+// h1 layout (written by phase 1 of the same geometry, w24_pix): pixel (s, y, x) of row k sits at k PIX + 8 (4 y + ((x + y + k) & 3)) + s
+// - the skew by y and by the channel parity puts the 32 lanes of a half wave (8 samples x 2 tile rows x 2 channels; the two tile rows
+// share the patch row at a = 0 / 3) on distinct banks for every patch row and column.
+template <class G> __device__ __forceinline__ int w24_pix(int s, int y, int x, int kpar) { return 8 * (4 * y + ((x + y + kpar) & 3)) + s; }
+
+template <class G>
+__device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const float* __restrict__ wsl, ws_rsrc_t rs, int lane,
+                                                  int wave) {
+    constexpr int W = G::W, H = G::H, HW = G::HW, PIX = G::PIX, HALF = G::HALF, RT16 = G::RT16, KG4 = G::KG4;
+    static_assert(G::W24 && RT16 % 4 == 0, "F(2x4, 3x3) geometry");
+    constexpr int RTW = RT16 / 4;                        // 16-row tiles of this wave
+    constexpr int NS = 6 * KG4;                          // (group, nu) steps per xi
+    // nu order inside a group: 0 and 5 first, so that A0 / A5 die early and A1 .. A4 live on as P, Q, R, D
+    constexpr int NU[6] = {0, 5, 1, 2, 3, 4};
+    typedef float f32x2w __attribute__((ext_vector_type(2)));
+    const int rt0 = __builtin_amdgcn_readfirstlane(wave * RTW);
+    float* H1 = lds + HALF * PIX;
+    const int l15 = lane & 15, lg = lane >> 4;
+    const int smp = l15 >> 1, ty = l15 & 1;
+    int yrow[4];                                          // reflect-padded patch rows of this lane's tile
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const int yy = 2 * ty - 1 + a;
+        yrow[a] = yy < 0 ? -yy : (yy >= H ? 2 * (H - 1) - yy : yy);
+    }
+    f32x4w Y[2][4][RTW];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int rt = 0; rt < RTW; ++rt) Y[i][j][rt] = f32x4w{0.f, 0.f, 0.f, 0.f};
+    // operand addresses of one xi: patch rows r1 / r2 (B2^T row xi = d[r1] + sigma d[r2]) x the six patch columns
+    // (BYTE offsets: an operand address is then this value + an immediate per k-step)
+    auto addrs = [&](int xi, int (&o)[2][6]) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int yy = h == 0 ? (xi == 0 ? yrow[0] : (xi == 2 ? yrow[2] : yrow[1]))
+                                  : (xi == 2 ? yrow[1] : (xi == 3 ? yrow[3] : yrow[2]));
+#pragma unroll
+            for (int c = 0; c < 6; ++c) {
+                const int xx = c == 0 ? 1 : (c == 5 ? 2 : c - 1);          // reflect-padded patch column
+                o[h][c] = 4 * (HALF * PIX + lg * PIX + w24_pix<G>(smp, yy, xx, lg & 1));
+            }
+        }
+    };
+    struct Raw { f32x2w d[2][6][2]; };                    // [row r1 / r2][patch column][k-step pair]
+    struct WFrag { float4 a[RTW]; };
+    auto load_raw = [&](const int (&o)[2][6], int kk, Raw& r) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int c = 0; c < 6; ++c)
+#pragma unroll
+                for (int e2 = 0; e2 < 2; ++e2) {
+                    const char* q0 = reinterpret_cast<const char*>(lds) + (16 * kk + 8 * e2) * PIX * 4;      // k-steps 4 kk + 2 e2 (+1)
+                    const char* q1 = q0 + 4 * PIX * 4;
+                    r.d[h][c][e2] = f32x2w{*reinterpret_cast<const float*>(q0 + o[h][c]), *reinterpret_cast<const float*>(q1 + o[h][c])};
+                }
+    };
+    auto load_w = [&](int xi, int s, WFrag& f) {          // step s = kk * 6 + (index of nu in NU) of vertical index xi
+        const int kk = s / 6, nu = NU[s % 6];
+        const int fr = G::OFF_AW24 + (((xi * 6 + nu) * RT16 + rt0) * KG4 + kk) * 256;
+#pragma unroll
+        for (int rt = 0; rt < RTW; ++rt) f.a[rt] = ws_frag(rs, lane, fr + rt * KG4 * 256);
+    };
+    int o[2][6];
+    addrs(0, o);
+    Raw raw;
+    WFrag wf[2];                                          // weight fragments requested one step ahead
+    load_raw(o, 0, raw);
+    load_w(0, 0, wf[0]);
+    // A2^T[0][xi] = (1, 1, 1, 0), A2^T[1][xi] = (0, 1, -1, -1): xi = 0 and xi = 3 are peeled so that their zero half of the
+    // output transform is not executed and, at xi = 0, Y[1] is not yet live (the loop keeps xi = 1, 2)
+    auto xi_body = [&](const int xi, auto has0, auto has1) {
+        const int xn = xi < 3 ? xi + 1 : 3;               // (after the last xi the prefetches re-read xi = 3: harmless)
+        const float sigma = xi == 1 ? 1.f : -1.f;
+        const float c0 = xi < 3 ? 1.f : 0.f, c1 = xi == 0 ? 0.f : (xi == 1 ? 1.f : -1.f);      // A2^T[0][xi], A2^T[1][xi]
+        f32x4w M[6][RTW];
+#pragma unroll
+        for (int nu = 0; nu < 6; ++nu)
+#pragma unroll
+            for (int rt = 0; rt < RTW; ++rt) M[nu][rt] = f32x4w{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < KG4; ++kk) {
+            f32x2w A[6][2];                               // vertical transform, once per patch column
+#pragma unroll
+            for (int c = 0; c < 6; ++c)
+#pragma unroll
+                for (int e2 = 0; e2 < 2; ++e2) A[c][e2] = raw.d[0][c][e2] + sigma * raw.d[1][c][e2];
+            if (kk + 1 < KG4) {
+                load_raw(o, kk + 1, raw);
+            } else {                                      // first group of the next xi: its operand addresses replace this xi's
+                addrs(xn, o);
+                load_raw(o, 0, raw);
+            }
+#pragma unroll
+            for (int t = 0; t < 6; ++t) {
+                const int s = kk * 6 + t, nu = NU[t];
+                if (s + 1 < NS) load_w(xi, s + 1, wf[(s + 1) & 1]);
+                else load_w(xn, 0, wf[0]);
+                __builtin_amdgcn_sched_barrier(0);
+                // horizontal transform B4^T row nu:  nu 0: A0/4 - 5/4 A2 + A4;  1, 2: P +- Q (P = A4 - A2/4, Q = A3 - A1/4);
+                // 3, 4: R +- (A3 - A1)/2 (R = A4 - A2);  5: A1/4 - 5/4 A3 + A5
+                f32x2w v[2];
+#pragma unroll
+                for (int e2 = 0; e2 < 2; ++e2) {
+                    const f32x2w a0 = A[0][e2], a1 = A[1][e2], a2 = A[2][e2], a3 = A[3][e2], a4 = A[4][e2], a5 = A[5][e2];
+                    if (nu == 0) v[e2] = 0.25f * a0 + (a4 - 1.25f * a2);
+                    else if (nu == 1) v[e2] = (a4 - 0.25f * a2) + (a3 - 0.25f * a1);
+                    else if (nu == 2) v[e2] = (a4 - 0.25f * a2) - (a3 - 0.25f * a1);
+                    else if (nu == 3) v[e2] = (a4 - a2) + 0.5f * (a3 - a1);
+                    else if (nu == 4) v[e2] = (a4 - a2) - 0.5f * (a3 - a1);
+                    else v[e2] = 0.25f * a1 + (a5 - 1.25f * a3);
+                }
+                const WFrag& f = wf[s & 1];
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int rt = 0; rt < RTW; ++rt)
+                        M[nu][rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(f4e(f.a[rt], e), v[e >> 1][e & 1], M[nu][rt], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        // output transform of this xi: Z = M A4 (A4^T rows: 1 1 1 1 1 0 / 0 1 -1 1/2 -1/2 0 / 0 1 1 1/4 1/4 0 / 0 1 -1 1/8 -1/8 1),
+        // Y[i] += A2^T[i][xi] Z
+#pragma unroll
+        for (int rt = 0; rt < RTW; ++rt) {
+            const f32x4w s12 = M[1][rt] + M[2][rt], d12 = M[1][rt] - M[2][rt], s34 = M[3][rt] + M[4][rt], d34 = M[3][rt] - M[4][rt];
+            const f32x4w Z[4] = {M[0][rt] + s12 + s34, d12 + 0.5f * d34, s12 + 0.25f * s34, d12 + 0.125f * d34 + M[5][rt]};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if constexpr (decltype(has0)::value) Y[0][j][rt] += c0 * Z[j];
+                if constexpr (decltype(has1)::value) Y[1][j][rt] += c1 * Z[j];
+            }
+        }
+    };
+    xi_body(0, std::true_type{}, std::false_type{});
+#pragma unroll 1
+    for (int xi = 1; xi < 3; ++xi) xi_body(xi, std::true_type{}, std::true_type{});
+    xi_body(3, std::false_type{}, std::true_type{});
+    __syncthreads();                 // every wave has finished reading h1
+#pragma unroll
+    for (int rt = 0; rt < RTW; ++rt) {
+        const float4 b = *reinterpret_cast<const float4*>(wsl + G::OFF_B2 + (rt0 + rt) * 16 + 4 * lg);
+        const float bb[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {        // the four pixels of an output row of the tile: one 16-byte store
+                float* dst = H1 + ((rt0 + rt) * 16 + 4 * lg + r) * PIX + smp * HW + (2 * ty + i) * W;
+                *reinterpret_cast<float4*>(dst) = make_float4(cf_relu(Y[i][0][rt][r] + bb[r]), cf_relu(Y[i][1][rt][r] + bb[r]),
+                                                              cf_relu(Y[i][2][rt][r] + bb[r]), cf_relu(Y[i][3][rt][r] + bb[r]));
+            }
+    }
+    __syncthreads();                 // phase 3 reads all rows of this wave's own columns: the other waves' row tiles in place
+}
+
 // ---- direct 3x3 on the bf16 matrix cores (phases 1 + 2 of the PIPE == 5 geometry: 16x16 images, HID = 32) -----------------------
 // `v_mfma_f32_*_f32` runs at the vector rate on the pipe the vector instructions use; `v_mfma_f32_16x16x32_bf16` has 16x that
 // rate on a pipe of its own.  An fp32 value is exactly three bf16 pieces (truncation split), piece products are exact in fp32,
@@ -1053,7 +1230,8 @@ __device__ __forceinline__ void conditioner_net(f32x16 (&acc3)[G::RT03][G::PTW],
         dense_phase<G, G::KS1, G::NG1, RT1>(acc, rs, G::OFF_A1, Y0, pix, lane);
         // the parity-split h1 order of the Winograd form scatters a wave's pixels over its whole SAMPLE: where a sample spans
         // several waves (16x16), every wave must be done with its columns of what the H region held before (x / z plane)
-        if constexpr (G::WINO && G::HW > 32 * PTW) __syncthreads();
+        // (the F(2x4) order spreads every sample over the whole row)
+        if constexpr (G::WINO && (G::HW > 32 * PTW || G::W24)) __syncthreads();
 #pragma unroll
         for (int rt = 0; rt < RT1; ++rt)
 #pragma unroll
@@ -1061,7 +1239,10 @@ __device__ __forceinline__ void conditioner_net(f32x16 (&acc3)[G::RT03][G::PTW],
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int row = rt * 32 + tile_row(r, lk);
-                    if constexpr (G::WINO) {     // parity-split pixel order of winograd_phase2 (row & 1 = r & 1)
+                    if constexpr (G::W24) {      // skewed pixel order of winograd24_phase2 (row & 1 = r & 1)
+                        const int pw = w24_pix<G>((pix[q] - pin[q]) / G::HW, pin[q] / W, pin[q] % W, r & 1);
+                        if (row < HID) H1[row * PIX + pw] = cf_relu(acc[rt][q][r]);
+                    } else if constexpr (G::WINO) {     // parity-split pixel order of winograd_phase2 (row & 1 = r & 1)
                         const int pw = wino_pix<G>(pix[q] - pin[q], pin[q] / W, pin[q] % W) ^ ((r & 1) * (W / 2));
                         if (row < HID) H1[row * PIX + pw] = cf_relu(acc[rt][q][r]);
                     } else {
@@ -1100,7 +1281,12 @@ __device__ __forceinline__ void conditioner_net(f32x16 (&acc3)[G::RT03][G::PTW],
 
     // ================= phase 2: h2 = relu(NN.2 (*) h1 + b), 3x3, reflect padding   (coupling.py:27)
     if constexpr (G::WINO) {
-        winograd_phase2<G>(lds, wsl, rs, lane, tid >> 6);
+        if constexpr (G::W24) {
+            static_assert(!DUMP, "the F(2x4) form runs in the evaluation forward only");
+            winograd24_phase2<G>(lds, wsl, rs, lane, tid >> 6);
+        } else {
+            winograd_phase2<G>(lds, wsl, rs, lane, tid >> 6);
+        }
         if constexpr (DUMP) {            // h2 sits in LDS in natural order (own columns): plane store + mask words from the plane
             rows_store_t<G, HID, HID>(tp.h2, H1, tile * G::SPW, B, tid >> 6, lane);
 #pragma unroll
@@ -1324,6 +1510,7 @@ using G16w = Geo<16, 16, 16, 1, 3>;      // Winograd F(2x2,3x3) form of the 3x3 
 using G32w = Geo<32, 8, 8, 4, 3>;
 using G64w = Geo<64, 4, 4, 16, 3>;
 using G64w2 = Geo<64, 4, 4, 8, 3>;       // 8 samples per workgroup, 2 workgroups / CU: two waves per column tile split the rows
+using G64w24 = Geo<64, 4, 4, 8, 6>;      // ... in the Winograd F(2x4, 3x3) form (winograd24_phase2): the four waves split the rows
 
 
 int shape_id(int C, int H, int W) {
