@@ -36,7 +36,7 @@ struct StepPackBatch {
         *w3[kPrepBatch], *b3[kPrepBatch];
     float* ws[kPrepBatch];
     int pieces;                          // also the bf16 pieces of the Winograd-domain weights (CONTEXTFLOW_BF16_SPLIT=1)
-    int w24;                             // also the F(2x4, 3x3) Winograd-domain weights of the 4x4 level (unless CONTEXTFLOW_WINO24=0)
+    int w24;                             // also the F(2x4, 3x3) Winograd-domain weights of the 4x4 / 8x8 levels (unless CONTEXTFLOW_WINO24=0)
 };
 template <class G>
 __global__ __launch_bounds__(256) void k_step_pack(const StepPackBatch pb) {
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void k_step_pack(const StepPackBatch pb) {
             }
         }
     }
-    if (G::H == 4 && G::W == 4 && pb.w24) {
+    if (G::HAS_W24 && pb.w24) {
         // Winograd-domain weights of the F(2x4, 3x3) form (winograd24_phase2): U[xi][nu] = G2 w G4^T (fp64, rounded once), G2 as above,
         // G4 = the F(4, 3) Toom-Cook rows on the points {0, 1, -1, 1/2, -1/2, inf}
         constexpr int HID = G::HID;
@@ -1370,11 +1370,18 @@ static bool direct_conv_only() {
     static const bool v = [] { const char* e = getenv("CONTEXTFLOW_DIRECT_CONV"); return e && e[0] == '1'; }();
     return v;
 }
-// the 4x4 level's evaluation forward in the Winograd F(2x4, 3x3) form (G64w24) unless CONTEXTFLOW_WINO24=0 (A/B: F(2x2, 3x3), G64w2)
+// the 4x4 / 8x8 levels' evaluation forward in the Winograd F(2x4, 3x3) form (G64w24 / G32w24) unless CONTEXTFLOW_WINO24=0
+// (A/B: F(2x2, 3x3) everywhere, G64w2 / G32w); CONTEXTFLOW_WINO24_8X8=0 switches only the 8x8 level back (A/B of that level)
 static bool wino24_enabled() {
     static const bool v = [] { const char* e = getenv("CONTEXTFLOW_WINO24"); return !(e && e[0] == '0'); }();
     return v;
 }
+static bool wino24_8x8_enabled() {
+    static const bool v = [] { const char* e = getenv("CONTEXTFLOW_WINO24_8X8"); return !(e && e[0] == '0'); }();
+    return v && wino24_enabled();
+}
+// smallest batch of the 8x8 level's F(2x4) form: 512 workgroups = one full round of 2 per CU, as at 4x4
+constexpr int kW24MinB8x8 = 512 * G32w24::SPW;
 
 extern "C" {
 
@@ -1555,6 +1562,7 @@ int cf_flow_step_fwd_debug(const float* x, float* z, float* ldj_acc, const void*
         case 12: rc = in_squeeze ? launch_step_small<G16w, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream))         // variant 4:
                                 : launch_step_small<G16w, false>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream)); break;  // Winograd form of the 3x3
         case 20: CF_STEP(G32w); break;
+        case 22: CF_STEP(G32w24); break;          // variant 6: the F(2x4, 3x3) form, two column tiles x two row halves
         case 28: CF_STEP(G64w); break;
         case 29: CF_STEP(G64w2); break;           // variant 5: row-split Winograd at 128 pixels per workgroup
         case 30: CF_STEP(G64w24); break;          // variant 6: ... in the F(2x4, 3x3) form, the rows split over all four waves
@@ -1628,6 +1636,8 @@ int cf_flow_step_fwd(const float* x, float* z, float* ldj_acc, const void* ws, i
     if (!direct_only && (sid == 0 || sid == 1 || (sid == 2 && B >= 256 * G32::SPW))) flags = 4 << 16;
     // 4x4: 8 samples per workgroup, rows split over wave pairs (F(2x2)) / over all four waves (F(2x4), 24 instead of 32 products per 8 pixels)
     if (!direct_only && sid == 3 && B >= 256 * G64w2::SPW) flags = (wino24_enabled() ? 6 : 5) << 16;
+    // 8x8: the F(2x4) form from 2 048 samples (below: F(2x2), G32w)
+    if (!direct_only && sid == 2 && B >= kW24MinB8x8 && wino24_8x8_enabled()) flags = 6 << 16;
     // CONTEXTFLOW_BF16_SPLIT=1 (off by default): the 16x16 level's Winograd-domain products as bf16-piece MFMAs (G16wb)
     // (mode 2, the direct bf16-piece form: from 1024 samples per launch - below that the chained launches of the fp32 form run)
     if (!direct_only && sid == 1 && bf16_split_mode() == 1) flags = 6 << 16;
@@ -1657,7 +1667,7 @@ int cf_flow_step_fwd(const float* x, float* z, float* ldj_acc, const void* ws, i
 // pass 0 = cf_flow_step_fwd, 1 = cf_flow_step_fwd_taped, 2 = cf_flow_step_bwd_taped (direct transposed 3x3), 3 = cf_flow_step_inv
 // (the forward's conditioner + W^-1 instead of W: the same count; Winograd form at every level).  The direct
 // form runs C^2 (Conv1x1) + C^2 + 36 C^2 + 2 C^2 = 40 C^2 per pixel; the Winograd form of the 3x3 runs 16 instead of 36
-// C^2 (F(2x2, 3x3)) or 12 C^2 (F(2x4, 3x3): the 4x4 level's evaluation forward).  The conditions below restate the dispatch of
+// C^2 (F(2x2, 3x3)) or 12 C^2 (F(2x4, 3x3): the 4x4 and 8x8 levels' evaluation forward).  The conditions below restate the dispatch of
 // the two entry points above / below - change them together.
 int64_t cf_flow_step_macs(int B, int C, int H, int W, int pass) {
     const int sid = shape_id(C, H, W);
@@ -1666,6 +1676,7 @@ int64_t cf_flow_step_macs(int B, int C, int H, int W, int pass) {
     if (pass == 2 || direct_conv_only()) return direct;
     if (pass == 3) return wino;
     if (sid == 3 && pass == 0 && wino24_enabled() && B >= 256 * G64w2::SPW) return wino24;
+    if (sid == 2 && pass == 0 && wino24_8x8_enabled() && B >= kW24MinB8x8) return wino24;
     bool w;
     if (sid == 0) w = pass == 0;                                  // mnist's C = 8 level: evaluation only
     else if (sid == 1) w = true;                                  // 16x16, C = 16: every batch size

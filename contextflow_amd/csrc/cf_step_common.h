@@ -60,7 +60,7 @@ struct Geo {
     static constexpr int OFF_SA2 = OFF_SA1 + (HID16 ? SG1 * 256 : 0);
     // Winograd F(2x2,3x3) form of the 3x3 (PIPE == 3, winograd_phase2 below): U = G w G^T for the 16 positions, packed as
     // 16x16x4 A fragments: [position][16-row tile][group of 4 k-steps][lane][4]
-    // PIPE == 6: Winograd F(2x4, 3x3) on the 4x4 level (winograd24_phase2): 24 products per 2x4 output tile instead of 2 x 16
+    // PIPE == 6: Winograd F(2x4, 3x3) on the 4x4 and 8x8 levels (winograd24_phase2): 24 products per 2x4 output tile instead of 2 x 16
     static constexpr bool W24 = (PIPE_ == 6);
     static constexpr bool WINO = (PIPE_ == 3 || PIPE_ == 4 || W24);
     // PIPE == 4: the Winograd-domain products on the bf16 matrix cores - every fp32 operand as three bf16 pieces, the six piece
@@ -88,10 +88,11 @@ struct Geo {
     // bf16 pieces of the direct 3x3 taps (DBF): [tap][16-row tile][32-channel block][piece][lane] 16 bytes = 8 bf16: element j of
     // lane l = piece of NN.2[16 rt + (l & 15)][32 kb + 8 (l >> 4) + j][tap] (the hardware's own k order)
     static constexpr int OFF_ADB = WS_END0 + 16 * RT16 * KB32 * 3 * 256;
-    // Winograd-domain weights of the F(2x4, 3x3) form (4x4 images only): U = G2 w G4^T for the 4 x 6 positions, packed as the
-    // 16 positions of the F(2x2) form: [position xi * 6 + nu][16-row tile][group of 4 k-steps][lane][4]
+    // Winograd-domain weights of the F(2x4, 3x3) form (4x4 and 8x8 images only): U = G2 w G4^T for the 4 x 6 positions, packed as
+    // the 16 positions of the F(2x2) form: [position xi * 6 + nu][16-row tile][group of 4 k-steps][lane][4]
+    static constexpr bool HAS_W24 = (H == 4 && W == 4) || (H == 8 && W == 8);
     static constexpr int OFF_AW24 = OFF_ADB + 9 * RT16 * KB32 * 3 * 256;
-    static constexpr int WS_FLOATS = OFF_AW24 + ((H == 4 && W == 4) ? 24 * HID * HID : 0);
+    static constexpr int WS_FLOATS = OFF_AW24 + (HAS_W24 ? 24 * HID * HID : 0);
     static constexpr int PP = 2 * W + 2 * H + 4;      // fold slots per sample: 2 patched rows, 2 patched columns, 4 corners
     static constexpr int RS = PATCH ? ((PIX + SPW * PP + 1 + 3) & ~3) : PIX;
     // C = 8 (HID = 16) in the Winograd form: all 16 Winograd-domain weight matrices are 16 KB - staged into LDS once per workgroup
@@ -106,7 +107,8 @@ struct Geo {
     // waves per SIMD the register allocator must leave room for = workgroups per CU the LDS footprint admits
     static constexpr int MINW = (160 * 1024) / (LDS_FLOATS * 4) >= 4 ? 4 : ((160 * 1024) / (LDS_FLOATS * 4) >= 2 ? 2 : 1);
     static_assert(PIX % 128 == 0 && PTW >= 1, "workgroup must own a multiple of 128 pixels");
-    static_assert(!W24 || (H == 4 && W == 4 && SPW == 8), "F(2x4, 3x3): 4x4 images, 8 samples = one column tile of 16 output tiles");
+    static_assert(!W24 || (H == 4 && W == 4 && SPW == 8) || (H == 8 && W == 8 && SPW == 4),
+                  "F(2x4, 3x3): 4x4 images, 8 samples = one column tile of 16 output tiles; 8x8 images, 4 samples = two column tiles");
     static_assert(HID % 8 == 0 && C % 4 == 0, "channel counts must fill whole k-steps");
     static_assert((HW & (HW - 1)) == 0 && (W & (W - 1)) == 0, "power-of-two images");
 };
@@ -892,7 +894,7 @@ __device__ __forceinline__ void winograd_phase2(float* __restrict__ lds, const f
     else cf_wave_sync();
 }
 
-// ---- Winograd F(2x4, 3x3) form of the reflect-padded 3x3 on the 4x4 level (phase 2 of PIPE == 6 geometries) -------------
+// ---- Winograd F(2x4, 3x3) form of the reflect-padded 3x3 on the 4x4 and 8x8 levels (phase 2 of PIPE == 6 geometries) ----
 // F(2, 3) down the rows and F(4, 3) along the columns: per 2x4 output tile and channel pair 24 products instead of the 2 x 16 of
 // two F(2x2) tiles, so the 3x3 runs 12 instead of 16 C^2 multiply-adds per pixel (a step 16 instead of 20):
 //     Y = A2^T [ sum_ci U[ci] (.) (B2^T d[ci] B4) ] A4,     U = G2 w G4^T (packed once, fp64 -> fp32, k_step_pack),
@@ -900,35 +902,69 @@ __device__ __forceinline__ void winograd_phase2(float* __restrict__ lds, const f
 // every entry of B4^T ({0, +-1/4, +-1/2, +-1, -5/4}) and A4^T ({0, +-1, +-1/2, 1/4, +-1/8}) is exact in fp32, the 1/f_k of the
 // construction (4, 2/3, -8/3) lives in the packed weights.  The integer points {0, +-1, +-2, inf} cost twice the error on the cifar10
 // "extreme" fixture (9.2e-6 bits/dim against a 1e-5 bar); the half points keep F(2x2)'s 4.6e-6 (tests/test_winograd24.py).
-// Mapping: 8 samples x 2 tiles = the 16 lanes of ONE 16x16x4 column tile per workgroup; the four waves split the output ROWS
-// (RTW = RT16 / 4 row tiles each) and each forms the Winograd-domain operands of all 16 tiles itself.  Per vertical index xi and
+// Mapping, 4x4: 8 samples x 2 tiles = the 16 lanes of ONE 16x16x4 column tile per workgroup; the four waves split the output ROWS
+// (RTW = RT16 / 4 row tiles each) and each forms the Winograd-domain operands of all 16 tiles itself.  8x8 (4 samples): an image is
+// 4 x 2 tiles, 2 samples fill a column tile, the workgroup has two; wave w takes column tile w & 1 and row half w >> 1 (RTW =
+// RT16 / 2 = 2 as at 4x4: the same accumulators, the operands of a column tile are formed by two waves).  Per vertical index xi and
 // group of 4 k-steps the lane sums its two patch rows once per patch column (A[c] = d[r1][c] + sigma d[r2][c], six values) and
 // the six horizontal positions come from those with constant FMAs; the six position products accumulate in M[nu] over all k,
 // and the output transform runs once per xi (Z = M A4, Y[i] += A2^T[i][xi] Z).
-// h1 layout (written by phase 1 of the same geometry, w24_pix): pixel (s, y, x) of row k sits at k PIX + 8 (4 y + ((x + y + k) & 3)) + s
+// h1 layout (written by phase 1 of the same geometry, w24_pix): 4x4: pixel (s, y, x) of row k sits at k PIX + 8 (4 y + ((x + y + k) & 3)) + s
 // - the skew by y and by the channel parity puts the 32 lanes of a half wave (8 samples x 2 tile rows x 2 channels; the two tile rows
 // share the patch row at a = 0 / 3) on distinct banks for every patch row and column.
-template <class G> __device__ __forceinline__ int w24_pix(int s, int y, int x, int kpar) { return 8 * (4 * y + ((x + y + kpar) & 3)) + s; }
+// 8x8: a ds_read_b32 is served in two groups of 32 lanes on 32 banks; a group of a patch read is (2 channel parities) x (2 samples)
+// x (4 tile rows) x (2 tile columns).  For a given patch element the four image rows have one parity and the two image columns are
+// {1,3}, {0,4}, {1,5}, {2,6}, {3,7} or {4,6}: the same parity, and g = x2 ^ x1 (bits of x) tells the two apart in every pair.
+// Word of pixel (s, y, x) inside row k (bits 7..0):
+//     s1 | x1 | y0 ^ k1 | y2 y1 | s0 | g | x0 ^ k0
+// - the low five bits (the bank) are distinct for the 32 lanes of a group for every patch element (lanes whose reflected row
+// coincides read the same word), and the low six for all 64 lanes.  The word is a row part + a column part (w24_row / w24_col), so an operand address is one
+// addition.  (tests/test_winograd24_8x8.py checks the order exhaustively.)
+template <class G> __device__ __forceinline__ int w24_row(int s, int y, int kq) {
+    return 128 * (s >> 1) + 32 * ((y ^ (kq >> 1)) & 1) + 8 * (y >> 1) + 4 * (s & 1);
+}
+template <class G> __device__ __forceinline__ int w24_col(int x, int kq) {
+    return 64 * ((x >> 1) & 1) + 2 * (((x >> 2) ^ (x >> 1)) & 1) + ((x ^ kq) & 1);
+}
+template <class G> __device__ __forceinline__ int w24_pix(int s, int y, int x, int kq) {      // kq = row & 3
+    if constexpr (G::H == 4) return 8 * (4 * y + ((x + y + kq) & 3)) + s;
+    else return w24_row<G>(s, y, kq) + w24_col<G>(x, kq);
+}
 
 template <class G>
 __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const float* __restrict__ wsl, ws_rsrc_t rs, int lane,
                                                   int wave) {
     constexpr int W = G::W, H = G::H, HW = G::HW, PIX = G::PIX, HALF = G::HALF, RT16 = G::RT16, KG4 = G::KG4;
-    static_assert(G::W24 && RT16 % 4 == 0, "F(2x4, 3x3) geometry");
-    constexpr int RTW = RT16 / 4;                        // 16-row tiles of this wave
+    constexpr int NCT = PIX / 128;                       // column tiles (16 output tiles of 2x4 pixels) of the workgroup
+    constexpr int RSP = kWaves / NCT;                    // waves that share a column tile and split the output rows
+    static_assert(G::W24 && (NCT == 1 || NCT == 2) && RT16 % RSP == 0 && W % 4 == 0, "F(2x4, 3x3) geometry");
+    constexpr int RTW = RT16 / RSP;                      // 16-row tiles of this wave
+    constexpr int TPS = HW / 8, TXN = W / 4;             // output tiles per sample / per image row
     constexpr int NS = 6 * KG4;                          // (group, nu) steps per xi
     // nu order inside a group: 0 and 5 first, so that A0 / A5 die early and A1 .. A4 live on as P, Q, R, D
     constexpr int NU[6] = {0, 5, 1, 2, 3, 4};
     typedef float f32x2w __attribute__((ext_vector_type(2)));
-    const int rt0 = __builtin_amdgcn_readfirstlane(wave * RTW);
+    const int rt0 = __builtin_amdgcn_readfirstlane((NCT == 1 ? wave : wave / NCT) * RTW);
     float* H1 = lds + HALF * PIX;
     const int l15 = lane & 15, lg = lane >> 4;
-    const int smp = l15 >> 1, ty = l15 & 1;
-    int yrow[4];                                          // reflect-padded patch rows of this lane's tile
+    const int tg = (wave % NCT) * 16 + l15;              // this lane's output tile
+    // (the 4x4 expressions are kept literally: hipcc's code for that instantiation is then instruction for instruction what it was)
+    const int smp = H == 4 ? l15 >> 1 : tg / TPS, ty = H == 4 ? l15 & 1 : (tg % TPS) / TXN, tx = H == 4 ? 0 : tg % TXN;
+    int yrow[4], xcol[6];                                 // reflect-padded patch rows / columns of this lane's tile
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
         const int yy = 2 * ty - 1 + a;
         yrow[a] = yy < 0 ? -yy : (yy >= H ? 2 * (H - 1) - yy : yy);
+    }
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        const int xx = 4 * tx - 1 + c;
+        xcol[c] = xx < 0 ? -xx : (xx >= W ? 2 * (W - 1) - xx : xx);
+    }
+    int cpart[6];                                         // 8x8: byte offset of a patch column (the order is row part + column part)
+    if constexpr (H != 4) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) cpart[c] = 4 * (HALF * PIX + lg * PIX + w24_col<G>(xcol[c], lg));
     }
     f32x4w Y[2][4][RTW];
 #pragma unroll
@@ -946,8 +982,12 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
                                   : (xi == 2 ? yrow[1] : (xi == 3 ? yrow[3] : yrow[2]));
 #pragma unroll
             for (int c = 0; c < 6; ++c) {
-                const int xx = c == 0 ? 1 : (c == 5 ? 2 : c - 1);          // reflect-padded patch column
-                o[h][c] = 4 * (HALF * PIX + lg * PIX + w24_pix<G>(smp, yy, xx, lg & 1));
+                if constexpr (H == 4) {
+                    const int xx = c == 0 ? 1 : (c == 5 ? 2 : c - 1);
+                    o[h][c] = 4 * (HALF * PIX + lg * PIX + w24_pix<G>(smp, yy, xx, lg & 1));
+                } else {
+                    o[h][c] = 4 * w24_row<G>(smp, yy, lg) + cpart[c];
+                }
             }
         }
     };
@@ -1055,7 +1095,7 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {        // the four pixels of an output row of the tile: one 16-byte store
-                float* dst = H1 + ((rt0 + rt) * 16 + 4 * lg + r) * PIX + smp * HW + (2 * ty + i) * W;
+                float* dst = H1 + ((rt0 + rt) * 16 + 4 * lg + r) * PIX + smp * HW + (2 * ty + i) * W + (H == 4 ? 0 : 4 * tx);
                 *reinterpret_cast<float4*>(dst) = make_float4(cf_relu(Y[i][0][rt][r] + bb[r]), cf_relu(Y[i][1][rt][r] + bb[r]),
                                                               cf_relu(Y[i][2][rt][r] + bb[r]), cf_relu(Y[i][3][rt][r] + bb[r]));
             }
@@ -1239,8 +1279,8 @@ __device__ __forceinline__ void conditioner_net(f32x16 (&acc3)[G::RT03][G::PTW],
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int row = rt * 32 + tile_row(r, lk);
-                    if constexpr (G::W24) {      // skewed pixel order of winograd24_phase2 (row & 1 = r & 1)
-                        const int pw = w24_pix<G>((pix[q] - pin[q]) / G::HW, pin[q] / W, pin[q] % W, r & 1);
+                    if constexpr (G::W24) {      // skewed pixel order of winograd24_phase2 (row & 3 = r & 3)
+                        const int pw = w24_pix<G>((pix[q] - pin[q]) / G::HW, pin[q] / W, pin[q] % W, G::H == 4 ? r & 1 : r & 3);
                         if (row < HID) H1[row * PIX + pw] = cf_relu(acc[rt][q][r]);
                     } else if constexpr (G::WINO) {     // parity-split pixel order of winograd_phase2 (row & 1 = r & 1)
                         const int pw = wino_pix<G>(pix[q] - pin[q], pin[q] / W, pin[q] % W) ^ ((r & 1) * (W / 2));
@@ -1511,6 +1551,7 @@ using G32w = Geo<32, 8, 8, 4, 3>;
 using G64w = Geo<64, 4, 4, 16, 3>;
 using G64w2 = Geo<64, 4, 4, 8, 3>;       // 8 samples per workgroup, 2 workgroups / CU: two waves per column tile split the rows
 using G64w24 = Geo<64, 4, 4, 8, 6>;      // ... in the Winograd F(2x4, 3x3) form (winograd24_phase2): the four waves split the rows
+using G32w24 = Geo<32, 8, 8, 4, 6>;      // the 8x8 level in that form: two column tiles x two row halves
 
 
 int shape_id(int C, int H, int W) {
