@@ -28,7 +28,7 @@ template <int V> __device__ __forceinline__ void vstore(float* p, const float (&
 // ---------------------------------------------------------------------------------------------
 // flat elementwise ops
 // ---------------------------------------------------------------------------------------------
-enum { OP_ADD2 = 0, OP_AFFINE_FWD, OP_AFFINE_INV, OP_SIGMOID, OP_FLOOR };
+enum { OP_ADD2 = 0, OP_AFFINE_FWD, OP_AFFINE_INV, OP_SIGMOID, OP_FLOOR, OP_CLAMP };
 
 template <int OP, int V>
 __global__ __launch_bounds__(256) void k_flat(const float* __restrict__ x, const float* __restrict__ x2,
@@ -44,6 +44,7 @@ __global__ __launch_bounds__(256) void k_flat(const float* __restrict__ x, const
             else if constexpr (OP == OP_AFFINE_INV) r[j] = (r[j] - a) * b;      // normalize.py:40
             else if constexpr (OP == OP_SIGMOID) r[j] = 1.0f / (1.0f + expf(-r[j]));
             else if constexpr (OP == OP_FLOOR) r[j] = floorf(r[j]);
+            else if constexpr (OP == OP_CLAMP) r[j] = fmaxf(fminf(r[j], b), a);
         }
         vstore<V>(y + i * V, r);
     }
@@ -400,9 +401,10 @@ __global__ __launch_bounds__(256) void k_activation(const float* __restrict__ x,
 // Dequantization.reverse = x[b, i] = floor(((sigmoid(z[b, i]) - t2) * s2 - t1) * s1) for the first n_keep elements of every sample
 // (z_bstride > n_keep drops the augmented channels).  The same operations in the same order as the four k_flat launches + the copy
 // of the channel slice it replaces - subtraction and multiplication kept apart (no fma contraction), so the results are bitwise equal.
-template <int V>
+// CLAMP: `sample` projects the pixels into [lo, hi] behind the floor (cf_postprocess_inv_clamped); `inverse` does not.
+template <int V, bool CLAMP>
 __global__ __launch_bounds__(256) void k_postprocess_inv(const float* __restrict__ z, float* __restrict__ x, int64_t n_items, int per_sample,
-                                                         int64_t zbs, float t2, float s2, float t1, float s1) {
+                                                         int64_t zbs, float t2, float s2, float t1, float s1, float lo, float hi) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_items; i += (int64_t)gridDim.x * 256) {
         const int64_t b = i / per_sample;
         const int j = (int)(i - b * per_sample);
@@ -413,10 +415,25 @@ __global__ __launch_bounds__(256) void k_postprocess_inv(const float* __restrict
             float v = 1.0f / (1.0f + expf(-r[e]));               // OP_SIGMOID
             v = __fmul_rn(__fsub_rn(v, t2), s2);                 // OP_AFFINE_INV, Normalization 2
             v = __fmul_rn(__fsub_rn(v, t1), s1);                 // OP_AFFINE_INV, Normalization 1
-            r[e] = floorf(v);                                    // OP_FLOOR
+            v = floorf(v);                                       // OP_FLOOR
+            if constexpr (CLAMP) v = fmaxf(fminf(v, hi), lo);    // OP_CLAMP
+            r[e] = v;
         }
         vstore<V>(x + i * V, r);
     }
+}
+
+template <bool CLAMP>
+int launch_postprocess_inv(const float* z, float* x, int B, int n_keep, int64_t z_bstride, float t2, float s2, float t1, float s1,
+                           float lo, float hi, hipStream_t s) {
+    const bool vec = n_keep % 4 == 0 && z_bstride % 4 == 0 && aligned16(z) && aligned16(x);
+    const int per = vec ? n_keep / 4 : n_keep;
+    const int64_t items = (int64_t)B * per;
+    int64_t blocks = (items + 255) / 256;
+    if (blocks > 16384) blocks = 16384;
+    if (vec) k_postprocess_inv<4, CLAMP><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(z, x, items, per, z_bstride, t2, s2, t1, s1, lo, hi);
+    else k_postprocess_inv<1, CLAMP><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(z, x, items, per, z_bstride, t2, s2, t1, s1, lo, hi);
+    return 0;
 }
 
 }  // namespace
@@ -455,13 +472,24 @@ int cf_postprocess_inv(const float* z, float* x, int B, int n_keep, int64_t z_bs
                        cf_stream_t stream) {
     if (B == 0 || n_keep == 0) return 0;
     CF_REQUIRE(z && x && B > 0 && n_keep > 0 && z_bstride >= n_keep);
-    const bool vec = n_keep % 4 == 0 && z_bstride % 4 == 0 && aligned16(z) && aligned16(x);
-    const int per = vec ? n_keep / 4 : n_keep;
-    const int64_t items = (int64_t)B * per;
-    int64_t blocks = (items + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    if (vec) k_postprocess_inv<4><<<dim3((unsigned)blocks), dim3(256), 0, cf_s(stream)>>>(z, x, items, per, z_bstride, t2, s2, t1, s1);
-    else k_postprocess_inv<1><<<dim3((unsigned)blocks), dim3(256), 0, cf_s(stream)>>>(z, x, items, per, z_bstride, t2, s2, t1, s1);
+    launch_postprocess_inv<false>(z, x, B, n_keep, z_bstride, t2, s2, t1, s1, 0.f, 0.f, cf_s(stream));
+    CF_LAUNCH_CHECK();
+    return 0;
+}
+
+int cf_postprocess_inv_clamped(const float* z, float* x, int B, int n_keep, int64_t z_bstride, float t2, float s2, float t1, float s1,
+                               float lo, float hi, cf_stream_t stream) {
+    if (B == 0 || n_keep == 0) return 0;
+    CF_REQUIRE(z && x && B > 0 && n_keep > 0 && z_bstride >= n_keep && lo <= hi);
+    launch_postprocess_inv<true>(z, x, B, n_keep, z_bstride, t2, s2, t1, s1, lo, hi, cf_s(stream));
+    CF_LAUNCH_CHECK();
+    return 0;
+}
+
+int cf_clamp(const float* x, float* y, int64_t n, float lo, float hi, cf_stream_t stream) {
+    if (n == 0) return 0;                       // empty batch: nothing to do (pointers may be null)
+    CF_REQUIRE(x && y && n >= 0 && lo <= hi);
+    launch_flat<OP_CLAMP>(x, nullptr, y, n, lo, hi, cf_s(stream));
     CF_LAUNCH_CHECK();
     return 0;
 }

@@ -810,6 +810,17 @@ class FlowSequential(nn.Module):
     def inverse(self, z, context=None):
         """Run every layer's `reverse` from the last to the first (the loop of flowsequential.py:35-37); groups
         Coupling <- ActNorm <- Conv1x1 of a supported shape run as one fused kernel."""
+        return self._inverse(z, context, None)
+
+    def _pixel_range(self):
+        """(0, bins - 1) of the image flows - Dequantization followed by Normalization(0, bins) (model.py:97-98) - else None."""
+        mods = self.sequence_modules
+        if len(mods) >= 2 and isinstance(mods[0], Dequantization) and isinstance(mods[1], Normalization) and mods[1]._t == 0.0:
+            return 0.0, mods[1]._s - 1.0
+        return None
+
+    def _inverse(self, z, context, clamp):
+        """`inverse`; clamp = (lo, hi): the output of the leading Dequantization's reverse is projected into that range."""
         _hip.require_device(z)
         mods = self.sequence_modules
         i = len(mods) - 1
@@ -823,10 +834,12 @@ class FlowSequential(nn.Module):
                     z = self._inverse_step(z, mods[i - 2], mods[i - 1], m, unsqueeze=sq)
                     i -= 4 if sq else 3
                 elif self.fused and self._tail_fusable(i, z):
-                    z = self._inverse_tail(z, i)
+                    z = self._inverse_tail(z, i, clamp)
                     i = -1
                 else:
                     z = m.reverse(z, context)
+                    if i == 0 and clamp is not None and isinstance(m, Dequantization):
+                        _hip.call("cf_clamp", _hip.p(z), _hip.p(z), z.numel(), clamp[0], clamp[1], _hip.stream())
                     i -= 1
         return z
 
@@ -839,20 +852,30 @@ class FlowSequential(nn.Module):
             return False
         return i == 3 or (isinstance(mods[4], Augment) and mods[4].split_dim == 1 and 0 < mods[4].aug_size < z.shape[1])
 
-    def _inverse_tail(self, z, i):
+    def _inverse_tail(self, z, i, clamp=None):
         mods = self.sequence_modules
         z, zbs = _hip.bview(z)
         B, C, H, W = z.shape
         keep = C - (mods[4].aug_size if i == 4 else 0)
         x = torch.empty(B, keep, H, W, device=z.device, dtype=torch.float32)
         n1, n2 = mods[1], mods[2]
-        _hip.call("cf_postprocess_inv", _hip.p(z), _hip.p(x), B, keep * H * W, zbs, n2._t, n2._s, n1._t, n1._s, _hip.stream())
+        if clamp is None:
+            _hip.call("cf_postprocess_inv", _hip.p(z), _hip.p(x), B, keep * H * W, zbs, n2._t, n2._s, n1._t, n1._s, _hip.stream())
+        else:
+            _hip.call("cf_postprocess_inv_clamped", _hip.p(z), _hip.p(x), B, keep * H * W, zbs, n2._t, n2._s, n1._t, n1._s,
+                      clamp[0], clamp[1], _hip.stream())
         return x
 
     def sample(self, n_samples, context=None):
+        """flowsequential.py:32-39: a prior draw through the reverse chain.  By specification, for the image flows: the pixels
+        are projected into [0, bins - 1].  The reverse chain ends in floor(bins (sigmoid(y) - a) / (1 - 2 a)) (dequantize.py:19-20,
+        normalize.py:36-40), which is -1 / bins wherever sigmoid(y) leaves [a, 1 - a) - logits no forward pass can produce, but
+        a prior draw does (1.2 % of the pixels of an untrained cifar10 flow) - and a cast of such an image to uint8 wraps -1
+        to 255.  The reference's categorical dequantisers clamp their reverse the same way (dequantize.py:67); `inverse` stays
+        the plain chain, bitwise."""
         z = self.dist.sample(n_samples, context, need_log_prob=False)[0] if isinstance(self.dist, GaussianMixtureDistribution) \
             else self.dist.sample(n_samples, context)[0]           # (the reference's sample() also returns log p(z): not needed here)
-        return self.inverse(z, context)
+        return self._inverse(z, context, self._pixel_range())
 
 
 class GraphedFlow:

@@ -52,6 +52,12 @@ int cf_floor(const float* x, float* y, int64_t n, cf_stream_t stream);
  * Bitwise the result of the single calls (cf_sigmoid, cf_affine inverse x 2, cf_floor). */
 int cf_postprocess_inv(const float* z, float* x, int B, int n_keep, int64_t z_bstride, float t2, float s2, float t1, float s1,
                        cf_stream_t stream);
+/* ... followed by min(max(x, lo), hi): the tail of FlowSequential.sample, which returns pixels of the data range (the reverse
+ * chain alone gives lo - 1 and hi + 1 where sigmoid(z) leaves [t2', 1 - t2'], as the reference's does). */
+int cf_postprocess_inv_clamped(const float* z, float* x, int B, int n_keep, int64_t z_bstride, float t2, float s2, float t1, float s1,
+                               float lo, float hi, cf_stream_t stream);
+/* y = min(max(x, lo), hi)                                       the same projection behind the layer-by-layer chain */
+int cf_clamp(const float* x, float* y, int64_t n, float lo, float hi, cf_stream_t stream);
 /* Fused layers 0-3 of the image flows (model.py:97-100): v = ((x+u)/s1 + t1)/s2 + t2,
  * y = logit(v) written with batch stride y_bstride, ldj[b] = ldj_const + sum(-log v - log(1-v)).   */
 int cf_preprocess_fwd(const float* x, const float* u, float* y, float* ldj, int B, int N, int64_t y_bstride,

@@ -662,15 +662,26 @@ def flow_forward(ops, params, x, u=None, eps=(), init_actnorm=False, trace=None,
     return x, logp + logdet
 
 
-def flow_inverse_layers(ops, params, z, upto=None):
-    """Per-layer `reverse` chain (flowsequential.py:32-39) over the invertible, context-free layers.
-    Stops at SplitPrior/Augment boundaries being handled by the caller (the reference's own
-    `SplitPrior.reverse` is broken), so `ops` must not contain them."""
-    for op in reversed(ops[:upto]):
+def flow_inverse(ops, params, z, halves=(), stop=None, trace=None):
+    """The `reverse` chain (flowsequential.py:32-39) over a whole context-free program, from the last op to the first.
+
+    At a `split` the split-off channel half is concatenated back: the reference's own `SplitPrior.reverse` does not run
+     and a sampler would draw it from the split's prior, so the caller supplies the halves -
+    `halves` in FORWARD order, consumed from the back.  `augment` drops the noise channels (augment.py:20-21), `dequant` is
+    `floor()` (dequantize.py:19-20).  `stop`: an op kind or an op index; the walk returns in front of the first such op it
+    meets, i.e. with that op's forward OUTPUT ("augment": the logit-space tensor with its noise channel, "dequant": the
+    pixels before the floor).  `trace`, if a list, receives (kind, index, z) per inverted op, z = the op's recovered input.
+    dtype-generic: fp64 in, fp64 out."""
+    halves = list(halves)
+    for op in reversed(ops):
         kind, idx = op[0], op[1]
+        if stop is not None and stop in (kind, idx):
+            break
         pre = "%d." % idx
         if kind == "squeeze":
             z = squeeze_inv(z, op[2])
+        elif kind == "permute":                                   # permute_axes.py:11,16-17: the argsort of the permutation
+            z = z.permute(torch.argsort(torch.tensor(op[2])).tolist()).contiguous()
         elif kind == "conv1x1":
             z = conv1x1_inv(z, params[pre + "NN"])
         elif kind == "actnorm":
@@ -679,6 +690,15 @@ def flow_inverse_layers(ops, params, z, upto=None):
             z = coupling_inv(z, params, pre, op[4])
         elif kind == "transcoupling":
             z = transcoupling_inv(z, params, pre, op[2], op[3])
+        elif kind == "split":
+            if not halves:
+                raise ValueError("no inverse for split %d: its split-off half was not supplied" % idx)
+            z2 = halves.pop()
+            if tuple(z2.shape) != tuple(z.shape):
+                raise ValueError("split %d: half of shape %s against %s" % (idx, tuple(z2.shape), tuple(z.shape)))
+            z = torch.cat([z, z2.to(z.dtype)], 1)
+        elif kind == "augment":
+            z = z[:, : z.shape[1] - op[2]]
         elif kind == "affine":
             z = affine_inv(z, op[2], op[3])
         elif kind == "logit":
@@ -687,7 +707,33 @@ def flow_inverse_layers(ops, params, z, upto=None):
             z = z.floor()                                         # dequantize.py:19-20
         else:
             raise ValueError("no inverse for %s" % kind)
+        if trace is not None:
+            trace.append((kind, idx, z))
+    if halves and stop is None:
+        raise ValueError("%d split halves left over" % len(halves))
     return z
+
+
+def flow_inverse_layers(ops, params, z, upto=None):
+    """Per-layer `reverse` chain (flowsequential.py:32-39) over the invertible, context-free layers.
+    SplitPrior/Augment boundaries are handled by the caller here (see `flow_inverse` for the whole program), so `ops`
+    must not contain them."""
+    ops = ops[:upto]
+    for op in ops:
+        if op[0] in ("split", "augment"):
+            raise ValueError("no inverse for %s" % op[0])
+    return flow_inverse(ops, params, z)
+
+
+def inverse_problem(ops, x, trace):
+    """The exact inverse problem a `flow_forward(ops, params, x, ..., trace=trace)` run poses: returns
+    (z, halves, inputs) - the final latent, the split-off channel halves in forward order (what `flow_inverse` takes) and
+    the len(ops) + 1 tensors along the flow: inputs[i] ENTERED ops[i] and inputs[i + 1] left it (inputs[0] is x,
+    inputs[-1] is z).  In exact arithmetic flow_inverse(ops, params, z, halves) walks back through exactly these tensors."""
+    assert len(trace) == len(ops) and all(t[0] == o[0] and t[1] == o[1] for t, o in zip(trace, ops))
+    inputs = [x] + [t[2] for t in trace]
+    halves = [inputs[i][:, inputs[i].shape[1] // 2:] for i, o in enumerate(ops) if o[0] == "split"]
+    return inputs[-1], halves, inputs
 
 
 def bits_per_dim(logp, dims):

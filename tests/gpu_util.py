@@ -1,4 +1,5 @@
 """Helpers for the -m gpu tests: build contextflow_amd models from the golden fixtures."""
+import contextlib
 import ctypes
 
 import numpy as np
@@ -25,6 +26,28 @@ def set_noise(model, u, eps, dev=DEV):
             m.dist.fixed_noise = None if u is None else u.to(dev)
         if isinstance(m, cfa.layers.Augment):
             m.distribution.fixed_noise = eps.pop(0).to(dev) if eps else None
+
+
+@contextlib.contextmanager
+def set_split_draws(model, halves, dev=DEV):
+    """Within the block every SplitPrior.reverse of `model` concatenates the given split-off half instead of a fresh draw
+    from its prior: `halves` in forward order, one (B, C/2, H, W) tensor per SplitPrior.  Test side only: `dist.sample` is
+    shadowed on the instance and the shadow is removed on the way out, whatever happened inside."""
+    splits = [m for m in model.sequence_modules if isinstance(m, cfa.layers.SplitPrior)]
+    assert len(splits) == len(halves), (len(splits), len(halves))
+    try:
+        for m, h in zip(splits, halves):
+            h = h.to(dev).float().contiguous()
+
+            def draw(n_samples, context=None, need_log_prob=True, _h=h):
+                assert n_samples == _h.shape[0], (n_samples, tuple(_h.shape))
+                return _h, None
+            assert "sample" not in m.dist.__dict__
+            m.dist.sample = draw
+        yield
+    finally:
+        for m in splits:
+            m.dist.__dict__.pop("sample", None)
 
 
 def fused_step_debug(x, conv, act, cpl, squeeze=False, variant=0):

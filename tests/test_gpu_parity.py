@@ -665,7 +665,7 @@ def _full_size_checks(model, name, B, ops, params, x, u, eps, g):
     # round 3's fused-vs-layers self-comparison at 2 x the bar: two fp32 evaluations that each sit within the bar of the exact
     # answer are within twice the bar of each other and no closer in general - on 4096 SMAP samples the reference's own fp32
     # arithmetic is 7.8e-6 from its fp64 run on the worst sample (rms 8.9e-7), the one-kernel steps 5.3e-6 (row-split) and
-    # 8.2e-6 (wave), the layer kernel 7.4e-6, all with the same rms (profiles/r4_vit_accuracy.txt): the tail belongs to the
+    # 8.2e-6 (wave), the layer kernel 7.4e-6, all with the same rms (profiles/r4_vit_step_wave.md, section 3): the tail belongs to the
     # samples with |logp| ~ 1500 nats, where one ulp of logp is already 9e-7 bits/dim.
     p64 = {k: (v.double() if v.is_floating_point() else v) for k, v in params.items()}
     _, ref64 = fo.flow_forward(ops, p64, x.double(), None if u is None else u.double(), [eps[0].double()])
@@ -755,7 +755,10 @@ def test_spline_activation(L, tag, indiv):
 
 @pytest.mark.parametrize("C,H,W,B", [(16, 16, 16, 3), (32, 8, 8, 5), (64, 4, 4, 21), (8, 16, 16, 2)])
 def test_fused_inverse_step(L, C, H, W, B):
-    """cf_flow_step_inv against the oracle's layer inverses, and forward(inverse(z)) == z through the fused pair."""
+    """cf_flow_step_inv against the oracle's layer inverses, and forward(inverse(z)) == z through the fused pair.
+    A smoke-sized check: 2 to 21 samples, Gaussian z, near-identity parameters, the fp32 oracle at 3e-5 of scale.  It does not
+    cover production batches and their partly filled last workgroup, a batch-strided z, the direct form of the conditioner or
+    trained-like parameters: tests/test_sampling.py holds the kernel to 1e-5 of scale against fp64 on all of those."""
     import contextflow_amd as cfa
     torch.manual_seed(C + B)
     conv, act, cpl = L.Conv1x1((C, H, W)), L.ActNorm((C, H, W)), L.Coupling(C, kernel_size=(3, 3), padding=(1, 1))

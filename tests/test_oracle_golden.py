@@ -117,10 +117,11 @@ def test_inverse_mnist():
         if k.startswith("param:"):
             params[k[6:]] = torch.from_numpy(v)
     z = torch.from_numpy(fx["z"])
-    # layers after the Augment (index 4): reverse chain; Augment.reverse drops the noise channel
-    h = fo.flow_inverse_layers(ops[5:], params, z)
-    h = h[:, :1]
-    h = fo.flow_inverse_layers(ops[:4], params, h)
+    # the whole reverse chain; Augment.reverse (index 4) drops the noise channel
+    h = fo.flow_inverse(ops, params, z)
+    # ... and the same numbers through the layer-only entry point, the Augment handled by hand
+    h2 = fo.flow_inverse_layers(ops[5:], params, z)
+    assert torch.equal(h, fo.flow_inverse_layers(ops[:4], params, h2[:, :1]))
     ref = torch.from_numpy(fx["x"])
     # floor() of the dequantisation makes this integer-valued: allow a flip only at exact boundaries
     assert (h - ref).abs().max() <= 1.0 and (h != ref).float().mean() < 2e-3
