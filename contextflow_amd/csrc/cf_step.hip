@@ -26,6 +26,22 @@
 
 namespace {
 
+// host: the arguments of one forward-step launch, whichever kernel family runs it (sq: the step sits behind a Squeeze((2,2)),
+// dbg: per-phase dumps of the test hook, sb: per-sample bias of the specialist coupling, tp: the training tape)
+struct StepArgs {
+    const float* x;
+    float* z;
+    float* ldj;
+    const float* ws;
+    int B;
+    int64_t xbs;
+    bool sq;
+    hipStream_t s;
+    float* dbg = nullptr;
+    const float* sb = nullptr;
+    StepTape tp = kNoTape;
+};
+
 // ---- weight packing (cf_flow_step_prepare) ---------------------------------------------------------
 // A fragment of k-step s, row tile rt, lane l: A[row = rt*32 + (l&31)][k = 2s + (l>>5)]; 4 k-steps
 // per float4: element ((g*RT + rt)*64 + l)*4 + e holds k-step 4g+e.
@@ -668,16 +684,20 @@ __global__ __launch_bounds__(256, (G::WINO && G::C == 16) ? CF_G16W_MINW : G::MI
         flow_step_small_body<G, false>(z, z, ldj_acc, wc.ws[st], B, (int64_t)G::C * G::HW, nullptr, kNoTape);
     }
 }
-template <class G, bool SQ>
-int launch_step_small_chain(const float* x, float* z, float* ldj, const WsChain& wc, int n, int B, int64_t xbs, hipStream_t s) {
-    k_flow_step_small_chain<G, SQ><<<dim3(B), dim3(256), (size_t)G::LDS_FLOATS * sizeof(float), s>>>(x, z, ldj, wc, n, B, xbs);
+// (the launch helpers take the squeeze flag at run time: a.sq picks the SQ instantiation)
+template <class G>
+int launch_step_small_chain(const StepArgs& a, const WsChain& wc, int n) {
+    const auto k = a.sq ? k_flow_step_small_chain<G, true> : k_flow_step_small_chain<G, false>;
+    k<<<dim3(a.B), dim3(256), (size_t)G::LDS_FLOATS * sizeof(float), a.s>>>(a.x, a.z, a.ldj, wc, n, a.B, a.xbs);
     return 0;
 }
 
-template <class G, bool SQ, bool DBG = false, bool DUMP = false, int CTX = 0>
-int launch_step_small(const float* x, float* z, float* ldj, const float* ws, int B, int64_t xbs, hipStream_t s,
-                      float* dbg = nullptr, StepTape tp = kNoTape, const float* sb = nullptr) {
-    k_flow_step_small<G, SQ, DBG, DUMP, CTX><<<dim3(B), dim3(256), (size_t)G::LDS_FLOATS * sizeof(float), s>>>(x, z, ldj, ws, B, xbs, dbg, tp, sb);
+// the specialist coupling (CTX != 0) never sits behind a squeeze: only its SQ = false form is built
+template <class G, bool DBG = false, bool DUMP = false, int CTX = 0>
+int launch_step_small(const StepArgs& a) {
+    auto k = k_flow_step_small<G, false, DBG, DUMP, CTX>;
+    if constexpr (CTX == 0) { if (a.sq) k = k_flow_step_small<G, true, DBG, DUMP, CTX>; }
+    k<<<dim3(a.B), dim3(256), (size_t)G::LDS_FLOATS * sizeof(float), a.s>>>(a.x, a.z, a.ldj, a.ws, a.B, a.xbs, a.dbg, a.tp, a.sb);
     return 0;
 }
 
@@ -969,27 +989,23 @@ __global__ __launch_bounds__(256 * KS) void k_flow_step_rs_chain(const float* x,
         flow_step_rs_body<G, NPT, false, false, KS>(z, z, ldj_acc, wc.ws[st], B, (int64_t)G::C * G::HW);
     }
 }
-template <class G, int NPT, bool SQ>
-int launch_step_rs_chain(const float* x, float* z, float* ldj, const WsChain& wc, int n, int B, int64_t xbs, hipStream_t s) {
+template <class G, int NPT>
+int launch_step_rs_chain(const StepArgs& a, const WsChain& wc, int n) {
     constexpr int SPWR = 32 * NPT / G::HW;
-    k_flow_step_rs_chain<G, NPT, SQ, 2><<<dim3((B + SPWR - 1) / SPWR), dim3(512), 0, s>>>(x, z, ldj, wc, n, B, xbs);
+    const auto k = a.sq ? k_flow_step_rs_chain<G, NPT, true, 2> : k_flow_step_rs_chain<G, NPT, false, 2>;
+    k<<<dim3((a.B + SPWR - 1) / SPWR), dim3(512), 0, a.s>>>(a.x, a.z, a.ldj, wc, n, a.B, a.xbs);
     return 0;
 }
 
-template <class G, int NPT, bool SQ, bool DUMP = false>
-int launch_step_rs(const float* x, float* z, float* ldj, const float* ws, int B, int64_t xbs, hipStream_t s, StepTape tp = kNoTape) {
+template <class G, int NPT, bool DUMP = false>
+int launch_step_rs(const StepArgs& a) {
     constexpr int SPWR = 32 * NPT / G::HW;
     constexpr int KS = 2;
-    k_flow_step_rs<G, NPT, SQ, DUMP, KS><<<dim3((B + SPWR - 1) / SPWR), dim3(256 * KS), 0, s>>>(x, z, ldj, ws, B, xbs, tp);
+    const auto k = a.sq ? k_flow_step_rs<G, NPT, true, DUMP, KS> : k_flow_step_rs<G, NPT, false, DUMP, KS>;
+    k<<<dim3((a.B + SPWR - 1) / SPWR), dim3(256 * KS), 0, a.s>>>(a.x, a.z, a.ldj, a.ws, a.B, a.xbs, a.tp);
     return 0;
 }
 
-#ifndef CF_RS_MAXB_C64
-#define CF_RS_MAXB_C64 1024          // evaluation forward of the 4x4 level: row-split / one-sample kernels up to here, Winograd above
-#endif
-#ifndef CF_RS16_MAXB
-#define CF_RS16_MAXB 1024
-#endif
 // ---- the 4x4 level at small batches: ONE sample per workgroup on 16-column tiles -------------------------------------------
 // tools/dev/rs_ticks.py: at a batch of 256 the row-split kernel above spends 45.6 K of its 65 K cycles in the 3x3 - against
 // 36.9 K of pure MFMA time: the 2 304 MFMAs of a workgroup's 3x3 (2 samples = 32 pixel columns of a 32x32x2 tile) share the
@@ -1183,6 +1199,18 @@ __global__ __launch_bounds__(256) void k_flow_step_rs16_chain(const float* x, fl
         flow_step_rs16_body<G, false>(z, z, ldj_acc, wc.ws[st], B, (int64_t)G::C * G::HW);
     }
 }
+template <class G>
+int launch_step_rs16_chain(const StepArgs& a, const WsChain& wc, int n) {
+    const auto k = a.sq ? k_flow_step_rs16_chain<G, true> : k_flow_step_rs16_chain<G, false>;
+    k<<<dim3(a.B), dim3(256), 0, a.s>>>(a.x, a.z, a.ldj, wc, n, a.B, a.xbs);
+    return 0;
+}
+template <class G, bool DUMP = false>
+int launch_step_rs16(const StepArgs& a) {
+    const auto k = a.sq ? k_flow_step_rs16<G, true, DUMP> : k_flow_step_rs16<G, false, DUMP>;
+    k<<<dim3(a.B), dim3(256), 0, a.s>>>(a.x, a.z, a.ldj, a.ws, a.B, a.xbs, a.tp);
+    return 0;
+}
 
 extern "C" int cf_slogdet_inverse_batch(int n, const float* const* Wm, int C, float* const* logabsdet, float* const* inv, cf_stream_t stream);
 
@@ -1200,17 +1228,23 @@ int launch_prepare(const StepPackBatch& pb, int n, float* const* winv, hipStream
     return 0;
 }
 
-template <class G, bool SQ, int CTX = 0, bool DUMP = false, bool DBG = false>
-int launch_step(const float* x, float* z, float* ldj, const float* ws, int B, int64_t xbs, float* dbg, int flags,
-                hipStream_t s, const float* sb = nullptr, StepTape tp = kNoTape) {
+template <class G, bool SQ, int CTX, bool DUMP, bool DBG>
+int launch_step_sq(const StepArgs& a) {
     constexpr size_t lds_bytes = (size_t)G::LDS_FLOATS * sizeof(float);
     if (lds_bytes > 64 * 1024) {          // one-time opt-in to > 64 KiB of dynamic LDS (immutable afterwards)
         static std::atomic<uint64_t> raised{0};
         if (int rc_ = cf_raise_dynamic_lds((const void*)k_flow_step<G, SQ, CTX, DUMP, DBG>, 160 * 1024, raised, __func__)) return rc_;
     }
-    const int grid = (B + G::SPW - 1) / G::SPW;
-    k_flow_step<G, SQ, CTX, DUMP, DBG><<<dim3(grid), dim3(256), lds_bytes, s>>>(x, z, ldj, ws, B, xbs, dbg, flags, sb, tp);
+    const int grid = (a.B + G::SPW - 1) / G::SPW;
+    // (the kernel's `flags` argument is unused: 0)
+    k_flow_step<G, SQ, CTX, DUMP, DBG><<<dim3(grid), dim3(256), lds_bytes, a.s>>>(a.x, a.z, a.ldj, a.ws, a.B, a.xbs, a.dbg, 0, a.sb, a.tp);
     return 0;
+}
+// the specialist coupling (CTX != 0) never sits behind a squeeze: only its SQ = false form is built
+template <class G, int CTX = 0, bool DUMP = false, bool DBG = false>
+int launch_step(const StepArgs& a) {
+    if constexpr (CTX == 0) { if (a.sq) return launch_step_sq<G, true, CTX, DUMP, DBG>(a); }
+    return launch_step_sq<G, false, CTX, DUMP, DBG>(a);
 }
 
 // ---- inverse step: x = Conv1x1^-1(ActNorm^-1(Coupling^-1(z)))   (coupling.py:68-73, actnorm.py:78, conv1x1.py:72)
@@ -1380,8 +1414,238 @@ static bool wino24_8x8_enabled() {
     static const bool v = [] { const char* e = getenv("CONTEXTFLOW_WINO24_8X8"); return !(e && e[0] == '0'); }();
     return v && wino24_enabled();
 }
-// smallest batch of the 8x8 level's F(2x4) form: 512 workgroups = one full round of 2 per CU, as at 4x4
+
+// ---- dispatch: the ONE place that says which kernel runs a step ---------------------------------------------------------
+// A kernel family with its geometry, one value per pair the library launches outside the test hook's alternates.
+enum class Kernel {
+    None,
+    Small_G8s, Small_G16s, Small_G8w, Small_G16w, Small_G16wb, Small_G16db,                                        // k_flow_step_small
+    Step_G8, Step_G16, Step_G32, Step_G32v2, Step_G32w, Step_G32w24, Step_G64, Step_G64v2, Step_G64w2, Step_G64w24,   // k_flow_step
+    Rs_G32,                                                                                                        // k_flow_step_rs<.., 2>
+    Rs16_G64,                                                                                                      // k_flow_step_rs16
+    Inv_G8, Inv_G8w, Inv_G16, Inv_G16w, Inv_G32, Inv_G32w, Inv_G64, Inv_G64w2,                                     // k_flow_step_inv
+};
+// CtxDirect: cf_flow_step_fwd_ctx with mode | 4; Chain: cf_flow_step_fwd_chain (the kernel whose chained form runs)
+enum class Pass { Eval, Taped, Ctx, CtxDirect, CtxTaped, Chain, Inverse };
+
+// Batch thresholds.  Small batches are latency-bound by the serial work of ONE workgroup (a launch of < 256 workgroups leaves CUs
+// idle anyway): below these, the geometry with half the samples per workgroup (same packed-weight workspace) ...
+constexpr int kFullMinB8x8 = 256 * G32::SPW;         // (also where the 8x8 level's 3x3 takes the Winograd F(2x2, 3x3) form)
+constexpr int kFullMinB4x4 = 256 * G64::SPW;
+// ... 4x4: 8 samples per workgroup, rows split over wave pairs (F(2x2)) / over all four waves (F(2x4), 24 instead of 32 products per 8 pixels)
+constexpr int kWinoMinB4x4 = 256 * G64w2::SPW;
+// smallest batch of the 8x8 level's F(2x4) form: 512 workgroups = one full round of 2 per CU, as at 4x4 (below: F(2x2), G32w)
 constexpr int kW24MinB8x8 = 512 * G32w24::SPW;
+// very small batches: the row-split kernel (a quarter of the serial chain per workgroup, 4x the workgroups)
+constexpr int kRsMaxB8x8 = 512;
+// 4x4: one sample per workgroup on 16-column tiles (twice the workgroups of the row-split kernel) up to here, Winograd above
+constexpr int kRs16MaxB4x4 = 1024;
+// 16x16 images: chained launches (cf_flow_step_fwd_chain) up to here; CONTEXTFLOW_BF16_SPLIT=2, the direct bf16-piece form, from
+// here - below, the chained launches of the fp32 form run
+constexpr int kChainMaxB16x16 = 1024;
+
+// largest batch cf_flow_step_fwd_chain takes: the range in which a step is one of the small-batch kernels anyway
+static int chain_max_batch(int sid) {
+    switch (sid) {
+        case 0: case 1: return direct_conv_only() ? 0 : kChainMaxB16x16;
+        case 2: return kRsMaxB8x8;
+        case 3: return kRs16MaxB4x4;
+    }
+    return 0;
+}
+
+// The kernel of one step.  Winograd F(2x2,3x3) form of the 3x3 (winograd_phase2): 40 instead of 80 C^2 HW multiply-adds per sample
+// and step; CONTEXTFLOW_DIRECT_CONV=1 keeps the direct form (A/B measurements, tools/step_bench.py), and so does CtxDirect - the
+// TRAINING forward under contextflow, whose backward (cf_flow_step_bwd_ctx) rebuilds the conditioner in that form.
+static Kernel select(Pass pass, int sid, int B) {
+    const bool direct = direct_conv_only() || pass == Pass::CtxDirect;
+    const bool eval = pass == Pass::Eval, ctx = pass == Pass::Ctx || pass == Pass::CtxDirect;
+    if (pass == Pass::Inverse)           // the conditioner is the forward's: Winograd form of its 3x3 at every batch size
+        switch (sid) {
+            case 0: return direct ? Kernel::Inv_G8 : Kernel::Inv_G8w;
+            case 1: return direct ? Kernel::Inv_G16 : Kernel::Inv_G16w;
+            case 2: return direct ? Kernel::Inv_G32 : Kernel::Inv_G32w;
+            case 3: return direct ? Kernel::Inv_G64 : Kernel::Inv_G64w2;
+            default: return Kernel::None;
+        }
+    if (pass == Pass::CtxTaped)          // (its backward is cf_flow_step_bwd_taped: direct, one geometry per shape)
+        switch (sid) {
+            case 0: return Kernel::Step_G8;
+            case 1: return Kernel::Step_G16;
+            case 2: return Kernel::Step_G32;
+            case 3: return Kernel::Step_G64;
+            default: return Kernel::None;
+        }
+    if (pass == Pass::Chain && B > chain_max_batch(sid)) return Kernel::None;
+    switch (sid) {
+        case 0:                          // mnist's C = 8 level, 16x16 images: k_flow_step_small; Winograd in the evaluation forward only
+            if (ctx) return Kernel::Step_G8;
+            return (pass != Pass::Taped && !direct) ? Kernel::Small_G8w : Kernel::Small_G8s;
+        case 1:                          // 16x16 images: k_flow_step_small, one sample per workgroup, Winograd at every batch size (taped: h1
+                                         // reaches the tape from the accumulators there, its LDS plane is in the parity-split order)
+            if (direct) return ctx ? Kernel::Step_G16 : Kernel::Small_G16s;
+            // CONTEXTFLOW_BF16_SPLIT=1 (off by default): the Winograd-domain products as bf16-piece MFMAs; 2: the direct bf16-piece form
+            if (eval && bf16_split_mode() == 1) return Kernel::Small_G16wb;
+            if (eval && bf16_split_mode() == 2 && B >= kChainMaxB16x16) return Kernel::Small_G16db;
+            return Kernel::Small_G16w;
+        case 2:
+            if (!ctx && B <= kRsMaxB8x8) return Kernel::Rs_G32;
+            if (B < kFullMinB8x8) return ctx ? Kernel::Step_G32 : Kernel::Step_G32v2;
+            if (direct) return Kernel::Step_G32;
+            if (eval && wino24_8x8_enabled() && B >= kW24MinB8x8) return Kernel::Step_G32w24;
+            return Kernel::Step_G32w;
+        case 3:
+            if (!ctx && B <= kRs16MaxB4x4) return Kernel::Rs16_G64;      // (taped: one sample per workgroup, as the evaluation forward)
+            if (!direct && B >= kWinoMinB4x4) return (eval && wino24_enabled()) ? Kernel::Step_G64w24 : Kernel::Step_G64w2;
+            return (!ctx && B < kFullMinB4x4) ? Kernel::Step_G64v2 : Kernel::Step_G64;
+    }
+    return Kernel::None;
+}
+
+// Multiply-adds per pixel and C^2 of a kernel's step, from its geometry's own traits: the direct form runs C^2 (Conv1x1) + C^2 +
+// 36 C^2 + 2 C^2 = 40 C^2, the Winograd form of the 3x3 runs 16 instead of 36 C^2 (F(2x2, 3x3)) or 12 C^2 (F(2x4, 3x3)).  The
+// bf16-piece forms of the 16x16 level (BF16S, DBF: off by default) count as the fp32 Winograd form they stand in for, as they
+// always have - their products run on another pipe, and the roofline these counts feed is the fp32 one.
+template <class G> constexpr int step_macs_c2hw() { return G::W24 ? 16 : (G::WINO || G::BF16S || G::DBF) ? 20 : 40; }
+static int step_macs_c2hw(Kernel k) {
+    switch (k) {
+        case Kernel::None: return 0;
+        case Kernel::Small_G8s: return step_macs_c2hw<G8s>();
+        case Kernel::Small_G16s: return step_macs_c2hw<G16s>();
+        case Kernel::Small_G8w: case Kernel::Inv_G8w: return step_macs_c2hw<G8w>();
+        case Kernel::Small_G16w: case Kernel::Inv_G16w: return step_macs_c2hw<G16w>();
+        case Kernel::Small_G16wb: return step_macs_c2hw<G16wb>();
+        case Kernel::Small_G16db: return step_macs_c2hw<G16db>();
+        case Kernel::Step_G8: case Kernel::Inv_G8: return step_macs_c2hw<G8>();
+        case Kernel::Step_G16: case Kernel::Inv_G16: return step_macs_c2hw<G16>();
+        case Kernel::Step_G32: case Kernel::Rs_G32: case Kernel::Inv_G32: return step_macs_c2hw<G32>();
+        case Kernel::Step_G32v2: return step_macs_c2hw<G32v2>();
+        case Kernel::Step_G32w: case Kernel::Inv_G32w: return step_macs_c2hw<G32w>();
+        case Kernel::Step_G32w24: return step_macs_c2hw<G32w24>();
+        case Kernel::Step_G64: case Kernel::Rs16_G64: case Kernel::Inv_G64: return step_macs_c2hw<G64>();
+        case Kernel::Step_G64v2: return step_macs_c2hw<G64v2>();
+        case Kernel::Step_G64w2: case Kernel::Inv_G64w2: return step_macs_c2hw<G64w2>();
+        case Kernel::Step_G64w24: return step_macs_c2hw<G64w24>();
+    }
+    return 0;
+}
+
+// Launch lists, one per pass: exactly the template combinations the library builds (a 160 KB k_flow_step instantiation is
+// minutes of compile time).  A kernel that a pass does not list is a bug in select().
+static int not_built(const char* fn, Kernel k) {
+    cf_set_error("%s: kernel %d is not built for this pass", fn, (int)k);
+    return CF_ERR_UNSUPPORTED;
+}
+static int launch_fwd(Kernel k, const StepArgs& a) {         // evaluation forward, and the test hook without dumps
+    switch (k) {
+        case Kernel::Small_G8s: return launch_step_small<G8s>(a);
+        case Kernel::Small_G16s: return launch_step_small<G16s>(a);
+        case Kernel::Small_G8w: return launch_step_small<G8w>(a);
+        case Kernel::Small_G16w: return launch_step_small<G16w>(a);
+        case Kernel::Small_G16wb: return launch_step_small<G16wb>(a);
+        case Kernel::Small_G16db: return launch_step_small<G16db>(a);
+        case Kernel::Step_G8: return launch_step<G8>(a);
+        case Kernel::Step_G16: return launch_step<G16>(a);
+        case Kernel::Step_G32: return launch_step<G32>(a);
+        case Kernel::Step_G32v2: return launch_step<G32v2>(a);
+        case Kernel::Step_G32w: return launch_step<G32w>(a);
+        case Kernel::Step_G32w24: return launch_step<G32w24>(a);
+        case Kernel::Step_G64: return launch_step<G64>(a);
+        case Kernel::Step_G64v2: return launch_step<G64v2>(a);
+        case Kernel::Step_G64w2: return launch_step<G64w2>(a);
+        case Kernel::Step_G64w24: return launch_step<G64w24>(a);
+        case Kernel::Rs_G32: return launch_step_rs<G32, 2>(a);
+        case Kernel::Rs16_G64: return launch_step_rs16<G64>(a);
+        default: return not_built(__func__, k);
+    }
+}
+static int launch_fwd_dumps(Kernel k, const StepArgs& a) {   // per-phase dumps (tests): the default geometry of each shape, and k_flow_step_small
+    switch (k) {
+        case Kernel::Small_G8s: return launch_step_small<G8s, true>(a);
+        case Kernel::Small_G16s: return launch_step_small<G16s, true>(a);
+        case Kernel::Step_G8: return launch_step<G8, 0, false, true>(a);
+        case Kernel::Step_G16: return launch_step<G16, 0, false, true>(a);
+        case Kernel::Step_G32: return launch_step<G32, 0, false, true>(a);
+        case Kernel::Step_G64: return launch_step<G64, 0, false, true>(a);
+        default: return not_built(__func__, k);
+    }
+}
+static int launch_fwd_taped(Kernel k, const StepArgs& a) {
+    switch (k) {
+        case Kernel::Small_G8s: return launch_step_small<G8s, false, true>(a);
+        case Kernel::Small_G16s: return launch_step_small<G16s, false, true>(a);
+        case Kernel::Small_G16w: return launch_step_small<G16w, false, true>(a);
+        case Kernel::Step_G32: return launch_step<G32, 0, true>(a);
+        case Kernel::Step_G32v2: return launch_step<G32v2, 0, true>(a);
+        case Kernel::Step_G32w: return launch_step<G32w, 0, true>(a);
+        case Kernel::Step_G64: return launch_step<G64, 0, true>(a);
+        case Kernel::Step_G64v2: return launch_step<G64v2, 0, true>(a);
+        case Kernel::Step_G64w2: return launch_step<G64w2, 0, true>(a);
+        case Kernel::Rs_G32: return launch_step_rs<G32, 2, true>(a);
+        case Kernel::Rs16_G64: return launch_step_rs16<G64, true>(a);
+        default: return not_built(__func__, k);
+    }
+}
+template <int CTX>
+static int launch_fwd_ctx(Kernel k, const StepArgs& a) {
+    switch (k) {
+        case Kernel::Small_G16w: return launch_step_small<G16w, false, false, CTX>(a);
+        case Kernel::Step_G8: return launch_step<G8, CTX>(a);
+        case Kernel::Step_G16: return launch_step<G16, CTX>(a);
+        case Kernel::Step_G32: return launch_step<G32, CTX>(a);
+        case Kernel::Step_G32w: return launch_step<G32w, CTX>(a);
+        case Kernel::Step_G64: return launch_step<G64, CTX>(a);
+        case Kernel::Step_G64w2: return launch_step<G64w2, CTX>(a);
+        default: return not_built(__func__, k);
+    }
+}
+static int launch_fwd_ctx_taped(Kernel k, const StepArgs& a) {
+    switch (k) {
+        case Kernel::Step_G8: return launch_step<G8, 2, true>(a);
+        case Kernel::Step_G16: return launch_step<G16, 2, true>(a);
+        case Kernel::Step_G32: return launch_step<G32, 2, true>(a);
+        case Kernel::Step_G64: return launch_step<G64, 2, true>(a);
+        default: return not_built(__func__, k);
+    }
+}
+static int launch_fwd_chain(Kernel k, const StepArgs& a, const WsChain& wc, int n) {      // the chained forms of the small-batch kernels
+    switch (k) {
+        case Kernel::Small_G8w: return launch_step_small_chain<G8w>(a, wc, n);
+        case Kernel::Small_G16w: return launch_step_small_chain<G16w>(a, wc, n);
+        case Kernel::Rs_G32: return launch_step_rs_chain<G32, 2>(a, wc, n);
+        case Kernel::Rs16_G64: return launch_step_rs16_chain<G64>(a, wc, n);
+        default: return not_built(__func__, k);
+    }
+}
+static int launch_inv(Kernel k, const float* z, float* x, const float* ws, const float* wsi, int B, int64_t zbs, int x_unsq, hipStream_t s) {
+    switch (k) {
+        case Kernel::Inv_G8: return launch_step_inv<G8>(z, x, ws, wsi, B, zbs, x_unsq, s);
+        case Kernel::Inv_G8w: return launch_step_inv<G8w>(z, x, ws, wsi, B, zbs, x_unsq, s);
+        case Kernel::Inv_G16: return launch_step_inv<G16>(z, x, ws, wsi, B, zbs, x_unsq, s);
+        case Kernel::Inv_G16w: return launch_step_inv<G16w>(z, x, ws, wsi, B, zbs, x_unsq, s);
+        case Kernel::Inv_G32: return launch_step_inv<G32>(z, x, ws, wsi, B, zbs, x_unsq, s);
+        case Kernel::Inv_G32w: return launch_step_inv<G32w>(z, x, ws, wsi, B, zbs, x_unsq, s);
+        case Kernel::Inv_G64: return launch_step_inv<G64>(z, x, ws, wsi, B, zbs, x_unsq, s);
+        case Kernel::Inv_G64w2: return launch_step_inv<G64w2>(z, x, ws, wsi, B, zbs, x_unsq, s);
+        default: return not_built(__func__, k);
+    }
+}
+static int unsupported_shape(const char* fn, int C, int H, int W) {
+    cf_set_error("%s: shape (%d,%d,%d) unsupported", fn, C, H, W);
+    return CF_ERR_UNSUPPORTED;
+}
+
+// test hook: (shape, variant = flags bits 16..19) -> kernel.  0: the default geometry of the shape in k_flow_step (the only one
+// with per-phase dumps besides 3), 2: half the samples per workgroup, 3: k_flow_step_small in the direct form, 4: Winograd
+// F(2x2, 3x3), 5: ... row-split at 128 pixels per workgroup, 6: the bf16-piece form of 4 at 16x16 / Winograd F(2x4, 3x3) at 8x8
+// and 4x4, 7: direct 3x3 on bf16 pieces.  (1 was an operand-pipeline alternate of each shape: gone with its geometries.)
+constexpr int kDebugVariants = 8;
+constexpr Kernel kDebugKernel[4][kDebugVariants] = {
+    {Kernel::Step_G8, Kernel::None, Kernel::None, Kernel::Small_G8s, Kernel::Small_G8w, Kernel::None, Kernel::None, Kernel::None},
+    {Kernel::Step_G16, Kernel::None, Kernel::None, Kernel::Small_G16s, Kernel::Small_G16w, Kernel::None, Kernel::Small_G16wb, Kernel::Small_G16db},
+    {Kernel::Step_G32, Kernel::None, Kernel::Step_G32v2, Kernel::None, Kernel::Step_G32w, Kernel::None, Kernel::Step_G32w24, Kernel::None},
+    {Kernel::Step_G64, Kernel::None, Kernel::Step_G64v2, Kernel::None, Kernel::None, Kernel::Step_G64w2, Kernel::Step_G64w24, Kernel::None},
+};
 
 extern "C" {
 
@@ -1477,140 +1741,50 @@ int cf_flow_step_inv(const float* z, float* x, const void* ws, const void* wsi, 
     if (B == 0) return 0;                       // empty batch: nothing to do (pointers may be null)
     CF_REQUIRE(z && x && ws && wsi && B >= 0 && z_bstride >= (int64_t)C * H * W && z_bstride % 4 == 0);
     CF_REQUIRE((reinterpret_cast<uintptr_t>(z) & 15) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0);
-    int rc;
-    const float* w = (const float*)ws;
-    const float* wi = (const float*)wsi;
-    switch (shape_id(C, H, W)) {
-        case 0: rc = direct_conv_only() ? launch_step_inv<G8>(z, x, w, wi, B, z_bstride, x_unsqueezed, cf_s(stream))
-                                        : launch_step_inv<G8w>(z, x, w, wi, B, z_bstride, x_unsqueezed, cf_s(stream)); break;
-        // the conditioner is the forward's: Winograd form of its 3x3 unless CONTEXTFLOW_DIRECT_CONV=1
-        case 1: rc = direct_conv_only() ? launch_step_inv<G16>(z, x, w, wi, B, z_bstride, x_unsqueezed, cf_s(stream))
-                                        : launch_step_inv<G16w>(z, x, w, wi, B, z_bstride, x_unsqueezed, cf_s(stream)); break;
-        case 2: rc = direct_conv_only() ? launch_step_inv<G32>(z, x, w, wi, B, z_bstride, x_unsqueezed, cf_s(stream))
-                                        : launch_step_inv<G32w>(z, x, w, wi, B, z_bstride, x_unsqueezed, cf_s(stream)); break;
-        case 3: rc = direct_conv_only() ? launch_step_inv<G64>(z, x, w, wi, B, z_bstride, x_unsqueezed, cf_s(stream))
-                                        : launch_step_inv<G64w2>(z, x, w, wi, B, z_bstride, x_unsqueezed, cf_s(stream)); break;
-        default: cf_set_error("cf_flow_step_inv: shape (%d,%d,%d) unsupported", C, H, W); return CF_ERR_UNSUPPORTED;
-    }
-    if (rc) return rc;
+    const Kernel k = select(Pass::Inverse, shape_id(C, H, W), B);
+    if (k == Kernel::None) return unsupported_shape(__func__, C, H, W);
+    if (int rc = launch_inv(k, z, x, (const float*)ws, (const float*)wsi, B, z_bstride, x_unsqueezed, cf_s(stream))) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }
 
-// test hook (not part of the public header): same as cf_flow_step_fwd plus per-phase dumps
+// test hook (not part of the public header): the step in the kernel of kDebugKernel, and per-phase dumps
 int cf_flow_step_fwd_debug(const float* x, float* z, float* ldj_acc, const void* ws, int B, int C, int H, int W,
                            int64_t x_bstride, int in_squeeze, float* dbg, int flags, cf_stream_t stream) {
     if (B == 0) return 0;                       // empty batch: nothing to do (pointers may be null)
     CF_REQUIRE(x && z && ldj_acc && ws && B >= 0 && x_bstride >= (int64_t)C * H * W);
     CF_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0 && x_bstride % 4 == 0);
-    if (B == 0) return 0;
-    const float* w = (const float*)ws;
-    int rc = 0;
-#define CF_STEP(G) rc = in_squeeze ? launch_step<G, true>(x, z, ldj_acc, w, B, x_bstride, dbg, flags, cf_s(stream)) \
-                                   : launch_step<G, false>(x, z, ldj_acc, w, B, x_bstride, dbg, flags, cf_s(stream))
-    const int variant = (flags >> 16) & 15;
-    if (dbg != nullptr && variant == 3 && shape_id(C, H, W) <= 1 && shape_id(C, H, W) >= 0) {     // dumps of k_flow_step_small
-        if (shape_id(C, H, W) == 0)
-            rc = in_squeeze ? launch_step_small<G8s, true, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream), dbg)
-                            : launch_step_small<G8s, false, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream), dbg);
-        else
-            rc = in_squeeze ? launch_step_small<G16s, true, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream), dbg)
-                            : launch_step_small<G16s, false, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream), dbg);
-        if (rc) return rc;
-        CF_LAUNCH_CHECK();
-        return 0;
+    const int sid = shape_id(C, H, W), variant = (flags >> 16) & 15;
+    const Kernel k = (sid >= 0 && variant < kDebugVariants) ? kDebugKernel[sid][variant] : Kernel::None;
+    if (k == Kernel::None) {
+        cf_set_error("cf_flow_step_fwd: shape (%d,%d,%d) variant %d unsupported", C, H, W, variant);
+        return CF_ERR_UNSUPPORTED;
     }
-    if (dbg != nullptr) {                  // per-phase dumps (tests): the default geometry of each shape only
-        CF_REQUIRE(variant == 0);
-#define CF_STEPD(G) rc = in_squeeze ? launch_step<G, true, 0, false, true>(x, z, ldj_acc, w, B, x_bstride, dbg, flags, cf_s(stream)) \
-                                    : launch_step<G, false, 0, false, true>(x, z, ldj_acc, w, B, x_bstride, dbg, flags, cf_s(stream))
-        switch (shape_id(C, H, W)) {
-            case 0: CF_STEPD(G8); break;
-            case 1: CF_STEPD(G16); break;
-            case 2: CF_STEPD(G32); break;
-            case 3: CF_STEPD(G64); break;
-            default: cf_set_error("cf_flow_step_fwd_debug: shape (%d,%d,%d) unsupported", C, H, W); return CF_ERR_UNSUPPORTED;
-        }
-#undef CF_STEPD
-        if (rc) return rc;
-        CF_LAUNCH_CHECK();
-        return 0;
-    }
-    switch (shape_id(C, H, W) * 8 + variant) {
-        case 0: CF_STEP(G8); break;
-        case 3: rc = in_squeeze ? launch_step_small<G8s, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream))
-                                : launch_step_small<G8s, false>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream)); break;
-        case 8: CF_STEP(G16); break;
-        case 9: CF_STEP(G16v1); break;
-        case 10: CF_STEP(G16v2); break;
-        case 11: rc = in_squeeze ? launch_step_small<G16s, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream))
-                                : launch_step_small<G16s, false>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream)); break;
-        case 16: CF_STEP(G32); break;
-        case 17: CF_STEP(G32v1); break;
-        case 18: CF_STEP(G32v2); break;
-        case 19: CF_STEP(G32v3); break;
-        case 24: CF_STEP(G64); break;
-        case 25: CF_STEP(G64v1); break;
-        case 26: CF_STEP(G64v2); break;
-        case 27: CF_STEP(G64v3); break;
-        case 4: rc = in_squeeze ? launch_step_small<G8w, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream))           // variant 4 at C = 8
-                               : launch_step_small<G8w, false>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream)); break;
-        case 14: rc = in_squeeze ? launch_step_small<G16wb, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream))        // variant 6: bf16-piece form of variant 4
-                                 : launch_step_small<G16wb, false>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream)); break;
-        case 15: rc = in_squeeze ? launch_step_small<G16db, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream))        // variant 7: direct 3x3 on bf16 pieces
-                                 : launch_step_small<G16db, false>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream)); break;
-        case 12: rc = in_squeeze ? launch_step_small<G16w, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream))         // variant 4:
-                                : launch_step_small<G16w, false>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream)); break;  // Winograd form of the 3x3
-        case 20: CF_STEP(G32w); break;
-        case 22: CF_STEP(G32w24); break;          // variant 6: the F(2x4, 3x3) form, two column tiles x two row halves
-        case 28: CF_STEP(G64w); break;
-        case 29: CF_STEP(G64w2); break;           // variant 5: row-split Winograd at 128 pixels per workgroup
-        case 30: CF_STEP(G64w24); break;          // variant 6: ... in the F(2x4, 3x3) form, the rows split over all four waves
-        default: cf_set_error("cf_flow_step_fwd: shape (%d,%d,%d) variant %d unsupported", C, H, W, variant); return CF_ERR_UNSUPPORTED;
-    }
-#undef CF_STEP
-    if (rc) return rc;
+    StepArgs a{x, z, ldj_acc, (const float*)ws, B, x_bstride, in_squeeze != 0, cf_s(stream)};
+    a.dbg = dbg;
+    if (int rc = dbg ? launch_fwd_dumps(k, a) : launch_fwd(k, a)) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }
-
 // n <= 4 consecutive flow steps of one shape in ONE launch, for the batch sizes at which a step is one of the small-batch
 // kernels anyway (cf_flow_step_chain_max_batch: 16x16 images up to 1 024 samples, 8x8 up to 512, 4x4 up to 1 024); ws: HOST array
 // of the n packed tables; in_squeeze applies to the first step.  z receives the output of the LAST step (the intermediate
 // activations live in z too: the steps after the first run in place).  Same numbers as n calls of cf_flow_step_fwd, bit for bit.
-int cf_flow_step_chain_max_batch(int C, int H, int W) {
-    switch (shape_id(C, H, W)) {
-        case 0: case 1: return direct_conv_only() ? 0 : 1024;
-        case 2: return 512;                                // k_flow_step_rs's range in cf_flow_step_fwd
-        case 3: return CF_RS16_MAXB < CF_RS_MAXB_C64 ? CF_RS16_MAXB : CF_RS_MAXB_C64;
-    }
-    return 0;
-}
+int cf_flow_step_chain_max_batch(int C, int H, int W) { return chain_max_batch(shape_id(C, H, W)); }
 
 int cf_flow_step_fwd_chain(const float* x, float* z, float* ldj_acc, const void* const* ws, int n, int B, int C, int H, int W,
                            int64_t x_bstride, int in_squeeze, cf_stream_t stream) {
     if (B == 0 || n == 0) return 0;
     CF_REQUIRE(x && z && ldj_acc && ws && n >= 1 && n <= kChain && B > 0 && x_bstride >= (int64_t)C * H * W);
     CF_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0 && x_bstride % 4 == 0);
-    const int sid = shape_id(C, H, W);
-    if (sid < 0 || B > cf_flow_step_chain_max_batch(C, H, W)) {
+    const Kernel k = select(Pass::Chain, shape_id(C, H, W), B);
+    if (k == Kernel::None) {
         cf_set_error("cf_flow_step_fwd_chain: shape (%d,%d,%d) at a batch of %d is not a chained case", C, H, W, B);
         return CF_ERR_UNSUPPORTED;
     }
     WsChain wc{};
     for (int i = 0; i < n; ++i) { CF_REQUIRE(ws[i]); wc.ws[i] = (const float*)ws[i]; }
-    hipStream_t s = cf_s(stream);
-    switch (sid) {
-        case 0: in_squeeze ? launch_step_small_chain<G8w, true>(x, z, ldj_acc, wc, n, B, x_bstride, s)
-                           : launch_step_small_chain<G8w, false>(x, z, ldj_acc, wc, n, B, x_bstride, s); break;
-        case 1: in_squeeze ? launch_step_small_chain<G16w, true>(x, z, ldj_acc, wc, n, B, x_bstride, s)
-                           : launch_step_small_chain<G16w, false>(x, z, ldj_acc, wc, n, B, x_bstride, s); break;
-        case 2: in_squeeze ? launch_step_rs_chain<G32, 2, true>(x, z, ldj_acc, wc, n, B, x_bstride, s)
-                           : launch_step_rs_chain<G32, 2, false>(x, z, ldj_acc, wc, n, B, x_bstride, s); break;
-        default:
-            if (in_squeeze) k_flow_step_rs16_chain<G64, true><<<dim3(B), dim3(256), 0, s>>>(x, z, ldj_acc, wc, n, B, x_bstride);
-            else k_flow_step_rs16_chain<G64, false><<<dim3(B), dim3(256), 0, s>>>(x, z, ldj_acc, wc, n, B, x_bstride);
-    }
+    if (int rc = launch_fwd_chain(k, StepArgs{x, z, ldj_acc, nullptr, B, x_bstride, in_squeeze != 0, cf_s(stream)}, wc, n)) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }
@@ -1624,65 +1798,26 @@ int cf_bf16_split(int on) {
 
 int cf_flow_step_fwd(const float* x, float* z, float* ldj_acc, const void* ws, int B, int C, int H, int W,
                      int64_t x_bstride, int in_squeeze, cf_stream_t stream) {
-    // Small batches are latency-bound by the serial work of ONE workgroup (a launch of < 256 workgroups leaves CUs
-    // idle anyway): pick the geometry with half the samples per workgroup (same packed-weight workspace).
-    int flags = 0;
-    const int sid = shape_id(C, H, W);
-    if ((sid == 2 && B < 256 * G32::SPW) || (sid == 3 && B < 256 * G64::SPW)) flags = 2 << 16;
-    if (sid == 0 || sid == 1) flags = 3 << 16;      // 16x16 images: k_flow_step_small
-    // Winograd F(2x2,3x3) form of the 3x3 (winograd_phase2): 40 instead of 80 C^2 HW multiply-adds per sample and step.
-    // CONTEXTFLOW_DIRECT_CONV=1 keeps the direct form (A/B measurements, tools/step_bench.py).
-    const bool direct_only = direct_conv_only();
-    if (!direct_only && (sid == 0 || sid == 1 || (sid == 2 && B >= 256 * G32::SPW))) flags = 4 << 16;
-    // 4x4: 8 samples per workgroup, rows split over wave pairs (F(2x2)) / over all four waves (F(2x4), 24 instead of 32 products per 8 pixels)
-    if (!direct_only && sid == 3 && B >= 256 * G64w2::SPW) flags = (wino24_enabled() ? 6 : 5) << 16;
-    // 8x8: the F(2x4) form from 2 048 samples (below: F(2x2), G32w)
-    if (!direct_only && sid == 2 && B >= kW24MinB8x8 && wino24_8x8_enabled()) flags = 6 << 16;
-    // CONTEXTFLOW_BF16_SPLIT=1 (off by default): the 16x16 level's Winograd-domain products as bf16-piece MFMAs (G16wb)
-    // (mode 2, the direct bf16-piece form: from 1024 samples per launch - below that the chained launches of the fp32 form run)
-    if (!direct_only && sid == 1 && bf16_split_mode() == 1) flags = 6 << 16;
-    if (!direct_only && sid == 1 && bf16_split_mode() == 2 && B >= 1024) flags = 7 << 16;
-    // very small batches: the row-split kernel (a quarter of the serial chain per workgroup, 4x the workgroups)
-    if ((sid == 2 && B <= 512) || (sid == 3 && B <= CF_RS_MAXB_C64)) {
-        CF_REQUIRE(x && z && ldj_acc && ws && B >= 0 && x_bstride >= (int64_t)C * H * W);
-        if (B == 0) return 0;
-        const float* w = (const float*)ws;
-        if (sid == 3 && B <= CF_RS16_MAXB) {   // 4x4: one sample per workgroup on 16-column tiles (twice the workgroups of the row-split kernel)
-            if (in_squeeze) k_flow_step_rs16<G64, true><<<dim3(B), dim3(256), 0, cf_s(stream)>>>(x, z, ldj_acc, w, B, x_bstride, kNoTape);
-            else k_flow_step_rs16<G64, false><<<dim3(B), dim3(256), 0, cf_s(stream)>>>(x, z, ldj_acc, w, B, x_bstride, kNoTape);
-            CF_LAUNCH_CHECK();
-            return 0;
-        }
-        if (sid == 2) { if (in_squeeze) launch_step_rs<G32, 2, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream));
-                        else launch_step_rs<G32, 2, false>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream)); }
-        else          { if (in_squeeze) launch_step_rs<G64, 1, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream));
-                        else launch_step_rs<G64, 1, false>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream)); }
-        CF_LAUNCH_CHECK();
-        return 0;
-    }
-    return cf_flow_step_fwd_debug(x, z, ldj_acc, ws, B, C, H, W, x_bstride, in_squeeze, nullptr, flags, stream);
+    if (B == 0) return 0;                       // empty batch: nothing to do (pointers may be null)
+    CF_REQUIRE(x && z && ldj_acc && ws && B >= 0 && x_bstride >= (int64_t)C * H * W);
+    CF_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0 && x_bstride % 4 == 0);
+    const Kernel k = select(Pass::Eval, shape_id(C, H, W), B);
+    if (k == Kernel::None) return unsupported_shape(__func__, C, H, W);
+    if (int rc = launch_fwd(k, StepArgs{x, z, ldj_acc, (const float*)ws, B, x_bstride, in_squeeze != 0, cf_s(stream)})) return rc;
+    CF_LAUNCH_CHECK();
+    return 0;
 }
 
 // Multiply-adds per sample the matrix pipe EXECUTES for one step at this batch size (bench.py's executed-flop roofline):
 // pass 0 = cf_flow_step_fwd, 1 = cf_flow_step_fwd_taped, 2 = cf_flow_step_bwd_taped (direct transposed 3x3), 3 = cf_flow_step_inv
-// (the forward's conditioner + W^-1 instead of W: the same count; Winograd form at every level).  The direct
-// form runs C^2 (Conv1x1) + C^2 + 36 C^2 + 2 C^2 = 40 C^2 per pixel; the Winograd form of the 3x3 runs 16 instead of 36
-// C^2 (F(2x2, 3x3)) or 12 C^2 (F(2x4, 3x3): the 4x4 and 8x8 levels' evaluation forward).  The conditions below restate the dispatch of
-// the two entry points above / below - change them together.
+// (the forward's conditioner + W^-1 instead of W: the same count; Winograd form at every level).  Passes 0, 1 and 3 are the
+// count of the kernel select() names for these arguments - the one the entry point launches.
 int64_t cf_flow_step_macs(int B, int C, int H, int W, int pass) {
     const int sid = shape_id(C, H, W);
     if (sid < 0 || pass < 0 || pass > 3) return 0;
-    const int64_t direct = 40ll * C * C * H * W, wino = 20ll * C * C * H * W, wino24 = 16ll * C * C * H * W;
-    if (pass == 2 || direct_conv_only()) return direct;
-    if (pass == 3) return wino;
-    if (sid == 3 && pass == 0 && wino24_enabled() && B >= 256 * G64w2::SPW) return wino24;
-    if (sid == 2 && pass == 0 && wino24_8x8_enabled() && B >= kW24MinB8x8) return wino24;
-    bool w;
-    if (sid == 0) w = pass == 0;                                  // mnist's C = 8 level: evaluation only
-    else if (sid == 1) w = true;                                  // 16x16, C = 16: every batch size
-    else if (sid == 2) w = B >= 256 * G32::SPW;
-    else w = B >= 256 * G64w2::SPW;
-    return w ? wino : direct;
+    const int per = pass == 2 ? step_macs_c2hw<G64>()         // (the backward's geometries are direct ones: any of them)
+                              : step_macs_c2hw(select(pass == 0 ? Pass::Eval : pass == 1 ? Pass::Taped : Pass::Inverse, sid, B));
+    return (int64_t)per * C * C * H * W;
 }
 
 // training forward: the same step, and the conditioner's intermediate planes y0 (B, C/2, H, W), h1, h2 (B, 2C, H, W;
@@ -1692,6 +1827,7 @@ int64_t cf_flow_step_tape_aux_bytes(int B, int C, int H, int W) {
     return shape_id(C, H, W) < 0 ? 0 : tape_aux_bytes(B, C, H, W);
 }
 
+// (small batches - the reference trains with 256 samples - take the small-batch kernels of the evaluation forward)
 int cf_flow_step_fwd_taped(const float* x, float* z, float* ldj_acc, const void* ws, float* t_y0, float* t_h1, float* t_h2,
                            void* t_aux, int B, int C, int H, int W, int64_t x_bstride, int in_squeeze, cf_stream_t stream) {
     if (B == 0) return 0;
@@ -1699,36 +1835,11 @@ int cf_flow_step_fwd_taped(const float* x, float* z, float* ldj_acc, const void*
     CF_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0 &&
                (reinterpret_cast<uintptr_t>(t_y0) & 15) == 0 && (reinterpret_cast<uintptr_t>(t_h1) & 15) == 0 &&
                (reinterpret_cast<uintptr_t>(t_h2) & 15) == 0 && (reinterpret_cast<uintptr_t>(t_aux) & 15) == 0);
-    const float* w = (const float*)ws;
-    const StepTape tp = make_tape(t_y0, t_h1, t_h2, t_aux, B, C, H, W);
-    const bool direct_only = direct_conv_only();
-    int rc = 0;
-#define CF_STEPT(G) rc = in_squeeze ? launch_step<G, true, 0, true>(x, z, ldj_acc, w, B, x_bstride, nullptr, 0, cf_s(stream), nullptr, tp) \
-                                    : launch_step<G, false, 0, true>(x, z, ldj_acc, w, B, x_bstride, nullptr, 0, cf_s(stream), nullptr, tp)
-    // small batches (the reference trains with 256 samples): the half-size workgroup geometry, as in cf_flow_step_fwd
-    switch (shape_id(C, H, W)) {
-        case 0: rc = in_squeeze ? launch_step_small<G8s, true, false, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream), nullptr, tp)
-                                : launch_step_small<G8s, false, false, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream), nullptr, tp); break;
-        // as in cf_flow_step_fwd: Winograd form of the 3x3 on 16x16 images and at saturating batches (h1 reaches the tape from
-        // the accumulators there, its LDS plane is in the parity-split order)
-        case 1: if (direct_only) rc = in_squeeze ? launch_step_small<G16s, true, false, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream), nullptr, tp)
-                                                 : launch_step_small<G16s, false, false, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream), nullptr, tp);
-                else rc = in_squeeze ? launch_step_small<G16w, true, false, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream), nullptr, tp)
-                                     : launch_step_small<G16w, false, false, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream), nullptr, tp);
-                break;
-        // very small batches: the row-split kernel, as in cf_flow_step_fwd (a quarter of the serial chain per workgroup)
-        case 2: if (B <= 512) rc = in_squeeze ? launch_step_rs<G32, 2, true, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream), tp)
-                                              : launch_step_rs<G32, 2, false, true>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream), tp);
-                else if (B < 256 * G32::SPW) CF_STEPT(G32v2); else if (direct_only) CF_STEPT(G32); else CF_STEPT(G32w); break;
-        case 3: if (B <= CF_RS16_MAXB) {    // one sample per workgroup, as the evaluation forward
-                    if (in_squeeze) k_flow_step_rs16<G64, true, true><<<dim3(B), dim3(256), 0, cf_s(stream)>>>(x, z, ldj_acc, w, B, x_bstride, tp);
-                    else k_flow_step_rs16<G64, false, true><<<dim3(B), dim3(256), 0, cf_s(stream)>>>(x, z, ldj_acc, w, B, x_bstride, tp);
-                }
-                else if (!direct_only && B >= 256 * G64w2::SPW) CF_STEPT(G64w2); else if (B < 256 * G64::SPW) CF_STEPT(G64v2); else CF_STEPT(G64); break;
-        default: cf_set_error("cf_flow_step_fwd_taped: shape (%d,%d,%d) unsupported", C, H, W); return CF_ERR_UNSUPPORTED;
-    }
-#undef CF_STEPT
-    if (rc) return rc;
+    const Kernel k = select(Pass::Taped, shape_id(C, H, W), B);
+    if (k == Kernel::None) return unsupported_shape(__func__, C, H, W);
+    StepArgs a{x, z, ldj_acc, (const float*)ws, B, x_bstride, in_squeeze != 0, cf_s(stream)};
+    a.tp = make_tape(t_y0, t_h1, t_h2, t_aux, B, C, H, W);
+    if (int rc = launch_fwd_taped(k, a)) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }
@@ -1737,30 +1848,19 @@ int cf_flow_step_fwd_taped(const float* x, float* z, float* ldj_acc, const void*
 // mode 1: sbias (B, C) added to the conditioner OUTPUT (contextflow); mode 2: sbias (B, 2C) added before the first ReLU
 // (CN(c) concatenated to the conditioner input).  The caller packs `ws` with cf_flow_step_prepare; with an identity
 // matrix / zero ActNorm there, the kernel is the Coupling layer alone (per-sample Conv1x1 / ActNorm run before it).
+// mode | 4: the direct form of the 3x3 whatever the batch size (Pass::CtxDirect).
 int cf_flow_step_fwd_ctx(const float* x, float* z, float* ldj_acc, const void* ws, const float* sbias, int mode, int B, int C,
                          int H, int W, int64_t x_bstride, cf_stream_t stream) {
     if (B == 0) return 0;
-    const bool keep_direct = (mode & 4) != 0;   // mode | 4: the direct form of the 3x3 whatever the batch size - the TRAINING forward under
-    mode &= 3;                                  // contextflow, whose backward (cf_flow_step_bwd_ctx) rebuilds the conditioner in that form
+    const Pass pass = (mode & 4) ? Pass::CtxDirect : Pass::Ctx;
+    mode &= 3;
     CF_REQUIRE(x && z && ldj_acc && ws && sbias && (mode == 1 || mode == 2) && B >= 0 && x_bstride >= (int64_t)C * H * W);
     CF_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0 && x_bstride % 4 == 0);
-    const float* w = (const float*)ws;
-    int rc = 0;
-#define CF_STEPC(G) rc = mode == 1 ? launch_step<G, false, 1>(x, z, ldj_acc, w, B, x_bstride, nullptr, 0, cf_s(stream), sbias) \
-                                   : launch_step<G, false, 2>(x, z, ldj_acc, w, B, x_bstride, nullptr, 0, cf_s(stream), sbias)
-    const bool wino = !direct_conv_only() && !keep_direct;      // as cf_flow_step_fwd: Winograd form of the 3x3 (16x16 always, 8x8 / 4x4 at saturating batches)
-    switch (shape_id(C, H, W)) {
-        case 0: CF_STEPC(G8); break;
-        case 1: if (!wino) CF_STEPC(G16);      // one sample per workgroup, as the generalist's 16x16 level (k_flow_step_small)
-                else rc = mode == 1 ? launch_step_small<G16w, false, false, false, 1>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream), nullptr, kNoTape, sbias)
-                                    : launch_step_small<G16w, false, false, false, 2>(x, z, ldj_acc, w, B, x_bstride, cf_s(stream), nullptr, kNoTape, sbias);
-                break;
-        case 2: if (wino && B >= 256 * G32::SPW) CF_STEPC(G32w); else CF_STEPC(G32); break;
-        case 3: if (wino && B >= 256 * G64w2::SPW) CF_STEPC(G64w2); else CF_STEPC(G64); break;
-        default: cf_set_error("cf_flow_step_fwd_ctx: shape (%d,%d,%d) unsupported", C, H, W); return CF_ERR_UNSUPPORTED;
-    }
-#undef CF_STEPC
-    if (rc) return rc;
+    const Kernel k = select(pass, shape_id(C, H, W), B);
+    if (k == Kernel::None) return unsupported_shape(__func__, C, H, W);
+    StepArgs a{x, z, ldj_acc, (const float*)ws, B, x_bstride, false, cf_s(stream)};
+    a.sb = sbias;
+    if (int rc = mode == 1 ? launch_fwd_ctx<1>(k, a) : launch_fwd_ctx<2>(k, a)) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }
@@ -1776,19 +1876,12 @@ int cf_flow_step_fwd_ctx_taped(const float* x, float* z, float* ldj_acc, const v
     CF_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0 &&
                (reinterpret_cast<uintptr_t>(t_y0) & 15) == 0 && (reinterpret_cast<uintptr_t>(t_h1) & 15) == 0 &&
                (reinterpret_cast<uintptr_t>(t_h2) & 15) == 0 && (reinterpret_cast<uintptr_t>(t_aux) & 15) == 0);
-    const float* w = (const float*)ws;
-    const StepTape tp = make_tape(t_y0, t_h1, t_h2, t_aux, B, C, H, W);
-    int rc = 0;
-#define CF_STEPCT(G) rc = launch_step<G, false, 2, true>(x, z, ldj_acc, w, B, x_bstride, nullptr, 0, cf_s(stream), sbias, tp)
-    switch (shape_id(C, H, W)) {
-        case 0: CF_STEPCT(G8); break;
-        case 1: CF_STEPCT(G16); break;
-        case 2: CF_STEPCT(G32); break;
-        case 3: CF_STEPCT(G64); break;
-        default: cf_set_error("cf_flow_step_fwd_ctx_taped: shape (%d,%d,%d) unsupported", C, H, W); return CF_ERR_UNSUPPORTED;
-    }
-#undef CF_STEPCT
-    if (rc) return rc;
+    const Kernel k = select(Pass::CtxTaped, shape_id(C, H, W), B);
+    if (k == Kernel::None) return unsupported_shape(__func__, C, H, W);
+    StepArgs a{x, z, ldj_acc, (const float*)ws, B, x_bstride, false, cf_s(stream)};
+    a.sb = sbias;
+    a.tp = make_tape(t_y0, t_h1, t_h2, t_aux, B, C, H, W);
+    if (int rc = launch_fwd_ctx_taped(k, a)) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }

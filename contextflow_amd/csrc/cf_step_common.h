@@ -1523,32 +1523,27 @@ __device__ __forceinline__ void conditioner_net(f32x16 (&acc3)[G::RT03][G::PTW],
     dense_phase<G, G::KS3, G::NG3, RT03>(acc3, rs, G::OFF_A3, H1, pix, lane);
 }
 
-// ---- dispatch ------------------------------------------------------------------------------------------
+// ---- geometries ----------------------------------------------------------------------------------------
 // Tile / loop form per shape, chosen by measurement on MI355X (tools/step_bench.py, B = 16384):
 //   C16: 1 sample (256 px, 40 KB LDS, 3-4 workgroups/CU), compiler-scheduled tap loop    113 TFLOP/s
 //   C32: 4 samples (256 px, 80 KB, 2/CU), explicit operand pipeline                        130 TFLOP/s
 //   C64: 16 samples (256 px, 160 KB = the whole LDS, 1/CU), explicit pipeline, 4x2 tiles   136 TFLOP/s
+// Which of them runs a step - per pass, shape, batch size and switch - is decided in ONE function, select() in cf_step.hip;
+// the flop accounting (cf_flow_step_macs) reads the traits of the geometry that function names.  The backward has one geometry
+// per shape (cf_step_bwd.hip).
 using G8 = Geo<8, 16, 16, 1, 0>;
 using G16 = Geo<16, 16, 16, 1, 0>;
 using G32 = Geo<32, 8, 8, 4, 1>;
 using G64 = Geo<64, 4, 4, 16, 1>;
-// alternates kept for tools/step_bench.py, reachable only through cf_flow_step_fwd_debug (flags bits 16..19)
 using G16s = Geo<16, 16, 16, 1, 2>;      // k_flow_step_small: 16x16x4 tiles for the 16-row phases, taps unrolled
 using G8s = Geo<8, 16, 16, 1, 2>;
-using G16v1 = Geo<16, 16, 16, 1, 1>;
-using G16v2 = Geo<16, 16, 16, 2, 1>;
-using G32v1 = Geo<32, 8, 8, 4, 0>;
-using G32v2 = Geo<32, 8, 8, 2, 1>;
-using G32v3 = Geo<32, 8, 8, 8, 0>;
-using G64v1 = Geo<64, 4, 4, 16, 1, 1>;
+using G32v2 = Geo<32, 8, 8, 2, 1>;       // half the samples per workgroup: batches below one workgroup per CU
 using G64v2 = Geo<64, 4, 4, 8, 1>;
-using G64v3 = Geo<64, 4, 4, 16, 0>;
 using G8w = Geo<8, 16, 16, 1, 3>;
 using G16wb = Geo<16, 16, 16, 1, 4>;     // ... with the Winograd-domain products as bf16-piece MFMAs (CONTEXTFLOW_BF16_SPLIT=1)
 using G16db = Geo<16, 16, 16, 1, 5>;     // direct 3x3 on the bf16 matrix cores, h1 split by its producer (CONTEXTFLOW_BF16_SPLIT=2)
 using G16w = Geo<16, 16, 16, 1, 3>;      // Winograd F(2x2,3x3) form of the 3x3 (winograd_phase2); 16x16: in k_flow_step_small
 using G32w = Geo<32, 8, 8, 4, 3>;
-using G64w = Geo<64, 4, 4, 16, 3>;
 using G64w2 = Geo<64, 4, 4, 8, 3>;       // 8 samples per workgroup, 2 workgroups / CU: two waves per column tile split the rows
 using G64w24 = Geo<64, 4, 4, 8, 6>;      // ... in the Winograd F(2x4, 3x3) form (winograd24_phase2): the four waves split the rows
 using G32w24 = Geo<32, 8, 8, 4, 6>;      // the 8x8 level in that form: two column tiles x two row halves

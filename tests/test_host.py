@@ -73,6 +73,68 @@ def test_host_side_size_queries_of_round_3(built):
     assert L.cf_linear_wgrad_group_ws_bytes(arr([1]), arr([1]), arr([1]), 0) == -1
 
 
+# ---- the step dispatch as the flop accounting sees it -----------------------------------------------------------------
+# (first B, multiply-adds in units of C^2 HW) of cf_flow_step_macs for B in 0..8192, per shape and pass 0..3, and the largest
+# chained batch.  Recorded from the library as it was BEFORE the dispatch became one function (commit 76e3db3), per switch
+# setting: the refactor must not move a breakpoint.  A setting lists only what differs from the default.
+SHAPES = ((8, 16, 16), (16, 16, 16), (32, 8, 8), (64, 4, 4))
+D40, W20 = [(0, 40)], [(0, 20)]
+DISPATCH_DEFAULT = {
+    (8, 16, 16): ([W20, D40, D40, W20], 1024),
+    (16, 16, 16): ([W20, W20, D40, W20], 1024),
+    (32, 8, 8): ([[(0, 40), (1024, 20), (2048, 16)], [(0, 40), (1024, 20)], D40, W20], 512),
+    (64, 4, 4): ([[(0, 40), (2048, 16)], [(0, 40), (2048, 20)], D40, W20], 1024),
+}
+DISPATCH_SETTINGS = {
+    "": {},
+    "CONTEXTFLOW_DIRECT_CONV=1": {(8, 16, 16): ([D40] * 4, 0), (16, 16, 16): ([D40] * 4, 0),
+                                  (32, 8, 8): ([D40] * 4, 512), (64, 4, 4): ([D40] * 4, 1024)},
+    "CONTEXTFLOW_WINO24=0": {(32, 8, 8): ([[(0, 40), (1024, 20)], [(0, 40), (1024, 20)], D40, W20], 512),
+                             (64, 4, 4): ([[(0, 40), (2048, 20)], [(0, 40), (2048, 20)], D40, W20], 1024)},
+    "CONTEXTFLOW_WINO24_8X8=0": {(32, 8, 8): ([[(0, 40), (1024, 20)], [(0, 40), (1024, 20)], D40, W20], 512)},
+    "CONTEXTFLOW_BF16_SPLIT=1": {},
+    "CONTEXTFLOW_BF16_SPLIT=2": {},
+}
+DISPATCH_SCRIPT = """
+import hashlib, sys
+sys.path.insert(0, %r)
+from contextflow_amd.layers import _hip
+L = _hip.lib()
+h = hashlib.sha256()
+for C, H, W in %r:
+    for p in range(4):
+        bp = []
+        for B in range(8193):
+            m = L.cf_flow_step_macs(B, C, H, W, p)
+            h.update(str(m).encode())
+            assert m %% (C * C * H * W) == 0, (B, C, p, m)
+            if not bp or bp[-1][1] != m // (C * C * H * W):
+                bp.append((B, m // (C * C * H * W)))
+        print(repr(bp))
+    print(L.cf_flow_step_chain_max_batch(C, H, W))
+print(h.hexdigest())
+"""
+
+
+@pytest.mark.parametrize("setting", list(DISPATCH_SETTINGS))
+def test_step_dispatch_breakpoints(built, setting):
+    """Every breakpoint of cf_flow_step_macs over B = 0..8192 and cf_flow_step_chain_max_batch, exactly, for the default
+    environment and each dispatch switch (a child process each: the switches are read once per process)."""
+    import ast
+    env = {k: v for k, v in os.environ.items() if not k.startswith("CONTEXTFLOW_")}
+    if setting:
+        env.update([setting.split("=")])
+    r = subprocess.run([sys.executable, "-c", DISPATCH_SCRIPT % (ROOT, SHAPES)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.split("\n")
+    want = {**DISPATCH_DEFAULT, **DISPATCH_SETTINGS[setting]}
+    for i, shape in enumerate(SHAPES):
+        got = [ast.literal_eval(s) for s in lines[5 * i:5 * i + 4]]
+        assert (got, int(lines[5 * i + 4])) == want[shape], (setting, shape, got, lines[5 * i + 4])
+    if setting in ("", "CONTEXTFLOW_BF16_SPLIT=1", "CONTEXTFLOW_BF16_SPLIT=2"):     # all 131 088 values, shape / pass / B ascending
+        assert lines[20] == "7c2a86c3ec00086a32d855de78c909fd1fc4e762fe67234ccf36ecf20a48c0cf"
+
+
 def test_gfx950_code_object(built):
     out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "--offloading", built], capture_output=True, text=True)
     blob = out.stdout + out.stderr

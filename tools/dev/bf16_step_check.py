@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """The bf16-piece forms of the 16x16 level's step kernel (G16wb: Winograd-domain products, debug variant 6 / CONTEXTFLOW_BF16_SPLIT=1;
-G16db: direct 3x3 with h1 split by its producer, variant 7 / CONTEXTFLOW_BF16_SPLIT=2) against the fp32 Winograd form (variant 4): z and the log-det of the same step on the same input, and both kernel times.
+G16db: direct 3x3 with h1 split by its producer, variant 7 / CONTEXTFLOW_BF16_SPLIT=2) against the fp32 Winograd form (variant 4)
+and the direct form (variant 3); the variants are those of kDebugKernel in csrc/cf_step.hip, flags = variant << 16: z and the log-det of
+the same step on the same input, and the kernel times.
 usage: bf16_step_check.py [B]"""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

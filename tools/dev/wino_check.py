@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Dev check: the Winograd-form step kernel (cf_flow_step_fwd_debug, variant 4) against the production step kernel on the
-same operands, and their kernel times.  usage: wino_check.py [B]"""
+"""Dev check: a variant of the step kernel (cf_flow_step_fwd_debug, flags = variant << 16; default 4 = Winograd F(2x2, 3x3), 5 =
+row-split 4x4, 6 = F(2x4, 3x3) at 8x8 / 4x4; a shape without the variant prints n/a) against the production step kernel on the
+same operands, and their kernel times.  usage: wino_check.py [B] [variant]"""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
-"""Micro-benchmark of the fused step kernel alone (GPU box).  usage: step_bench.py [B] ; prints TFLOP/s per shape
-and experiment flag (bit0 stagger, bit1 one workgroup per CU; flags>>8 = stagger units of 64*64 cycles)."""
+"""Micro-benchmark of the fused step kernel alone (GPU box).  usage: step_bench.py [B] [flags...] ; prints TFLOP/s per shape
+for the default geometry ("base") and for each `flags` value given: bits 16..19 = kernel variant of the test hook
+cf_flow_step_fwd_debug (e.g. 0x40000 = variant 4; its table is kDebugKernel in csrc/cf_step.hip: 2 half-size workgroups,
+3 k_flow_step_small direct, 4 Winograd F(2x2), 5 row-split 4x4, 6 bf16 pieces at 16x16 / F(2x4) at 8x8 and 4x4, 7 direct
+bf16 pieces); the other bits are unused.  A shape without that variant prints "n/a"."""
 import ctypes
 import sys
 import os
@@ -21,7 +24,7 @@ dev = "cuda:0"
 variants = [("base", 0)]
 for a in sys.argv[2:]:
     variants.append((a, int(a, 0)))
-for C, H, W, nslots in ((8, 16, 16, 4), (16, 16, 16, 4), (32, 8, 8, 2), (64, 4, 4, 2)):
+for C, H, W in ((8, 16, 16), (16, 16, 16), (32, 8, 8), (64, 4, 4)):
     torch.manual_seed(0)
     conv, act, cpl = L.Conv1x1((C, H, W)).to(dev), L.ActNorm((C, H, W)).to(dev), L.Coupling(C, (3, 3), (1, 1)).to(dev)
     x = torch.randn(B, C, H, W, device=dev)
@@ -35,8 +38,6 @@ for C, H, W, nslots in ((8, 16, 16, 4), (16, 16, 16, 4), (32, 8, 8, 2), (64, 4, 
     ldj = torch.zeros(B, device=dev)
     res = []
     for name, flags in variants:
-        if flags & 1:
-            flags |= nslots << 4
         try:
             for _ in range(3):
                 _hip.check(fn(pp(x), pp(z), pp(ldj), pp(ws), B, C, H, W, C * H * W, 0, None, flags, _hip.stream()))
