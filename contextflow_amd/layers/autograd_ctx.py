@@ -12,7 +12,7 @@ import os
 
 import torch
 
-from . import _hip
+from . import _derived, _hip
 from .actnorm import ActNorm
 from .context import (ArgmaxCatDequantization, CatEmbeddings, EyeSampling, ProbSampling, UniformCatDequantization,
                       VariationalCatDequantization)
@@ -284,23 +284,15 @@ def coupling_ctx_backward(m, rec, context, gz, gld, grads):
     c1, c2, c3 = m.NN[0], m.NN[2], m.NN[4]
     w1 = f(c1.weight.detach())
     # transposed fragments of the backward kernel: kept while the three weights are unchanged (frozen under contextflow)
-    key = (rec["mode"], C, H, W, str(dev)) + tuple((t._version, t.data_ptr()) for t in (c1.weight, c2.weight, c3.weight))
-    hit = m.__dict__.get("_ctx_wsb")
-    capturing = torch.cuda.is_current_stream_capturing()
-    if hit is not None and hit[0] == key and not capturing:
-        wsb = hit[1]
-        torch.cuda.current_stream(dev).wait_event(hit[2])
-    else:
+    def build():
         eye = torch.eye(C, device=dev, dtype=torch.float32)
         zero = torch.zeros(C, device=dev, dtype=torch.float32)
         wsb = torch.empty(L.cf_flow_step_bwd_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
         w1x = w1 if rec["mode"] == 1 else w1[:, :D].contiguous()
         _hip.call("cf_flow_step_bwd_prepare", pp(eye), pp(zero), pp(w1x), pp(f(c2.weight.detach())),
                   pp(f(c3.weight.detach())), pp(wsb), C, H, W, st)
-        if not capturing:
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))
-            m.__dict__["_ctx_wsb"] = (key, wsb, ev)
+        return wsb
+    wsb = _derived.get(m, "ctx_wsb", _derived.key((c1.weight, c2.weight, c3.weight), rec["mode"], C, H, W, str(dev)), build, dev)
     gx = torch.empty(B, C, H, W, device=dev, dtype=torch.float32)
     s_gh = torch.empty(B, C, HW, device=dev, dtype=torch.float32)
     gzc = f(gz).contiguous()

@@ -3,7 +3,7 @@ and the per-sample triangular matrix CN(c) of the specialist mode (conv1x1.py:34
 import torch
 import torch.nn as nn
 
-from . import _hip
+from . import _derived, _hip
 from .flowlayer import FlowLayer, encoder_noise
 
 
@@ -60,14 +60,8 @@ class Conv1x1(FlowLayer):
         _hip.call("cf_conv1x1_ctx", _hip.p(x), _hip.p(m), _hip.p(Wm), _hip.p(z), _hip.p(ldj), B, C, H * W, xbs, _hip.stream())
         if self.contextflow:
             # H W log|det NN| of the frozen shared matrix: kept while NN is unchanged (one factorisation per layer and call otherwise)
-            key = (self.NN._version, self.NN.data_ptr(), H * W, str(x.device))
-            hit = self.__dict__.get("_lad_cache")
-            if hit is None or hit[0] != key or torch.cuda.is_current_stream_capturing():
-                lad, _ = slogdet_inverse(Wm, False)
-                hit = (key, lad * float(H * W))
-                if not torch.cuda.is_current_stream_capturing():
-                    self.__dict__["_lad_cache"] = hit
-            ldj = ldj + hit[1]
+            ldj = ldj + _derived.get(self, "lad", _derived.key((self.NN,), H * W, str(x.device)),
+                                     lambda: slogdet_inverse(Wm, False)[0] * float(H * W), x.device)
         if tape is not None:
             tape.append(dict(x=x, c=_hip.f32(c), m=m, eps=encoder_noise(self.context_net)))
         return z, ldj + logp_c * float(H * W)
@@ -87,15 +81,8 @@ class Conv1x1(FlowLayer):
         if self.context_net:
             raise NotImplementedError("Conv1x1.reverse with a context net (the reference's own is marked 'to update')")
         # W^-1 follows NN's version counter and storage (`sample` inverts every layer's matrix per call otherwise)
-        key = (self.NN._version, self.NN.data_ptr(), str(z.device))
-        hit = self.__dict__.get("_winv_cache")
-        capturing = torch.cuda.is_current_stream_capturing()
-        if hit is None or hit[0] != key or capturing:
-            _, inv = slogdet_inverse(_hip.f32(self.NN.detach()), True)
-            if not capturing:
-                self.__dict__["_winv_cache"] = (key, inv)
-        else:
-            inv = hit[1]
+        inv = _derived.get(self, "winv", _derived.key((self.NN,), str(z.device)),
+                           lambda: slogdet_inverse(_hip.f32(self.NN.detach()), True)[1], z.device)
         return conv1x1_apply(z, inv)                       # conv1x1.py:72
 
     def logdet(self, input, context=None):

@@ -9,7 +9,7 @@ runs in the HIP kernels."""
 import torch
 import torch.nn as nn
 
-from . import _hip
+from . import _derived, _hip
 from .flowlayer import FlowLayer, encoder_noise
 
 VIT_EVENTS = None        # bench.py: list collecting (start, end, batch) HIP events per fused ViT-coupling launch
@@ -38,6 +38,20 @@ def coupling_apply(x, h, inverse):
     ldj = None if inverse else torch.empty(B, device=x.device, dtype=torch.float32)
     _hip.call("cf_coupling_apply", _hip.p(x), _hip.p(h), _hip.p(z), _hip.p(ldj), B, C, HW, int(inverse), _hip.stream())
     return z, ldj
+
+
+def identity_front_step_tables(cpl, w1, C, H, W, dev):
+    """Packed tables of the fused flow-step kernel for the Coupling `cpl` alone: an identity 1x1 and a zero ActNorm in front of
+    its conditioner.  w1: the weight of the conditioner's first 1x1 (its data columns when CN(c) is concatenated to the input)."""
+    f, pp = _hip.f32, _hip.p
+    c1, c2, c3 = cpl.NN[0], cpl.NN[2], cpl.NN[4]
+    eye = torch.eye(C, device=dev, dtype=torch.float32)
+    zero = torch.zeros(C, device=dev, dtype=torch.float32)
+    ws = torch.empty(_hip.lib().cf_flow_step_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
+    _hip.call("cf_flow_step_prepare", pp(eye), pp(zero), pp(zero), pp(w1), pp(f(c1.bias.detach())),
+              pp(f(c2.weight.detach())), pp(f(c2.bias.detach())), pp(f(c3.weight.detach())), pp(f(c3.bias.detach())),
+              pp(ws), C, H, W, _hip.stream())
+    return ws
 
 
 class _AffineCoupling(FlowLayer):
@@ -138,23 +152,8 @@ class Coupling(_AffineCoupling):
         # packed tables of the step: kept while the conditioner is unchanged (version counter + storage of its six tensors) - under
         # contextflow it is frozen, and a training step otherwise factorises an identity and packs the same tables for every coupling
         srcs = (c1.weight, c1.bias, c2.weight, c2.bias, c3.weight, c3.bias)
-        key = (mode, C, H, W, str(dev)) + tuple((t._version, t.data_ptr()) for t in srcs)
-        hit = self.__dict__.get("_ctx_ws")
-        capturing = torch.cuda.is_current_stream_capturing()
-        if hit is not None and hit[0] == key and not capturing:
-            ws = hit[1]
-            torch.cuda.current_stream(dev).wait_event(hit[2])
-        else:
-            eye = torch.eye(C, device=dev, dtype=torch.float32)
-            zero = torch.zeros(C, device=dev, dtype=torch.float32)
-            ws = torch.empty(_hip.lib().cf_flow_step_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
-            _hip.call("cf_flow_step_prepare", pp(eye), pp(zero), pp(zero), pp(w1), pp(f(c1.bias.detach())),
-                      pp(f(c2.weight.detach())), pp(f(c2.bias.detach())), pp(f(c3.weight.detach())), pp(f(c3.bias.detach())),
-                      pp(ws), C, H, W, st)
-            if not capturing:
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(dev))
-                self.__dict__["_ctx_ws"] = (key, ws, ev)
+        ws = _derived.get(self, "ctx_ws", _derived.key(srcs, mode, C, H, W, str(dev)),
+                          lambda: identity_front_step_tables(self, w1, C, H, W, dev), dev)
         z = torch.empty(B, C, H, W, device=dev, dtype=torch.float32)
         ldj = torch.zeros(B, device=dev, dtype=torch.float32)
         planes = None
@@ -284,9 +283,10 @@ class TransCoupling(_AffineCoupling):
     def step_sources(self):
         """Parameters the packed step workspace derives from (cache key of FlowSequential).  The tuple is built once: walking
         the module tree costs more host time per call than the whole step kernel takes at a batch of 256."""
-        src = getattr(self, "_step_src", None)
-        if src is None:
-            src = self._step_src = tuple(self.NN[0].parameters())
+        entries = self.__dict__.get("_derived")
+        src = entries.get("step_src") if entries else None
+        if src is None:              # (not a parameter-VALUE entry - no key, no event - but dropped with them: layers/_derived.py)
+            src = self.__dict__.setdefault("_derived", {})["step_src"] = tuple(self.NN[0].parameters())
         return src
 
     # batches up to this size take the row-split step kernel (cf_vit_step_rs_fwd: 4 samples per workgroup, an eighth of the
@@ -362,13 +362,7 @@ class TransCoupling(_AffineCoupling):
         """The ViT parameters as one flat fp32 tensor in the order the pack kernels read them; kept until a parameter's
         version counter moves (a training step asks for it twice: forward and backward)."""
         src = self.step_sources()
-        ver = tuple(p._version for p in src) + tuple(p.data_ptr() for p in src)
-        hit = getattr(self, "_flat_cache", None)
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-        flat = self._flat_params_build()
-        self._flat_cache = (ver, flat)
-        return flat
+        return _derived.get(self, "flat", _derived.key(src), self._flat_params_build, src[0].device)
 
     def _flat_params_build(self):
         vit = self.NN[0]
@@ -391,19 +385,12 @@ class TransCoupling(_AffineCoupling):
         assert flat.numel() == L.cf_vit_flat_params(pd, dim, depth)
         st = _hip.stream()
         # the packed table follows the flat parameter tensor (rebuilt when a version counter moves): packed once per parameter version,
-        # not once per call (`sample` walks eight such layers per call)
-        hit = self.__dict__.get("_fused_ws")
-        capturing = torch.cuda.is_current_stream_capturing()
-        if hit is not None and hit[0] is flat and hit[1] == (pd, dim, depth, str(x.device)) and not capturing:
-            ws = hit[2]
-            torch.cuda.current_stream(x.device).wait_event(hit[3])
-        else:
+        # not once per call (`sample` walks eight such layers per call).  The entry holds `flat`, so its id stays taken.
+        def build():
             ws = torch.empty(L.cf_vit_ws_bytes(pd, dim, depth), device=x.device, dtype=torch.uint8)
             _hip.call("cf_vit_prepare", _hip.p(flat), _hip.p(ws), pd, dim, depth, st)
-            if not capturing:
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(x.device))
-                self.__dict__["_fused_ws"] = (flat, (pd, dim, depth, str(x.device)), ws, ev)
+            return flat, ws
+        ws = _derived.get(self, "fused_ws", (id(flat), pd, dim, depth, str(x.device)), build, x.device)[1]
         if vit.pos_embedding.device != x.device:
             vit.pos_embedding = vit.pos_embedding.to(x.device).contiguous()
         z = torch.empty(B, C, H, W, device=x.device, dtype=torch.float32)

@@ -8,7 +8,7 @@ import math
 import torch
 import torch.nn as nn
 
-from .. import _hip
+from .. import _derived, _hip
 from ..flowlayer import no_context
 
 
@@ -229,10 +229,8 @@ class GaussianMixtureDistribution(nn.Module):
             return None
         dev = self.sG.device
         # (storage, version) of every tensor the tables are built from; writes through `.data` bump no version counter:
-        # callers that do that (none in this package) must drop `_tab_cache` themselves (FlowSequential.invalidate_caches)
-        ver = (need_dsig, self.sG._version, self.sG.data_ptr(), str(dev)) + tuple((e.weight._version, e.weight.data_ptr()) for e in embs)
-        cache = getattr(self, "_tab_cache", None)
-        if cache is None or cache[0] != ver:
+        # callers that do that (none in this package) must drop the entry themselves (FlowSequential.invalidate_caches)
+        def build():
             def rows(U, rel, strides):
                 grid = torch.zeros(U, len(embs), dtype=torch.long, device=dev)
                 u = torch.arange(U, device=dev)
@@ -246,7 +244,9 @@ class GaussianMixtureDistribution(nn.Module):
             lsum = torch.empty(Us, self.M * self.K, device=dev, dtype=torch.float32)
             _hip.call("cf_gmm_ctx_tables", _hip.p(_hip.f32(self.sG.detach())), _hip.p(cs_tab), _hip.p(inv), _hip.p(dsig),
                       _hip.p(lsum), Us, self.M * self.K, D, H * W, _hip.stream())
-            cache = self._tab_cache = (ver, inv, dsig, lsum, cm_tab)
+            return inv, dsig, lsum, cm_tab
+        inv, dsig, lsum, cm_tab = _derived.get(self, "tab", _derived.key([self.sG] + [e.weight for e in embs], need_dsig, str(dev)),
+                                               build, dev)
         ctx = context.to(device=dev, dtype=torch.long)
 
         def key_of(rel, strides):
@@ -264,19 +264,18 @@ class GaussianMixtureDistribution(nn.Module):
             _key_cache.append((context, sig, key))
             del _key_cache[:-4]               # the two keys of the current context (+ those of the one before)
             return key
-        return (key_of(rel_s, st_s),) + cache[1:4] + (key_of(rel_m, st_m), cache[4])
+        return key_of(rel_s, st_s), inv, dsig, lsum, key_of(rel_m, st_m), cm_tab
 
     def _keyed_tables(self, tab, logw):
-        """Per-key parameter rows of cf_gmm_logprob_keyed, cached with the scale tables: nm (Um, M*K*N) = -(mG + mean shift)
-        - the reference's `self.mG + cond_mean` rounded once (gaussian.py:143) - and cst (Us, M*K)."""
-        cache = self._tab_cache
-        if len(cache) == 5 or cache[5][0] is not tab[1]:
+        """Per-key parameter rows of cf_gmm_logprob_keyed, kept as long as the scale tables `tab` they belong to: nm (Um, M*K*N) =
+        -(mG + mean shift) - the reference's `self.mG + cond_mean` rounded once (gaussian.py:143) - and cst (Us, M*K)."""
+        def build():
             D, H, W = self.size
             MK = self.M * self.K
             nm = -(_hip.f32(self.mG.detach()).view(1, MK, D, H * W) + tab[5].view(-1, MK, D, 1))
             cst = logw.reshape(1, MK) - tab[3] - 0.5 * D * H * W * math.log(2 * math.pi)
-            cache = self._tab_cache = cache[:5] + ((tab[1], nm.reshape(nm.shape[0], -1).contiguous(), cst.contiguous()),)
-        return cache[5][1:]
+            return tab[1], nm.reshape(nm.shape[0], -1).contiguous(), cst.contiguous()     # (tab[1] is held: its id stays taken)
+        return _derived.get(self, "keyed", (id(tab[1]),), build, tab[1].device)[1:]
 
     def _log_prob_ctx(self, input, context, tape=None):
         """gaussian.py:146-158: per-sample shifts (B, 2, M, K, D) of the component means / pre-softplus scales."""

@@ -18,7 +18,7 @@ import math
 import torch
 import torch.nn as nn
 
-from . import _hip
+from . import _derived, _hip
 from .actnorm import ActNorm
 from .augment import Augment
 from .conv1x1 import Conv1x1
@@ -99,13 +99,25 @@ class FlowSequential(nn.Module):
     def __iter__(self):
         yield from self.sequence_modules
 
-    def __getstate__(self):              # streams / cached plans are per-process runtime state
+    def __getstate__(self):              # streams / cached plans / derived tables are per-process runtime state
+        self._drop_derived()
         d = self.__dict__.copy()
         d["_plans"], d["_side"], d["step_events"], d["inv_events"] = {}, {}, None, None
         d["_prep"], d["_graphs"], d["_graph_policy"], d["_tensors"] = {}, {}, {}, None
         d["_grad_bucket"] = None
-        d.pop("_cache_holders", None)
+        d.pop("_derived_owners", None)
         return d
+
+    def _drop_derived(self):
+        """Forget every table kept while parameters are unchanged (layers/_derived.py), the flow's own and its modules'."""
+        _derived.drop(self)
+        # the modules that can own derived entries: collected once per module tree (`hasattr` on 636 modules cost 1-4 ms of host
+        # time per call - a captured SMAP training step at a batch of 256 takes 2 ms and ends with invalidate_caches)
+        owners = self.__dict__.get("_derived_owners")
+        if owners is None:
+            owners = self.__dict__["_derived_owners"] = [m for m in self.modules() if isinstance(m, (TransCoupling, GaussianMixtureDistribution, Coupling, Conv1x1))]
+        for m in owners:
+            _derived.drop(m)
 
     def invalidate_caches(self):
         """Drop everything derived from parameter VALUES (packed step workspaces, mixture tables, captured graphs).  Needed
@@ -117,36 +129,12 @@ class FlowSequential(nn.Module):
         self._tensors = None                         # a Parameter OBJECT may have been replaced (load_state_dict(assign=True), m.w = nn.Parameter(..))
         self.__dict__.pop("_fusable_ok", None)       # (an ActNorm may have been reset)
         self.__dict__.pop("_all_params", None)
-        self.__dict__.pop("_spec_ws", None)          # layers/specialist.py: packed coupling tables, log|det NN| of frozen Conv1x1,
-        self.__dict__.pop("_spec_lad", None)         # Conv1x1.CN in blocked row order
-        self.__dict__.pop("_spec_cnb", None)
-        self.__dict__.pop("_inv_ws", None)           # packed tables of the inverse steps (`inverse` / `sample`)
-        # the modules that keep parameter-derived state of their own: collected once per module tree (`hasattr` on 636 modules
-        # cost 1-4 ms of host time per call - a captured SMAP training step at a batch of 256 takes 2 ms and ends with this call)
-        holders = self.__dict__.get("_cache_holders")
-        if holders is None:
-            holders = self.__dict__["_cache_holders"] = [m for m in self.modules() if isinstance(m, (TransCoupling, GaussianMixtureDistribution, Coupling, Conv1x1))]
-        for m in holders:
-            d = m.__dict__
-            d.pop("_lad_cache", None)                # Conv1x1 with a context net under contextflow: H W log|det NN|
-            d.pop("_winv_cache", None)               # Conv1x1.reverse: W^-1
-            d.pop("_fused_ws", None)                 # TransCoupling._fused: packed ViT table
-            d.pop("_ctx_ws", None)                   # Coupling with a context net: packed step tables (forward / backward)
-            d.pop("_ctx_wsb", None)
-            if "_tab_cache" in d:
-                d["_tab_cache"] = None
-            if "_flat_cache" in d:
-                d["_flat_cache"] = None
-            if "_step_src" in d:
-                d["_step_src"] = None
+        self._drop_derived()
 
     def _apply(self, fn, *a, **k):         # .to() / .cuda() / .float(): new storages, same version counters
         self._prep, self._graphs, self._plans, self._tensors = {}, {}, {}, None
         self._grad_bucket = None
-        self.__dict__.pop("_spec_ws", None)
-        self.__dict__.pop("_spec_lad", None)
-        self.__dict__.pop("_spec_cnb", None)
-        self.__dict__.pop("_inv_ws", None)           # packed tables of the inverse steps (`inverse` / `sample`)
+        self._drop_derived()
         return super()._apply(fn, *a, **k)
 
     def _versions(self):
@@ -340,28 +328,22 @@ class FlowSequential(nn.Module):
         _hip.call("cf_flow_step_bwd_prepare_batch", n, A(cols[0]), A(cols[2]), A(cols[3]), A(cols[5]), A(cols[7]), A(wsb), C, H, W, _hip.stream())
         return list(zip(ws, winv, wsb))
 
-    def _forward_fused(self, x, context, tape=None):
-        B, M, dev = x.shape[0], self.mixtures, x.device
-        key = tuple(x.shape[1:])
-        plan = self._plans.get(key)
-        if plan is None:
-            plan = self._plans[key] = self._build_plan(key)
-        main = torch.cuda.current_stream(dev)
-        side = self._side_stream(dev)
+    def _tables(self, plan, key, B, dev, main, tape):
+        """The parameter transforms of a fused call: kept from the previous call while the parameters they derive from are
+        unchanged (evaluation); otherwise rebuilt on the side stream, overlapping the main stream's kernels.  Returns
+        (prepared: plan index -> (buffers, producer's event | None), prior tables, their event | None, fresh: the entries built
+        by THIS call).
 
-        # ---- parameter transforms: kept from the previous call while the parameters they derive from are unchanged
-        # (evaluation); otherwise rebuilt on the side stream, overlapping the main stream's kernels
-        prepared = {}
+        `_prep` has a rule of its own (not layers/_derived.py's): a HIT is allowed while capturing, without the event wait.  A
+        capturing stream must not wait on an event recorded outside the capture - and need not: torch.cuda.graph synchronises
+        the device before the capture begins, so cached tables are complete by then.  GraphedFlow depends on it: it warms the
+        cache up before it captures, and its graph then holds no prepare launches.  Tables built DURING a capture live in the
+        graph's private pool and their events belong to the capture: they must not outlive it as cache entries (a later eager
+        call would wait on a captured event and read buffers that only exist after a replay), so a user-side capture with a
+        cold cache simply rebuilds the tables inside its graph."""
+        prepared, todo, vkey = {}, [], {}
         cache_ok = tape is None
-        todo = []
-        vkey = {}
-        # a capturing stream must not wait on an event recorded outside the capture - and need not: torch.cuda.graph
-        # synchronises the device before the capture begins, so cached tables are complete by then
         capturing = torch.cuda.is_current_stream_capturing()
-        # tables built DURING a capture live in the graph's private pool and their events belong to the capture: they must not
-        # outlive it as cache entries (a later eager call would wait on a captured event and read buffers that only exist
-        # after a replay).  GraphedFlow warms the cache up before it captures; a user-side capture with a cold cache simply
-        # rebuilds the tables inside its graph.
         store_ok = cache_ok and not capturing
         for k, op in enumerate(plan):
             if op[0] == "step":
@@ -373,72 +355,109 @@ class FlowSequential(nn.Module):
                 srcs = (op[1].dist.mG, op[1].dist.sG, op[1].dist.wG)
             else:
                 continue
-            ver = tuple(t._version for t in srcs) + (dev.index,)
+            ver = _derived.key(srcs, dev.index)
             hit = self._prep.get((key, k, vkey.get(k))) if cache_ok else None
             if hit is not None and hit[0] == ver:
                 prepared[k] = (hit[1], None if capturing else hit[2])      # the producer's event stays with the entry: a later call on ANOTHER
             else:                                    # stream is ordered against the side stream that wrote the buffers
                 todo.append((k, op, ver))
-        pver = tuple(t._version for t in (self.dist.mG, self.dist.sG, self.dist.wG)) + (dev.index,)
+        pver = _derived.key((self.dist.mG, self.dist.sG, self.dist.wG), dev.index)
         hit = self._prep.get((key, "prior")) if cache_ok else None
         prior, ev_prior = (hit[1], None if capturing else hit[2]) if (hit is not None and hit[0] == pver) else (None, None)
-        fresh = set()                # entries built by THIS call (their buffers get a record_stream below)
-        if todo or prior is None:
-            # (one side stream: spreading the tables of the flow steps over 2 / 4 streams was measured on the captured training
-            # step at a batch of 256 - smap 2.10 -> 2.16 ms, cifar10 2.49 -> 2.48 ms: tools/dev/prep_streams_ab.py - and dropped)
-            sides = [self._side_stream(dev)]
-            sides[0].wait_stream(main)
-            side = sides[0]
-            with torch.cuda.stream(side):
-                # conv steps: the tables of all steps of one shape in ONE factorisation + ONE packing launch (+ one for the
-                # backward kernel's fragments when training) - cf_flow_step_prepare_batch
-                groups = {}
-                for k, op, ver in todo:
-                    if op[0] == "step":
-                        groups.setdefault(tuple(op[4]), []).append((k, op, ver))
-                # (one event per group, recorded right behind its launches: the first level's steps start as soon as THEIR
-                # tables exist - the 64-channel factorisation alone takes 50 us - instead of behind every table of the flow)
-                done, done_ev = {}, {}
-                for shape, items in groups.items():
-                    bufs = self._prepare_steps([(it[1][1], it[1][2], it[1][3]) for it in items], shape, dev, train=tape is not None)
-                    gev = torch.cuda.Event()
-                    gev.record(side)
-                    for (k, op, ver), buf in zip(items, bufs):
-                        done[k] = buf
-                        done_ev[k] = gev
-                # transformer steps at small batches: the row-split tables of all steps in one launch triple (training: with
-                # Wm^-1 and the backward kernel's tables) - cf_vit_step_rs_prepare_batch
-                vitems = [(k, op, ver) for k, op, ver in todo if op[0] == "vstep" and vkey[k] == "rs"]
-                if vitems:
-                    bufs = TransCoupling.step_prepare_rs_batch([(it[1][3], it[1][1].NN, it[1][2].NN_t, it[1][2].NN_logs) for it in vitems], dev,
-                                                               train=tape is not None)
-                    gev = torch.cuda.Event()
-                    gev.record(side)
-                    for (k, op, ver), buf in zip(vitems, bufs):
-                        done[k] = buf
-                        done_ev[k] = gev
-                for k, op, ver in todo:
-                    if k in done:
-                        buf, ev = done[k], done_ev[k]
+        fresh = set()                # (their buffers get a record_stream at the end of the call: _consumed_on)
+        if not todo and prior is not None:
+            return prepared, prior, ev_prior, fresh
+        # (one side stream: spreading the tables of the flow steps over 2 / 4 streams was measured on the captured training
+        # step at a batch of 256 - smap 2.10 -> 2.16 ms, cifar10 2.49 -> 2.48 ms: tools/dev/prep_streams_ab.py - and dropped)
+        side = self._side_stream(dev)
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            # conv steps: the tables of all steps of one shape in ONE factorisation + ONE packing launch (+ one for the
+            # backward kernel's fragments when training) - cf_flow_step_prepare_batch
+            groups = {}
+            for k, op, ver in todo:
+                if op[0] == "step":
+                    groups.setdefault(tuple(op[4]), []).append((k, op, ver))
+            # (one event per group, recorded right behind its launches: the first level's steps start as soon as THEIR
+            # tables exist - the 64-channel factorisation alone takes 50 us - instead of behind every table of the flow)
+            done, done_ev = {}, {}
+            for shape, items in groups.items():
+                bufs = self._prepare_steps([(it[1][1], it[1][2], it[1][3]) for it in items], shape, dev, train=tape is not None)
+                gev = torch.cuda.Event()
+                gev.record(side)
+                for (k, op, ver), buf in zip(items, bufs):
+                    done[k] = buf
+                    done_ev[k] = gev
+            # transformer steps at small batches: the row-split tables of all steps in one launch triple (training: with
+            # Wm^-1 and the backward kernel's tables) - cf_vit_step_rs_prepare_batch
+            vitems = [(k, op, ver) for k, op, ver in todo if op[0] == "vstep" and vkey[k] == "rs"]
+            if vitems:
+                bufs = TransCoupling.step_prepare_rs_batch([(it[1][3], it[1][1].NN, it[1][2].NN_t, it[1][2].NN_logs) for it in vitems], dev,
+                                                           train=tape is not None)
+                gev = torch.cuda.Event()
+                gev.record(side)
+                for (k, op, ver), buf in zip(vitems, bufs):
+                    done[k] = buf
+                    done_ev[k] = gev
+            for k, op, ver in todo:
+                if k in done:
+                    buf, ev = done[k], done_ev[k]
+                else:
+                    if op[0] == "vstep":
+                        buf = op[3].step_prepare(op[1].NN, op[2].NN_t, op[2].NN_logs, dev, vkey[k])
                     else:
-                        if op[0] == "vstep":
-                            buf = op[3].step_prepare(op[1].NN, op[2].NN_t, op[2].NN_logs, dev, vkey[k])
-                        else:
-                            buf = op[1].dist.prepared()
-                        ev = torch.cuda.Event()
-                        ev.record(side)
-                    prepared[k] = (buf, ev)
-                    fresh.add(k)
-                    if store_ok:
-                        self._prep[(key, k, vkey.get(k))] = (ver, buf, ev)
+                        buf = op[1].dist.prepared()
+                    ev = torch.cuda.Event()
+                    ev.record(side)
+                prepared[k] = (buf, ev)
+                fresh.add(k)
+                if store_ok:
+                    self._prep[(key, k, vkey.get(k))] = (ver, buf, ev)
             if prior is None:
-                with torch.cuda.stream(side):
-                    prior = self.dist.prepared()
-                    ev_prior = torch.cuda.Event()
-                    ev_prior.record(side)
-                    fresh.add("prior")
-                    if store_ok:
-                        self._prep[(key, "prior")] = (pver, prior, ev_prior)
+                prior = self.dist.prepared()
+                ev_prior = torch.cuda.Event()
+                ev_prior.record(side)
+                fresh.add("prior")
+                if store_ok:
+                    self._prep[(key, "prior")] = (pver, prior, ev_prior)
+        return prepared, prior, ev_prior, fresh
+
+    @staticmethod
+    def _consumed_on(main, prepared, prior, fresh):
+        """Buffers written on the side stream by this call are consumed on the main stream: keep the allocator informed."""
+        def bufs(t):
+            if torch.is_tensor(t):
+                yield t
+            elif isinstance(t, tuple):
+                for u in t:
+                    yield from bufs(u)
+
+        for k in fresh:
+            for buf in bufs(prior if k == "prior" else prepared[k][0]):
+                buf.record_stream(main)
+
+    def _forward_fused(self, x, context, tape=None):
+        B, M, dev = x.shape[0], self.mixtures, x.device
+        key = tuple(x.shape[1:])
+        plan = self._plans.get(key)
+        if plan is None:
+            plan = self._plans[key] = self._build_plan(key)
+        main = torch.cuda.current_stream(dev)
+        prepared, prior, ev_prior, fresh = self._tables(plan, key, B, dev, main, tape)
+
+        def chain_run(k, ws, nmax, joins):
+            """Plan indices and tables of the run of at most nmax steps that starts at step k (tables ws) and goes on while
+            joins(next op) holds; the main stream waits on the members' tables."""
+            run = [k]
+            while len(run) < nmax and run[-1] + 1 < len(plan) and joins(plan[run[-1] + 1]):
+                run.append(run[-1] + 1)
+            tabs = [ws]
+            for j in run[1:]:
+                wj, evj = prepared[j]
+                if evj is not None:
+                    main.wait_event(evj)
+                tabs.append(wj)
+            return run, tabs
 
         # running log-dets: per-sample scalar terms / per-mixture terms (priors).  The first writer ASSIGNS (no zero-fill
         # launches): the pre-processing kernel for ld1, the first mixture kernel for ldM
@@ -511,17 +530,8 @@ class FlowSequential(nn.Module):
                 events = self.step_events
                 if events is None and 0 < B <= self._chain_max(C, H, W):
                     # small batch: this step and the following steps of the same shape (a resolution level) in ONE launch
-                    run = [k]
-                    while (len(run) < 4 and run[-1] + 1 < len(plan) and plan[run[-1] + 1][0] == "step"
-                           and tuple(plan[run[-1] + 1][4]) == (C, H, W) and not plan[run[-1] + 1][5]):
-                        run.append(run[-1] + 1)
+                    run, tabs = chain_run(k, ws, 4, lambda nxt: nxt[0] == "step" and tuple(nxt[4]) == (C, H, W) and not nxt[5])
                     if len(run) > 1:
-                        tabs = [ws]
-                        for j in run[1:]:
-                            wj, evj = prepared[j]
-                            if evj is not None:
-                                main.wait_event(evj)
-                            tabs.append(wj)
                         _hip.call("cf_flow_step_fwd_chain", _hip.p(x), _hip.p(z), _hip.p(ld1), _hip.ptr_array(tabs), len(run), B, C, H, W, xbs,
                                   int(sq), st)
                         chained.update(run[1:])
@@ -537,6 +547,7 @@ class FlowSequential(nn.Module):
                 x = z
             elif kind == "vstep":
                 ws, ev = prepared[k]
+                variant = op[3].step_variant(B)
                 winv_v = wsb_v = None
                 if isinstance(ws, tuple):    # training, row-split form: (tables, Wm^-1, backward tables) from the batched prepare
                     ws, winv_v, wsb_v = ws
@@ -548,28 +559,20 @@ class FlowSequential(nn.Module):
                     if VSTEP_TAPE:
                         depth = len(op[3].NN[0].transformer.layers)
                         xt = torch.empty(_hip.lib().cf_vit_step_tape_floats(B, x.shape[1], depth), device=dev, dtype=torch.float32)
-                    tape.append(("vstep", x, op[1], op[2], op[3], ws if vkey[k] == "rs" else None, xt, winv_v, wsb_v))
+                    tape.append(("vstep", x, op[1], op[2], op[3], ws if variant == "rs" else None, xt, winv_v, wsb_v))
                     if ev is not None:
                         main.wait_event(ev)
-                    x = op[3].step_forward(x, ws, ld1, variant=vkey[k], xtape=xt)
+                    x = op[3].step_forward(x, ws, ld1, variant=variant, xtape=xt)
                     continue
                 if ev is not None:
                     main.wait_event(ev)
-                if self.CHAIN_STEPS and vkey[k] == "rs" and _cpl.VIT_EVENTS is None:
+                if self.CHAIN_STEPS and variant == "rs" and _cpl.VIT_EVENTS is None:
                     # small batch (row-split form): this step and the transformer steps that follow it in ONE launch
-                    run = [k]
-                    nmax = int(_hip.lib().cf_vit_step_rs_chain_max_steps())
                     depth = len(op[3].NN[0].transformer.layers)
-                    while (len(run) < nmax and run[-1] + 1 < len(plan) and plan[run[-1] + 1][0] == "vstep" and vkey.get(run[-1] + 1) == "rs"
-                           and len(plan[run[-1] + 1][3].NN[0].transformer.layers) == depth):
-                        run.append(run[-1] + 1)
+                    run, tabs = chain_run(k, ws, int(_hip.lib().cf_vit_step_rs_chain_max_steps()),
+                                          lambda nxt: (nxt[0] == "vstep" and nxt[3].step_variant(B) == "rs"
+                                                       and len(nxt[3].NN[0].transformer.layers) == depth))
                     if len(run) > 1:
-                        tabs = [ws]
-                        for j in run[1:]:
-                            wj, evj = prepared[j]
-                            if evj is not None:
-                                main.wait_event(evj)
-                            tabs.append(wj)
                         xv, xbs = _hip.bview(x)
                         z = torch.empty(B, xv.shape[1], xv.shape[2], xv.shape[3], device=dev, dtype=torch.float32)
                         _hip.call("cf_vit_step_rs_fwd_chain", _hip.p(xv), _hip.p(z), _hip.p(ld1), _hip.ptr_array(tabs), len(run), B, xv.shape[1],
@@ -577,7 +580,7 @@ class FlowSequential(nn.Module):
                         chained.update(run[1:])
                         x = z
                         continue
-                x = op[3].step_forward(x, ws, ld1, variant=vkey[k])
+                x = op[3].step_forward(x, ws, ld1, variant=variant)
             elif kind == "squeeze":
                 if tape is not None:
                     tape.append(("squeeze", tuple(op[1].p)))
@@ -620,22 +623,7 @@ class FlowSequential(nn.Module):
             gmm_logprob(x, prior, out=ldM, accumulate=ldM_set)
             logp = torch.empty(B, M, device=dev, dtype=torch.float32)
             _hip.call("cf_logdet_combine", _hip.p(ldM), _hip.p(ld1), _hip.p(logp), B, M, st)
-        # buffers written on the side stream are consumed on the main stream: keep the allocator informed
-        def _bufs(t):
-            if torch.is_tensor(t):
-                yield t
-            elif isinstance(t, tuple):
-                for u in t:
-                    yield from _bufs(u)
-
-        for k, v in prepared.items():
-            if k in fresh:
-                for buf in _bufs(v[0]):
-                    buf.record_stream(main)
-        if "prior" in fresh:
-            for buf in prior:
-                if torch.is_tensor(buf):
-                    buf.record_stream(main)
+        self._consumed_on(main, prepared, prior, fresh)
         return x, logp
 
     # ------------------------------------------------------------------ reference API
@@ -643,7 +631,7 @@ class FlowSequential(nn.Module):
         _hip.require_device(input)
         if self._gen != _PARAM_GENERATION[0]:            # a Parameter object was (re)registered somewhere: see _PARAM_GENERATION
             self._gen = _PARAM_GENERATION[0]
-            self.__dict__.pop("_cache_holders", None)
+            self.__dict__.pop("_derived_owners", None)
             self.invalidate_caches()
         if torch.is_grad_enabled() and self._specialist():
             from .autograd_ctx import trainable as _trainable
@@ -780,22 +768,13 @@ class FlowSequential(nn.Module):
         # (two factorisations + two packing launches per step and call before: 13 - 17 % of a `sample` call at 16 384 samples)
         srcs = (conv.NN, act.NN_t, act.NN_logs, cpl.NN[0].weight, cpl.NN[0].bias, cpl.NN[2].weight, cpl.NN[2].bias, cpl.NN[4].weight,
                 cpl.NN[4].bias)
-        ver = tuple((t._version, t.data_ptr()) for t in srcs) + (C, H, W, str(dev))
-        cache = self.__dict__.setdefault("_inv_ws", {})
-        hit = cache.get(id(cpl))
-        capturing = torch.cuda.is_current_stream_capturing()
-        if hit is not None and hit[0] == ver and not capturing:
-            ws, wsi = hit[1], hit[2]
-            torch.cuda.current_stream(dev).wait_event(hit[3])      # (another stream than the one that packed them: ordered behind it)
-        else:
+        def build():
             ws = self._prepare_step(conv, act, cpl, (C, H, W), dev)
             wsi = torch.empty(_hip.lib().cf_flow_step_inv_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
             _hip.call("cf_flow_step_inv_prepare", pp(f(conv.NN.detach())), pp(f(act.NN_t.detach())), pp(f(act.NN_logs.detach())),
                       pp(wsi), C, H, W, st)
-            if not capturing:
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(dev))
-                cache[id(cpl)] = (ver, ws, wsi, ev)
+            return ws, wsi
+        ws, wsi = _derived.get(self, ("inv_ws", id(cpl)), _derived.key(srcs, C, H, W, str(dev)), build, dev)
         x = torch.empty((B, C // 4, 2 * H, 2 * W) if unsqueeze else (B, C, H, W), device=dev, dtype=torch.float32)
         events = self.inv_events
         if events is not None:               # HIP events on the launch stream, bracketing exactly this kernel

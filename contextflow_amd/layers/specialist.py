@@ -18,10 +18,10 @@ import os
 
 import torch
 
-from . import _hip
+from . import _derived, _hip
 from .actnorm import ActNorm
 from .conv1x1 import Conv1x1, slogdet_inverse
-from .coupling import Coupling
+from .coupling import Coupling, identity_front_step_tables
 from .dequantize import Dequantization
 from .distributions.gaussian import StandardNormal
 from .distributions.uniform import UniformDistribution
@@ -74,34 +74,15 @@ def _affine_ok(conv, act, shape):
 
 def _coupling_ws(flow, cpl, C, H, W, dev):
     """Packed weights of the coupling step (identity 1x1 / ActNorm in front), kept while the conditioner is unchanged."""
-    convs = (cpl.NN[0], cpl.NN[2], cpl.NN[4])
-    srcs = tuple(p for c in convs for p in (c.weight, c.bias))
-    ver = tuple(t._version for t in srcs) + tuple(t.data_ptr() for t in srcs) + (C, H, W, str(dev))
-    cache = flow.__dict__.setdefault("_spec_ws", {})
-    hit = cache.get(id(cpl))
-    if hit is not None and hit[0] == ver:
-        return hit[1]
-    f, pp = _hip.f32, _hip.p
-    eye = torch.eye(C, device=dev, dtype=torch.float32)
-    zero = torch.zeros(C, device=dev, dtype=torch.float32)
-    ws = torch.empty(_hip.lib().cf_flow_step_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
-    _hip.call("cf_flow_step_prepare", pp(eye), pp(zero), pp(zero), pp(f(convs[0].weight.detach())), pp(f(convs[0].bias.detach())),
-              pp(f(convs[1].weight.detach())), pp(f(convs[1].bias.detach())), pp(f(convs[2].weight.detach())),
-              pp(f(convs[2].bias.detach())), pp(ws), C, H, W, _hip.stream())
-    cache[id(cpl)] = (ver, ws)
-    return ws
+    srcs = tuple(p for c in (cpl.NN[0], cpl.NN[2], cpl.NN[4]) for p in (c.weight, c.bias))
+    return _derived.get(flow, ("spec_ws", id(cpl)), _derived.key(srcs, C, H, W, str(dev)),
+                        lambda: identity_front_step_tables(cpl, _hip.f32(srcs[0].detach()), C, H, W, dev), dev)
 
 
 def _lad(flow, conv, dev):
     """log|det NN| of a frozen Conv1x1 (device scalar), kept while NN is unchanged."""
-    cache = flow.__dict__.setdefault("_spec_lad", {})
-    ver = (conv.NN._version, conv.NN.data_ptr(), str(dev))
-    hit = cache.get(id(conv))
-    if hit is not None and hit[0] == ver:
-        return hit[1]
-    lad, _ = slogdet_inverse(_hip.f32(conv.NN.detach()), False)
-    cache[id(conv)] = (ver, lad)
-    return lad
+    return _derived.get(flow, ("spec_lad", id(conv)), _derived.key((conv.NN,), str(dev)),
+                        lambda: slogdet_inverse(_hip.f32(conv.NN.detach()), False)[0], dev)
 
 
 def blocked_rows(C):
@@ -118,16 +99,12 @@ def blocked_rows(C):
 def _cn_blocked(flow, conv, C, dev):
     """Conv1x1.CN with its rows in blocked order (weight (Nc, width), bias (Nc)), kept while the CN parameters are unchanged:
     the blocks above the diagonal of the per-sample matrix are never computed, written or read."""
-    cache = flow.__dict__.setdefault("_spec_cnb", {})
     w, b = conv.CN.weight, conv.CN.bias
-    ver = (w._version, b._version, w.data_ptr(), b.data_ptr(), str(dev))
-    hit = cache.get(id(conv))
-    if hit is not None and hit[0] == ver:
-        return hit[1], hit[2]
-    idx = torch.tensor(blocked_rows(C), device=dev, dtype=torch.long)
-    wp, bp = _hip.f32(w.detach())[idx].contiguous(), _hip.f32(b.detach())[idx].contiguous()
-    cache[id(conv)] = (ver, wp, bp)
-    return wp, bp
+
+    def build():
+        idx = torch.tensor(blocked_rows(C), device=dev, dtype=torch.long)
+        return _hip.f32(w.detach())[idx].contiguous(), _hip.f32(b.detach())[idx].contiguous()
+    return _derived.get(flow, ("spec_cnb", id(conv)), _derived.key((w, b), str(dev)), build, dev)
 
 
 def supported(flow):

@@ -845,7 +845,9 @@ def test_inverse_step_tables_follow_the_parameters(L):
     torch.manual_seed(1)
     z = model.dist.sample(9)[0]
     a, b = model.inverse(z), model.inverse(z)
-    assert torch.equal(a, b) and len(model.__dict__["_inv_ws"]) >= 2
+    def inv_slots():
+        return [s for s in model.__dict__["_derived"] if s[0] == "inv_ws"]
+    assert torch.equal(a, b) and len(inv_slots()) >= 2
     from contextflow_amd.layers import ActNorm, Conv1x1, Coupling
     mods = list(model.sequence_modules)
     conv = next(m for m in mods if isinstance(m, Conv1x1))
@@ -856,13 +858,15 @@ def test_inverse_step_tables_follow_the_parameters(L):
         act.NN_t.add_(0.05)
         cpl.NN[2].weight.mul_(0.9)
     c = model.inverse(z)                       # the version counters moved: the three steps concerned are packed again
-    model.__dict__.pop("_inv_ws")
+    for s in inv_slots():
+        del model.__dict__["_derived"][s]
     d = model.inverse(z)                       # everything packed from scratch
     assert torch.equal(c, d) and not torch.equal(a, c)
     conv.NN.data.mul_(0.5)                     # a write the version counter does not see
     model.invalidate_caches()
     e = model.inverse(z)
-    model.__dict__.pop("_inv_ws")
+    for s in inv_slots():
+        del model.__dict__["_derived"][s]
     assert torch.equal(e, model.inverse(z)) and not torch.equal(e, c)
 
 
@@ -1488,6 +1492,66 @@ def test_user_side_capture_with_a_cold_cache_leaves_no_stale_entries(L):
         torch.cuda.synchronize()
         assert torch.equal(captured, ref)
         assert torch.equal(model.log_prob(xd), ref)                     # eager call afterwards: own tables, same numbers
+
+
+def _specialist_eval_model(fxname):
+    """(model with every noise source fixed, x, context) of a specialist fixture, on the device."""
+    import contextflow_amd as cfa
+    from tests.gpu_util import set_noise
+    from tests.helpers import load_specialist
+    name, ctx, ops, M, params, inp = load_specialist(fxname)
+    cfg, ds, MM = cfa.preset_config(name)
+    cfg.update(generalist=False, enc_emb=ctx["enc_emb"], enc_type=ctx.get("enc_type", "uniform"), contextflow=ctx["contextflow"])
+    model = cfa.create_model(cfg, ds, MM, contexts=ctx["contexts"])
+    model.load_state_dict(params, strict=True)
+    model = model.to(DEV).eval()
+    set_noise(model, inp["u"], inp["eps"])
+    encs = [m for m in model.modules() if isinstance(m, cfa.layers.UniformCatDequantization)]
+    assert len(encs) == len(inp["cnoise"])
+    for e, c in zip(encs, inp["cnoise"]):
+        e.fixed_noise = c.to(DEV)
+    return model, inp["x"].to(DEV), inp["context"].to(DEV)
+
+
+def test_parameter_derived_tables_are_built_once_per_parameter_version(L):
+    """Every table derived from parameter values (layers/_derived.py, and the `_prep` entries of the fused forward) is built by
+    the first call and kept: the second `log_prob`, the second `inverse` and the second specialist evaluation forward launch no
+    entry point whose name contains `prepare` and no cf_gmm_ctx_tables.  An in-place update of one Conv1x1 matrix brings the
+    prepare launches back for exactly one call, and so does `invalidate_caches()`.  (The bitwise tests cannot see a change that
+    quietly stops caching: same numbers, more launches.)"""
+    from tests.gpu_util import build_model, set_noise
+    ops, _, M, params, fx = load_e2e("mnist")
+    x, u, eps = e2e_inputs("mnist", fx)
+    xd = x.to(DEV)
+    model = build_model("mnist", params)
+    set_noise(model, u, eps)
+    model.auto_graph = False
+    spec, xs, cs = _specialist_eval_model("mnist_eye_cf")
+    torch.manual_seed(1)
+    z = model.dist.sample(9)[0]
+    log = []
+
+    def builds(run):
+        del log[:]
+        run()
+        return [n for n in log if "prepare" in n or n == "cf_gmm_ctx_tables"]
+    undo = _hip_call_counter(log)
+    try:
+        with torch.no_grad():
+            for run in (lambda: model.log_prob(xd), lambda: model.inverse(z)):
+                assert builds(run) and not builds(run)
+            first = builds(lambda: spec(xs, cs))
+            assert "cf_flow_step_prepare" in first and "cf_gmm_ctx_tables" in first, first
+            assert not builds(lambda: spec(xs, cs))
+            conv = next(m for m in model.sequence_modules if isinstance(m, L.Conv1x1))
+            conv.NN.mul_(1.03)
+            for run in (lambda: model.log_prob(xd), lambda: model.inverse(z)):
+                assert builds(run) and not builds(run)
+            model.invalidate_caches()
+            spec.invalidate_caches()
+            assert builds(lambda: model.log_prob(xd)) and builds(lambda: model.inverse(z)) and builds(lambda: spec(xs, cs))
+    finally:
+        undo()
 
 
 def test_auto_graph_keeps_eager_where_replay_loses(L):
