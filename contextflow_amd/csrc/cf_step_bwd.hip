@@ -2,17 +2,19 @@
 // path (contextflow/experiment_cl.py:130-136 `cost.backward()`), as ONE gfx950 kernel per step.
 //
 // What the data-gradient chain needs of the forward - y1, the log-scale and the two ReLU masks - comes from the tape the
-// training forward wrote (TAPED, the default: cf_flow_step_fwd_taped; no step input, no recompute), or is recomputed from
-// the step input in LDS with the forward's own code (invertible flow: nothing else stored).  Then, on the fp32 matrix
-// cores with TRANSPOSED weight fragments:
+// training forward wrote (the generalist: cf_flow_step_fwd_taped; no step input, no recompute), or - the specialist coupling
+// under contextflow, whose generalist weights are frozen - is recomputed from the step input in LDS with the forward's own
+// code.  (A generalist step whose tape was not kept re-runs the taping FORWARD kernel first: layers/autograd.py
+// step_backward.)  Then, on the fp32 matrix cores with TRANSPOSED weight fragments:
 //     g_h   = [ g_z1 ,  (g_z1 * y1 * e^{ls} + g_ld) * (1 - (ls/2)^2) ]           affine map + log-det
 //     g_h2  = (NN.4^T g_h)            * [h2 > 0]
 //     g_h1  = (NN.2^T (*) g_h2)       * [h1 > 0]     3x3 transposed conv = adjoint of the reflect-padded gather
 //     g_y0  =  NN.0^T g_h1 + g_z0 ;   g_y1 = g_z1 * e^{ls}
 //     g_x   = (e^{-logs} Wm)^T g_y
-// and writes, next to g_x, the gradient planes the weight gradients contract over (g_h, g_h2, g_h1, g_y; in the recompute
-// form also y0, h1, h2).  The weight gradients themselves are split-K MFMA GEMMs over (sample, pixel): cf_wgrad.hip,
-// called from contextflow_amd/layers/autograd.py.  ReLU masks are 16-bit lane masks in registers.
+// and writes, next to g_x, the gradient planes the weight gradients contract over (taped form: g_h, g_h2, g_h1, g_y; their
+// other operands y0, h1, h2 are the tape's; recompute form: g_h only).  The weight gradients themselves are split-K MFMA
+// GEMMs over (sample, pixel): cf_wgrad.hip, called from contextflow_amd/layers/autograd.py.  ReLU masks are 16-bit lane masks
+// in registers.
 // The adjoint of the reflected gather reads, per tap, ONE source per operand: every LDS plane row carries the fold sums of
 // its border rows / columns behind its pixels (PATCH geometries, see patch_build below); 4x4 images keep the class-by-class
 // weighted sums (adj_tap<NS>).
@@ -226,13 +228,16 @@ __device__ __forceinline__ void adj_axis(int c, int d, int N, int (&src)[2], boo
     src[1] = ok[1] ? e : 0;
 }
 
-// CTX = 1: specialist coupling under contextflow (coupling.py:44): the conditioner output carries a per-sample bias
-// sb (B, C) = CN(c); only its log-scale half matters for the recompute (t does not enter any gradient); d/d sb is the
-// per-sample row sum of the s_gh plane, taken by the caller.  The generalist's weights are frozen in that mode, so the
-// six operand planes of the weight-gradient GEMMs are not written at all (156 of 172 KB per sample at C = 16).
-// TAPED: s_y0 / s_h1 / s_h2 are INPUTS written by the training forward (cf_flow_step_fwd_taped): h1 / h2 are loaded for
-// their ReLU masks and as the operand of phase 3, the two big contractions of the recompute (phases 1, 2) are skipped.
-template <class G, bool SQ, int CTX = 0, bool TAPED = false>
+// The kernel has two forms:
+// CTX = false, the generalist (cf_flow_step_bwd_taped): log-scale, y1 and the two ReLU masks are read from the tape tp that
+// the training forward wrote - no step input (x, ws, sb unused), no recompute; all four gradient planes are written.
+// CTX = true, the specialist coupling under contextflow (cf_flow_step_bwd_ctx; coupling.py:44): the forward is re-run from x
+// in LDS, and the conditioner output carries a per-sample bias sb (B, C) = CN(c); only its log-scale half matters for the
+// recompute (t does not enter any gradient); d/d sb is the per-sample row sum of the s_gh plane, taken by the caller.  The
+// generalist's weights are frozen in that mode, so of the operand planes of the weight-gradient GEMMs only s_gh is written
+// (156 of 172 KB per sample at C = 16 are not).
+// Neither form touches s_y0 / s_h1 / s_h2: they stay in the argument list that the two entry points share.
+template <class G, bool CTX>
 __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
     const float* __restrict__ x, const float* __restrict__ gz, const float* __restrict__ gld,
     const float* __restrict__ ws, const float* __restrict__ wsb, float* __restrict__ gx,
@@ -240,6 +245,7 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
     float* __restrict__ s_gh2, float* __restrict__ s_gh1, float* __restrict__ s_gy, int B, int64_t xbs,
     const float* __restrict__ sb, StepTape tp, int gx_unsq) {
     using Bw = GeoBwd<G>;
+    constexpr bool TAPED = !CTX;
     constexpr int C = G::C, HW = G::HW, W = G::W, H = G::H, RS = G::RS, HALF = G::HALF, HID = G::HID;   // RS: row stride of the LDS planes
     constexpr int PTW = G::PTW, RT03 = G::RT03, RT1 = G::RT1, NR = (HALF <= 16 ? 8 : 16);
     constexpr int XI = C * PTW / 8;
@@ -256,7 +262,7 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
 
     // ---------------------------------------------------------------- what the data-gradient chain needs of the forward
     // y1 (second half of the Conv1x1 + ActNorm output), ls (log-scale) in the packed-row register layout, and the ReLU
-    // masks of h1 / h2, one bit per accumulator register.  TAPED: all four were written by the training forward
+    // masks of h1 / h2, one bit per accumulator register.  TAPED (the generalist): all four were written by the training forward
     // (StepTape: ls / y1 as (B, C/2, HW) planes read 128 contiguous bytes per row and half wave, the masks as words in
     // exactly this layout) - no step input, no recompute.  Otherwise: the forward is re-run from x in LDS.
     float y1[PTW][NR], ls[PTW][NR];
@@ -298,8 +304,8 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
     } else {
     {
         float4 xr[XI];
-        x_load<G, SQ>(xr, x, xbs, tile, B, wave, lane);
-        x_to_lds<G, SQ>(xr, H1, wave, lane);
+        x_load<G, false>(xr, x, xbs, tile, B, wave, lane);
+        x_to_lds<G, false>(xr, H1, wave, lane);
         f32x16 acc0[RT03][PTW];
 #pragma unroll
         for (int rt = 0; rt < RT03; ++rt)
@@ -311,10 +317,9 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
 #pragma unroll
             for (int r = 0; r < NR; ++r) {
                 const int idx = tile_row(r, lk);
-                if constexpr (!TAPED) { if (idx < HALF) Y0[idx * RS + pix[q]] = acc0[0][q][r]; }   // operand of phase 1
+                if (idx < HALF) Y0[idx * RS + pix[q]] = acc0[0][q][r];   // operand of phase 1
                 y1[q][r] = (HALF <= 16) ? acc0[0][q][r + 8] : acc0[RT03 - 1][q][r];
             }
-        if constexpr (CTX == 0 && !TAPED) rows_store_t<G, HALF, HALF>(s_y0, Y0, b0, B, wave, lane);   // weight-gradient operand plane
     }
     {   // phase 1
         f32x16 acc[RT1][PTW];
@@ -338,7 +343,6 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
                 m1[rt][q] = m;
             }
         tiles_to_plane<G, RT1>(acc, H1, HID, pix, lk);
-        if constexpr (CTX == 0) rows_store_t<G, HID, HID>(s_h1, H1, b0, B, wave, lane);   // weight-gradient operand plane
     }
     __syncthreads();                     // h1 complete (taps cross waves)
     {   // phase 2 (compiler-scheduled form; the backward is not yet tuned per shape)
@@ -399,7 +403,6 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
                 m2[rt][q] = m;
             }
         tiles_to_plane<G, RT1>(acc, H1, HID, pix, lk);
-        if constexpr (CTX == 0) rows_store_t<G, HID, HID>(s_h2, H1, b0, B, wave, lane);   // weight-gradient operand plane
     }
     // phase 3 -> t, raw
     {
@@ -414,10 +417,8 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
 #pragma unroll
             for (int r = 0; r < NR; ++r) {
                 float raw = (HALF <= 16) ? acc3[0][q][r + 8] : acc3[RT03 - 1][q][r];
-                if constexpr (CTX == 1) {
-                    const int idx = tile_row(r, lk);
-                    if (idx < HALF) raw += sb[(int64_t)min(b0 + pix[q] / HW, B - 1) * C + HALF + idx];
-                }
+                const int idx = tile_row(r, lk);
+                if (idx < HALF) raw += sb[(int64_t)min(b0 + pix[q] / HW, B - 1) * C + HALF + idx];
                 ls[q][r] = cf_log_scale(raw);
             }
     }
@@ -446,7 +447,7 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
             }
         }
         rows_store_t<G, C, C>(s_gh, GH, b0, B, wave, lane);
-        if constexpr (CTX == 0) rows_store_t<G, HALF, C>(s_gy + HALF * HW, Y0, b0, B, wave, lane);   // g_y1 rows of the g_y plane
+        if constexpr (!CTX) rows_store_t<G, HALF, C>(s_gy + HALF * HW, Y0, b0, B, wave, lane);   // g_y1 rows of the g_y plane
         // g_h2 = (NN.4^T g_h) * [h2 > 0]
         f32x16 acc[RT1][PTW];
 #pragma unroll
@@ -464,7 +465,7 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
                 for (int r = 0; r < 16; ++r)
                     if (!((m2[rt][q] >> r) & 1u)) acc[rt][q][r] = 0.f;
         tiles_to_plane<G, RT1>(acc, H1, HID, pix, lk);       // g_h2 plane over the whole H region (own columns)
-        if constexpr (CTX == 0) rows_store_t<G, HID, HID>(s_gh2, H1, b0, B, wave, lane);   // weight-gradient operand plane
+        if constexpr (!CTX) rows_store_t<G, HID, HID>(s_gh2, H1, b0, B, wave, lane);   // weight-gradient operand plane
     }
     // g_z0, the start value of the g_y0 accumulators two phases on (rows of that single tile = channels 0..31 in natural
     // order; 128 contiguous bytes per row and half wave): in flight during the transposed 3x3
@@ -602,7 +603,7 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
                 for (int r = 0; r < 16; ++r)
                     if (!((m1[rt][q] >> r) & 1u)) acc[rt][q][r] = 0.f;
         tiles_to_plane<G, RT1>(acc, H1, HID, pix, lk);       // g_h1 plane
-        if constexpr (CTX == 0) rows_store_t<G, HID, HID>(s_gh1, H1, b0, B, wave, lane);   // weight-gradient operand plane
+        if constexpr (!CTX) rows_store_t<G, HID, HID>(s_gh1, H1, b0, B, wave, lane);   // weight-gradient operand plane
     }
     {   // g_y0 = NN.0^T g_h1 + g_z0: the accumulators start from g_z0 (requested before the transposed 3x3)
         f32x16 (&acc)[1][PTW] = accy;
@@ -617,7 +618,7 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
                 const int row = tile_row(r, lk);
                 if (row < HALF) H1[row * RS + pix[q]] = acc[0][q][r];
             }
-        if constexpr (CTX == 0) rows_store_t<G, HALF, C>(s_gy, H1, b0, B, wave, lane);   // g_y0 rows (weight-gradient operand plane)
+        if constexpr (!CTX) rows_store_t<G, HALF, C>(s_gy, H1, b0, B, wave, lane);   // g_y0 rows (weight-gradient operand plane)
         // g_x = (e^{-logs} Wm)^T g_y
         f32x16 ax[Bw::RTI][PTW];
 #pragma unroll
@@ -842,16 +843,16 @@ int launch_prepare_bwd(const StepPackBwdBatch& pb, int n, hipStream_t s) {
     return 0;
 }
 
-template <class G, bool SQ, int CTX = 0, bool TAPED = false>
+template <class G, bool CTX>
 int launch_step_bwd(const float* x, const float* gz, const float* gld, const float* ws, const float* wsb, float* gx,
                     float* s_y0, float* s_h1, float* s_h2, float* s_gh, float* s_gh2, float* s_gh1, float* s_gy, int B,
                     int64_t xbs, hipStream_t s, const float* sb = nullptr, StepTape tp = kNoTape, int gx_unsq = 0) {
     constexpr size_t lds_bytes = (size_t)G::LDS_FLOATS * sizeof(float);
     if (lds_bytes > 64 * 1024) {
         static std::atomic<uint64_t> raised{0};
-        if (int rc_ = cf_raise_dynamic_lds((const void*)k_flow_step_bwd<G, SQ, CTX, TAPED>, 160 * 1024, raised, __func__)) return rc_;
+        if (int rc_ = cf_raise_dynamic_lds((const void*)k_flow_step_bwd<G, CTX>, 160 * 1024, raised, __func__)) return rc_;
     }
-    k_flow_step_bwd<G, SQ, CTX, TAPED><<<dim3((B + G::SPW - 1) / G::SPW), dim3(256), lds_bytes, s>>>(
+    k_flow_step_bwd<G, CTX><<<dim3((B + G::SPW - 1) / G::SPW), dim3(256), lds_bytes, s>>>(
         x, gz, gld, ws, wsb, gx, s_y0, s_h1, s_h2, s_gh, s_gh2, s_gh1, s_gy, B, xbs, sb, tp, gx_unsq);
     return 0;
 }
@@ -921,8 +922,8 @@ int cf_flow_step_bwd_taped(const float* gz, const float* gld, const void* wsb, c
     const float* wb = (const float*)wsb;
     const StepTape tp = make_tape(nullptr, nullptr, nullptr, const_cast<void*>(t_aux), B, C, H, W);
     int rc = 0;
-#define CF_BWDT(G) rc = launch_step_bwd<G, false, 0, true>(nullptr, gz, gld, nullptr, wb, gx, nullptr, nullptr, nullptr, s_gh, s_gh2, \
-                                                           s_gh1, s_gy, B, (int64_t)C * H * W, cf_s(stream), nullptr, tp, gx_unsqueezed != 0)
+#define CF_BWDT(G) rc = launch_step_bwd<G, false>(nullptr, gz, gld, nullptr, wb, gx, nullptr, nullptr, nullptr, s_gh, s_gh2, \
+                                                s_gh1, s_gy, B, (int64_t)C * H * W, cf_s(stream), nullptr, tp, gx_unsqueezed != 0)
     switch (shape_id(C, H, W)) {
         case 0: CF_BWDT(B8); break;
         case 1: CF_BWDT(B16); break;
@@ -953,7 +954,7 @@ int cf_flow_step_bwd_ctx(const float* x, const float* gz, const float* gld, cons
     const float* w = (const float*)ws;
     const float* wb = (const float*)wsb;
     int rc = 0;
-#define CF_BWDC(G) rc = launch_step_bwd<G, false, 1>(x, gz, gld, w, wb, gx, s_y0, s_h1, s_h2, s_gh, s_gh2, s_gh1, s_gy, B, x_bstride, cf_s(stream), sbias)
+#define CF_BWDC(G) rc = launch_step_bwd<G, true>(x, gz, gld, w, wb, gx, s_y0, s_h1, s_h2, s_gh, s_gh2, s_gh1, s_gy, B, x_bstride, cf_s(stream), sbias)
     switch (shape_id(C, H, W)) {
         case 0: CF_BWDC(B8); break;
         case 1: CF_BWDC(B16); break;

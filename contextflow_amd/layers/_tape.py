@@ -1,0 +1,77 @@
+"""Records of the training tape: FlowSequential._forward_fused writes one per plan group, autograd.FlowLogProb.backward walks
+them in reverse and dispatches on `kind` (a class attribute: nothing per record).  Fields that only a training forward on the
+device knows default to None, so a tape can be laid out from the modules alone (autograd._bucket_for)."""
+from typing import Any, NamedTuple
+
+import torch
+
+from . import _hip
+
+
+def step_tape(B, C, H, W, dev):
+    """Buffers of one step's training tape (cf_flow_step_fwd_taped): y0 (B, C/2, HW), h1, h2 (B, 2C, HW) - the operands of
+    the weight-gradient GEMMs - and the opaque aux buffer (log-scales, second half of the Conv1x1+ActNorm output, ReLU
+    masks) that is all the step-backward kernel reads of the forward."""
+    planes = [torch.empty(B, r, H * W, device=dev, dtype=torch.float32) for r in (C // 2, 2 * C, 2 * C)]
+    planes.append(torch.empty(_hip.lib().cf_flow_step_tape_aux_bytes(B, C, H, W), device=dev, dtype=torch.uint8))
+    return tuple(planes)
+
+
+class Pre(NamedTuple):
+    """pre-processing: nothing trainable at or above it"""
+    kind = "pre"
+
+
+class Step(NamedTuple):
+    """[Squeeze ->] Conv1x1 -> ActNorm -> Coupling in one kernel"""
+    kind = "step"
+    conv: Any
+    act: Any
+    cpl: Any
+    shape: tuple             # (C, H, W) of the step (behind its Squeeze)
+    squeeze: Any             # truthy: x is the tensor in front of the Squeeze
+    x: Any = None            # step input
+    ws: Any = None           # packed forward tables
+    winv: Any = None         # Wm^-1
+    planes: Any = None       # step_tape(...) of the forward, or None = rebuilt from x at backward time
+    wsb: Any = None          # packed backward tables
+
+
+class VStep(NamedTuple):
+    """Conv1x1 -> ActNorm -> TransCoupling in one kernel"""
+    kind = "vstep"
+    conv: Any
+    act: Any
+    cpl: Any
+    x: Any = None
+    ws: Any = None           # packed row-split tables, or None = the forward ran the wave form
+    xtape: Any = None        # residual-stream tape, or None = recomputed
+    winv: Any = None
+    wsb: Any = None
+
+
+class Squeeze(NamedTuple):
+    kind = "squeeze"
+    p: tuple
+
+
+class Split(NamedTuple):
+    """SplitPrior: x is the full tensor before the split"""
+    kind = "split"
+    dist: Any
+    x: Any = None
+    prepared: Any = None
+
+
+class Prior(NamedTuple):
+    kind = "prior"
+    dist: Any
+    x: Any = None
+    prepared: Any = None
+
+
+class Layer(NamedTuple):
+    """any other layer, run by its own kernels (autograd_layers.layer_backward)"""
+    kind = "layer"
+    module: Any
+    x: Any = None

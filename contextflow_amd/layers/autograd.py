@@ -13,44 +13,37 @@ Backward walks the tape in reverse:
   * Squeeze / SplitPrior / Augment : index maps (squeeze kernel with `inverse`, concatenation).
 Reference quirks carried into the gradients: ActNorm's ldj = +sum(logs) (d/dlogs gets sum_b g_ld), Conv1x1's
 ldj = H*W*log|det W| (d/dW gets sum_b g_ld * H*W * W^-T).  Layers that run layer by layer in the plan (TransCoupling + its ViT,
-Conv1x1 / ActNorm of other shapes, Augment: the SMAP topology) go through autograd_layers.py.  Weight-gradient partial sums are combined in a fixed order (no float atomics)."""
+Conv1x1 / ActNorm of other shapes, Augment: the SMAP topology) go through autograd_layers.py.  Weight-gradient partial sums are combined in a fixed order (no float atomics).
+
+The tape is a list of the named records of _tape.py.  A record's backward has a data half (the chain to the record before, on
+the main stream) and a parameter half (at small batches on a side stream).  The parameter half of a conv step is ONE function
+over n steps (_step_param_part_batch: the steps of a resolution level at small batches, a single step otherwise), fed by named
+items (StepWork); the Conv1x1 / ActNorm chain that closes it is shared with the transformer steps (_affine_param_grads)."""
+import contextlib
+import ctypes
+from collections import namedtuple
+
 import torch
 
 from . import _hip
+from ._tape import step_tape
 from .autograd_layers import layer_backward
 from .squeeze import squeeze_op
 
 
-
-def _param_part_on(side, keep, alive, fn, defer, dev):
+def _param_part_on(side, keep, alive, fn, dev):
     """Run fn() - the parameter half of a record's backward - on the stream `side`, behind what the current stream has been
-    given so far; `alive` (what it reads) goes to `keep`.  With `defer` (a list) the launch is POSTPONED: a thunk that does it
-    is appended and None returned - the caller runs the thunk once it has issued the next record's kernels on the main
-    stream.  (A captured HIP graph runs its nodes on a few hardware queues in creation order, and a node that waits for a node of
-    another queue waits for everything created on that queue before the waiter: created right behind its backward kernel, a
-    step's weight-gradient chain held up the NEXT step's backward kernel - tools/dev/step_timeline.py.)"""
-    import contextlib
+    given so far; `alive` (what it reads) goes to `keep`."""
     if side is None:
         return fn()
-    main = torch.cuda.current_stream(dev)
     keep.append(alive)
-    if defer is None:
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            return fn()
-    ev = torch.cuda.Event()
-    ev.record(main)
-
-    def thunk():
-        side.wait_event(ev)
-        with torch.cuda.stream(side):
-            return fn()
-    defer.append(thunk)
-    return None
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        return fn()
 
 
 # ------------------------------------------------------------------------------------------------ GMM prior
-def gmm_backward(x, dist, prepared, g, gcol=None, side=None, keep=None, sink=None, defer=None):
+def gmm_backward(x, dist, prepared, g, gcol=None, side=None, keep=None, sink=None):
     """x: (B, D...) possibly a channel slice; g: (B, M) upstream; gcol: its column sums (M,) if the caller has them (the
     priors of one backward pass share g).  Returns (gx like x, {param: grad})."""
     a, nm, cst, M, K, D = prepared
@@ -76,7 +69,7 @@ def gmm_backward(x, dist, prepared, g, gcol=None, side=None, keep=None, sink=Non
     # over the samples (cf_linear_wgrad: the bias-gradient column gives S0; x is squared while it is staged for S2)
     # (small batches: on the side stream - the chain to the previous layer needs gx only)
     return gx.view(xv.shape), _param_part_on(side, keep, (xv, r, a, nm, gcol),
-                                             lambda: _gmm_param_part(xv, xbs, r, dist, a, nm, g, gcol, B, M, K, D, dev, sink), defer, dev)
+                                             lambda: _gmm_param_part(xv, xbs, r, dist, a, nm, g, gcol, B, M, K, D, dev, sink), dev)
 
 
 def _out(sink, p, shape, dev):
@@ -116,23 +109,34 @@ def _gmm_param_part(xv, xbs, r, dist, a, nm, g, gcol, B, M, K, D, dev, sink=None
 # ------------------------------------------------------------------------------------------------ flow step
 WGRAD_SIDE_MAX_BATCH = 1024      # below: the weight gradients of a step run on a side stream, next to the data-gradient chain
 WGRAD_SIDE_STREAMS = int(__import__("os").environ.get("CONTEXTFLOW_WGRAD_STREAMS", "4"))
-WGRAD_DEFER = __import__("os").environ.get("CONTEXTFLOW_WGRAD_DEFER", "0") == "1"    # see _param_part_on (measured: slower)
 WGRAD_BATCH = __import__("os").environ.get("CONTEXTFLOW_WGRAD_BATCH", "1") == "1"    # see _step_param_part_batch
 
 
-def step_backward(x, squeeze, conv, act, cpl, shape, ws, gz, gld, winv=None, planes=None, gsum=None, side=None, keep=None, wsb=None,
-                  sink=None, defer=None, collect=None):
-    """x: saved step input (un-squeezed when `squeeze`), gz: dL/dz (B,C,H,W), gld: dL/d(ld1) (B,).
-    planes: the step tape (y0, h1, h2, aux) written by cf_flow_step_fwd_taped, or None = rebuild it from x with the same kernel.
+# Conv1x1 -> ActNorm in front of a coupling with what their parameter chain reads (_affine_param_grads): Wm = conv.NN, t = act.NN_t,
+# logs = act.NN_logs as dense fp32; winv = Wm^-1 from the training forward, or None = inverted in the chain
+Affine = namedtuple("Affine", "conv act Wm t logs winv")
+# What the parameter half of one conv step reads (step_backward writes it, _step_param_part_batch reads it): x = the step input, read
+# in place (batch stride xbs; the tensor in front of the step's Squeeze when `squeeze`); gh (B, C, HW), gh2, gh1 (B, 2C, HW),
+# gy (B, C, HW) = the gradient planes the backward kernel wrote; h2, h1 (B, 2C, HW), y0 (B, C/2, HW) = the tape planes of the forward;
+# alive = what else has to live until the streams have joined
+StepWork = namedtuple("StepWork", "affine cpl shape x xbs squeeze gh gh2 gh1 gy h2 h1 y0 alive")
+
+
+def step_backward(rec, gz, gld, gsum=None, side=None, keep=None, sink=None, collect=None):
+    """rec: the step's tape record (_tape.Step; x un-squeezed when rec.squeeze; planes = the step tape (y0, h1, h2, aux) written
+    by cf_flow_step_fwd_taped, or None = rebuild it from x with the same kernel), gz: dL/dz (B,C,H,W), gld: dL/d(ld1) (B,).
     gsum: 1-element tensor sum(gld) (the same for every step of a backward pass), or None.
-    side / keep (small batches): the weight gradients and the parameter chain - which the data-gradient chain of the steps
-    before does not wait for - are launched on the stream `side` once the backward kernel has written its planes; what they
-    read is appended to `keep` (the caller holds it until it has joined the streams: a block handed back to the allocator could
-    be given out again on the main stream while the side stream still reads it).
-    Returns (dL/dx in the layout of x, {param: grad})."""
-    C, H, W = shape
-    HW, HALF, HID = H * W, C // 2, 2 * C
-    xv, xbs = _hip.bview(x)
+    The weight gradients and the parameter chain - which the data-gradient chain of the steps before does not wait for - are
+    either handed to the caller (`collect`, a list: the StepWork item is appended and None returned for the gradients; the
+    caller launches a level's items together) or launched now: on the stream `side` (small batches) once the backward kernel
+    has written its planes, what they read being appended to `keep` (the caller holds it until it has joined the streams: a
+    block handed back to the allocator could be given out again on the main stream while the side stream still reads it), or
+    on the current stream (side = None).  Both ways end in _step_param_part_batch.
+    Returns (dL/dx in the layout of x, {param: grad} | None)."""
+    conv, act, cpl, squeeze, winv, planes, wsb = rec.conv, rec.act, rec.cpl, rec.squeeze, rec.winv, rec.planes, rec.wsb
+    C, H, W = rec.shape
+    HW, HID = H * W, 2 * C
+    xv, xbs = _hip.bview(rec.x)
     B, dev = xv.shape[0], xv.device
     L = _hip.lib()
     f, pp, st = _hip.f32, _hip.p, _hip.stream()
@@ -153,117 +157,80 @@ def step_backward(x, squeeze, conv, act, cpl, shape, ws, gz, gld, winv=None, pla
         # that produced the loss, whichever form (Winograd / direct, by batch size) the dispatch chose for the 3x3.
         # (Round 2 rebuilt h2 inside the backward kernel in the direct form: under the Winograd forward, units within
         # rounding of zero got another mask bit and a tensor's gradient could differ by 1e-3..1e-2 of its largest entry.)
-        from .flowsequential import step_tape
         planes = step_tape(B, C, H, W, dev)
         zs = torch.empty(B, C, H, W, device=dev, dtype=torch.float32)
         lds = torch.zeros(B, device=dev, dtype=torch.float32)
-        _hip.call("cf_flow_step_fwd_taped", pp(xv), pp(zs), pp(lds), pp(ws), pp(planes[0]), pp(planes[1]), pp(planes[2]),
+        _hip.call("cf_flow_step_fwd_taped", pp(xv), pp(zs), pp(lds), pp(rec.ws), pp(planes[0]), pp(planes[1]), pp(planes[2]),
                   pp(planes[3]), B, C, H, W, xbs, int(squeeze), st)
         del zs, lds
     s_y0, s_h1, s_h2, aux = planes
     _hip.call("cf_flow_step_bwd_taped", pp(gzc), pp(f(gld)), pp(wsb), pp(aux), pp(gx), pp(s_gh), pp(s_gh2), pp(s_gh1),
               pp(s_gy), B, C, H, W, int(bool(squeeze)), st)
-    # ---- weight gradients: split-K MFMA GEMMs over (batch, pixel) with the 3x3 tap shifts, the four of a step in one call
-    # (cf_step_wgrads: four k_wgrad launches, ONE reduce launch)
+    work = StepWork(Affine(conv, act, Wm, t, logs, winv), cpl, (C, H, W), xv, xbs, squeeze, s_gh, s_gh2, s_gh1, s_gy, s_h2, s_h1,
+                    s_y0, (planes, wsb, gzc))
     if collect is not None:
-        # small batches: the parameter halves of the steps of a resolution level are launched TOGETHER once the level's
-        # backward kernels are in the queue (_step_param_part_batch); what they read travels in `collect`
-        collect.append((conv, act, cpl, (C, H, W), xv, xbs, squeeze, s_gh, s_gh2, s_gh1, s_gy, s_h2, s_h1, s_y0, Wm, t, logs, winv,
-                        (planes, wsb, gzc)))
+        collect.append(work)
         return gx, None
-    return gx, _param_part_on(side, keep, (s_gh, s_gh2, s_gh1, s_gy, planes, xv, wsb, gzc, winv, gsum),
-                              lambda: _step_param_part(conv, act, cpl, (C, H, W), xv, xbs, squeeze, s_gh, s_gh2, s_gh1, s_gy, s_h2, s_h1,
-                                                       s_y0, Wm, t, logs, winv, gsum, gld, B, dev, sink), defer, dev)
+    return gx, _param_part_on(side, keep, (work, gsum), lambda: _step_param_part_batch([work], gsum, gld, B, dev, sink), dev)[0]
 
 
-def _step_param_part(conv, act, cpl, shape, xv, xbs, squeeze, s_gh, s_gh2, s_gh1, s_gy, s_h2, s_h1, s_y0, Wm, t, logs, winv, gsum,
-                     gld, B, dev, sink=None):
-    """Second half of step_backward: the four weight gradients of the step and the Conv1x1 / ActNorm parameter chain."""
-    C, H, W = shape
-    HW, HALF, HID = H * W, C // 2, 2 * C
-    L = _hip.lib()
-    f, pp, st = _hip.f32, _hip.p, _hip.stream()
-    c1, c2, c3 = cpl.NN[0], cpl.NN[2], cpl.NN[4]
-    e = lambda *sh: torch.empty(*sh, device=dev, dtype=torch.float32)
-    o = lambda p, *sh: _out(sink, p, sh, dev)
-    gw3, gb3, gw2, gb2 = o(c3.weight, 1, C, HID), o(c3.bias, C), o(c2.weight, HID, HID, 3, 3), o(c2.bias, HID)
-    gw1, gb1, gWp, gbp = o(c1.weight, 1, HID, HALF), o(c1.bias, HID), e(1, C, C), e(C)
-    # the step input is read in place by the Conv1x1 weight gradient: through its batch stride (a channel slice after a
-    # SplitPrior) and, behind a Squeeze, through the squeeze index map - no squeezed / contiguous copy
-    wsw = torch.empty(L.cf_step_wgrads_ws_bytes(B, C, H, W), device=dev, dtype=torch.uint8)
-    _hip.call("cf_step_wgrads", pp(s_gh), pp(s_gh2), pp(s_gh1), pp(s_gy), pp(s_h2), pp(s_h1), pp(s_y0), pp(xv), pp(gw3), pp(gb3),
-              pp(gw2), pp(gb2), pp(gw1), pp(gb1), pp(gWp), pp(gbp), pp(wsw), B, C, H, W, xbs, int(bool(squeeze)), st)
-    gw3, gw1, gWp = gw3[0], gw1[0], gWp[0]
-    # ---- chain to Conv1x1 / ActNorm parameters (W' = diag(s) Wm, b' = -t s, s = exp(-logs)): one small kernel
-    if gsum is None:
-        gsum = gld.sum().reshape(1)
-    if winv is None:
-        lad = torch.empty(1, device=dev, dtype=torch.float32)
-        winv = torch.empty(C, C, device=dev, dtype=torch.float32)
-        _hip.call("cf_slogdet_inverse", pp(Wm), C, pp(lad), pp(winv), st)
-    gNN, gt, glogs = o(conv.NN, C, C), o(act.NN_t, C), o(act.NN_logs, C)
-    gWpc = gWp.contiguous()
-    _hip.call("cf_step_param_grads", pp(gWpc), pp(gbp), pp(Wm), pp(t), pp(logs), pp(f(winv)), pp(f(gsum)), HW, pp(gNN), pp(gt),
-              pp(glogs), C, st)
-    grads = {
-        conv.NN: gNN.view_as(conv.NN), act.NN_t: gt.view_as(act.NN_t), act.NN_logs: glogs.view_as(act.NN_logs),   # quirk: ldj = +sum(logs)
-        c1.weight: gw1.reshape(c1.weight.shape), c1.bias: gb1,
-        c2.weight: gw2, c2.bias: gb2,
-        c3.weight: gw3.reshape(c3.weight.shape), c3.bias: gb3,
-    }
-    return grads
-
-
-
-def _step_param_part_batch(items, gsum, gld, B, dev, sink=None):
-    """_step_param_part for the n steps of one shape in 6 - 7 launches instead of 6 n (cf_step_wgrads_batch: one launch per
-    product over all steps + one reduce; cf_step_param_grads_batch: one workgroup per step): at the reference's batch of 256
-    the parameter work of a backward pass is latency, not arithmetic.  Same kernels on the same operands: bitwise equal.
-    items: what step_backward collected.  Returns one {param: grad} per item."""
-    import ctypes
-    L = _hip.lib()
+def _affine_param_grads(affs, gWps, gbps, HW, gsum, gld, dev, sink=None):
+    """Chain to the Conv1x1 / ActNorm parameters of n steps of one width from the gradients of their folded matrix / bias
+    (W' = diag(s) Wm, b' = -t s, s = exp(-logs); gWps[i] (C, C), gbps[i] (C,), dense): one launch, one workgroup per step
+    (cf_step_param_grads_batch).  affs: [Affine].  Returns one {param: grad} per step."""
     f, pp, st, A = _hip.f32, _hip.p, _hip.stream(), _hip.ptr_array
-    C, H, W = items[0][3]
-    HW, HALF, HID = H * W, C // 2, 2 * C
-    e = lambda *sh: torch.empty(*sh, device=dev, dtype=torch.float32)
-    o = lambda p, *sh: _out(sink, p, sh, dev)
-    n = len(items)
-    outs = []
-    for (conv, act, cpl, _, xv, xbs, squeeze, s_gh, s_gh2, s_gh1, s_gy, s_h2, s_h1, s_y0, Wm, t, logs, winv, _alive) in items:
-        c1, c2, c3 = cpl.NN[0], cpl.NN[2], cpl.NN[4]
-        outs.append(dict(gw3=o(c3.weight, 1, C, HID), gb3=o(c3.bias, C), gw2=o(c2.weight, HID, HID, 3, 3), gb2=o(c2.bias, HID),
-                         gw1=o(c1.weight, 1, HID, HALF), gb1=o(c1.bias, HID), gWp=e(1, C, C), gbp=e(C),
-                         gNN=o(conv.NN, C, C), gt=o(act.NN_t, C), glogs=o(act.NN_logs, C),
-                         wsw=torch.empty(L.cf_step_wgrads_ws_bytes(B, C, H, W), device=dev, dtype=torch.uint8)))
-    col = lambda k: [it[k] for it in items]
-    oc = lambda k: [d[k] for d in outs]
-    xbs_arr = (ctypes.c_int64 * n)(*[int(it[5]) for it in items])
-    sq_arr = (ctypes.c_int * n)(*[int(bool(it[6])) for it in items])
-    _hip.call("cf_step_wgrads_batch", n, A(col(7)), A(col(8)), A(col(9)), A(col(10)), A(col(11)), A(col(12)), A(col(13)), A(col(4)),
-              A(oc("gw3")), A(oc("gb3")), A(oc("gw2")), A(oc("gb2")), A(oc("gw1")), A(oc("gb1")), A(oc("gWp")), A(oc("gbp")),
-              A(oc("wsw")), B, C, H, W, ctypes.cast(xbs_arr, ctypes.c_void_p), ctypes.cast(sq_arr, ctypes.c_void_p), st)
+    C = affs[0].Wm.shape[0]
     if gsum is None:
         gsum = gld.sum().reshape(1)
     winvs = []
-    for it in items:
-        winv = it[17]
+    for a in affs:
+        winv = a.winv
         if winv is None:
             lad = torch.empty(1, device=dev, dtype=torch.float32)
             winv = torch.empty(C, C, device=dev, dtype=torch.float32)
-            _hip.call("cf_slogdet_inverse", pp(it[14]), C, pp(lad), pp(winv), st)
+            _hip.call("cf_slogdet_inverse", pp(a.Wm), C, pp(lad), pp(winv), st)
         winvs.append(f(winv))
-    _hip.call("cf_step_param_grads_batch", n, A(oc("gWp")), A(oc("gbp")), A(col(14)), A(col(15)), A(col(16)), A(winvs), pp(f(gsum)), HW,
-              A(oc("gNN")), A(oc("gt")), A(oc("glogs")), C, st)
-    res = []
-    for it, d in zip(items, outs):
-        conv, act, cpl = it[0], it[1], it[2]
-        c1, c2, c3 = cpl.NN[0], cpl.NN[2], cpl.NN[4]
-        res.append({
-            conv.NN: d["gNN"].view_as(conv.NN), act.NN_t: d["gt"].view_as(act.NN_t), act.NN_logs: d["glogs"].view_as(act.NN_logs),
-            c1.weight: d["gw1"][0].reshape(c1.weight.shape), c1.bias: d["gb1"],
-            c2.weight: d["gw2"], c2.bias: d["gb2"],
-            c3.weight: d["gw3"][0].reshape(c3.weight.shape), c3.bias: d["gb3"],
-        })
+    gNN = [_out(sink, a.conv.NN, (C, C), dev) for a in affs]
+    gt = [_out(sink, a.act.NN_t, (C,), dev) for a in affs]
+    glogs = [_out(sink, a.act.NN_logs, (C,), dev) for a in affs]
+    _hip.call("cf_step_param_grads_batch", len(affs), A(gWps), A(gbps), A([a.Wm for a in affs]), A([a.t for a in affs]),
+              A([a.logs for a in affs]), A(winvs), pp(f(gsum)), HW, A(gNN), A(gt), A(glogs), C, st)
+    return [{a.conv.NN: n_.view_as(a.conv.NN), a.act.NN_t: t_.view_as(a.act.NN_t),
+             a.act.NN_logs: l_.view_as(a.act.NN_logs)}                         # quirk: ldj = +sum(logs)
+            for a, n_, t_, l_ in zip(affs, gNN, gt, glogs)]
+
+
+def _step_param_part_batch(items, gsum, gld, B, dev, sink=None):
+    """Second half of step_backward for the n steps of one shape: the four weight gradients of each step and its Conv1x1 /
+    ActNorm parameter chain in 6 - 7 launches instead of 6 n (cf_step_wgrads_batch: one launch per product over all steps +
+    one reduce; cf_step_param_grads_batch: one workgroup per step): at the reference's batch of 256 the parameter work of a
+    backward pass is latency, not arithmetic.  The library's single-step entry points are these with n = 1: same kernels on
+    the same operands, bitwise equal.  items: [StepWork].  Returns one {param: grad} per item."""
+    L = _hip.lib()
+    st, A = _hip.stream(), _hip.ptr_array
+    C, H, W = items[0].shape
+    HW, HALF, HID = H * W, C // 2, 2 * C
+    n = len(items)
+    nets = [(it.cpl.NN[0], it.cpl.NN[2], it.cpl.NN[4]) for it in items]
+    o = lambda p, *sh: _out(sink, p, sh, dev)
+    e = lambda *sh: torch.empty(*sh, device=dev, dtype=torch.float32)
+    gw3, gb3 = [o(c3.weight, 1, C, HID) for _, _, c3 in nets], [o(c3.bias, C) for _, _, c3 in nets]
+    gw2, gb2 = [o(c2.weight, HID, HID, 3, 3) for _, c2, _ in nets], [o(c2.bias, HID) for _, c2, _ in nets]
+    gw1, gb1 = [o(c1.weight, 1, HID, HALF) for c1, _, _ in nets], [o(c1.bias, HID) for c1, _, _ in nets]
+    gWp, gbp = [e(1, C, C) for _ in items], [e(C) for _ in items]
+    wsw = [torch.empty(L.cf_step_wgrads_ws_bytes(B, C, H, W), device=dev, dtype=torch.uint8) for _ in items]
+    # the step input is read in place by the Conv1x1 weight gradient: through its batch stride (a channel slice after a
+    # SplitPrior) and, behind a Squeeze, through the squeeze index map - no squeezed / contiguous copy
+    xbs_arr = (ctypes.c_int64 * n)(*[int(it.xbs) for it in items])
+    sq_arr = (ctypes.c_int * n)(*[int(bool(it.squeeze)) for it in items])
+    col = lambda name: A([getattr(it, name) for it in items])
+    _hip.call("cf_step_wgrads_batch", n, col("gh"), col("gh2"), col("gh1"), col("gy"), col("h2"), col("h1"), col("y0"), col("x"),
+              A(gw3), A(gb3), A(gw2), A(gb2), A(gw1), A(gb1), A(gWp), A(gbp), A(wsw), B, C, H, W,
+              ctypes.cast(xbs_arr, ctypes.c_void_p), ctypes.cast(sq_arr, ctypes.c_void_p), st)
+    res = _affine_param_grads([it.affine for it in items], gWp, gbp, HW, gsum, gld, dev, sink)
+    for i, (c1, c2, c3) in enumerate(nets):
+        res[i].update({c1.weight: gw1[i][0].reshape(c1.weight.shape), c1.bias: gb1[i], c2.weight: gw2[i], c2.bias: gb2[i],
+                       c3.weight: gw3[i][0].reshape(c3.weight.shape), c3.bias: gb3[i]})
     return res
 
 
@@ -298,13 +265,14 @@ def wgrad_group(members, dev, dests=None):
     return res
 
 
-def vstep_backward(x, conv, act, cpl, gz, gld, gsum=None, ws=None, xtape=None, side=None, keep=None, sink=None, winv=None, wsb=None,
-                   defer=None):
-    """Conv1x1 -> ActNorm -> TransCoupling (one fused step of the transformer flows) backwards: ONE kernel re-runs the step
-    from its input and walks back (cf_vit_step_bwd), ONE grouped launch contracts the 26 weight-gradient operand pairs it
-    leaves (cf_linear_wgrad_group), the LayerNorm gradients are column sums of its per-workgroup partials, and the Conv1x1 /
-    ActNorm chain is cf_step_param_grads - as for the conv flows.  Returns (dL/dx, {param: grad})."""
-    xv, xbs = _hip.bview(x)
+def vstep_backward(rec, gz, gld, gsum=None, side=None, keep=None, sink=None):
+    """Conv1x1 -> ActNorm -> TransCoupling (one fused step of the transformer flows, tape record _tape.VStep) backwards: ONE
+    kernel re-runs the step from its input and walks back (cf_vit_step_bwd), ONE grouped launch contracts the 26
+    weight-gradient operand pairs it leaves (cf_linear_wgrad_group), the LayerNorm gradients are column sums of its
+    per-workgroup partials, and the Conv1x1 / ActNorm chain is _affine_param_grads - as for the conv flows.
+    Returns (dL/dx, {param: grad})."""
+    conv, act, cpl, ws, xtape, wsb = rec.conv, rec.act, rec.cpl, rec.ws, rec.xtape, rec.wsb
+    xv, xbs = _hip.bview(rec.x)
     B, C = xv.shape[0], xv.shape[1]
     dev = xv.device
     vit = cpl.NN[0]
@@ -331,14 +299,13 @@ def vstep_backward(x, conv, act, cpl, gz, gld, gsum=None, ws=None, xtape=None, s
     # ---- weight gradients: the planes as (rows, width) matrices (layout: include/contextflow_hip.h, cf_vit_step_bwd)
     # (small batches: on the side stream, as in step_backward)
     HWv = xv.shape[2] * xv.shape[3]
-    return gx, _param_part_on(side, keep, (planes, lnp, xv, ws, wsb, gsum, winv),
-                              lambda: _vstep_param_part(conv, act, cpl, vit, depth, planes, lnp, nwg, C, HWv, Wm, t, logs, gsum, gld, dev,
-                                                        sink, winv), defer, dev)
+    aff = Affine(conv, act, Wm, t, logs, rec.winv)
+    return gx, _param_part_on(side, keep, (planes, lnp, xv, ws, wsb, gsum, aff),
+                              lambda: _vstep_param_part(aff, vit, depth, planes, lnp, nwg, C, HWv, gsum, gld, dev, sink), dev)
 
 
-def _vstep_param_part(conv, act, cpl, vit, depth, planes, lnp, nwg, C, HW, Wm, t, logs, gsum, gld, dev, sink=None, winv=None):
+def _vstep_param_part(aff, vit, depth, planes, lnp, nwg, C, HW, gsum, gld, dev, sink=None):
     """Second half of vstep_backward: grouped weight gradients, LayerNorm sums, Conv1x1 / ActNorm parameter chain."""
-    f, pp, st = _hip.f32, _hip.p, _hip.stream()
     Bp = nwg * 4
     R4, P8, PD, DIM = 4 * Bp, 8 * Bp, C, 2 * C
     o = [0]
@@ -379,17 +346,7 @@ def _vstep_param_part(conv, act, cpl, vit, depth, planes, lnp, nwg, C, HW, Wm, t
     grads[vit.transformer.norm.weight], grads[vit.transformer.norm.bias] = ln[b:b + DIM], ln[b + 64:b + 64 + DIM]
     # ---- Conv1x1 / ActNorm chain from the folded matrix / bias gradient (W' = diag(s) Wm, b' = -t s)
     gWp, gbp = wg[0]
-    if gsum is None:
-        gsum = gld.sum().reshape(1)
-    if winv is None:
-        lad = torch.empty(1, device=dev, dtype=torch.float32)
-        winv = torch.empty(C, C, device=dev, dtype=torch.float32)
-        _hip.call("cf_slogdet_inverse", pp(Wm), C, pp(lad), pp(winv), st)
-    gNN, gt, glogs = _out(sink, conv.NN, (C, C), dev), _out(sink, act.NN_t, (C,), dev), _out(sink, act.NN_logs, (C,), dev)
-    _hip.call("cf_step_param_grads", pp(gWp.contiguous()), pp(gbp.contiguous()), pp(Wm), pp(t), pp(logs), pp(winv), pp(f(gsum)),
-              HW, pp(gNN), pp(gt), pp(glogs), C, st)
-    grads[conv.NN] = gNN.view_as(conv.NN)
-    grads[act.NN_t], grads[act.NN_logs] = gt.view_as(act.NN_t), glogs.view_as(act.NN_logs)
+    grads.update(_affine_param_grads([aff], [gWp.contiguous()], [gbp.contiguous()], HW, gsum, gld, dev, sink)[0])
     return grads
 
 
@@ -454,7 +411,6 @@ class FlowLogProb(torch.autograd.Function):
         keep = []
 
         def add_on(d, ri, side):     # parameter gradients produced on a side stream are accumulated there
-            import contextlib
             with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
                 if side is not None:
                     for p in d:                                  # a parameter shared by two records: behind its first producer
@@ -474,79 +430,52 @@ class FlowLogProb(torch.autograd.Function):
                         red.wait_stream(s_)
                     flush(seg_done)
         gz, turn = None, -1
-        held = []                    # [(thunk, record index, side)]: the previous record's parameter half, not launched yet
         group, group_ri, group_side = [], [], None      # the steps of the current resolution level (WGRAD_BATCH)
-
-        def run_pending():
-            while held:
-                thunk, ri_p, side_p = held.pop(0)
-                add_on(thunk(), ri_p, side_p)
-
-        def finish(gp, ri, defer):
-            """this record's kernels of the data-gradient chain are in the queue: launch the previous record's parameter half,
-            then hold this one's back in turn (WGRAD_DEFER) or account for its gradients at once"""
-            run_pending()
-            if defer:
-                held.append((defer[0], ri, side))
-            else:
-                add_on(gp, ri, side)
         for ri in range(len(tape) - 1, -1, -1):
             rec = tape[ri]
-            kind = rec[0]
+            kind = rec.kind
             if sides and kind in ("prior", "split", "step", "vstep"):
                 turn += 1
                 side = sides[turn % len(sides)]
-            defer = [] if (sides and WGRAD_DEFER) else None
             if kind == "prior":
-                _, xin, dist, prep = rec
-                gz, gp = gmm_backward(xin, dist, prep, glogp, gcol, side, keep, sink, defer)
-                finish(gp, ri, defer)
+                gz, gp = gmm_backward(rec.x, rec.dist, rec.prepared, glogp, gcol, side, keep, sink)
+                add_on(gp, ri, side)
             elif kind == "split":
-                _, xin, dist, prep = rec                      # xin: full tensor before the split
-                c = xin.shape[1] // 2
-                g2, gp = gmm_backward(xin[:, c:], dist, prep, glogp, gcol, side, keep, sink, defer)
+                c = rec.x.shape[1] // 2                      # rec.x: full tensor before the split
+                g2, gp = gmm_backward(rec.x[:, c:], rec.dist, rec.prepared, glogp, gcol, side, keep, sink)
                 gz = torch.cat([gz, g2], dim=1)
-                finish(gp, ri, defer)
+                add_on(gp, ri, side)
             elif kind == "step":
-                _, xin, sq, conv, act, cpl, shape, ws, winv, planes, wsb = rec
                 if sides and WGRAD_BATCH:
                     # the level's steps share ONE side stream and ONE set of batched launches, issued behind its last backward kernel
                     if not group:
                         group_side = side
-                    gz, _ = step_backward(xin, sq, conv, act, cpl, shape, ws, gz, gld, winv, planes, gsum, None, None, wsb, sink,
-                                          None, group)
+                    gz, _ = step_backward(rec, gz, gld, gsum, sink=sink, collect=group)
                     group_ri.append(ri)
                     nxt = tape[ri - 1] if ri > 0 else None
-                    if nxt is None or nxt[0] != "step" or tuple(nxt[6]) != tuple(shape):
-                        run_pending()
+                    if nxt is None or nxt.kind != "step" or tuple(nxt.shape) != tuple(rec.shape):
                         items, ris = list(group), list(group_ri)
                         del group[:], group_ri[:]
-                        gps = _param_part_on(group_side, keep, items, lambda: _step_param_part_batch(items, gsum, gld, B0, dev, sink),
-                                             None, dev)
+                        gps = _param_part_on(group_side, keep, items, lambda: _step_param_part_batch(items, gsum, gld, B0, dev, sink), dev)
                         for gp_i, ri_i in zip(gps, ris):
                             add_on(gp_i, ri_i, group_side)
                 else:
-                    gz, gp = step_backward(xin, sq, conv, act, cpl, shape, ws, gz, gld, winv, planes, gsum, side, keep, wsb, sink, defer)
-                    finish(gp, ri, defer)
+                    gz, gp = step_backward(rec, gz, gld, gsum, side, keep, sink)
+                    add_on(gp, ri, side)
             elif kind == "vstep":
-                _, xin, conv, act, cpl, ws_rs, xtape = rec[:7]
-                winv_v, wsb_v = rec[7:9] if len(rec) >= 9 else (None, None)
-                gz, gp = vstep_backward(xin, conv, act, cpl, gz, gld, gsum, ws_rs, xtape, side, keep, sink, winv_v, wsb_v, defer)
-                finish(gp, ri, defer)
+                gz, gp = vstep_backward(rec, gz, gld, gsum, side, keep, sink)
+                add_on(gp, ri, side)
             elif kind == "squeeze":
-                gz = squeeze_op(gz, rec[1], True)
+                gz = squeeze_op(gz, rec.p, True)
             elif kind == "pre":
                 break                                        # nothing trainable upstream of the pre-processing
             elif kind == "layer":
-                _, mod, xin = rec
-                gz, gp = layer_backward(mod, xin, gz, gld)
-                run_pending()
+                gz, gp = layer_backward(rec.module, rec.x, gz, gld)
                 add(gp)
                 if bucket is not None:
                     flush(bucket.closes.get(ri, ()))
             else:
                 raise NotImplementedError("no backward for tape record %r" % (kind,))
-        run_pending()
         if sides:
             main = torch.cuda.current_stream(dev)
             for s_ in sides:
@@ -568,18 +497,17 @@ SEGMENT_MIN_BYTES = 1 << 20      # data-parallel bucket: a segment is closed at 
 
 def _record_params(rec):
     """trainable tensors of a tape record, in the order the backward lists them"""
-    kind = rec[0]
+    kind = rec.kind
     if kind in ("prior", "split"):
-        d = rec[2]
+        d = rec.dist
         return [d.mG, d.sG, d.wG]
     if kind == "step":
-        conv, act, cpl = rec[3], rec[4], rec[5]
-        c1, c2, c3 = cpl.NN[0], cpl.NN[2], cpl.NN[4]
-        return [conv.NN, act.NN_t, act.NN_logs, c1.weight, c1.bias, c2.weight, c2.bias, c3.weight, c3.bias]
+        c1, c2, c3 = rec.cpl.NN[0], rec.cpl.NN[2], rec.cpl.NN[4]
+        return [rec.conv.NN, rec.act.NN_t, rec.act.NN_logs, c1.weight, c1.bias, c2.weight, c2.bias, c3.weight, c3.bias]
     if kind == "vstep":
-        return [p for m in rec[2:5] for p in m.parameters()]
+        return [p for m in (rec.conv, rec.act, rec.cpl) for p in m.parameters()]
     if kind == "layer":
-        return list(rec[1].parameters())
+        return list(rec.module.parameters())
     return []
 
 
@@ -593,9 +521,9 @@ def _bucket_for(flow, tape, params):
     groups, closes, cur, size = [], {}, [], 0
     for ri in range(len(tape) - 1, -1, -1):
         rec = tape[ri]
-        if rec[0] == "pre":
+        if rec.kind == "pre":
             break
-        if rec[0] == "split" and cur:                        # the level above is complete
+        if rec.kind == "split" and cur:                        # the level above is complete
             closes.setdefault(last, []).append(len(groups))
             groups.append(cur)
             cur, size = [], 0

@@ -10,6 +10,7 @@ import torch
 import torch.nn as nn
 
 from . import _derived, _hip
+from ._tape import step_tape
 from .flowlayer import FlowLayer, encoder_noise
 
 VIT_EVENTS = None        # bench.py: list collecting (start, end, batch) HIP events per fused ViT-coupling launch
@@ -159,7 +160,6 @@ class Coupling(_AffineCoupling):
         planes = None
         if tape is not None and mode == 2:
             # every parameter trains: the forward kernel also writes the step tape for the backward kernel and the weight gradients
-            from .flowsequential import step_tape
             planes = step_tape(B, C, H, W, dev)
             _hip.call("cf_flow_step_fwd_ctx_taped", pp(x), pp(z), pp(ldj), pp(ws), pp(sbias), pp(planes[0]), pp(planes[1]),
                       pp(planes[2]), pp(planes[3]), B, C, H, W, xbs, st)

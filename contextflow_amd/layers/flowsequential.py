@@ -18,7 +18,8 @@ import math
 import torch
 import torch.nn as nn
 
-from . import _derived, _hip
+from . import _derived, _hip, _tape
+from ._tape import step_tape
 from .actnorm import ActNorm
 from .augment import Augment
 from .conv1x1 import Conv1x1
@@ -56,15 +57,6 @@ def _on_parameter_registration(module, name, param):
 
 
 torch.nn.modules.module.register_module_parameter_registration_hook(_on_parameter_registration)
-
-
-def step_tape(B, C, H, W, dev):
-    """Buffers of one step's training tape (cf_flow_step_fwd_taped): y0 (B, C/2, HW), h1, h2 (B, 2C, HW) - the operands of
-    the weight-gradient GEMMs - and the opaque aux buffer (log-scales, second half of the Conv1x1+ActNorm output, ReLU
-    masks) that is all the step-backward kernel reads of the forward."""
-    planes = [torch.empty(B, r, H * W, device=dev, dtype=torch.float32) for r in (C // 2, 2 * C, 2 * C)]
-    planes.append(torch.empty(_hip.lib().cf_flow_step_tape_aux_bytes(B, C, H, W), device=dev, dtype=torch.uint8))
-    return tuple(planes)
 
 
 class FlowSequential(nn.Module):
@@ -473,7 +465,7 @@ class FlowSequential(nn.Module):
                 continue
             if kind == "pre":
                 if tape is not None:
-                    tape.append(("pre",))
+                    tape.append(_tape.Pre())
                 _, deq, n1, n2, aug = op
                 xin = _hip.f32(x)
                 C, H, W = xin.shape[1:]
@@ -517,7 +509,7 @@ class FlowSequential(nn.Module):
                     # backward uses are bit for bit those of the forward that produced the loss.
                     keep = TAPE_PLANES and 18 * B * C * H * W <= torch.cuda.get_device_properties(dev).total_memory // 64
                     planes = step_tape(B, C, H, W, dev)
-                    tape.append(("step", x, sq, conv, act, cpl, (C, H, W), ws, winv, planes if keep else None, wsb))
+                    tape.append(_tape.Step(conv, act, cpl, (C, H, W), sq, x, ws, winv, planes if keep else None, wsb))
                     x, xbs = _hip.bview(x)
                     z = torch.empty(B, C, H, W, device=dev, dtype=torch.float32)
                     _hip.call("cf_flow_step_fwd_taped", _hip.p(x), _hip.p(z), _hip.p(ld1), _hip.p(ws), _hip.p(planes[0]),
@@ -559,7 +551,7 @@ class FlowSequential(nn.Module):
                     if VSTEP_TAPE:
                         depth = len(op[3].NN[0].transformer.layers)
                         xt = torch.empty(_hip.lib().cf_vit_step_tape_floats(B, x.shape[1], depth), device=dev, dtype=torch.float32)
-                    tape.append(("vstep", x, op[1], op[2], op[3], ws if variant == "rs" else None, xt, winv_v, wsb_v))
+                    tape.append(_tape.VStep(op[1], op[2], op[3], x, ws if variant == "rs" else None, xt, winv_v, wsb_v))
                     if ev is not None:
                         main.wait_event(ev)
                     x = op[3].step_forward(x, ws, ld1, variant=variant, xtape=xt)
@@ -583,14 +575,14 @@ class FlowSequential(nn.Module):
                 x = op[3].step_forward(x, ws, ld1, variant=variant)
             elif kind == "squeeze":
                 if tape is not None:
-                    tape.append(("squeeze", tuple(op[1].p)))
+                    tape.append(_tape.Squeeze(tuple(op[1].p)))
                 x = squeeze_op(x, op[1].p, False)
             elif kind == "split":
                 prep, ev = prepared[k]
                 if ev is not None:
                     main.wait_event(ev)
                 if tape is not None:
-                    tape.append(("split", x, op[1].dist, prep))
+                    tape.append(_tape.Split(op[1].dist, x, prep))
                 c = x.shape[1] // 2
                 if levels is not None:       # small batch: every mixture of the flow in one launch pair at the end
                     levels.append((x[:, c:], prep))
@@ -600,7 +592,7 @@ class FlowSequential(nn.Module):
                 x = x[:, :c]
             else:                        # any other layer: its own kernels
                 if tape is not None:
-                    tape.append(("layer", op[1], x))
+                    tape.append(_tape.Layer(op[1], x))
                 x, ldj = op[1](x, context)
                 if ldj.dim() == 2:
                     if ldM_set:
@@ -613,7 +605,7 @@ class FlowSequential(nn.Module):
         if ev_prior is not None:
             main.wait_event(ev_prior)
         if tape is not None:
-            tape.append(("prior", x, self.dist, prior))
+            tape.append(_tape.Prior(self.dist, x, prior))
         if levels is not None and gmm_levels_ok(levels + [(x, prior)]):
             logp = gmm_logprob_levels(levels + [(x, prior)], ldM if ldM_set else None, ld1)
         else:

@@ -1611,7 +1611,8 @@ def test_batched_parameter_work_of_a_level_equals_the_per_step_launches(L, name,
     """At small batches the weight gradients and parameter chains of the steps of a resolution level go out in one set of
     launches (cf_step_wgrads_batch / cf_step_param_grads_batch, blockIdx.z = step) on a side stream, behind the level's last
     backward kernel: the gradients of every parameter equal those of the per-step launches bit for bit - with the
-    data-parallel bucket as their destination as well."""
+    data-parallel bucket as their destination as well.  Third setting: WGRAD_SIDE_MAX_BATCH = 0, no side streams, every
+    step's parameter work launched by itself on the main stream - the path of every batch above 1 024."""
     import contextflow_amd as cfa
     from contextflow_amd.layers import autograd as ag
     cfg, ds, M = cfa.preset_config(name)
@@ -1621,8 +1622,10 @@ def test_batched_parameter_work_of_a_level_equals_the_per_step_launches(L, name,
     y = torch.randint(0, M, (B,), generator=g).to(DEV)
     inv = 1.0 / x[0].numel()
     got = {}
-    for batch in (True, False):
-        monkeypatch.setattr(ag, "WGRAD_BATCH", batch)
+    for batch in (True, False, "main stream"):
+        monkeypatch.setattr(ag, "WGRAD_BATCH", batch is not False)
+        if batch == "main stream":
+            monkeypatch.setattr(ag, "WGRAD_SIDE_MAX_BATCH", 0)
         torch.manual_seed(0)
         m = cfa.create_model(cfg, ds, M).to(DEV)
         for q in m.sequence_modules:
@@ -1637,10 +1640,11 @@ def test_batched_parameter_work_of_a_level_equals_the_per_step_launches(L, name,
         torch.nn.functional.cross_entropy(m.log_prob(x) * inv, y).backward()
         torch.cuda.synchronize()
         got[batch] = {k: p.grad.clone() for k, p in m.named_parameters()}
-    assert len(got[True]) == len(got[False]) > 20
+    assert len(got[True]) == len(got[False]) == len(got["main stream"]) > 20
     for k, a in got[True].items():
         assert torch.isfinite(a).all(), k
         assert torch.equal(a, got[False][k]), k
+        assert torch.equal(a, got["main stream"][k]), k
 
 
 @pytest.mark.parametrize("wd,maximize", [(1e-2, False), (0.0, False), (0.3, True)])

@@ -423,21 +423,22 @@ def test_gradient_bucket_follows_the_backward(built, name):
             m.initialized.fill_(1)
             m._init_done = True
     plan = flow._build_plan(tuple(ds))
+    from contextflow_amd.layers import _tape
     tape = []
     for op in plan:
         if op[0] == "pre":
-            tape.append(("pre",))
+            tape.append(_tape.Pre())
         elif op[0] == "step":
-            tape.append(("step", None, op[5], op[1], op[2], op[3], op[4], None, None, None, None))
+            tape.append(_tape.Step(conv=op[1], act=op[2], cpl=op[3], shape=op[4], squeeze=op[5]))
         elif op[0] == "vstep":
-            tape.append(("vstep", None, op[1], op[2], op[3], None, None))
+            tape.append(_tape.VStep(conv=op[1], act=op[2], cpl=op[3]))
         elif op[0] == "split":
-            tape.append(("split", None, op[1].dist, None))
+            tape.append(_tape.Split(dist=op[1].dist))
         elif op[0] == "squeeze":
-            tape.append(("squeeze", tuple(op[1].p)))
+            tape.append(_tape.Squeeze(p=tuple(op[1].p)))
         else:
-            tape.append(("layer", op[1], None))
-    tape.append(("prior", None, flow.dist, None))
+            tape.append(_tape.Layer(module=op[1]))
+    tape.append(_tape.Prior(dist=flow.dist))
     params = [p for p in flow.parameters() if p.requires_grad]
     b = ag._bucket_for(flow, tape, params)
     assert set(b.slots) == set(params) and len(b.slots) == len(params)
@@ -449,7 +450,7 @@ def test_gradient_bucket_follows_the_backward(built, name):
         lo_prev = lo + n - 1
     assert b.segments[0][0] == 0 and all(a[1] == c[0] for a, c in zip(b.segments, b.segments[1:])) and b.segments[-1][1] == b.flat.numel()
     assert b.segment_of(flow.dist.mG) == 0                 # the final prior leads the first message
-    nsplit = sum(1 for r in tape if r[0] == "split")
+    nsplit = sum(1 for r in tape if r.kind == "split")
     assert len(b.segments) >= nsplit + 1
     closed = sorted(i for v in b.closes.values() for i in v)
     assert closed == list(range(len(b.segments)))
