@@ -84,6 +84,10 @@ SIGNATURES = {
     "cf_step_param_grads": (_c_int, [_c_p] * 7 + [_c_int] + [_c_p] * 3 + [_c_int, _c_p]),
     "cf_bf16_split": (_c_int, [_c_int]),
     "cf_adamw_step_batch": (_c_int, [_c_int] + [_c_p] * 6 + [ctypes.c_double] * 5 + [_c_int, _c_p]),
+    "cf_adamw_step_batch_dev": (_c_int, [_c_int] + [_c_p] * 8 + [ctypes.c_double] * 4 + [_c_int, _c_p]),
+    "cf_grad_norm_partials": (_c_i64, [_c_int, _c_p]),
+    "cf_grad_norm_batch": (_c_int, [_c_int, _c_p, _c_p, ctypes.c_double, _c_p, _c_i64, _c_p, _c_p]),
+    "cf_grad_scale_batch": (_c_int, [_c_int, _c_p, _c_p, _c_p, _c_p]),
     "cf_step_param_grads_batch": (_c_int, [_c_int] + [_c_p] * 7 + [_c_int] + [_c_p] * 3 + [_c_int, _c_p]),
     "cf_wgrad_ws_bytes": (_c_i64, [_c_int] * 6),
     "cf_wgrad": (_c_int, [_c_p] * 5 + [_c_int] * 6 + [_c_p]),

@@ -727,8 +727,11 @@ class FlowSequential(nn.Module):
         (at the reference's batch of 256 a step is ~330 launches of a few microseconds each: launch-bound).  Returns
         `step(x, *loss_args) -> loss` that copies its arguments into static buffers and replays; `loss_fn(logp, *loss_args)`
         maps the (B, M) log-densities to a scalar.  The optimizer must be capturable (`torch.optim.AdamW(..., capturable=
-        True)`); ActNorm layers must be initialised (run one forward first).  The first call runs `warmup` eager steps
-        (real updates; default 1) and captures; see GraphedTrainStep.
+        True)`, or `optim.FusedAdamW`).  Learning-rate schedules: only `optim.FusedAdamW` follows `param_group['lr']` after the
+        capture (assign Python floats; its `max_grad_norm` is the reference's `clip_grad_norm_` inside the step);
+        `torch.optim.AdamW` with a float `lr` keeps the rate it was captured with for ever.  ActNorm layers must be
+        initialised (run one forward first).  The first call runs `warmup` eager steps (real updates; default 1) and
+        captures; see GraphedTrainStep.
         data_parallel (default: whether a process group of more than one rank exists): every rank steps on ITS shard of the
         batch and the gradients are averaged over the ranks inside the step - written by the backward kernels into one flat
         bucket that `p.grad` views, all-reduced (RCCL) segment by segment while the backward of the lower levels still runs,
@@ -886,10 +889,15 @@ class GraphedTrainStep:
     First call: `warmup` (default 1) EAGER training steps on the given batch - real optimizer updates, off the default
     stream - then the capture of one more step (a capture records, it does not execute: no update).  It returns the loss
     of the last eager step, so with the default warmup the first call is exactly one update, like every later call.
-    Later calls replay.  A replay changes the parameters on the device without moving their version counters, which
-    the evaluation caches of the flow key on (packed step tables, mixture tables, auto-captured forward graphs): every
-    call therefore ends with `flow.invalidate_caches()`, and a `log_prob` between training steps sees the current
-    parameters."""
+    Later calls replay.  Before the capture and before every replay the optimizer's `push_hyperparameters()` is called if it
+    has one: `optim.FusedAdamW` keeps the learning rate in a device scalar that the captured update reads, so a loop that
+    assigns floats to `param_group['lr']` between calls (the reference's `warmup_lr`, `scheduler.step()` of `StepLR`) drives the
+    captured step unchanged, and `FusedAdamW(max_grad_norm=...)` puts the reference's `clip_grad_norm_` between backward and
+    update.  `torch.optim.AdamW(capturable=True)` with a float `lr` stays FROZEN at the rate of the capture - the float is
+    baked into its captured launches and later assignments are silently ignored.
+    A replay changes the parameters on the device without moving their version counters, which the evaluation caches of
+    the flow key on (packed step tables, mixture tables, auto-captured forward graphs): every call therefore ends with
+    `flow.invalidate_caches()`, and a `log_prob` between training steps sees the current parameters."""
 
     def __init__(self, flow, example, loss_fn, optimizer, warmup=1, loss_args=()):
         _hip.require_device(example)
@@ -918,6 +926,13 @@ class GraphedTrainStep:
             torch.cuda.synchronize(dev)
             time.sleep(0.35)
 
+    def _push(self):
+        # an optimizer that keeps hyper-parameters on the device (optim.FusedAdamW: the learning rate) refreshes them from
+        # param_groups here, outside the graph: the captured launches read them from there
+        push = getattr(self.opt, "push_hyperparameters", None)
+        if push is not None:
+            push()
+
     def _step(self):
         # grads start as None: the autograd engine then TAKES the gradient buffers the backward returns (allocated from
         # the graph's private pool during capture, so their addresses are the ones every replay writes and the
@@ -934,6 +949,7 @@ class GraphedTrainStep:
             self.static_args = tuple(a.detach().clone() if torch.is_tensor(a) else a for a in loss_args)
             self.static_in.copy_(x)
             dev = self.static_in.device
+            self._push()
             s = torch.cuda.Stream(device=dev)
             s.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(s):                   # warm-up steps are real optimizer steps
@@ -952,6 +968,7 @@ class GraphedTrainStep:
         for dst, src in zip(self.static_args, loss_args):
             if torch.is_tensor(dst):
                 dst.copy_(src)
+        self._push()
         self.graph.replay()
         self.updates += 1
         self.flow.invalidate_caches()

@@ -26,6 +26,8 @@
 extern "C" {
 #endif
 
+/* Version 13 also covers the entry points added after it that only ADD symbols (cf_adamw_step_batch_dev, cf_grad_norm_partials,
+ * cf_grad_norm_batch, cf_grad_scale_batch): no existing signature or behaviour moved, so no caller of version 13 breaks. */
 #define CF_ABI_VERSION 13
 #define CF_ERR_ARG (-1)          /* bad argument (shape, null pointer, unsupported size) */
 #define CF_ERR_UNSUPPORTED (-2)  /* shape not covered by this kernel; caller uses the generic path */
@@ -648,6 +650,29 @@ int cf_nll_sum(const float* logp, double* acc, int B, int M, cf_stream_t stream)
 int cf_adamw_step_batch(int n, float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* numel,
                         const float* step, double lr, double beta1, double beta2, double eps, double weight_decay, int maximize,
                         cf_stream_t stream);
+/* The same update, bit for bit for an equal rate, with the learning rate read from the DEVICE scalar `lr` (fp64): a captured launch
+ * follows a schedule when the host refills the scalar between replays (the reference assigns param_group['lr'] before every batch
+ * of the warm-up, experiment_cl.py:98-105, and at every StepLR boundary, model.py:290).  1 - lr weight_decay and lr / (1 - beta1^t)
+ * are formed on the device in double.  norm_rec: NULL, or the record cf_grad_norm_batch wrote - every gradient element is then
+ * multiplied by its coefficient in a register before use (one fp32 product, as g.mul_(coef) gives; g itself is not rewritten). */
+int cf_adamw_step_batch_dev(int n, float* const* p, const float* const* g, float* const* m, float* const* v, const int64_t* numel,
+                            const float* step, const double* lr, const float* norm_rec, double beta1, double beta2, double eps,
+                            double weight_decay, int maximize, cf_stream_t stream);
+
+/* ---- global gradient norm and clipping (experiment_cl.py:135, experiment_ad.py:212: nn.utils.clip_grad_norm_) -------------------- */
+/* Host only: the number of fp64 partials (= workgroups: one per 1024 elements of a tensor) cf_grad_norm_batch writes for these
+ * element counts; negative on a bad argument.                                                                                  */
+int64_t cf_grad_norm_partials(int n, const int64_t* numel);
+/* 2-norm over all n gradients (host arrays of device pointers and element counts, as above) and the clipping coefficient of
+ * torch's clip_grad_norm_: norm_rec[0] = (float)sqrt(sum g^2), norm_rec[1] = min(1, max_norm / (norm + 1e-6)) in fp32, NaN kept.
+ * Squares and sums are fp64 throughout, in a fixed order (no atomics): the same gradients give the same bits, eager or replayed.
+ * A non-finite gradient gives a non-finite norm and a coefficient of 0 (inf) or NaN (NaN), which the scaled update inherits exactly as
+ * with torch's error_if_nonfinite = False; there is no skip-step policy.  ceil(n / 224) launches + 1; partials: workspace of
+ * partials_cap >= cf_grad_norm_partials(n, numel) doubles.                                                                       */
+int cf_grad_norm_batch(int n, const float* const* g, const int64_t* numel, double max_norm, double* partials, int64_t partials_cap,
+                       float* norm_rec, cf_stream_t stream);
+/* g *= norm_rec[1] in place over the n gradients (the second half of clip_grad_norm_), ceil(n / 224) launches.                      */
+int cf_grad_scale_batch(int n, float* const* g, const int64_t* numel, const float* norm_rec, cf_stream_t stream);
 
 #ifdef __cplusplus
 }
