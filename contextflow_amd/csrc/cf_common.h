@@ -84,3 +84,27 @@ __device__ __forceinline__ float cf_block_sum(float v, float* scratch) {
     for (int i = 0; i < NW; ++i) s += scratch[i];
     return s;
 }
+
+// ---- counter-based noise inside a kernel: Philox4x32-10, one call = four 32-bit words ---------------------------
+// (k_preprocess_rng: dequantisation uniforms and Augment normals; k_gmm_draw: component uniform and prior normals)
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
+                                              unsigned (&out)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
+        const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+__device__ __forceinline__ float u01(unsigned r) { return (float)(r >> 8) * 5.9604644775390625e-08f; }   // [0, 1), 24 bits
+// Box-Muller on the word pairs (0, 1) and (2, 3) of one Philox call: four standard normals
+__device__ __forceinline__ void cf_normal4(const unsigned (&rn)[4], float (&e)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; j += 2) {
+        const float rad = sqrtf(-2.0f * logf(1.0f - u01(rn[j]))), ang = 6.28318530717958647692f * u01(rn[j + 1]);
+        e[j] = rad * cosf(ang); e[j + 1] = rad * sinf(ang);
+    }
+}

@@ -127,20 +127,7 @@ int launch_sample(const float* x, const float* u, float* y, float* ldj, int B, i
 // state[0] = offset: either a per-call value the caller draws from its own generator (FlowSequential: torch's CUDA
 // generator, graph-safe), or a self-advancing word (`advance` = 1: k_rng_advance on the same stream).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned (&out)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
-        const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-__device__ __forceinline__ float u01(unsigned r) { return (float)(r >> 8) * 5.9604644775390625e-08f; }   // [0, 1), 24 bits
-
+// (philox4x32_10, u01 and the Box-Muller pairing cf_normal4: cf_common.h - cf_gmm_draw draws from the same generator)
 template <int NT>
 __global__ __launch_bounds__(NT) void k_preprocess_rng(const float* __restrict__ x, float* __restrict__ y,
                                                        float* __restrict__ ldj, const unsigned long long* __restrict__ state,
@@ -173,11 +160,7 @@ __global__ __launch_bounds__(NT) void k_preprocess_rng(const float* __restrict__
         float e[4];
         const unsigned long long idx = (unsigned long long)b * (unsigned)(n4 + aug4) + (unsigned)(n4 + i);
         philox4x32_10((unsigned)idx, (unsigned)(idx >> 32), (unsigned)off, (unsigned)(off >> 32), k0, k1, rn);
-#pragma unroll
-        for (int j = 0; j < 4; j += 2) {
-            const float rad = sqrtf(-2.0f * logf(1.0f - u01(rn[j]))), ang = 6.28318530717958647692f * u01(rn[j + 1]);
-            e[j] = rad * cosf(ang); e[j + 1] = rad * sinf(ang);
-        }
+        cf_normal4(rn, e);
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc += 0.5f * e[j] * e[j] + 0.5f * kLog2Pi;
         vstore<4>(yb + (int64_t)(n4 + i) * 4, e);

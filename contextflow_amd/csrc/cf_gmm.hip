@@ -571,6 +571,99 @@ __global__ __launch_bounds__(256) void k_gmm_sample4(const float* __restrict__ m
     }
 }
 
+// class-conditional, tempered prior draw + concatenate in one launch (cf_gmm_draw):
+//   out[b, :D1] = z1[b, :]                                       (the kept half of a SplitPrior, bit for bit)
+//   out[b, D1 + d] = fmaf(temperature * softplus(sG[m k, d]), eps[b, d], mG[m k, d]),  m = clamp(labels[b]), k: first u_b < cdf[m][k]
+// Pure streaming: one write of the row, one read of z1; the M K parameter rows stay in L2.  2^TL threads own a sample (a
+// whole 256-thread workgroup for rows of 256 items and more, several samples per workgroup below), each of them picks
+// the component itself (<= 16 compares on one cached cdf row - no LDS, no barrier).  VEC: items are float4.
+// Noise: eps == nullptr -> Philox4x32-10, key = seed, counter = (b (1 + ceil(D / 4)) + j, state[0]): j = 0 -> word 0 is the
+// component uniform, j >= 1 -> cf_normal4 gives elements 4 (j - 1) .. 4 (j - 1) + 3.  The scalar form runs the same
+// cf_normal4 and keeps one of its four results: both forms give the same bits for every (seed, state, b, d).  (That is a whole
+// Philox call and two Box-Muller pairs per ELEMENT in the scalar form, four times the vector form's arithmetic: the price of the
+// fallback for ragged D / misaligned operands; the flows' levels all take the vector form.)
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_gmm_draw(const float* __restrict__ mG, const float* __restrict__ sG,
+                                                  const float* __restrict__ cdf, const int32_t* __restrict__ labels, int label0,
+                                                  const float* __restrict__ u, const float* __restrict__ eps,
+                                                  const unsigned long long* __restrict__ state, unsigned long long seed,
+                                                  const float* __restrict__ z1, int64_t z1_bstride, int D1,
+                                                  float* __restrict__ out, int B, int M, int K, int D, float temperature, int TL) {
+    const int tpr = 1 << TL;
+    const int64_t b = (int64_t)blockIdx.x * (256 >> TL) + (threadIdx.x >> TL);
+    const int lane = threadIdx.x & (tpr - 1);
+    if (b >= B) return;
+    const bool philox = eps == nullptr;
+    const unsigned long long off = philox ? state[0] : 0ull;
+    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+    const unsigned long long base = (unsigned long long)b * (unsigned long long)(1 + (D + 3) / 4);
+    int m = labels ? labels[b] : label0;
+    m = min(max(m, 0), M - 1);
+    float ub;
+    if (philox) {
+        unsigned rn[4];
+        philox4x32_10((unsigned)base, (unsigned)(base >> 32), (unsigned)off, (unsigned)(off >> 32), k0, k1, rn);
+        ub = u01(rn[0]);
+    } else
+        ub = u[b];
+    const float* cr = cdf + (int64_t)m * K;
+    int k = K - 1;                                   // (the last column is 1 and u < 1; an explicit u >= 1 lands here too)
+    for (int i = K - 2; i >= 0; --i)
+        if (ub < cr[i]) k = i;
+    const int64_t prow = ((int64_t)m * K + k) * D;
+    const float* mr = mG + prow;
+    const float* sr = sG + prow;
+    const float* zr = z1 + b * z1_bstride;           // (read only where D1 > 0)
+    const float* er = eps + b * (int64_t)D;          // (read only in the explicit mode)
+    float* orow = out + b * ((int64_t)D1 + D);
+    if (VEC) {
+        const int n1 = D1 >> 2, n = n1 + (D >> 2);
+        for (int i = lane; i < n; i += tpr) {
+            if (i < n1) {
+                reinterpret_cast<float4*>(orow)[i] = reinterpret_cast<const float4*>(zr)[i];
+                continue;
+            }
+            const int g = i - n1;
+            const float4 mu = reinterpret_cast<const float4*>(mr)[g], sg = reinterpret_cast<const float4*>(sr)[g];
+            float e[4];
+            if (philox) {
+                unsigned rn[4];
+                const unsigned long long idx = base + 1ull + (unsigned)g;
+                philox4x32_10((unsigned)idx, (unsigned)(idx >> 32), (unsigned)off, (unsigned)(off >> 32), k0, k1, rn);
+                cf_normal4(rn, e);
+            } else {
+                const float4 ev = reinterpret_cast<const float4*>(er)[g];
+                e[0] = ev.x; e[1] = ev.y; e[2] = ev.z; e[3] = ev.w;
+            }
+            float4 o;
+            o.x = fmaf(temperature * softplus_ref(sg.x), e[0], mu.x); o.y = fmaf(temperature * softplus_ref(sg.y), e[1], mu.y);
+            o.z = fmaf(temperature * softplus_ref(sg.z), e[2], mu.z); o.w = fmaf(temperature * softplus_ref(sg.w), e[3], mu.w);
+            reinterpret_cast<float4*>(orow)[i] = o;
+        }
+    } else {
+        const int n = D1 + D;
+        for (int i = lane; i < n; i += tpr) {
+            if (i < D1) {
+                orow[i] = zr[i];
+                continue;
+            }
+            const int d = i - D1;
+            float ev;
+            if (philox) {
+                unsigned rn[4];
+                float e[4];
+                const unsigned long long idx = base + 1ull + (unsigned)(d >> 2);
+                philox4x32_10((unsigned)idx, (unsigned)(idx >> 32), (unsigned)off, (unsigned)(off >> 32), k0, k1, rn);
+                cf_normal4(rn, e);
+                const int j = d & 3;
+                ev = j == 0 ? e[0] : j == 1 ? e[1] : j == 2 ? e[2] : e[3];
+            } else
+                ev = er[d];
+            orow[i] = fmaf(temperature * softplus_ref(sr[d]), ev, mr[d]);
+        }
+    }
+}
+
 // D-split heuristic: enough workgroups to cover the chip (~2 per CU), chunks stay multiples of DC
 // ---- parameter sums of the mixture backward: S0[mk] = sum_b r[b][mk], S1[mk][d] = sum_b r[b][mk] x[b][d],
 // S2[mk][d] = sum_b r[b][mk] x[b][d]^2 - one (MK x B)(B x D) product with two right-hand sides.  MK = 80 rows are five
@@ -748,6 +841,32 @@ int cf_gmm_sample(const float* mG, const float* sG, const int64_t* rows, const f
         k_gmm_sample4<<<dim3((unsigned)b4), dim3(256), 0, cf_s(stream)>>>(mG, sG, rows, eps, out, D / 4, (int)(total / 4));
     } else
         k_gmm_sample<<<dim3((unsigned)blocks), dim3(256), 0, cf_s(stream)>>>(mG, sG, rows, eps, out, D, total);
+    CF_LAUNCH_CHECK();
+    return 0;
+}
+
+int cf_gmm_draw(const float* mG, const float* sG, const float* cdf, const int32_t* labels, int label0, const float* u,
+                const float* eps, const unsigned long long* state, unsigned long long seed, const float* z1,
+                int64_t z1_bstride, int D1, float* out, int B, int M, int K, int D, float temperature, cf_stream_t stream) {
+    if (B == 0) return 0;                       // empty batch: nothing to do (pointers may be null)
+    CF_REQUIRE(mG && sG && cdf && out && B > 0 && M > 0 && K > 0 && K <= 16 && D > 0 && D1 >= 0);
+    CF_REQUIRE((u == nullptr) == (eps == nullptr));          // explicit noise: both; Philox: neither
+    CF_REQUIRE(eps != nullptr || state != nullptr);
+    CF_REQUIRE(D1 == 0 || (z1 != nullptr && z1_bstride >= D1));
+    CF_REQUIRE((int64_t)D1 + D < (1ll << 31));
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const bool vec = D % 4 == 0 && D1 % 4 == 0 && al16(mG) && al16(sG) && al16(out) && (eps == nullptr || al16(eps)) &&
+                     (D1 == 0 || (z1_bstride % 4 == 0 && al16(z1)));
+    const int64_t items = vec ? ((int64_t)D1 + D) / 4 : (int64_t)D1 + D;
+    int tl = 0;
+    while (tl < 8 && (1ll << tl) < items) ++tl;
+    const int rows = 256 >> tl;                 // samples per workgroup
+    const int64_t blocks = ((int64_t)B + rows - 1) / rows;
+    const float* z = D1 ? z1 : nullptr;
+#define CF_GO(V) k_gmm_draw<V><<<dim3((unsigned)blocks), dim3(256), 0, cf_s(stream)>>>(mG, sG, cdf, labels, label0, u, eps, state, seed, \
+                                                                                       z, z1_bstride, D1, out, B, M, K, D, temperature, tl)
+    if (vec) CF_GO(true); else CF_GO(false);
+#undef CF_GO
     CF_LAUNCH_CHECK();
     return 0;
 }

@@ -23,19 +23,23 @@ def key(tensors, *extra):
 def get(owner, slot, key, build, dev):
     """The value of `slot` (a string, or a tuple such as ("inv_ws", id(layer))) on `owner` for this key; `build()` makes it, with
     launches on the current stream of `dev` only."""
-    if torch.cuda.is_current_stream_capturing():
+    host = torch.device(dev).type == "cpu"       # a table of host tensors (component_cdf of a module not moved yet): no streams
+    if not host and torch.cuda.is_current_stream_capturing():
         return build()
     entries = owner.__dict__.get("_derived")
     if entries is None:
         entries = owner.__dict__["_derived"] = {}
     hit = entries.get(slot)
-    stream = torch.cuda.current_stream(dev)
+    stream = None if host else torch.cuda.current_stream(dev)
     if hit is not None and hit[0] == key:
-        stream.wait_event(hit[2])
+        if not host:
+            stream.wait_event(hit[2])
         return hit[1]
     value = build()
-    ev = torch.cuda.Event()
-    ev.record(stream)
+    ev = None
+    if not host:
+        ev = torch.cuda.Event()
+        ev.record(stream)
     entries[slot] = (key, value, ev)
     return value
 

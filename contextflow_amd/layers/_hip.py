@@ -55,6 +55,7 @@ SIGNATURES = {
     "cf_gmm_levels_ws_bytes": (_c_i64, [_c_int, _c_p] + [_c_int] * 3),
     "cf_gmm_logprob_levels": (_c_int, [_c_int] + [_c_p] * 10 + [_c_int] * 3 + [_c_p]),
     "cf_gmm_sample": (_c_int, [_c_p] * 5 + [_c_int, _c_int, _c_p]),
+    "cf_gmm_draw": (_c_int, [_c_p] * 4 + [_c_int] + [_c_p] * 3 + [ctypes.c_uint64, _c_p, _c_i64, _c_int, _c_p] + [_c_int] * 4 + [_c_f, _c_p]),
     "cf_flow_step_supported": (_c_int, [_c_int] * 5),
     "cf_flow_step_ws_bytes": (_c_i64, [_c_int] * 3),
     "cf_flow_step_prepare": (_c_int, [_c_p] * 10 + [_c_int] * 3 + [_c_p]),
@@ -338,3 +339,19 @@ def p(t):
 
 
 _WRAPPED = (_Ptr, _PtrArray)             # the argument wrappers that carry tensors (device_of)
+
+
+NOISE_KEY = 0x243F6A8885A308D3           # Philox key of the in-kernel noise (the rank of a data-parallel process is folded in)
+
+
+def noise_nonce(dev):
+    """(key, state) of one call's in-kernel Philox stream.  state: one 63-bit draw from torch's CUDA generator of `dev`, as an
+    int64 tensor on `dev`, consumed the way torch's own random ops consume it - so the noise follows `torch.manual_seed`
+    (re-seeding reproduces it), the generator moves on by one draw per call whatever the user does with it in between, and
+    under graph capture torch registers the generator with the graph: every replay reads a fresh value.  key: data-parallel
+    ranks fold their rank in - equal seeds on every rank still give every rank its own noise."""
+    rank = 0
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        rank = torch.distributed.get_rank()
+    key = (NOISE_KEY ^ (rank * 0x9E3779B97F4A7C15)) & 0xFFFFFFFFFFFFFFFF
+    return key, torch.empty(1, device=dev, dtype=torch.int64).random_()

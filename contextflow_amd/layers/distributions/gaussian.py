@@ -177,6 +177,14 @@ class GaussianDistribution(nn.Module):
         return x, self.log_prob(x, context)
 
 
+class _ClassLabels(tuple):
+    """(labels tensor | None, label0): checked class labels in the form cf_gmm_draw takes.  A type of its own, so that a user's
+    tuple of class indices is never taken for it (GaussianMixtureDistribution._class_labels)."""
+
+    def __new__(cls, tensor, label0):
+        return super().__new__(cls, (tensor, label0))
+
+
 class GaussianMixtureDistribution(nn.Module):
     def __init__(self, size, mixtures=2, components=8, context_net=None, contextflow=False):
         super().__init__()
@@ -331,9 +339,88 @@ class GaussianMixtureDistribution(nn.Module):
             return self._log_prob_ctx(input, context)
         return gmm_logprob(input, self.prepared())
 
-    def sample(self, n_samples, context=None, need_log_prob=True):
+    def component_cdf(self):
+        """(M, K) float32: cumulative component weights of every class-mixture, the table cf_gmm_draw picks the component from
+        (the first k with u < cdf[m, k]).  softmax(wG, -1) and its running sum in fp64, rounded once; the last column is
+        exactly 1, so every u in [0, 1) finds its component.  Kept while wG is unchanged (layers/_derived.py); lives where
+        wG lives, a host tensor included."""
+        wG = self.wG.detach()
+
+        def build():
+            cdf = torch.cumsum(torch.softmax(wG.double(), dim=-1), dim=-1).to(torch.float32)
+            cdf[:, -1] = 1.0
+            return cdf.contiguous()
+        return _derived.get(self, "cdf", _derived.key([self.wG], str(wG.device)), build, wG.device)
+
+    def _class_labels(self, labels, n_samples):
+        """`labels` of `sample` in the form cf_gmm_draw takes, a _ClassLabels: (None, m) for one class-mixture m for every sample, or
+        ((n,) int32 tensor on the device, 0).  An int, a sequence (list, tuple, ...) or a host tensor is checked here - ValueError for
+        a value outside [0, M) or a length other than n; a device tensor is only checked for its length (no host sync): the
+        kernel clamps its values as the keyed mixture kernels clamp their keys (a 0-dim device tensor is that class for every
+        sample).  None: class-mixture 1, the reference's hard-coded `x[:, 1]` (0 when M == 1).  A _ClassLabels (what
+        FlowSequential.sample prepared once for every level) is returned as it is."""
+        M = self.M
+        if isinstance(labels, _ClassLabels):
+            return labels
+        if labels is None:
+            return _ClassLabels(None, 1 if M > 1 else 0)
+        try:
+            t = labels if torch.is_tensor(labels) else torch.as_tensor(labels)
+        except (TypeError, RuntimeError, ValueError) as e:
+            raise ValueError("labels: an int or a sequence / tensor of integer class indices expected (%s)" % e) from None
+        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise ValueError("labels: integer class indices expected, got %s" % t.dtype)
+        if t.dim() == 0 and not t.is_cuda:
+            m = int(t)
+            if not 0 <= m < M:
+                raise ValueError("labels: class %d outside [0, %d)" % (m, M))
+            return _ClassLabels(None, m)
+        if t.dim() == 0:
+            t = t.reshape(1).expand(n_samples)
+        if t.dim() != 1 or t.shape[0] != n_samples:
+            raise ValueError("labels: shape %s for %d samples" % (tuple(t.shape), n_samples))
+        if not t.is_cuda and t.numel() and not (0 <= int(t.min()) and int(t.max()) < M):
+            raise ValueError("labels: values outside [0, %d)" % M)
+        return _ClassLabels(t.to(device=self.mG.device, dtype=torch.int32).contiguous(), 0)
+
+    def draw(self, n_samples, labels=None, temperature=1.0, z1=None):
+        """One cf_gmm_draw launch: per sample the class-mixture of `labels` (see _class_labels), a component by its weight,
+        mG + temperature * softplus(sG) * eps - noise from the in-kernel Philox stream, positioned by torch's CUDA generator
+        (`_hip.noise_nonce`) - written behind the channels of z1 (B, C1, H, W), if given: the draw and the concatenate of
+        SplitPrior.reverse in one pass.  Returns (n, C1 + C, H, W)."""
+        _hip.require_device(self.mG, z1)
+        if self.context_net:
+            raise NotImplementedError("class-conditional / tempered sampling of a mixture with a context net")
+        temperature = float(temperature)
+        if not (temperature >= 0.0 and math.isfinite(temperature)):
+            raise ValueError("temperature must be finite and >= 0, got %r" % temperature)
+        dev = self.mG.device
+        lab, label0 = self._class_labels(labels, n_samples)
+        C, H, W = self.mG.shape[2:]
+        D = C * H * W
+        C1, D1, zbs = 0, 0, 0
+        if z1 is not None:
+            z1, zbs = _hip.bview(z1)
+            if z1.dim() != 4 or z1.shape[0] != n_samples or tuple(z1.shape[2:]) != (H, W):
+                raise ValueError("draw: kept half of shape %s for %d samples of a prior over %s" % (tuple(z1.shape), n_samples, (C, H, W)))
+            C1 = z1.shape[1]
+            D1 = C1 * H * W
+        key, nonce = _hip.noise_nonce(dev)
+        out = torch.empty(n_samples, C1 + C, H, W, device=dev, dtype=torch.float32)
+        _hip.call("cf_gmm_draw", _hip.p(_hip.f32(self.mG.detach())), _hip.p(_hip.f32(self.sG.detach())), _hip.p(self.component_cdf()),
+                  _hip.p(lab), label0, None, None, _hip.p(nonce), key, _hip.p(z1 if D1 else None), zbs, D1, _hip.p(out), n_samples,
+                  self.M, self.K, D, temperature, _hip.stream())
+        return out
+
+    def sample(self, n_samples, context=None, need_log_prob=True, *, labels=None, temperature=1.0):
         """gaussian.py:163-169: draw from the mixture of class-mixture index 1 (the reference hard-codes `x[:, 1]`;
-        with a single mixture, where the reference raises, index 0 is used) and return (x, log_prob(x))."""
+        with a single mixture, where the reference raises, index 0 is used) and return (x, log_prob(x)).
+        labels (an int, or n class indices) / temperature (the components' scales are multiplied by it): the draw of
+        `draw` instead - any class-mixture, per sample; with both left at their defaults the reference's draw above runs,
+        in its torch.multinomial / torch.randn order."""
+        if labels is not None or temperature != 1.0:
+            x = self.draw(n_samples, labels, temperature)
+            return x, (self.log_prob(x, context) if need_log_prob else None)
         _hip.require_device(self.mG)
         dev = self.mG.device
         m = 1 if self.M > 1 else 0

@@ -136,10 +136,13 @@ class FlowSequential(nn.Module):
         return tuple(t._version for t in ts)
 
     # ------------------------------------------------------------------ layer-by-layer mode
-    def _forward_layers(self, input, context):
+    def _forward_layers(self, input, context, halves=None):
+        """halves, if a list, receives the channel half every SplitPrior scores and drops (`encode`)."""
         M, B = self.mixtures, input.shape[0]
         logdet = torch.zeros((B, M), device=input.device)
         for module in self.sequence_modules:
+            if halves is not None and isinstance(module, SplitPrior):
+                halves.append(input[:, input.shape[1] // 2:])
             input, ldj = module(input, context)
             logdet += ldj if ldj.dim() == 2 else ldj.unsqueeze(-1)      # flowsequential.py:23
         return input, self.dist.log_prob(input, context) + logdet
@@ -173,12 +176,23 @@ class FlowSequential(nn.Module):
     def _specialist(self):
         return bool(getattr(self.dist, "context_net", None))
 
+    def _has_context_nets(self):
+        """True when the prior, a layer or a layer's prior carries a context net (a specialist flow)."""
+        return bool(getattr(self.dist, "context_net", None)) or any(
+            getattr(m, "context_net", None) or getattr(getattr(m, "dist", None), "context_net", None) for m in self.sequence_modules)
+
     def _needs_only_init(self):
         """True when the fused plan is blocked only by ActNorm layers that have not seen their first batch yet."""
-        if not self.fused or not isinstance(self.dist, GaussianMixtureDistribution) or getattr(self.dist, "context_net", None):
+        if not self.fused or not isinstance(self.dist, GaussianMixtureDistribution):
             return False
-        return not any(getattr(m, "context_net", None) or getattr(getattr(m, "dist", None), "context_net", None)
-                       for m in self.sequence_modules)
+        return not self._has_context_nets()
+
+    def _refresh_generation(self):
+        """A Parameter object was (re)registered somewhere since the last call (see _PARAM_GENERATION): drop what was derived."""
+        if self._gen != _PARAM_GENERATION[0]:
+            self._gen = _PARAM_GENERATION[0]
+            self.__dict__.pop("_derived_owners", None)
+            self.invalidate_caches()
 
     @staticmethod
     def _step_supported(conv, act, cpl, shape):
@@ -248,17 +262,11 @@ class FlowSequential(nn.Module):
         return ops
 
     def _noise_nonce(self, dev):
-        """Per-call position of the in-kernel noise stream: one 63-bit draw from torch's CUDA generator of `dev`, consumed
-        the way torch's own random ops consume it.  So the noise follows `torch.manual_seed` (re-seeding reproduces it,
-        as it does for the reference's torch.rand / randn draws: uniform.py:32, gaussian.py:69), the generator moves on
-        by one draw per forward whatever the user does with it in between, and under graph capture torch registers the
-        generator with the graph: every replay reads a fresh value.  Data-parallel ranks fold their rank into the Philox
-        KEY: equal seeds on every rank still give every rank its own dequantisation / Augment noise."""
-        rank = 0
-        if torch.distributed.is_available() and torch.distributed.is_initialized():
-            rank = torch.distributed.get_rank()
-        self._rng_key = (0x243F6A8885A308D3 ^ (rank * 0x9E3779B97F4A7C15)) & 0xFFFFFFFFFFFFFFFF
-        return torch.empty(1, device=dev, dtype=torch.int64).random_()
+        """Per-call position of the in-kernel noise stream (dequantisation / Augment noise): `_hip.noise_nonce`, which the
+        tempered / class-conditional prior draws use too - one 63-bit draw from torch's CUDA generator per call; the Philox
+        key (rank folded in) goes to `_rng_key`."""
+        self._rng_key, nonce = _hip.noise_nonce(dev)
+        return nonce
 
     def _side_stream(self, dev, k=0):
         s = self._side.get((dev.index, k))
@@ -428,7 +436,8 @@ class FlowSequential(nn.Module):
             for buf in bufs(prior if k == "prior" else prepared[k][0]):
                 buf.record_stream(main)
 
-    def _forward_fused(self, x, context, tape=None):
+    def _forward_fused(self, x, context, tape=None, halves=None):
+        """halves, if a list, receives the channel slice every SplitPrior's mixture kernel scores, in forward order (`encode`)."""
         B, M, dev = x.shape[0], self.mixtures, x.device
         key = tuple(x.shape[1:])
         plan = self._plans.get(key)
@@ -584,6 +593,8 @@ class FlowSequential(nn.Module):
                 if tape is not None:
                     tape.append(_tape.Split(op[1].dist, x, prep))
                 c = x.shape[1] // 2
+                if halves is not None:
+                    halves.append(x[:, c:])
                 if levels is not None:       # small batch: every mixture of the flow in one launch pair at the end
                     levels.append((x[:, c:], prep))
                 else:
@@ -593,6 +604,8 @@ class FlowSequential(nn.Module):
             else:                        # any other layer: its own kernels
                 if tape is not None:
                     tape.append(_tape.Layer(op[1], x))
+                if halves is not None and isinstance(op[1], SplitPrior):
+                    halves.append(x[:, x.shape[1] // 2:])
                 x, ldj = op[1](x, context)
                 if ldj.dim() == 2:
                     if ldM_set:
@@ -621,10 +634,7 @@ class FlowSequential(nn.Module):
     # ------------------------------------------------------------------ reference API
     def forward(self, input, context=None):
         _hip.require_device(input)
-        if self._gen != _PARAM_GENERATION[0]:            # a Parameter object was (re)registered somewhere: see _PARAM_GENERATION
-            self._gen = _PARAM_GENERATION[0]
-            self.__dict__.pop("_derived_owners", None)
-            self.invalidate_caches()
+        self._refresh_generation()
         if torch.is_grad_enabled() and self._specialist():
             from .autograd_ctx import trainable as _trainable
             params = self._trainable_params()
@@ -793,8 +803,12 @@ class FlowSequential(nn.Module):
             return 0.0, mods[1]._s - 1.0
         return None
 
-    def _inverse(self, z, context, clamp):
-        """`inverse`; clamp = (lo, hi): the output of the leading Dequantization's reverse is projected into that range."""
+    def _inverse(self, z, context, clamp, latents=None, labels=None, temperature=1.0):
+        """`inverse`; clamp = (lo, hi): the output of the leading Dequantization's reverse is projected into that range.
+        latents: the split-off halves in forward order, put back by the SplitPriors instead of fresh draws (`decode`);
+        labels / temperature: passed to every SplitPrior's draw (`sample`).  All at their defaults: the plain chain."""
+        if latents is not None:
+            latents = list(latents)
         _hip.require_device(z)
         mods = self.sequence_modules
         i = len(mods) - 1
@@ -811,7 +825,14 @@ class FlowSequential(nn.Module):
                     z = self._inverse_tail(z, i, clamp)
                     i = -1
                 else:
-                    z = m.reverse(z, context)
+                    if isinstance(m, SplitPrior) and latents is not None:
+                        if not latents:
+                            raise ValueError("decode: no latent left for the SplitPrior at layer %d" % i)
+                        z = m.reverse(z, context, latent=latents.pop())
+                    elif isinstance(m, SplitPrior) and (labels is not None or temperature != 1.0):
+                        z = m.reverse(z, context, labels=labels, temperature=temperature)
+                    else:
+                        z = m.reverse(z, context)
                     if i == 0 and clamp is not None and isinstance(m, Dequantization):
                         _hip.call("cf_clamp", _hip.p(z), _hip.p(z), z.numel(), clamp[0], clamp[1], _hip.stream())
                     i -= 1
@@ -840,16 +861,64 @@ class FlowSequential(nn.Module):
                       clamp[0], clamp[1], _hip.stream())
         return x
 
-    def sample(self, n_samples, context=None):
+    def sample(self, n_samples, context=None, labels=None, temperature=1.0):
         """flowsequential.py:32-39: a prior draw through the reverse chain.  By specification, for the image flows: the pixels
         are projected into [0, bins - 1].  The reverse chain ends in floor(bins (sigmoid(y) - a) / (1 - 2 a)) (dequantize.py:19-20,
         normalize.py:36-40), which is -1 / bins wherever sigmoid(y) leaves [a, 1 - a) - logits no forward pass can produce, but
         a prior draw does (1.2 % of the pixels of an untrained cifar10 flow) - and a cast of such an image to uint8 wraps -1
         to 255.  The reference's categorical dequantisers clamp their reverse the same way (dequantize.py:67); `inverse` stays
-        the plain chain, bitwise."""
+        the plain chain, bitwise.
+        labels (an int, or one class index per sample) / temperature: the prior and every SplitPrior on the way back draw
+        from the class-mixture of each sample's label, with the components' scales multiplied by `temperature` - one
+        cf_gmm_draw launch per level (GaussianMixtureDistribution.draw).  labels=None is class-mixture 1, as the default
+        call.  Mixture priors only: ValueError otherwise."""
+        if labels is not None or temperature != 1.0:
+            if not isinstance(self.dist, GaussianMixtureDistribution):
+                raise ValueError("sample: labels / temperature need a mixture prior, not %s" % type(self.dist).__name__)
+            labels = self.dist._class_labels(labels, n_samples)      # checked and moved to the device once, for every level
+            z = self.dist.draw(n_samples, labels, temperature)
+            return self._inverse(z, context, self._pixel_range(), labels=labels, temperature=temperature)
         z = self.dist.sample(n_samples, context, need_log_prob=False)[0] if isinstance(self.dist, GaussianMixtureDistribution) \
             else self.dist.sample(n_samples, context)[0]           # (the reference's sample() also returns log p(z): not needed here)
         return self._inverse(z, context, self._pixel_range())
+
+    def _split_priors(self):
+        return [m for m in self.sequence_modules if isinstance(m, SplitPrior)]
+
+    def encode(self, x, context=None):
+        """(latents, logp): the complete latent of x - latents = [half_1, ..., half_n, z], the channel half every SplitPrior
+        split off, in forward order, and the final z, each a fresh contiguous tensor - and the (B, M) log-densities.  The
+        same kernels as `forward` (the fused plan when it applies; never a replayed graph): the halves are the slices the
+        mixture kernels score, copied out, and under the same seed / injected noise z and logp are `forward`'s bit for bit.
+        `decode` is the way back."""
+        _hip.require_device(x)
+        if self._has_context_nets():
+            raise NotImplementedError("encode of a context-conditioned (specialist) flow")
+        self._refresh_generation()
+        halves = []
+        with torch.no_grad():
+            if self._fusable():
+                z, logp = self._forward_fused(x, context, halves=halves)
+            else:
+                z, logp = self._forward_layers(x, context, halves=halves)
+            assert len(halves) == len(self._split_priors())
+            latents = [h.clone(memory_format=torch.contiguous_format) for h in halves + [z]]
+        return latents, logp
+
+    def decode(self, latents, context=None, clamp=False):
+        """The reverse chain on a complete latent (`encode`'s list: one half per SplitPrior in forward order, then z): every
+        SplitPrior puts its half back instead of drawing one.  clamp=True: the projection into the pixel range that `sample`
+        applies.  ValueError for a wrong number of latents or a latent whose shape is not its level's."""
+        latents = list(latents)
+        n = len(self._split_priors())
+        if len(latents) != n + 1:
+            raise ValueError("decode: %d latents for a flow with %d SplitPriors (%d expected: the halves, then z)" % (len(latents), n, n + 1))
+        z = latents[-1]
+        if any(h.shape[0] != z.shape[0] for h in latents):
+            raise ValueError("decode: latents of different batch sizes %s" % [h.shape[0] for h in latents])
+        if isinstance(self.dist, GaussianMixtureDistribution) and tuple(z.shape[1:]) != tuple(self.dist.mG.shape[2:]):
+            raise ValueError("decode: z of shape %s, the prior is over %s" % (tuple(z.shape), tuple(self.dist.mG.shape[2:])))
+        return self._inverse(z, context, self._pixel_range() if clamp else None, latents=latents[:-1])
 
 
 class GraphedFlow:

@@ -204,6 +204,22 @@ int cf_gmm_resp(const float* x, const float* a, const float* nm, const float* cs
  * rows[n] = m*K + k_n (int64, component drawn by the caller), eps ~ N(0,1) supplied by the caller.      */
 int cf_gmm_sample(const float* mG, const float* sG, const int64_t* rows, const float* eps, float* out, int N, int D,
                   cf_stream_t stream);
+/* class-conditional, tempered prior draw and the SplitPrior concatenate in ONE launch.  Per sample b:
+ *   m = clamp(labels[b], 0, M - 1)  (labels == NULL: label0 for every sample),  k = the first index with u_b < cdf[m][k]
+ *   (cdf (M, K): cumulative component weights, last column 1),
+ *   out[b, :D1]    = z1[b * z1_bstride + :D1]   bit for bit (the kept half; z1 == NULL / D1 == 0: none),
+ *   out[b, D1 + d] = fmaf(ts, eps[b, d], mG[m K + k, d]),  ts = temperature * softplus(sG[m K + k, d]) rounded to fp32 first
+ *   (softplus as cf_gmm_sample: v > 20 ? v : log1pf(expf(v))); out (B, D1 + D) contiguous.
+ * Noise: u (B) and eps (B, D) both given, or both NULL: Philox4x32-10 inside the kernel, key = seed, counter low 64 bits
+ * = b * (1 + ceil(D / 4)) + j, high 64 bits = state[0] (one uint64 on the device): j = 0 -> u_b = the first word's upper
+ * 24 bits / 2^24, j >= 1 -> the four normals d = 4 (j - 1) .. 4 (j - 1) + 3 (Box-Muller on the word pairs, as
+ * cf_preprocess_rng_fwd).  The numbers depend on (seed, state[0], b, d) only - not on the launch geometry, on alignment or
+ * on `temperature`: equal (seed, state) give the same component and the same eps at every temperature.
+ * 16 bytes per lane when D, D1, z1_bstride are multiples of 4 and mG, sG, eps, z1, out are 16-byte aligned, a scalar form
+ * otherwise; both give the same bits.  K <= 16.  B == 0: no-op.                                                        */
+int cf_gmm_draw(const float* mG, const float* sG, const float* cdf, const int32_t* labels, int label0, const float* u,
+                const float* eps, const unsigned long long* state, unsigned long long seed, const float* z1,
+                int64_t z1_bstride, int D1, float* out, int B, int M, int K, int D, float temperature, cf_stream_t stream);
 
 /* ---- fused flow step: Conv1x1 -> ActNorm -> Coupling(conv net) in ONE kernel, fp32 MFMA ---------
  * (model.py:129-147 per-step triple; coupling.py:26-29 net; conv1x1.py:52-57; actnorm.py:53-60)
