@@ -75,3 +75,59 @@ class Layer(NamedTuple):
     kind = "layer"
     module: Any
     x: Any = None
+
+
+# ---- specialist (context-conditioned) flows: each layer's training forward appends its own record, autograd_ctx.SpecialistLogProb
+# walks them; besides these the specialist tape holds Pre and Squeeze.  c: the code of the layer's context encoder, eps: the
+# Gaussian draw of a flow-type encoder (flowlayer.encoder_noise) or None
+class Permute(NamedTuple):
+    kind = "permute"
+    inverse: tuple           # PermuteAxes.inverse_permutation
+
+
+class CtxAffine(NamedTuple):
+    """Conv1x1 / ActNorm with a context net: m = CN(c), the per-sample matrix / shift and log-scale"""
+    kind = "ctx_affine"
+    module: Any
+    x: Any
+    c: Any
+    m: Any
+    eps: Any
+
+
+class CtxCoupling(NamedTuple):
+    """Coupling with a context net, fused step kernel: a1, a2, cn = the activations of its CN chain"""
+    kind = "ctx_coupling"
+    module: Any
+    x: Any
+    c: Any
+    a1: Any
+    a2: Any
+    cn: Any
+    ws: Any                  # packed forward tables
+    mode: int                # 1: CN(c) on the conditioner output (contextflow), 2: in front of its first ReLU
+    planes: Any              # step_tape(...) of the forward (mode 2), else None
+    eps: Any
+
+
+class CtxTransCoupling(NamedTuple):
+    kind = "ctx_transcoupling"
+    module: Any
+    x: Any
+    c: Any
+    a1: Any
+    a2: Any
+    cn: Any
+    eps: Any
+
+
+class CtxMixture(NamedTuple):
+    """context-shifted mixture (a SplitPrior's or the final prior): x is the part it scores, c the embedding rows"""
+    kind = "ctx_mixture"
+    dist: Any
+    x: Any
+    c: Any
+    logw: Any
+    context: Any
+    lp: Any                  # per-component log-joints of the forward
+    tab: Any                 # (key, inv, dsig, lsum) scale tables of the embedding-lookup form, or None

@@ -5,7 +5,8 @@ first forward in any mode, uses the unbiased std and log(std + 1e-8); ldj = +sum
 import torch
 import torch.nn as nn
 
-from . import _hip
+from . import _hip, _tape
+from .context import cn_linear
 from .flowlayer import FlowLayer, encoder_noise
 
 
@@ -78,25 +79,20 @@ class ActNorm(FlowLayer):
     def _forward_ctx(self, x, context, tape=None, pre=None):
         """actnorm.py:40-60: per-sample shift / log-scale CN(c), added to the shared ones under contextflow (the only
         branch that runs the data-dependent init).  pre: code, log-density and CN(c) from the grouped front end (specialist.py)."""
-        from .simple_vit import _linear
-        if pre is not None:
-            c, logp_c = pre["c"], pre["logp"]
-        else:
-            c, logp_c = self.context_net(context)
         if self.contextflow and not self._init_done:
             self.initialize(x)
+        cn = cn_linear(self, context, pre)                                      # m: (B, 2C)
         x, xbs = _hip.bview(x)
         B, C, H, W = x.shape
-        m = pre["m"] if pre is not None else _linear(_hip.f32(c), self.CN)      # (B, 2C)
         t = _hip.f32(self.NN_t.detach()) if self.contextflow else None
         logs = _hip.f32(self.NN_logs.detach()) if self.contextflow else None
         z = torch.empty(B, C, H, W, device=x.device, dtype=torch.float32)
         ldj = torch.empty(B, device=x.device, dtype=torch.float32)
-        _hip.call("cf_actnorm_ctx", _hip.p(x), _hip.p(m), _hip.p(t), _hip.p(logs), _hip.p(z), _hip.p(ldj), B, C, H * W, xbs,
+        _hip.call("cf_actnorm_ctx", _hip.p(x), _hip.p(cn.m), _hip.p(t), _hip.p(logs), _hip.p(z), _hip.p(ldj), B, C, H * W, xbs,
                   _hip.stream())
         if tape is not None:
-            tape.append(dict(x=x, c=_hip.f32(c), m=m, eps=encoder_noise(self.context_net)))
-        return z, ldj + logp_c * float(H * W)
+            tape.append(_tape.CtxAffine(self, x, cn.c, cn.m, encoder_noise(self.context_net)))
+        return z, ldj + cn.logp * float(H * W)
 
     def forward(self, x, context=None):
         _hip.require_device(x)

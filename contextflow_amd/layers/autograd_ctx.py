@@ -9,11 +9,13 @@ cf_gmm_ctx_bwd) and turns the per-sample parameter gradients into CN / embedding
 Built for the conv couplings with the encoders that have no trainable parameters of their own (eye | onehot + uniform)
 and for embedding lookups (embed + eyesample)."""
 import os
+from typing import Any, NamedTuple
 
 import torch
 
-from . import _derived, _hip
+from . import _derived, _hip, _tape
 from .actnorm import ActNorm
+from .autograd_layers import _new, _relu_mask
 from .context import (ArgmaxCatDequantization, CatEmbeddings, EyeSampling, ProbSampling, UniformCatDequantization,
                       VariationalCatDequantization)
 from .conv1x1 import Conv1x1
@@ -22,28 +24,18 @@ from .permute_axes import PermuteAxes
 from .splitprior import SplitPrior
 from .squeeze import Squeeze, squeeze_op
 
-
-def _new(*shape, like):
-    return torch.empty(*shape, device=like.device, dtype=torch.float32)
+TRAINABLE_ENCODERS = (UniformCatDequantization, EyeSampling, VariationalCatDequantization, ArgmaxCatDequantization, ProbSampling)
 
 
 def trainable(flow):
     """True when this specialist flow can be trained here: every context encoder create_model builds, conv and
-    transformer couplings, with contextflow (frozen generalist) or without (every parameter trains)."""
-    ok = (UniformCatDequantization, EyeSampling, VariationalCatDequantization, ArgmaxCatDequantization, ProbSampling)
+    transformer couplings, with contextflow (frozen generalist) or without (every parameter trains).  FlowSequential.forward
+    enters SpecialistLogProb only behind this check (a captured training step goes through it too)."""
     for m in list(flow.sequence_modules) + [flow.dist]:
         cn = getattr(m, "context_net", None) or getattr(getattr(m, "dist", None), "context_net", None)
-        if not cn:
-            continue
-        if not isinstance(cn[1], ok):
+        if cn and not isinstance(cn[1], TRAINABLE_ENCODERS):
             return False
     return True
-
-
-def _check_encoder(enc):
-    if not isinstance(enc[1], (UniformCatDequantization, EyeSampling, VariationalCatDequantization, ArgmaxCatDequantization,
-                               ProbSampling)):
-        raise NotImplementedError("specialist training with a %s context encoder" % type(enc[1]).__name__)
 
 
 def _encoder_backward(enc, context, gc, grads, glq=None, eps=None):
@@ -97,8 +89,8 @@ def _couplingfc_backward(m, x_in, gz, gld, grads):
     _hip.call("cf_coupling_apply_bwd", _hip.p(xc), _hip.p(h), _hip.p(gzc), _hip.p(gldc), _hip.p(gx), _hip.p(gh), B, n, 1, n, n,
               st)
     g2, gW3, gb3 = _dense_bwd(a2, Ws[2], gh)
-    g1, gW2, gb2 = _dense_bwd(a1, Ws[1], _relu_bwd(a2, g2))
-    g0, gW1, gb1 = _dense_bwd(x0, Ws[0], _relu_bwd(a1, g1))
+    g1, gW2, gb2 = _dense_bwd(a1, Ws[1], _relu_mask(a2, g2))
+    g0, gW1, gb1 = _dense_bwd(x0, Ws[0], _relu_mask(a1, g1))
     for c, gW, gb in zip(convs, (gW1, gW2, gW3), (gb1, gb2, gb3)):
         grads[c.weight], grads[c.bias] = gW.view_as(c.weight), gb
     gx[:, :half] += g0
@@ -178,21 +170,29 @@ def _embedding_grads(emb, context, gc, grads):
 
 
 DEFER_LINEAR_WGRADS = os.environ.get("CONTEXTFLOW_SPEC_DEFER_WGRADS", "1") != "0"      # A/B switch (tools/specialist_train_bench.py)
-_DEFER = "_deferred_linear_wgrads"      # key of `grads`: [(x_in, gy, lin)] whose weight gradients are formed at the end of the backward
 
 
-def _linear_bwd(x_in, lin, gy, grads, need_gx=True):
+class _Pass(NamedTuple):
+    """One specialist backward: what every record's backward reads, and where the gradients go.  The encoder, embedding, ViT and
+    autograd_layers functions receive by_param alone."""
+    context: Any
+    glogp: Any               # d/d logp (B, M)
+    gld: Any                 # d/d of a per-sample log-det (B,): its row sums
+    by_param: dict           # Parameter -> gradient
+    deferred: Any            # [(x_in, gy, lin)]: CN Linears whose weight gradients are formed at the end of the backward; None = one by one
+
+
+def _linear_bwd(x_in, lin, gy, bw, need_gx=True):
     """nn.Linear of a CN net: weight / bias gradients and the data gradient through cf_linear_wgrad / cf_linear.  With a deferral
-    list in `grads` (the specialist backward) only the data gradient is formed here; the weight gradients of all CN Linears of the
+    list (`bw.deferred`) only the data gradient is formed here; the weight gradients of all CN Linears of the
     flow - 60 operand pairs in the cifar10 flow, 420 launches of 7 - 10 us one by one - leave in grouped launches at the end
     (_flush_linear_wgrads: cf_linear_wgrad_group, the transformer step's LDS-free kernel)."""
-    defer = grads.get(_DEFER)
-    if defer is None:
+    if bw.deferred is None:
         gx, gW, gb = _dense_bwd(_hip.f32(x_in), _hip.f32(lin.weight.detach()), _hip.f32(gy), need_gx)
-        grads[lin.weight], grads[lin.bias] = gW, gb
+        bw.by_param[lin.weight], bw.by_param[lin.bias] = gW, gb
         return gx
     x_in, gy = _hip.f32(x_in).contiguous(), _hip.f32(gy).contiguous()
-    defer.append((x_in, gy, lin))
+    bw.deferred.append((x_in, gy, lin))
     if not need_gx:
         return None
     W2d = _hip.f32(lin.weight.detach())
@@ -202,14 +202,14 @@ def _linear_bwd(x_in, lin, gy, grads, need_gx=True):
     return gx
 
 
-def _flush_linear_wgrads(grads, dev):
+def _flush_linear_wgrads(bw, dev):
     from .autograd import wgrad_group
-    todo = grads.pop(_DEFER, None) or []
+    todo = bw.deferred or []
     for i0 in range(0, len(todo), 32):                  # cf_linear_wgrad_group takes up to 32 members per launch pair
         part = todo[i0:i0 + 32]
         res = wgrad_group([(x_in, gy, True) for x_in, gy, _ in part], dev)
         for (_, _, lin), (gW, gb) in zip(part, res):
-            grads[lin.weight], grads[lin.bias] = gW.view_as(lin.weight), gb
+            bw.by_param[lin.weight], bw.by_param[lin.bias] = gW.view_as(lin.weight), gb
 
 
 def _encoder_needs_gc(enc):
@@ -221,63 +221,55 @@ def _encoder_needs_gc(enc):
     return True
 
 
-def _relu_bwd(act, gy):
-    out = torch.empty_like(gy)
-    _hip.call("cf_relu_bwd", _hip.p(act), _hip.p(gy), _hip.p(out), gy.numel(), _hip.stream())
-    return out
+def _cn_input_backward(rec, lin, gy, ldscale, bw):
+    """The end of every CN backward: `lin`, the Linear that takes the context code rec.c (gy = d/d of its output), and the encoder
+    behind it.  The layer's log-det holds ldscale * logp_c, so d/d logp_c = ldscale * gld - formed only where the encoder reads it."""
+    need = _encoder_needs_gc(rec.module.context_net)
+    gc = _linear_bwd(rec.c, lin, gy, bw, need)
+    if need:
+        glq = _hip.f32(bw.gld)
+        _encoder_backward(rec.module.context_net, bw.context, gc, bw.by_param, glq if ldscale == 1.0 else glq * ldscale, rec.eps)
 
 
-def conv1x1_ctx_backward(m, rec, context, gz, gld, grads):
-    x, xbs = _hip.bview(rec["x"])
+def affine_ctx_backward(rec, gz, bw):
+    """Conv1x1 / ActNorm with a context net: the data gradient and d/d m of the per-sample parameters m = CN(c) in one kernel."""
+    m, gld = rec.module, bw.gld
+    x, xbs = _hip.bview(rec.x)
     gzv, gzbs = _hip.bview(gz)
     B, C, H, W = x.shape
     gx = _new(B, C, H, W, like=x)
-    gm = _new(B, C * C, like=x)
-    Wm = _hip.f32(m.NN.detach()) if m.contextflow else None
-    _hip.call("cf_conv1x1_ctx_bwd", _hip.p(x), _hip.p(rec["m"]), _hip.p(Wm), _hip.p(gzv), _hip.p(gld), _hip.p(gx), _hip.p(gm),
-              B, C, H * W, xbs, gzbs, _hip.stream())
-    need = _encoder_needs_gc(m.context_net)
-    gc = _linear_bwd(rec["c"], m.CN, gm, grads, need)
-    if need:
-        _encoder_backward(m.context_net, context, gc, grads, _hip.f32(gld) * float(H * W), rec.get("eps"))   # ldj += H W logp_c
+    if isinstance(m, Conv1x1):
+        gm = _new(B, C * C, like=x)
+        Wm = _hip.f32(m.NN.detach()) if m.contextflow else None
+        _hip.call("cf_conv1x1_ctx_bwd", _hip.p(x), _hip.p(rec.m), _hip.p(Wm), _hip.p(gzv), _hip.p(gld), _hip.p(gx), _hip.p(gm),
+                  B, C, H * W, xbs, gzbs, _hip.stream())
+    else:
+        gm = _new(B, 2 * C, like=x)
+        t = _hip.f32(m.NN_t.detach()) if m.contextflow else None
+        logs = _hip.f32(m.NN_logs.detach()) if m.contextflow else None
+        _hip.call("cf_actnorm_ctx_bwd", _hip.p(x), _hip.p(rec.m), _hip.p(t), _hip.p(logs), _hip.p(gzv), _hip.p(gld), _hip.p(gx),
+                  _hip.p(gm), B, C, H * W, xbs, gzbs, _hip.stream())
+    _cn_input_backward(rec, m.CN, gm, float(H * W), bw)                     # ldj += H W logp_c
     return gx
 
 
-def actnorm_ctx_backward(m, rec, context, gz, gld, grads):
-    x, xbs = _hip.bview(rec["x"])
-    gzv, gzbs = _hip.bview(gz)
-    B, C, H, W = x.shape
-    gx = _new(B, C, H, W, like=x)
-    gm = _new(B, 2 * C, like=x)
-    t = _hip.f32(m.NN_t.detach()) if m.contextflow else None
-    logs = _hip.f32(m.NN_logs.detach()) if m.contextflow else None
-    _hip.call("cf_actnorm_ctx_bwd", _hip.p(x), _hip.p(rec["m"]), _hip.p(t), _hip.p(logs), _hip.p(gzv), _hip.p(gld), _hip.p(gx),
-              _hip.p(gm), B, C, H * W, xbs, gzbs, _hip.stream())
-    need = _encoder_needs_gc(m.context_net)
-    gc = _linear_bwd(rec["c"], m.CN, gm, grads, need)
-    if need:
-        _encoder_backward(m.context_net, context, gc, grads, _hip.f32(gld) * float(H * W), rec.get("eps"))   # ldj += H W logp_c
-    return gx
+def _cn_chain_backward(rec, gcn, ldscale, bw):
+    """CN = Linear -> ReLU -> Linear -> ReLU -> Linear (coupling.py:37) and the context encoder behind it; gcn = d/d CN(c),
+    ldscale: the factor of the encoder's log-density in the layer's log-det."""
+    CN = rec.module.CN
+    ga2 = _relu_mask(rec.a2, _linear_bwd(rec.a2, CN[4], gcn, bw))
+    ga1 = _relu_mask(rec.a1, _linear_bwd(rec.a1, CN[2], ga2, bw))
+    _cn_input_backward(rec, CN[0], ga1, ldscale, bw)
 
 
-def _cn_chain_backward(m, rec, context, gcn, grads, glq):
-    """CN = Linear -> ReLU -> Linear -> ReLU -> Linear (coupling.py:37) and the context encoder behind it; glq = d/d of the
-    encoder's log-density term of the layer's log-det."""
-    ga2 = _relu_bwd(rec["a2"], _linear_bwd(rec["a2"], m.CN[4], gcn, grads))
-    ga1 = _relu_bwd(rec["a1"], _linear_bwd(rec["a1"], m.CN[2], ga2, grads))
-    need = _encoder_needs_gc(m.context_net)
-    gc = _linear_bwd(rec["c"], m.CN[0], ga1, grads, need)
-    if need:
-        _encoder_backward(m.context_net, context, gc, grads, glq() if callable(glq) else glq, rec.get("eps"))
-
-
-def coupling_ctx_backward(m, rec, context, gz, gld, grads):
+def coupling_ctx_backward(rec, gz, bw):
     """Coupling with a context net through the fused step-backward kernel (identity 1x1 / ActNorm in front).
     contextflow (mode 1): the conditioner is frozen, CN(c) is a bias on its output - d/d CN(c) = per-sample row sums of the
     conditioner-output gradient plane.  Without contextflow (mode 2): CN(c) enters through the extra input channels of
     the first 1x1 (a per-sample bias before its ReLU) and every parameter trains - the backward kernel loads the planes the
     forward taped, the weight gradients are the generalist's GEMMs plus two small products for the context columns."""
-    x, xbs = _hip.bview(rec["x"])
+    m, gld = rec.module, bw.gld
+    x, xbs = _hip.bview(rec.x)
     B, C, H, W = x.shape
     HW, D, HID = H * W, C // 2, 2 * C
     dev, st, f, pp, L = x.device, _hip.stream(), _hip.f32, _hip.p, _hip.lib()
@@ -288,23 +280,23 @@ def coupling_ctx_backward(m, rec, context, gz, gld, grads):
         eye = torch.eye(C, device=dev, dtype=torch.float32)
         zero = torch.zeros(C, device=dev, dtype=torch.float32)
         wsb = torch.empty(L.cf_flow_step_bwd_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
-        w1x = w1 if rec["mode"] == 1 else w1[:, :D].contiguous()
+        w1x = w1 if rec.mode == 1 else w1[:, :D].contiguous()
         _hip.call("cf_flow_step_bwd_prepare", pp(eye), pp(zero), pp(w1x), pp(f(c2.weight.detach())),
                   pp(f(c3.weight.detach())), pp(wsb), C, H, W, st)
         return wsb
-    wsb = _derived.get(m, "ctx_wsb", _derived.key((c1.weight, c2.weight, c3.weight), rec["mode"], C, H, W, str(dev)), build, dev)
+    wsb = _derived.get(m, "ctx_wsb", _derived.key((c1.weight, c2.weight, c3.weight), rec.mode, C, H, W, str(dev)), build, dev)
     gx = torch.empty(B, C, H, W, device=dev, dtype=torch.float32)
     s_gh = torch.empty(B, C, HW, device=dev, dtype=torch.float32)
     gzc = f(gz).contiguous()
-    if rec["mode"] == 1:                                                  # s_gh is the only plane this mode writes
-        _hip.call("cf_flow_step_bwd_ctx", pp(x), pp(gzc), pp(f(gld)), pp(rec["ws"]), pp(wsb), pp(rec["cn"]), pp(gx), None,
+    if rec.mode == 1:                                                  # s_gh is the only plane this mode writes
+        _hip.call("cf_flow_step_bwd_ctx", pp(x), pp(gzc), pp(f(gld)), pp(rec.ws), pp(wsb), pp(rec.cn), pp(gx), None,
                   None, None, pp(s_gh), None, None, None, B, C, H, W, xbs, st)
         gcn = _new(B, C, like=x)
         _hip.call("cf_sample_channel_sums", pp(s_gh), pp(gcn), B, C, HW, st)
-        _cn_chain_backward(m, rec, context, gcn, grads, lambda: f(gld) * float(HW))      # ldj += H W logp_c (coupling.py:43)
+        _cn_chain_backward(rec, gcn, float(HW), bw)                    # ldj += H W logp_c (coupling.py:43)
         return gx
     new = lambda rows: torch.empty(B, rows, HW, device=dev, dtype=torch.float32)
-    y0, h1, h2, aux = rec["planes"]
+    y0, h1, h2, aux = rec.planes
     s_gh2, s_gh1, s_gy = new(HID), new(HID), new(C)
     _hip.call("cf_flow_step_bwd_taped", pp(gzc), pp(f(gld)), pp(wsb), pp(aux), pp(gx), pp(s_gh), pp(s_gh2), pp(s_gh1), pp(s_gy),
               B, C, H, W, 0, st)
@@ -324,32 +316,34 @@ def coupling_ctx_backward(m, rec, context, gz, gld, grads):
     s1 = _new(B, HID, like=x)
     _hip.call("cf_sample_channel_sums", pp(s_gh1), pp(s1), B, HID, HW, st)
     wc = w1[:, D:, 0, 0]                                                  # (HID, O)
-    _, gwc, _ = _dense_bwd(_hip.f32(rec["cn"]), wc.contiguous(), s1, need_gx=False)      # (HID, O) = s1^T CN(c)
-    grads[c1.weight] = torch.cat([gw1[0], gwc], dim=1).reshape(c1.weight.shape)
-    grads[c1.bias] = gb1
-    grads[c2.weight], grads[c2.bias] = gw2.permute(1, 2, 0).reshape(c2.weight.shape), gb2
-    grads[c3.weight], grads[c3.bias] = gw3[0].reshape(c3.weight.shape), gb3
+    _, gwc, _ = _dense_bwd(_hip.f32(rec.cn), wc.contiguous(), s1, need_gx=False)      # (HID, O) = s1^T CN(c)
+    by = bw.by_param
+    by[c1.weight] = torch.cat([gw1[0], gwc], dim=1).reshape(c1.weight.shape)
+    by[c1.bias] = gb1
+    by[c2.weight], by[c2.bias] = gw2.permute(1, 2, 0).reshape(c2.weight.shape), gb2
+    by[c3.weight], by[c3.bias] = gw3[0].reshape(c3.weight.shape), gb3
     gcn = _new(B, wc.shape[1], like=x)
     _hip.call("cf_linear", pp(s1), pp(wc.t().contiguous()), None, None, pp(gcn), B, HID, wc.shape[1], 0, st)   # s1 wc
-    _cn_chain_backward(m, rec, context, gcn, grads, lambda: f(gld) * float(HW))
+    _cn_chain_backward(rec, gcn, float(HW), bw)
     return gx
 
 
-def transcoupling_ctx_backward(m, rec, context, gz, gld, grads):
+def transcoupling_ctx_backward(rec, gz, bw):
     """TransCoupling with a context net (coupling.py:123-133).  contextflow: h = ViT(x0) + CN(c) with the ViT frozen -
     the ViT is re-run with a tape (as in the generalist backward), d/d CN(c) = per-sample row sums of d/dh, d/dx0 through
     the ViT (data gradient only).  Without contextflow: h = ViT([x0 ; CN(c) broadcast over the window]) and every
     parameter trains - d/d CN(c) = the row sums of the ViT's input gradient over its context channels."""
     from .autograd_layers import vit_backward, vit_forward_taped
-    x, xbs = _hip.bview(rec["x"])
+    m, gld = rec.module, bw.gld
+    x, xbs = _hip.bview(rec.x)
     gzv, gzbs = _hip.bview(gz)
     B, C, H, W = x.shape
     half, st = C // 2, _hip.stream()
     if m.contextflow:
         h, vtape = vit_forward_taped(m.NN[0], x[:, :half])
-        _hip.call("cf_add_sample_bias", _hip.p(h), _hip.p(rec["cn"]), B, C, H * W, 0, st)
+        _hip.call("cf_add_sample_bias", _hip.p(h), _hip.p(rec.cn), B, C, H * W, 0, st)
     else:
-        cn = rec["cn"]
+        cn = rec.cn
         xin = torch.cat([_hip.f32(x[:, :half]), cn.view(B, -1, 1, 1).expand(B, cn.shape[1], H, W)], dim=1)   # index op
         h, vtape = vit_forward_taped(m.NN, xin)
     gx = _new(B, C, H, W, like=x)
@@ -359,51 +353,67 @@ def transcoupling_ctx_backward(m, rec, context, gz, gld, grads):
     if m.contextflow:
         gcn = _new(B, C, like=x)
         _hip.call("cf_sample_channel_sums", _hip.p(ghd), _hip.p(gcn), B, C, H * W, st)
-        gx[:, :half] += vit_backward(m.NN[0], vtape, ghd, None)       # grads = None: the ViT is frozen, data gradient only
+        gx[:, :half] += vit_backward(m.NN[0], vtape, ghd, None)       # bw = None: the ViT is frozen, data gradient only
     else:
-        gxin = vit_backward(m.NN, vtape, ghd, grads)
+        gxin = vit_backward(m.NN, vtape, ghd, bw.by_param)
         gx[:, :half] += gxin[:, :half]
         gctx = gxin[:, half:].contiguous()
         gcn = _new(B, gctx.shape[1], like=x)
         _hip.call("cf_sample_channel_sums", _hip.p(gctx), _hip.p(gcn), B, gctx.shape[1], H * W, st)
-    _cn_chain_backward(m, rec, context, gcn, grads, _hip.f32(gld))          # quirk: no H W factor here (coupling.py:126)
+    _cn_chain_backward(rec, gcn, 1.0, bw)                                # quirk: no H W factor here (coupling.py:126)
     return gx
 
 
-def gmm_ctx_backward(dist, rec, g, grads):
-    """Context-shifted GMM: d/dx and the embedding-table gradients (mG / sG / wG are frozen under contextflow)."""
-    x, xbs = _hip.bview(rec["x"])
+def gmm_ctx_backward(rec, g, grads):
+    """Context-shifted GMM: d/dx and the embedding-table gradients (mG / sG / wG are frozen under contextflow).  grads: Parameter ->
+    gradient."""
+    dist = rec.dist
+    x, xbs = _hip.bview(rec.x)
     B, D, H, W = x.shape
     M, K = dist.M, dist.K
     gx = _new(B, D, H, W, like=x)
     gc = _new(B, 2 * M * K * D, like=x)
-    tab = rec.get("tab")
+    tab = rec.tab
     if tab is not None:                       # scale shifts by table lookup (embedding context net)
         key, inv, dsig, lsum = tab
         _hip.call("cf_gmm_ctx_bwd_tab", _hip.p(x), _hip.p(_hip.f32(dist.mG.detach())), _hip.p(inv), _hip.p(dsig), _hip.p(lsum),
-                  _hip.p(rec["logw"]), _hip.p(rec["c"]), _hip.p(key), _hip.p(_hip.f32(g)), _hip.p(rec.get("lp")), _hip.p(gx),
+                  _hip.p(rec.logw), _hip.p(rec.c), _hip.p(key), _hip.p(_hip.f32(g)), _hip.p(rec.lp), _hip.p(gx),
                   _hip.p(gc), B, M, K, D, H * W, xbs, _hip.stream())
     else:
         _hip.call("cf_gmm_ctx_bwd", _hip.p(x), _hip.p(_hip.f32(dist.mG.detach())), _hip.p(_hip.f32(dist.sG.detach())),
-                  _hip.p(rec["logw"]), _hip.p(rec["c"]), _hip.p(_hip.f32(g)), _hip.p(rec.get("lp")), _hip.p(gx), _hip.p(gc), B, M,
+                  _hip.p(rec.logw), _hip.p(rec.c), _hip.p(_hip.f32(g)), _hip.p(rec.lp), _hip.p(gx), _hip.p(gc), B, M,
                   K, D, H * W, xbs, _hip.stream())
-    _embedding_grads(dist.context_net[0], rec["context"], gc, grads)
+    _embedding_grads(dist.context_net[0], rec.context, gc, grads)
     if not dist.contextflow:                  # the prior's own parameters train too (gaussian.py:130-137)
-        if tab is None or rec.get("lp") is None:
+        if tab is None or rec.lp is None:
             raise NotImplementedError("prior parameter gradients need the embedding-lookup context net (table form)")
         gf = _hip.f32(g)
-        r = (torch.softmax(rec["lp"].view(B, M, K), dim=-1) * gf.unsqueeze(-1)).reshape(B, M * K).contiguous()
+        r = (torch.softmax(rec.lp.view(B, M, K), dim=-1) * gf.unsqueeze(-1)).reshape(B, M * K).contiguous()
         slab = 256
         nb = (B + slab - 1) // slab
         pgm = _new(nb, M * K, D * H * W, like=x)
         pgs = _new(nb, M * K, D * H * W, like=x)
         _hip.call("cf_gmm_ctx_pgrad_tab", _hip.p(x), _hip.p(_hip.f32(dist.mG.detach())), _hip.p(inv), _hip.p(dsig),
-                  _hip.p(rec["c"]), _hip.p(key), _hip.p(r), _hip.p(pgm), _hip.p(pgs), B, M, K, D, H * W, xbs, slab, _hip.stream())
+                  _hip.p(rec.c), _hip.p(key), _hip.p(r), _hip.p(pgm), _hip.p(pgs), B, M, K, D, H * W, xbs, slab, _hip.stream())
         grads[dist.mG] = pgm.sum(0).view_as(dist.mG)
         grads[dist.sG] = pgs.sum(0).view_as(dist.sG)
         R = r.sum(0).view(M, K)
         grads[dist.wG] = R - R.sum(-1, keepdim=True) * torch.softmax(_hip.f32(dist.wG.detach()), dim=-1)
     return gx
+
+
+# What SpecialistLogProb.forward and the layers' training forwards (_forward_ctx, _log_prob_ctx) append to the tape, and the
+# backward of each kind: (record, d/d of the layer's output, the pass) -> d/d of its input
+RECORDS = (_tape.Pre, _tape.Squeeze, _tape.Permute, _tape.CtxAffine, _tape.CtxCoupling, _tape.CtxTransCoupling, _tape.CtxMixture)
+BACKWARD = {
+    "pre": None,                                         # ends the walk: nothing trainable at or above the pre-processing
+    "squeeze": lambda rec, gz, bw: squeeze_op(gz, rec.p, True),
+    "permute": lambda rec, gz, bw: gz.permute(rec.inverse).contiguous(),
+    "ctx_affine": affine_ctx_backward,
+    "ctx_coupling": coupling_ctx_backward,
+    "ctx_transcoupling": transcoupling_ctx_backward,
+    "ctx_mixture": lambda rec, gz, bw: torch.cat([gz, gmm_ctx_backward(rec, bw.glogp, bw.by_param)], dim=1),   # a SplitPrior's
+}
 
 
 class SpecialistLogProb(torch.autograd.Function):
@@ -412,7 +422,7 @@ class SpecialistLogProb(torch.autograd.Function):
     @staticmethod
     def forward(ctx, flow, x, context, *params):
         B, M = x.shape[0], flow.mixtures
-        tape = []
+        tape = [_tape.Pre()]                             # whatever runs before the first record below is pre-processing
         logdet = torch.zeros(B, M, device=x.device, dtype=torch.float32)
         # everything the CN nets compute from the context alone, for all layers at once (the uniform encoders' codes are formed
         # inside the first grouped launch and kept for the backward): 36 encodings + 60 Linears one by one otherwise
@@ -420,64 +430,39 @@ class SpecialistLogProb(torch.autograd.Function):
         specialist._draw_encoder_noise(flow, B, x.device)
         pre = specialist._front_end(flow, context, B, x.device, train=True)
         for mod in flow.sequence_modules:
-            rec = []
-            if isinstance(mod, Conv1x1) and mod.context_net:
-                _check_encoder(mod.context_net)
-                x, ldj = mod._forward_ctx(x, context, rec, pre.get(id(mod)))
-            elif isinstance(mod, ActNorm) and mod.context_net:
-                _check_encoder(mod.context_net)
-                x, ldj = mod._forward_ctx(x, context, rec, pre.get(id(mod)))
-            elif type(mod) is Coupling and mod.context_net:
-                _check_encoder(mod.context_net)
-                if not mod._fused_ctx_ok(x):
-                    raise NotImplementedError("specialist training needs the fused coupling geometry (3x3, C in 8..64)")
-                x, ldj = mod._fused_ctx(x, context, rec, pre.get(id(mod)))
-            elif isinstance(mod, TransCoupling) and mod.context_net:
-                _check_encoder(mod.context_net)
-                x, ldj = mod._forward_ctx(x, context, rec)
+            if isinstance(mod, (Conv1x1, ActNorm, Coupling, TransCoupling)) and mod.context_net:
+                x, ldj = mod._forward_ctx(x, context, tape, pre.get(id(mod)))
             elif isinstance(mod, SplitPrior) and getattr(mod.dist, "context_net", None):
                 c = x.shape[1] // 2
-                ldj = mod.dist._log_prob_ctx(x[:, c:], context, rec)
-                rec[0]["full"] = x
+                ldj = mod.dist._log_prob_ctx(x[:, c:], context, tape)
                 x = x[:, :c]
             else:
                 if any(p.requires_grad for p in mod.parameters()):
                     raise NotImplementedError("specialist training: %s has trainable parameters" % type(mod).__name__)
+                if isinstance(mod, Squeeze):
+                    tape.append(_tape.Squeeze(tuple(mod.p)))
+                elif isinstance(mod, PermuteAxes):
+                    tape.append(_tape.Permute(tuple(mod.inverse_permutation)))
+                elif len(tape) > 1:
+                    raise NotImplementedError("specialist training: no backward through %s behind the pre-processing" % type(mod).__name__)
                 x, ldj = mod(x, context)
-            tape.append((mod, rec[0] if rec else None))
             logdet += ldj if ldj.dim() == 2 else ldj.unsqueeze(-1)
-        rec = []
-        logp = flow.dist._log_prob_ctx(x, context, rec) + logdet
-        ctx.flow, ctx.tape, ctx.prior, ctx.params, ctx.context = flow, tape, rec[0], params, context
+        logp = flow.dist._log_prob_ctx(x, context, tape) + logdet
+        ctx.prior = tape.pop()                           # the final prior's record: the backward starts from it
+        ctx.tape, ctx.params, ctx.context = tape, params, context
         ctx.mark_non_differentiable(x)
         return x, logp
 
     @staticmethod
     def backward(ctx, _gz_unused, glogp):
-        flow, tape, params, context = ctx.flow, ctx.tape, ctx.params, ctx.context
         glogp = _hip.f32(glogp)
         gld = glogp.sum(1).contiguous()
-        grads = {_DEFER: []} if DEFER_LINEAR_WGRADS else {}
-        gz = gmm_ctx_backward(flow.dist, ctx.prior, glogp, grads)
-        for mod, rec in reversed(tape):
-            if rec is None:
-                if isinstance(mod, Squeeze):
-                    gz = squeeze_op(gz, mod.p, True)
-                    continue
-                if isinstance(mod, PermuteAxes):
-                    gz = gz.permute(mod.inverse_permutation).contiguous()
-                    continue
-                break                                    # pre-processing: nothing trainable upstream
-            if isinstance(mod, SplitPrior):
-                g2 = gmm_ctx_backward(mod.dist, rec, glogp, grads)
-                gz = torch.cat([gz, g2], dim=1)
-            elif isinstance(mod, Conv1x1):
-                gz = conv1x1_ctx_backward(mod, rec, context, gz, gld, grads)
-            elif isinstance(mod, ActNorm):
-                gz = actnorm_ctx_backward(mod, rec, context, gz, gld, grads)
-            elif isinstance(mod, TransCoupling):
-                gz = transcoupling_ctx_backward(mod, rec, context, gz, gld, grads)
-            else:
-                gz = coupling_ctx_backward(mod, rec, context, gz, gld, grads)
-        _flush_linear_wgrads(grads, glogp.device)
-        return (None, None, None) + tuple(grads.get(p) for p in params)
+        bw = _Pass(ctx.context, glogp, gld, {}, [] if DEFER_LINEAR_WGRADS else None)
+        gz = gmm_ctx_backward(ctx.prior, glogp, bw.by_param)
+        for rec in reversed(ctx.tape):
+            bwd = BACKWARD[rec.kind]
+            if bwd is None:
+                break
+            gz = bwd(rec, gz, bw)
+        _flush_linear_wgrads(bw, glogp.device)
+        return (None, None, None) + tuple(bw.by_param.get(p) for p in ctx.params)

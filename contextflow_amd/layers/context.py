@@ -9,10 +9,13 @@ eyesample (embedding rows, also the priors' lookup) and embed + probsample (sigm
 
 Module and buffer names follow the reference so that checkpoints load: ContextEncoder = Sequential(emb, encoder);
 OneHotEncoder.cardinalities, UniformCatDequantization.{qbins, ldj_per_dim}, CatEmbeddings._embeddings.N.weight."""
+from typing import Any, NamedTuple
+
 import torch
 import torch.nn as nn
 
 from . import _hip
+from .simple_vit import _linear
 
 
 class EyeEncoder(nn.Module):
@@ -298,3 +301,37 @@ class ContextEncoder(nn.Sequential):
             if isinstance(emb, EyeEncoder):
                 return enc.encode(input)
         return super().forward(input)
+
+
+class ContextCode(NamedTuple):
+    """What one layer computes from the context alone: the code of its encoder and the activations of its CN net - formed by the
+    layer itself (cn_linear / cn_chain) or for all layers at once by the grouped front end (specialist._front_end: one of these per
+    layer it serves).  What was not formed is None."""
+    c: Any = None            # code (B, width), fp32 and dense (the front end forms it for a training forward only)
+    logp: Any = None         # its log-density (B,)
+    m: Any = None            # Conv1x1 / ActNorm: CN(c)
+    blocked: Any = None      # Conv1x1, front end: 1 = m holds only the 16 x 16 blocks on and below the diagonal (specialist.blocked_rows)
+    a1: Any = None           # Coupling / TransCoupling: CN = Linear -> ReLU (a1) -> Linear -> ReLU (a2) -> Linear (cn)
+    a2: Any = None
+    cn: Any = None
+
+
+def cn_linear(layer, context, pre=None):
+    """Conv1x1 / ActNorm with a context net: code, log-density and m = CN(c) of the layer's single Linear.  pre: the front end's
+    entry for the layer, or None = the layer's own encoder (stochastic: a training forward keeps the code) and one cf_linear."""
+    if pre is not None:
+        return pre
+    c, logp = layer.context_net(context)
+    c = _hip.f32(c)
+    return ContextCode(c, logp, m=_linear(c, layer.CN))
+
+
+def cn_chain(layer, context, pre=None):
+    """Coupling / TransCoupling with a context net (coupling.py:37): code, log-density and the three Linears of CN."""
+    if pre is not None:
+        return pre
+    c, logp = layer.context_net(context)
+    c = _hip.f32(c)
+    a1 = _linear(c, layer.CN[0], act=2)
+    a2 = _linear(a1, layer.CN[2], act=2)
+    return ContextCode(c, logp, a1=a1, a2=a2, cn=_linear(a2, layer.CN[4]))

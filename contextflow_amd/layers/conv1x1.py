@@ -3,7 +3,8 @@ and the per-sample triangular matrix CN(c) of the specialist mode (conv1x1.py:34
 import torch
 import torch.nn as nn
 
-from . import _derived, _hip
+from . import _derived, _hip, _tape
+from .context import cn_linear
 from .flowlayer import FlowLayer, encoder_noise
 
 
@@ -45,26 +46,21 @@ class Conv1x1(FlowLayer):
     def _forward_ctx(self, x, context, tape=None, pre=None):
         """conv1x1.py:34-50: per-sample triangular matrix from CN(c).  `tape` (training): receives what the backward
         needs - the encoder is stochastic, so its output must be kept, not recomputed.  pre: the code, its log-density and CN(c)
-        already formed by the grouped front end (layers/specialist.py::_front_end, train form)."""
-        from .simple_vit import _linear
+        already formed by the grouped front end (layers/specialist.py::_front_end)."""
         x, xbs = _hip.bview(x)
         B, C, H, W = x.shape
-        if pre is not None:
-            c, logp_c, m = pre["c"], pre["logp"], pre["m"]
-        else:
-            c, logp_c = self.context_net(context)
-            m = _linear(_hip.f32(c), self.CN)              # (B, C*C)
+        cn = cn_linear(self, context, pre)
         Wm = _hip.f32(self.NN.detach()) if self.contextflow else None
         z = torch.empty(B, C, H, W, device=x.device, dtype=torch.float32)
         ldj = torch.empty(B, device=x.device, dtype=torch.float32)
-        _hip.call("cf_conv1x1_ctx", _hip.p(x), _hip.p(m), _hip.p(Wm), _hip.p(z), _hip.p(ldj), B, C, H * W, xbs, _hip.stream())
+        _hip.call("cf_conv1x1_ctx", _hip.p(x), _hip.p(cn.m), _hip.p(Wm), _hip.p(z), _hip.p(ldj), B, C, H * W, xbs, _hip.stream())
         if self.contextflow:
             # H W log|det NN| of the frozen shared matrix: kept while NN is unchanged (one factorisation per layer and call otherwise)
             ldj = ldj + _derived.get(self, "lad", _derived.key((self.NN,), H * W, str(x.device)),
                                      lambda: slogdet_inverse(Wm, False)[0] * float(H * W), x.device)
         if tape is not None:
-            tape.append(dict(x=x, c=_hip.f32(c), m=m, eps=encoder_noise(self.context_net)))
-        return z, ldj + logp_c * float(H * W)
+            tape.append(_tape.CtxAffine(self, x, cn.c, cn.m, encoder_noise(self.context_net)))
+        return z, ldj + cn.logp * float(H * W)
 
     def forward(self, x, context=None):
         _hip.require_device(x, self.NN)

@@ -9,8 +9,8 @@ runs in the HIP kernels."""
 import torch
 import torch.nn as nn
 
-from . import _derived, _hip
-from ._tape import step_tape
+from . import _derived, _hip, _tape
+from .context import cn_chain
 from .flowlayer import FlowLayer, encoder_noise
 
 VIT_EVENTS = None        # bench.py: list collecting (start, end, batch) HIP events per fused ViT-coupling launch
@@ -100,9 +100,8 @@ class Coupling(_AffineCoupling):
     def _net_ctx(self, x0, context):
         """coupling.py:39-47: h = NN(x0) + CN(c) (contextflow) or NN([x0 ; CN(c) broadcast]) — the broadcast part of the
         first 1x1 convolution is a per-sample bias W[:, D:] CN(c) + b."""
-        from .simple_vit import _linear
-        c, logp_c = self.context_net(context)
-        cn = _linear(_linear(_linear(_hip.f32(c), self.CN[0], act=2), self.CN[2], act=2), self.CN[4])    # (B, O)
+        code = cn_chain(self, context)
+        cn, logp_c = code.cn, code.logp                                                            # cn: (B, O)
         x0, xbs = _hip.bview(x0)
         B, D, H, W = x0.shape
         st = _hip.stream()
@@ -128,15 +127,8 @@ class Coupling(_AffineCoupling):
         """The Coupling layer as ONE fp32-MFMA kernel (the fused flow-step kernel with an identity 1x1 / ActNorm in
         front) with the CN(c) term as a per-sample bias: on the conditioner output (contextflow) or before its first
         ReLU (CN(c) concatenated to the conditioner input: W[:, D:] CN(c))."""
-        from .simple_vit import _linear
-        if pre is not None:          # code, log-density and the CN chain from the grouped front end (layers/specialist.py, train form)
-            c, logp_c, a1, a2, cn = pre["c"], pre["logp"], pre["a1"], pre["a2"], pre["cn"]
-        else:
-            c, logp_c = self.context_net(context)
-            c = _hip.f32(c)
-            a1 = _linear(c, self.CN[0], act=2)
-            a2 = _linear(a1, self.CN[2], act=2)
-            cn = _linear(a2, self.CN[4])                                                          # (B, O)
+        code = cn_chain(self, context, pre)         # pre: formed by the grouped front end (layers/specialist.py)
+        cn = code.cn                                                                              # (B, O)
         x, xbs = _hip.bview(x)
         B, C, H, W = x.shape
         D = C // 2
@@ -160,7 +152,7 @@ class Coupling(_AffineCoupling):
         planes = None
         if tape is not None and mode == 2:
             # every parameter trains: the forward kernel also writes the step tape for the backward kernel and the weight gradients
-            planes = step_tape(B, C, H, W, dev)
+            planes = _tape.step_tape(B, C, H, W, dev)
             _hip.call("cf_flow_step_fwd_ctx_taped", pp(x), pp(z), pp(ldj), pp(ws), pp(sbias), pp(planes[0]), pp(planes[1]),
                       pp(planes[2]), pp(planes[3]), B, C, H, W, xbs, st)
         else:
@@ -169,8 +161,8 @@ class Coupling(_AffineCoupling):
             _hip.call("cf_flow_step_fwd_ctx", pp(x), pp(z), pp(ldj), pp(ws), pp(sbias), mode | (4 if tape is not None else 0), B, C, H, W,
                       xbs, st)
         if tape is not None:
-            tape.append(dict(x=x, c=c, a1=a1, a2=a2, cn=cn, ws=ws, mode=mode, planes=planes, eps=encoder_noise(self.context_net)))
-        return z, ldj + logp_c * float(H * W)
+            tape.append(_tape.CtxCoupling(self, x, code.c, code.a1, code.a2, cn, ws, mode, planes, encoder_noise(self.context_net)))
+        return z, ldj + code.logp * float(H * W)
 
     def _fused_ctx_ok(self, x):
         k = self.NN[2]
@@ -181,8 +173,14 @@ class Coupling(_AffineCoupling):
         if not self.context_net:
             return super().forward(x, context)
         _hip.require_device(x)
+        return self._forward_ctx(x, context)
+
+    def _forward_ctx(self, x, context, tape=None, pre=None):
+        """tape (training): receives the layer's record; pre: the front end's entry for this layer, or None."""
         if self._fused_ctx_ok(x):
-            return self._fused_ctx(x, context)
+            return self._fused_ctx(x, context, tape, pre)
+        if tape is not None:
+            raise NotImplementedError("specialist training needs the fused coupling geometry (3x3, C in 8..64)")
         h, logp_c = self._net_ctx(x[:, : x.shape[1] // 2], context)
         z, ldj = coupling_apply(x, h, False)
         return z, ldj + logp_c * float(x.shape[2] * x.shape[3])
@@ -235,24 +233,19 @@ class TransCoupling(_AffineCoupling):
         """Conditioner output h (layer-by-layer kernels; also the fallback for unsupported geometries)."""
         return self.NN[0](x0)
 
-    def _net_ctx(self, x0, context, tape=None):
-        """coupling.py:123-133 with a context net: h = ViT(x0) + CN(c) (contextflow) or ViT([x0 ; CN(c) broadcast]).
-        Quirk kept: logp_c is not multiplied by H*W here (unlike Coupling)."""
-        from .simple_vit import _linear
-        c, logp_c = self.context_net(context)
-        c = _hip.f32(c)
-        a1 = _linear(c, self.CN[0], act=2)
-        a2 = _linear(a1, self.CN[2], act=2)
-        cn = _linear(a2, self.CN[4])                                                              # (B, O)
-        if tape is not None:                  # training (contextflow): what the CN-net backward needs
-            tape.append(dict(c=c, a1=a1, a2=a2, cn=cn, eps=encoder_noise(self.context_net)))
+    def _net_ctx(self, x0, context, pre=None):
+        """coupling.py:123-133 with a context net: h = ViT(x0) + CN(c) (contextflow) or ViT([x0 ; CN(c) broadcast]); returns h and
+        the code with its CN chain (what a training forward tapes).  Quirk kept: the code's log-density is not multiplied by H*W
+        here (unlike Coupling)."""
+        code = cn_chain(self, context, pre)
+        cn = code.cn                                                                              # (B, O)
         B, _, H, W = x0.shape
         if self.contextflow:
             h = self.NN[0](x0)
             _hip.call("cf_add_sample_bias", _hip.p(h), _hip.p(cn), B, h.shape[1], H * W, 0, _hip.stream())
-            return h, logp_c
+            return h, code
         xin = torch.cat([_hip.f32(x0), cn.view(B, -1, 1, 1).expand(B, cn.shape[1], H, W)], dim=1)   # concatenation: index op
-        return self.NN(xin), logp_c
+        return self.NN(xin), code
 
     # ---- fused path: patchify -> ViT -> un-patchify -> affine map -> log-det in one kernel
     def _fused_ok(self, x):
@@ -414,12 +407,12 @@ class TransCoupling(_AffineCoupling):
             return self._fused(x, False)
         return super().forward(x, context)
 
-    def _forward_ctx(self, x, context, tape=None):
-        h, logp_c = self._net_ctx(x[:, : x.shape[1] // 2], context, tape)
+    def _forward_ctx(self, x, context, tape=None, pre=None):
+        h, code = self._net_ctx(x[:, : x.shape[1] // 2], context, pre)
         if tape is not None:
-            tape[-1]["x"] = x
+            tape.append(_tape.CtxTransCoupling(self, x, code.c, code.a1, code.a2, code.cn, encoder_noise(self.context_net)))
         z, ldj = coupling_apply(x, h, False)
-        return z, ldj + logp_c
+        return z, ldj + code.logp
 
     def reverse(self, z, context=None):
         _hip.require_device(z)

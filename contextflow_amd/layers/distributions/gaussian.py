@@ -8,7 +8,7 @@ import math
 import torch
 import torch.nn as nn
 
-from .. import _derived, _hip
+from .. import _derived, _hip, _tape
 from ..flowlayer import no_context
 
 
@@ -329,7 +329,7 @@ class GaussianMixtureDistribution(nn.Module):
             _hip.call("cf_gmm_ctx_logprob", _hip.p(x), _hip.p(_hip.f32(self.mG.detach())), _hip.p(_hip.f32(self.sG.detach())),
                       _hip.p(logw), _hip.p(_hip.f32(c)), _hip.p(out), _hip.p(lp), B, M, K, D, H * W, xbs, 0, _hip.stream())
         if tape is not None:
-            tape.append(dict(x=x, c=_hip.f32(c), logw=logw, context=context, lp=lp, tab=tab))
+            tape.append(_tape.CtxMixture(self, x, _hip.f32(c), logw, context, lp, tab))
         return out + (logp_c * float(H * W)).unsqueeze(-1)
 
     def log_prob(self, input, context=None):

@@ -20,6 +20,7 @@ import torch
 
 from . import _derived, _hip
 from .actnorm import ActNorm
+from .context import ContextCode, cn_chain, cn_linear
 from .conv1x1 import Conv1x1, slogdet_inverse
 from .coupling import Coupling, identity_front_step_tables
 from .dequantize import Dequantization
@@ -152,10 +153,9 @@ def _front_end(flow, context, B, dev, train=False):
     """Everything a specialist flow computes from the CONTEXT ALONE, ahead of the data path and in three launches instead of ~96:
     the code of every uniform context encoder is formed inside the first Linear that consumes it (Conv1x1.CN, ActNorm.CN,
     Coupling.CN[0]: one grouped launch, cf_linear_group with ctx), then the second and third Linears of the coupling CN nets
-    (one grouped launch each).  Returns {id(layer): tensor}: Conv1x1 -> (m1, blocked), ActNorm -> m2, Coupling -> CN(c).
-    train (layers/autograd_ctx.py): the training forward's form - every intermediate the backward needs is kept and returned as
-    {id(layer): dict(c=code, logp=log-density of the code, m=CN(c) | a1=.., a2=.., cn=..)}, the per-sample matrix in full (C, C) form,
-    couplings with and without contextflow."""
+    (one grouped launch each).  Returns {id(layer): ContextCode}: m (and blocked) for Conv1x1, m for ActNorm, a1 / a2 / cn for Coupling.
+    train (layers/autograd_ctx.py): the training forward's form - the code c and its log-density logp are kept too (everything the
+    backward needs), the per-sample matrix in full (C, C) form, couplings with and without contextflow."""
     import ctypes
     mods, n = flow.sequence_modules, len(flow.sequence_modules)
     if not torch.is_tensor(context) or context.dim() != 2 or not FRONT_END:
@@ -206,12 +206,12 @@ def _front_end(flow, context, B, dev, train=False):
                 w, b, blocked = f(m.CN.weight.detach()), f(m.CN.bias.detach()), 0
             y = torch.empty(B, w.shape[0], device=dev, dtype=torch.float32)
             first.append((u, enc.qbins, w, b, y, 0, cbuf))
-            out[id(m)] = dict(c=cbuf, logp=lc, m=y) if train else (y, blocked)
+            out[id(m)] = ContextCode(cbuf, lc, m=y, blocked=blocked)
         elif isinstance(m, ActNorm):
             w, b = f(m.CN.weight.detach()), f(m.CN.bias.detach())
             y = torch.empty(B, w.shape[0], device=dev, dtype=torch.float32)
             first.append((u, enc.qbins, w, b, y, 0, cbuf))
-            out[id(m)] = dict(c=cbuf, logp=lc, m=y) if train else y
+            out[id(m)] = ContextCode(cbuf, lc, m=y)
         elif type(m) is Coupling and (m.contextflow or train):
             l0, l1, l2 = m.CN[0], m.CN[2], m.CN[4]
             a1 = torch.empty(B, l0.weight.shape[0], device=dev, dtype=torch.float32)
@@ -220,7 +220,7 @@ def _front_end(flow, context, B, dev, train=False):
             first.append((u, enc.qbins, f(l0.weight.detach()), f(l0.bias.detach()), a1, 2, cbuf))
             second.append((a1, None, f(l1.weight.detach()), f(l1.bias.detach()), a2, 2, None))
             third.append((a2, None, f(l2.weight.detach()), f(l2.bias.detach()), cn, 0, None))
-            out[id(m)] = dict(c=cbuf, logp=lc, a1=a1, a2=a2, cn=cn) if train else cn
+            out[id(m)] = ContextCode(cbuf, lc, a1=a1, a2=a2, cn=cn)
     if not first:
         return {}
     _, enc, card, onehot = enc0
@@ -249,7 +249,6 @@ def _front_end(flow, context, B, dev, train=False):
 def forward_eval(flow, x, context):
     """(z, logp (B, M)) of a specialist flow, evaluation.  Same results as FlowSequential._forward_layers to fp32 rounding
     (the per-sample log-dets are summed in another order)."""
-    from .simple_vit import _linear
     mods, n = flow.sequence_modules, len(flow.sequence_modules)
     B, dev = x.shape[0], x.device
     _draw_encoder_noise(flow, B, dev)
@@ -290,64 +289,50 @@ def forward_eval(flow, x, context):
             C, H, W = sshape
             xv, xbs = _hip.bview(x)
             aligned = xbs % 4 == 0 and xv.data_ptr() % 16 == 0
-            lp1 = lp2 = None
-            if id(conv) in pre and (aligned or not pre[id(conv)][1]):      # formed by the front end (grouped launch)
-                m1, blocked = pre[id(conv)]
-            else:
-                c1, lp1 = conv.context_net(context)
+            cn1 = pre.get(id(conv))                                # formed by the front end (grouped launch)
+            if cn1 is None or (cn1.blocked and not aligned):
                 nblk = _hip.lib().cf_affine_ctx_blocked_floats(C, H, W) if aligned else 0
                 if nblk and nblk < C * C:                          # (B, 10/16 C*C) at C = 64, 3/4 at C = 32: lower blocks only
+                    c1, lp1 = conv.context_net(context)
                     wp, bp = _cn_blocked(flow, conv, C, dev)
                     c1f = f(c1)
                     m1 = torch.empty(B, nblk, device=dev, dtype=torch.float32)
                     _hip.call("cf_linear", pp(c1f), pp(wp), pp(bp), None, pp(m1), B, c1f.shape[1], nblk, 0, st)
-                    blocked = 1
+                    cn1 = ContextCode(c1f, lp1, m=m1, blocked=1)
                 else:
-                    m1 = _linear(f(c1), conv.CN)                   # (B, C*C)
-                    blocked = 0
-            if id(act) in pre:
-                m2 = pre[id(act)]
-            else:
-                c2, lp2 = act.context_net(context)
-                m2 = _linear(f(c2), act.CN)                        # (B, 2C)
+                    cn1 = cn_linear(conv, context)                 # m: (B, C*C)
+            cn2 = cn_linear(act, context, pre.get(id(act)))        # m: (B, 2C)
             cadd = 0.0
-            for net, lp in ((conv.context_net, lp1), (act.context_net, lp2)):
+            for net, code in ((conv.context_net, cn1), (act.context_net, cn2)):
                 k = _const_logp(net)
                 if k is not None:
                     cadd += k * float(H * W)
                 else:
-                    acc.add(lp * float(H * W))
+                    acc.add(code.logp * float(H * W))
             Wm = f(conv.NN.detach()) if conv.contextflow else None
             t = f(act.NN_t.detach()) if act.contextflow else None
             logs = f(act.NN_logs.detach()) if act.contextflow else None
             lad = _lad(flow, conv, dev) if conv.contextflow else None
             z = torch.empty(B, C, H, W, device=dev, dtype=torch.float32)
             buf, accum = acc.buffer()
-            _hip.call("cf_affine_ctx_fwd", pp(xv), pp(m1), pp(Wm), pp(m2), pp(t), pp(logs), pp(lad), cadd, pp(z), pp(buf), B, C, H, W,
-                      xbs, int(sq), accum, blocked, st)
+            _hip.call("cf_affine_ctx_fwd", pp(xv), pp(cn1.m), pp(Wm), pp(cn2.m), pp(t), pp(logs), pp(lad), cadd, pp(z), pp(buf), B, C, H, W,
+                      xbs, int(sq), accum, cn1.blocked or 0, st)
             x = z
             i = j + 2
             continue
         # ---- Coupling(c''): the fused step kernel, CN bias on the conditioner output (contextflow)
         if (type(m) is Coupling and m.context_net and m.contextflow and len(shape) == 3 and m._fused_ctx_ok(x)):
             C, H, W = shape
-            lp = None
-            if id(m) in pre:
-                cn = pre[id(m)]
-            else:
-                c, lp = m.context_net(context)
-                a1 = _linear(f(c), m.CN[0], act=2)
-                a2 = _linear(a1, m.CN[2], act=2)
-                cn = _linear(a2, m.CN[4])
+            code = cn_chain(m, context, pre.get(id(m)))
             xv, xbs = _hip.bview(x)
             ws = _coupling_ws(flow, m, C, H, W, dev)
             z = torch.empty(B, C, H, W, device=dev, dtype=torch.float32)
-            _hip.call("cf_flow_step_fwd_ctx", pp(xv), pp(z), pp(acc.zeroed()), pp(ws), pp(cn), 1, B, C, H, W, xbs, st)
+            _hip.call("cf_flow_step_fwd_ctx", pp(xv), pp(z), pp(acc.zeroed()), pp(ws), pp(code.cn), 1, B, C, H, W, xbs, st)
             k = _const_logp(m.context_net)
             if k is not None:
                 acc.cadd += k * float(H * W)
             else:
-                acc.add(lp * float(H * W))
+                acc.add(code.logp * float(H * W))
             x = z
             i += 1
             continue

@@ -2378,6 +2378,91 @@ def test_encoder_noise_is_taped_per_forward(L):
     assert checked >= 20
 
 
+@pytest.mark.parametrize("fxname", ["mnist_eye_cf", "mnist_onehot"])
+def test_specialist_tape_holds_named_records_and_the_layers_own_cn_path(L, fxname, monkeypatch):
+    """The tape a specialist training forward leaves (SpecialistLogProb: first 2 samples of the fixture, injected noise): a flat
+    list of layers/_tape.py records, the pre-processing one first, one mixture record per SplitPrior and the final prior's kept
+    apart, and the records of the layers the grouped front end served hold the very tensors specialist._front_end returned.
+    Then the same step with the front end switched off - every layer forms its own code and CN activations (context.cn_linear /
+    cn_chain) - against the same fp64 oracle run, at the tolerances of test_specialist_backward_against_autograd_oracle."""
+    import contextflow_amd as cfa
+    from contextflow_amd.layers import _tape, autograd_ctx, specialist
+    from tests.helpers import load_specialist
+    from tests.gpu_util import set_noise
+    name, ctx, ops, M, params, inp = load_specialist(fxname)
+    B = 2
+    x, u, eps, context = inp["x"][:B], inp["u"][:B], [e[:B] for e in inp["eps"]], inp["context"][:B]
+    cnoise = [c[:B] for c in inp["cnoise"]]
+    wts = torch.randn(B, M, generator=torch.Generator().manual_seed(33))
+    p64 = {k: (v.double().clone().requires_grad_(True) if v.is_floating_point() else v) for k, v in params.items()}
+    _, lp = fo.flow_forward(ops, p64, x.double(), u.double(), [e.double() for e in eps], ctx=ctx, context=context,
+                            cnoise=[c.double() for c in cnoise])
+    (lp * wts.double()).sum().backward()
+    cfg, ds, MM = cfa.preset_config(name)
+    cfg.update(generalist=False, enc_emb=ctx["enc_emb"], enc_type="uniform", contextflow=ctx["contextflow"])
+    model = cfa.create_model(cfg, ds, MM, contexts=ctx["contexts"])
+    model.load_state_dict(params, strict=True)
+    model = model.to(DEV).train()
+    set_noise(model, u, eps)
+    encs = [m for m in model.modules() if isinstance(m, cfa.layers.UniformCatDequantization)]
+    assert len(encs) == len(cnoise)
+    for e, c in zip(encs, cnoise):
+        e.fixed_noise = c.to(DEV)
+    served, real = [], specialist._front_end
+    monkeypatch.setattr(specialist, "_front_end", lambda *a, **k: served.append(real(*a, **k)) or served[-1])
+    ctx_layers = [m for m in model.sequence_modules if getattr(m, "context_net", None)]
+    nsplit = sum(isinstance(m, cfa.layers.SplitPrior) for m in model.sequence_modules)
+
+    def step():
+        """one training step: the tape of its forward, after logp and every gradient passed the oracle's check"""
+        model.zero_grad(set_to_none=True)
+        _, logp = model(x.to(DEV), context.to(DEV))
+        fn = logp.grad_fn
+        tape, prior = list(fn.tape), fn.prior
+        assert all(type(r) in autograd_ctx.RECORDS for r in tape + [prior]), [type(r) for r in tape]
+        assert [type(r) is _tape.Pre for r in tape] == [True] + [False] * (len(tape) - 1)
+        assert sum(type(r) is _tape.CtxMixture for r in tape) == nsplit
+        assert type(prior) is _tape.CtxMixture and prior.dist is model.dist
+        assert [r.module for r in tape if hasattr(r, "module")] == ctx_layers
+        tol = max(BPD_TOL, 1e-5 * bpd(lp.detach().float(), name).abs().max().item())
+        assert (bpd(logp.detach().cpu(), name) - bpd(lp.detach().float(), name)).abs().max() < tol
+        (logp * wts.to(DEV)).sum().backward()
+        checked = 0
+        for k, p in model.named_parameters():
+            if not p.requires_grad:
+                assert p.grad is None, k
+                continue
+            ref = p64[k].grad
+            if ref is None or float(ref.abs().max()) == 0.0:
+                assert p.grad is None or float(p.grad.abs().max()) == 0.0, k
+                continue
+            assert p.grad is not None, k
+            scale = max(ref.abs().max().item(), 1e-3)
+            err = (p.grad.detach().cpu().double() - ref).abs().max().item() / scale
+            assert err < 2e-4, "%s: relative grad error %.3e (scale %.3e)" % (k, err, scale)
+            checked += 1
+        assert checked >= 20
+        return tape
+
+    tape = step()
+    pre = served[-1]
+    hit = 0
+    for r in tape:
+        e = pre.get(id(getattr(r, "module", None)))
+        if e is None:
+            continue
+        hit += 1
+        assert r.c is e.c and e.c is not None and e.logp is not None
+        if type(r) is _tape.CtxAffine:
+            assert r.m is e.m
+        else:
+            assert r.a1 is e.a1 and r.a2 is e.a2 and r.cn is e.cn
+    assert hit == len(pre) == len(ctx_layers)             # uniform encoders, conv couplings: the front end serves every layer
+    monkeypatch.setattr(specialist, "FRONT_END", False)
+    tape = step()
+    assert served[-1] == {} and all(r.c is not None for r in tape if hasattr(r, "module"))
+
+
 @pytest.mark.parametrize("name,contexts,emb,typ,cflow", [
     ("mnist", [64], "eye", "uniform", False),            # README.md:56
     ("cifar10", [15, 5], "onehot", "vardeq", False),     # README.md:61

@@ -243,6 +243,18 @@ def test_specialist_front_end_takes_uniform_encoders_only():
         assert specialist._front_end(flow, None, 4, "cpu") == {}
 
 
+def test_specialist_tape_records_and_their_backwards():
+    """layers/_tape.py: every record class has a kind of its own, and the specialist backward (autograd_ctx.BACKWARD, keyed by
+    kind) covers exactly the records the specialist training forward appends (autograd_ctx.RECORDS).  Host logic only."""
+    from contextflow_amd.layers import _tape, autograd_ctx
+    classes = [c for c in vars(_tape).values() if isinstance(c, type) and issubclass(c, tuple) and hasattr(c, "kind")]
+    kinds = [c.kind for c in classes]
+    assert len(classes) >= 12 and len(set(kinds)) == len(kinds), kinds
+    assert len(set(autograd_ctx.RECORDS)) == len(autograd_ctx.RECORDS) and all(r in classes for r in autograd_ctx.RECORDS)
+    assert {r.kind for r in autograd_ctx.RECORDS} == set(autograd_ctx.BACKWARD)
+    assert all(fn is None or callable(fn) for fn in autograd_ctx.BACKWARD.values())
+
+
 def test_shard_bounds():
     from contextflow_amd.dist import shard_bounds
     for total in (0, 1, 7, 64, 65536 + 3):
