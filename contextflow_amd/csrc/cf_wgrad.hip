@@ -16,6 +16,7 @@
 // [t][m][n]; the caller permutes to the reference's [m][n][kh][kw].
 // The 3x3 runs in the Winograd form F(3x3, 2x2) (further down: 16 MFMAs per 8 pixels instead of 36) unless
 // CONTEXTFLOW_DIRECT_CONV=1; the direct 3x3 path stays as the second implementation the tests compare it with.
+// Host side (behind the kernels): wg_plan decides kernel, partial count and layout once; every entry point reads that plan.
 #include "cf_common.h"
 #include <cstdlib>
 
@@ -628,18 +629,16 @@ __global__ __launch_bounds__(256) void k_wgrad1x1(const WgBatch wb, int MR, int 
     }
 }
 
-// out[e] = sum_s part[s][e] in a fixed order: a wave covers 64 consecutive outputs, the 4 waves of a block split S.
-// The first n0 outputs go to out0 (weights), the rest to out1 (bias; may be null).
-__global__ __launch_bounds__(256) void k_wgrad_reduce(const float* __restrict__ part, float* __restrict__ out0,
-                                                      float* __restrict__ out1, int n0, int n, int S) {
-    __shared__ float red[4][64];
+// out[e] = sum_s part[s][e] in a fixed order: a wave covers 64 consecutive outputs, the 4 waves of a block split S.  The ONE
+// summation body of both reduce kernels (the bitwise guarantee batched == single == four cf_wgrad calls rests on it): every
+// thread of the block calls it, the sum is valid in wave 0 for e < n.
+__device__ __forceinline__ float wg_sum_partials(const float* __restrict__ part, int n, int S, int e, float (&red)[4][64]) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int e = blockIdx.x * 64 + lane;
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
     if (e < n) {
         int i = w;
         for (; i + 60 < S; i += 64) {                 // the same sums in the same order as the loop below, 16 loads in flight
-            float v[16];                               // (one partial per WAVE of k_wgrad1x1: a thread walks up to 512 of them)
+            float v[16];                               // (one partial per WORKGROUP of k_wgrad1x1: a thread walks up to 256 of them)
 #pragma unroll
             for (int j = 0; j < 16; ++j) v[j] = part[(int64_t)(i + 4 * j) * n + e];
 #pragma unroll
@@ -653,8 +652,16 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(const float* __restrict__ 
     }
     red[w][lane] = (s0 + s1) + (s2 + s3);
     __syncthreads();
-    if (w == 0 && e < n) {
-        const float v = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+    return (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+}
+
+// cf_wgrad: the first n0 outputs go to out0 (weights, [tap][m][n]), the rest to out1 (bias; may be null)
+__global__ __launch_bounds__(256) void k_wgrad_reduce(const float* __restrict__ part, float* __restrict__ out0,
+                                                      float* __restrict__ out1, int n0, int n, int S) {
+    __shared__ float red[4][64];
+    const int e = blockIdx.x * 64 + (threadIdx.x & 63);
+    const float v = wg_sum_partials(part, n, S, e, red);
+    if (threadIdx.x < 64 && e < n) {
         if (e < n0) out0[e] = v;
         else if (out1 != nullptr) out1[e - n0] = v;
     }
@@ -666,55 +673,56 @@ struct WgReduce4B { WgReduce4 d[kWgBatch]; };         // blockIdx.z = flow step
 __global__ __launch_bounds__(256) void k_wgrad_reduce4(const WgReduce4B db) {
     __shared__ float red[4][64];
     const WgReduce4& d = db.d[blockIdx.z];
-    const int q = blockIdx.y;
-    const float* __restrict__ part = d.part[q];
-    const int n = d.n[q], n0 = d.n0[q], S = d.S[q];
+    const int q = blockIdx.y, n = d.n[q], n0 = d.n0[q];
     if ((int)blockIdx.x * 64 >= n) return;            // uniform per block
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int e = blockIdx.x * 64 + lane;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (e < n) {
-        int i = w;
-        for (; i + 60 < S; i += 64) {                 // the same sums in the same order as the loop below, 16 loads in flight
-            float v[16];                               // (one partial per WAVE of k_wgrad1x1: a thread walks up to 512 of them)
-#pragma unroll
-            for (int j = 0; j < 16; ++j) v[j] = part[(int64_t)(i + 4 * j) * n + e];
-#pragma unroll
-            for (int j = 0; j < 16; j += 4) { s0 += v[j]; s1 += v[j + 1]; s2 += v[j + 2]; s3 += v[j + 3]; }
-        }
-        for (; i + 12 < S; i += 16) {
-            s0 += part[(int64_t)i * n + e]; s1 += part[(int64_t)(i + 4) * n + e];
-            s2 += part[(int64_t)(i + 8) * n + e]; s3 += part[(int64_t)(i + 12) * n + e];
-        }
-        for (; i < S; i += 4) s0 += part[(int64_t)i * n + e];
-    }
-    red[w][lane] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (w == 0 && e < n) {
-        const float v = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+    const int e = blockIdx.x * 64 + (threadIdx.x & 63);
+    const float v = wg_sum_partials(d.part[q], n, d.S[q], e, red);
+    if (threadIdx.x < 64 && e < n) {
         const int tp = d.taps[q], mn = n0 / tp;       // partials are [tap][m][n]; the 3x3 leaves as the reference's [m][n][kh][kw]
         if (e < n0) d.out0[q][tp > 1 ? (e % mn) * tp + e / mn : e] = v;
         else if (d.out1[q] != nullptr) d.out1[q][e - n0] = v;
     }
 }
 
-// cf_step_wgrads: the k_wgrad launches leave their partials in place and report their split count; one reduce follows
-static thread_local bool g_wgrad_defer = false;
-static thread_local int g_wgrad_last_S = 0;
-// cf_step_wgrads_batch: the launch covers g_wgrad_nb steps whose operands are g_wgrad_batch's (the pointer arguments of the
-// launchers are step 0's then)
-static thread_local const WgBatch* g_wgrad_batch = nullptr;
-static thread_local int g_wgrad_nb = 1;
-inline WgBatch wg_batch(const float* A, const float* Bm, float* part) {
-    if (g_wgrad_batch) return *g_wgrad_batch;
-    WgBatch wb{};
-    wb.A[0] = A; wb.Bm[0] = Bm; wb.part[0] = part;
-    return wb;
+// ---- the launch plan ----------------------------------------------------------------------------------------------------------
+// Which kernel runs, how many partials it leaves and where they lie is decided ONCE, by wg_plan; the workspace queries, the flop
+// accounting, the launchers and the batching of cf_step_wgrads_batch all read the plan.
+enum class WgKernel { Direct, Wino, Skinny };          // k_wgrad<.., WINO = false>, k_wgrad<.., WINO = true>, k_wgrad1x1
+enum class WgForm { Env = -1, Direct = 0, Wino = 1 };  // the 3x3: as CONTEXTFLOW_DIRECT_CONV says / as the caller says (cf_wgrad_form)
+
+// the k_wgrad1x1<RT, CT, *, NF> that are built: 16-row tiles of A, of Bm, float4 per lane (2 on 16x16 / 8x8 images, 1 on 4x4).
+// wg_plan chooses from this table and launch_skinny instantiates from it: what may be chosen is what is built.
+struct WgTile { int rt, ct, nf; };
+constexpr WgTile kWgTiles[] = {{1, 1, 2}, {1, 2, 2}, {2, 1, 2}, {2, 2, 2}, {2, 4, 2}, {4, 1, 2}, {4, 2, 2},
+                               {1, 1, 1}, {1, 2, 1}, {2, 1, 1}, {2, 2, 1}, {2, 4, 1}, {4, 1, 1}, {4, 2, 1}, {4, 4, 1}, {4, 8, 1}, {8, 2, 1}};
+constexpr int kWgTileCount = sizeof(kWgTiles) / sizeof(kWgTiles[0]);
+inline int wgrad1x1_nf(int HW) { return HW >= 64 ? 2 : 1; }      // a unit is 32 pixels on 16x16 / 8x8 images (NF = 2), 16 on 4x4
+// Tile counts within the register budget of k_wgrad1x1, built or not.  ONLY cf_wgrad_ws_bytes asks: workspaces have always been
+// sized for the skinny kernel's split on every such shape, and stay so byte for byte (historical for the tiles that are not built)
+inline bool wgrad1x1_sized(int MR, int NR, int HW) {
+    const int rt = (MR + 15) / 16, ct = (NR + 15) / 16;
+    return HW % 16 == 0 && rt <= 8 && ct <= 8 && rt * ct <= (wgrad1x1_nf(HW) == 2 ? 8 : 32);
+}
+
+struct WgPlan {
+    int B, MR, NR, H, W, taps;                         // the product: gw[taps][MR][NR] over B samples of H x W pixels
+    int64_t bsB;                                       // batch stride of Bm in floats
+    bool sqB;                                          // Bm is the tensor before Squeeze((2,2)), read through the index map (taps == 1)
+    WgKernel kernel;
+    // Direct / Wino: nt = 32-column tiles of Bm (1, 2 or 4).  Skinny: tile = index into kWgTiles, Q / qper = (sample, pixel group)
+    // units in all / per wave.  S = partials: grid.y of k_wgrad, grid.x of k_wgrad1x1
+    int nt, tile, Q, qper, S;
+    int64_t per() const { return (int64_t)taps * MR * NR + MR; }     // floats of a partial: [taps][MR][NR] | [MR]
+};
+// two plans of ONE product (same B, shape and taps) that differ only in their operands: may their members share a launch?
+inline bool wg_same_launch(const WgPlan& a, const WgPlan& b) {
+    return a.kernel == b.kernel && a.nt == b.nt && a.tile == b.tile && a.S == b.S && a.qper == b.qper && a.bsB == b.bsB && a.sqB == b.sqB;
 }
 
 // wgs = workgroups to aim for: 512 (two per CU in flight) for the direct forms; the Winograd form runs one workgroup per
 // CU (512 registers per lane), so 256 - one round, one epilogue per CU
-inline int wgrad_splits(int B, int MR, int HW, int wgs = 512) {
+inline int wgrad_splits(int B, int MR, int HW, int wgs) {
+    if (MR <= 0 || HW <= 0) return 1;                 // (a size query on a shape the launch refuses)
     const int KC = HW >= 64 ? HW : 64, SPC = KC / HW;
     const int mtiles = (MR + 31) / 32, nchunks = (B + SPC - 1) / SPC;
     int splits = wgs / mtiles;
@@ -728,142 +736,144 @@ inline int wgrad_splits(int B, int MR, int HW, int wgs = 512) {
     return splits < 1 ? 1 : splits;
 }
 
-// k_wgrad1x1: one partial per wave; about two waves per SIMD, at least 8 units each.  A unit is 32 pixels on 16x16 / 8x8
-// images (NF = 2), 16 on 4x4
-inline int wgrad1x1_nf(int HW) { return HW >= 64 ? 2 : 1; }
-// nsplit = number of PARTIALS = workgroups of four waves; waves: about 4 per SIMD for the small tiles (<= 128 registers), 2 otherwise
-inline void wgrad1x1_split(int B, int MR, int NR, int HW, int& Q, int& qper, int& nsplit) {
-    const int rt = (MR + 15) / 16, ct = (NR + 15) / 16;
+// S = number of PARTIALS = workgroups of four waves; waves: about 4 per SIMD for the small tiles (<= 128 registers), 2 otherwise
+inline void wgrad1x1_split(WgPlan& p) {
+    const int rt = (p.MR + 15) / 16, ct = (p.NR + 15) / 16, HW = p.H * p.W;
     const int waves = rt * ct <= 2 ? 4096 : 2048;
-    Q = B * (HW / (16 * wgrad1x1_nf(HW)));
-    qper = (Q + waves - 1) / waves;                    // (small batches: one unit per wave - the units are what fills the chip)
+    p.Q = p.B * (HW / (16 * wgrad1x1_nf(HW)));
+    p.qper = (p.Q + waves - 1) / waves;                // (small batches: one unit per wave - the units are what fills the chip)
 #ifndef CF_W1_MIN_UNITS
 #define CF_W1_MIN_UNITS 1
 #endif
-    if (qper < CF_W1_MIN_UNITS) qper = CF_W1_MIN_UNITS;
-    nsplit = ((Q + qper - 1) / qper + 3) / 4;
-}
-inline bool wgrad1x1_ok(int MR, int NR, int HW) {
-    const int rt = (MR + 15) / 16, ct = (NR + 15) / 16;
-    return HW % 16 == 0 && rt <= 8 && ct <= 8 && rt * ct <= (wgrad1x1_nf(HW) == 2 ? 8 : 32);
+    if (p.qper < CF_W1_MIN_UNITS) p.qper = CF_W1_MIN_UNITS;
+    p.S = ((p.Q + p.qper - 1) / p.qper + 3) / 4;
 }
 
-template <int RT, int CT, int NF>
-int launch_wgrad1x1(const float* A, const float* Bm, float* ws, int MR, int NR, int HW, int W, int64_t bsB, int sqB, int Q,
-                    int qper, int nsplit, hipStream_t s) {
-    const dim3 grid(nsplit, 1, g_wgrad_nb), blk(256);
-    const size_t lds = (size_t)(RT * CT * 4 + RT) * 64 * sizeof(float);          // <= 33 KB
-    const WgBatch wb = wg_batch(A, Bm, ws);
-    if (sqB) k_wgrad1x1<RT, CT, true, NF><<<grid, blk, lds, s>>>(wb, MR, NR, HW, W, bsB, Q, qper, nsplit);
-    else k_wgrad1x1<RT, CT, false, NF><<<grid, blk, lds, s>>>(wb, MR, NR, HW, W, bsB, Q, qper, nsplit);
-    return 0;
+// Pure in its arguments (and the environment switch when form == Env).  aligned: both operand pointers are 16-byte aligned.
+static WgPlan wg_plan(int B, int MR, int NR, int H, int W, int taps, bool aligned, int64_t bsB, bool sqB, WgForm form) {
+    WgPlan p{B, MR, NR, H, W, taps, bsB, sqB};
+    const int HW = H * W;
+    // the skinny 1x1 gradients: operands straight from global memory in MFMA layout, as float4 - where a tile of the shape is built
+    if (taps == 1 && H == W && (H == 16 || H == 8 || H == 4) && aligned && bsB % 4 == 0) {
+        const int rt = (MR + 15) / 16, ct = (NR + 15) / 16, nf = wgrad1x1_nf(HW);
+        for (int i = 0; i < kWgTileCount; ++i)
+            if (kWgTiles[i].rt == rt && kWgTiles[i].ct == ct && kWgTiles[i].nf == nf) {
+                p.kernel = WgKernel::Skinny; p.tile = i;
+                wgrad1x1_split(p);
+                return p;
+            }
+    }
+    // staged through LDS; the 3x3 takes the Winograd form unless CONTEXTFLOW_DIRECT_CONV=1 (same switch as the step kernels).
+    // (16x16 with 128 columns would stage 160 values per thread next to the 256 accumulators: it keeps the direct form)
+    static const bool direct_env = [] { const char* e = getenv("CONTEXTFLOW_DIRECT_CONV"); return e && e[0] == '1'; }();
+    p.nt = NR <= 32 ? 1 : (NR <= 64 ? 2 : 4);
+    const bool wino = taps == 9 && !(form == WgForm::Env ? direct_env : form == WgForm::Direct) && !(HW == 256 && p.nt == 4);
+    p.kernel = wino ? WgKernel::Wino : WgKernel::Direct;
+    p.S = wgrad_splits(B, MR, HW, wino ? 256 : 512);
+    return p;
 }
 
-template <int H, int W, int TAPS, int NT, bool WINO>
-int launch_wgrad(const float* A, const float* Bm, float* gw, float* gbias, float* ws, int B, int MR, int NR, hipStream_t s,
-                 int64_t bsB, int sqB) {
-    constexpr int HW = H * W, KC = HW >= 64 ? HW : 64, KW = 4 / NT;
+// ---- launchers: the GEMM kernel of plan p over the nb members of wb (blockIdx.z); the caller enqueues the reduce ------------
+template <int H, int TAPS, int NT, bool WINO>
+int launch_k_wgrad(const WgPlan& p, const WgBatch& wb, int nb, hipStream_t s) {
+    constexpr int HW = H * H, KC = HW >= 64 ? HW : 64, KW = 4 / NT;
     constexpr size_t lds_main = (size_t)(KC * 33 + KC * (NT * 32 + 1)) * 4;
     constexpr size_t lds_comb = KW > 1 ? (size_t)(NT * TAPS * 1024 + NT * 64) * 4 : 0;
     constexpr size_t lds = lds_main > lds_comb ? lds_main : lds_comb;
+    static_assert(lds <= 160 * 1024, "the staged tiles of a chunk fit the LDS of a CU");
     if (lds > 64 * 1024) {
         static std::atomic<uint64_t> raised{0};
-        if (int rc_ = cf_raise_dynamic_lds((const void*)k_wgrad<H, W, TAPS, NT, WINO>, 160 * 1024, raised, __func__)) return rc_;
+        if (int rc_ = cf_raise_dynamic_lds((const void*)k_wgrad<H, H, TAPS, NT, WINO>, 160 * 1024, raised, __func__)) return rc_;
     }
-    const int mtiles = (MR + 31) / 32;
-    const int splits = wgrad_splits(B, MR, HW, WINO ? 256 : 512);
-    const int S = splits, nw = TAPS * MR * NR;
     // partials: [S][TAPS*MR*NR + MR] (weights | bias of one split contiguous: ONE reduce launch)
-    k_wgrad<H, W, TAPS, NT, WINO><<<dim3(mtiles, splits, g_wgrad_nb), dim3(256), lds, s>>>(wg_batch(A, Bm, ws), B, MR, NR, bsB, sqB);
-    g_wgrad_last_S = S;
-    if (!g_wgrad_defer) k_wgrad_reduce<<<dim3((nw + MR + 63) / 64), dim3(256), 0, s>>>(ws, gw, gbias, nw, nw + MR, S);
+    k_wgrad<H, H, TAPS, NT, WINO><<<dim3((p.MR + 31) / 32, p.S, nb), dim3(256), lds, s>>>(wb, p.B, p.MR, p.NR, p.bsB, p.sqB);
     return 0;
 }
 
-// the 3x3 takes the Winograd form unless CONTEXTFLOW_DIRECT_CONV=1 (same switch as the step kernels)
-static thread_local int g_wgrad_form = -1;            // test hook (cf_wgrad_form): 0 direct, 1 Winograd, -1 environment
-static bool wgrad_direct_only() {
-    static const bool v = [] { const char* e = getenv("CONTEXTFLOW_DIRECT_CONV"); return e && e[0] == '1'; }();
-    return g_wgrad_form < 0 ? v : g_wgrad_form == 0;
+// the k_wgrad of one (image, column tiles): 1x1, 3x3 direct, 3x3 Winograd
+template <int H, int NT>
+int launch_staged(const WgPlan& p, const WgBatch& wb, int nb, hipStream_t s) {
+    if (p.taps == 1) return launch_k_wgrad<H, 1, NT, false>(p, wb, nb, s);
+    return p.kernel == WgKernel::Wino ? launch_k_wgrad<H, 9, NT, true>(p, wb, nb, s) : launch_k_wgrad<H, 9, NT, false>(p, wb, nb, s);
 }
 
-template <int H, int W, int TAPS, int NT>
-int launch_form(const float* A, const float* Bm, float* gw, float* gbias, float* ws, int B, int MR, int NR, hipStream_t s,
-                int64_t bsB, int sqB) {
-    // (16x16 with 128 columns would stage 160 values per thread next to the 256 accumulators: it keeps the direct form)
-    if constexpr (TAPS == 9 && !(H * W == 256 && NT == 4)) {
-        if (!wgrad_direct_only()) return launch_wgrad<H, W, TAPS, NT, true>(A, Bm, gw, gbias, ws, B, MR, NR, s, bsB, sqB);
+template <int I = 0>
+int launch_skinny(const WgPlan& p, const WgBatch& wb, int nb, hipStream_t s) {
+    if constexpr (I < kWgTileCount) {
+        if (p.tile != I) return launch_skinny<I + 1>(p, wb, nb, s);
+        constexpr WgTile t = kWgTiles[I];
+        const dim3 grid(p.S, 1, nb), blk(256);
+        const size_t lds = (size_t)(t.rt * t.ct * 4 + t.rt) * 64 * sizeof(float);          // <= 33 KB
+        if (p.sqB) k_wgrad1x1<t.rt, t.ct, true, t.nf><<<grid, blk, lds, s>>>(wb, p.MR, p.NR, p.H * p.W, p.W, p.bsB, p.Q, p.qper, p.S);
+        else k_wgrad1x1<t.rt, t.ct, false, t.nf><<<grid, blk, lds, s>>>(wb, p.MR, p.NR, p.H * p.W, p.W, p.bsB, p.Q, p.qper, p.S);
+        return 0;
     }
-    return launch_wgrad<H, W, TAPS, NT, false>(A, Bm, gw, gbias, ws, B, MR, NR, s, bsB, sqB);
+    return CF_ERR_UNSUPPORTED;
 }
 
-template <int H, int W, int TAPS>
-int dispatch_nt(const float* A, const float* Bm, float* gw, float* gbias, float* ws, int B, int MR, int NR, hipStream_t s,
-                int64_t bsB, int sqB) {
-    if (NR <= 32) return launch_form<H, W, TAPS, 1>(A, Bm, gw, gbias, ws, B, MR, NR, s, bsB, sqB);
-    if (NR <= 64) return launch_form<H, W, TAPS, 2>(A, Bm, gw, gbias, ws, B, MR, NR, s, bsB, sqB);
-    return launch_form<H, W, TAPS, 4>(A, Bm, gw, gbias, ws, B, MR, NR, s, bsB, sqB);
+// Every launch passes here.  One case per staged (image, column tiles) that is built; a plan without a kernel is refused, never
+// run as something else.  16x16 with more than 64 columns (NT = 4) has none: its tiles would need 162 KB of LDS (the launch used to
+// fail with `invalid argument`); no flow level has that shape.
+static int wgrad_launch(const WgPlan& p, const WgBatch& wb, int nb, hipStream_t s) {
+    CF_REQUIRE(p.MR > 0 && p.NR > 0 && p.NR <= 128 && (p.taps == 1 || p.taps == 9));
+    CF_REQUIRE(p.bsB >= (int64_t)p.NR * p.H * p.W && p.bsB < (1 << 24) && (!p.sqB || (p.taps == 1 && p.NR % 4 == 0)));
+    int rc = CF_ERR_UNSUPPORTED;
+    if (p.kernel == WgKernel::Skinny) rc = launch_skinny(p, wb, nb, s);
+    else switch (p.H == p.W ? p.H * 8 + p.nt : 0) {
+        case 16 * 8 + 1: rc = launch_staged<16, 1>(p, wb, nb, s); break;
+        case 16 * 8 + 2: rc = launch_staged<16, 2>(p, wb, nb, s); break;
+        case 8 * 8 + 1: rc = launch_staged<8, 1>(p, wb, nb, s); break;
+        case 8 * 8 + 2: rc = launch_staged<8, 2>(p, wb, nb, s); break;
+        case 8 * 8 + 4: rc = launch_staged<8, 4>(p, wb, nb, s); break;
+        case 4 * 8 + 1: rc = launch_staged<4, 1>(p, wb, nb, s); break;
+        case 4 * 8 + 2: rc = launch_staged<4, 2>(p, wb, nb, s); break;
+        case 4 * 8 + 4: rc = launch_staged<4, 4>(p, wb, nb, s); break;
+    }
+    if (rc == CF_ERR_UNSUPPORTED) cf_set_error("cf_wgrad: no kernel for %d taps on %dx%d with %d columns", p.taps, p.H, p.W, p.NR);
+    if (rc) return rc;
+    CF_LAUNCH_CHECK();
+    return 0;
+}
+
+inline bool wg_aligned(const float* A, const float* Bm) { return ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(Bm)) & 15) == 0; }
+
+// cf_wgrad: the batch of one with its own reduce
+static int wgrad_single(const float* A, const float* Bm, float* gw, float* gbias, void* ws, int B, int MR, int NR, int H, int W,
+                        int taps, WgForm form, cf_stream_t stream) {
+    if (B == 0) return 0;                       // empty batch: nothing to do (pointers may be null)
+    CF_REQUIRE(A && Bm && gw && ws);
+    const WgPlan p = wg_plan(B, MR, NR, H, W, taps, wg_aligned(A, Bm), (int64_t)NR * H * W, false, form);
+    WgBatch wb{};
+    wb.A[0] = A; wb.Bm[0] = Bm; wb.part[0] = (float*)ws;
+    if (int rc = wgrad_launch(p, wb, 1, cf_s(stream))) return rc;
+    const int n = (int)p.per();
+    k_wgrad_reduce<<<dim3((n + 63) / 64), dim3(256), 0, cf_s(stream)>>>(wb.part[0], gw, gbias, n - MR, n, p.S);
+    CF_LAUNCH_CHECK();
+    return 0;
 }
 
 }  // namespace
 
 extern "C" {
 
-// workspace for the split-K partials: [splits][taps*MR*NR + MR] floats (sized for the larger split count of the two forms)
+// workspace for the split-K partials, [S][taps*MR*NR + MR] floats: large enough for whichever kernel the pointers end up
+// selecting - the larger of the plans for aligned and for unaligned operands, with the 3x3 in the direct form (512 workgroups
+// to aim for: its split count is never below the Winograd form's 256)
 int64_t cf_wgrad_ws_bytes(int B, int MR, int NR, int H, int W, int taps) {
-    int S = wgrad_splits(B, MR, H * W);
-    if (taps == 1 && wgrad1x1_ok(MR, NR, H * W)) {        // k_wgrad1x1: one partial per wave
-        int Q, qper, nsplit;
-        wgrad1x1_split(B, MR, NR, H * W, Q, qper, nsplit);
-        if (nsplit > S) S = nsplit;
+    const int64_t dense = (int64_t)NR * H * W;
+    const WgPlan a = wg_plan(B, MR, NR, H, W, taps, true, dense, false, WgForm::Direct);
+    WgPlan u = wg_plan(B, MR, NR, H, W, taps, false, dense, false, WgForm::Direct);
+    int S = a.S > u.S ? a.S : u.S;
+    if (taps == 1 && a.kernel != WgKernel::Skinny && wgrad1x1_sized(MR, NR, H * W)) {     // (see wgrad1x1_sized)
+        wgrad1x1_split(u);
+        if (u.S > S) S = u.S;
     }
-    return (int64_t)S * ((int64_t)taps * MR * NR + MR) * 4;
-}
-
-// bsB: batch stride of Bm in floats; sqB (taps == 1 only): Bm is the tensor before Squeeze((2,2)), read through the index map
-static int wgrad_impl(const float* A, const float* Bm, float* gw, float* gbias, void* ws, int B, int MR, int NR, int H, int W,
-                      int taps, int64_t bsB, int sqB, cf_stream_t stream) {
-    if (B == 0) return 0;                       // empty batch: nothing to do (pointers may be null)
-    CF_REQUIRE(A && Bm && gw && ws && MR > 0 && NR > 0 && NR <= 128 && (taps == 1 || taps == 9));
-    CF_REQUIRE(bsB >= (int64_t)NR * H * W && bsB < (1 << 24) && (!sqB || (taps == 1 && NR % 4 == 0)));
-    int rc;
-    hipStream_t s = cf_s(stream);
-    float* w = (float*)ws;
-    if (taps == 1 && wgrad1x1_ok(MR, NR, H * W) && (H == W) && (H == 16 || H == 8 || H == 4) &&
-        ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(Bm)) & 15) == 0 && bsB % 4 == 0) {
-        // the skinny 1x1 gradients: operands straight from global memory in MFMA layout (k_wgrad1x1)
-        int Q, qper, nsplit;
-        wgrad1x1_split(B, MR, NR, H * W, Q, qper, nsplit);
-        const int rt = (MR + 15) / 16, ct = (NR + 15) / 16;
-        rc = -1;
-#define CF_W1(R, Cc, F) if (rt == R && ct == Cc && nf == F) rc = launch_wgrad1x1<R, Cc, F>(A, Bm, w, MR, NR, H * W, W, bsB, sqB, Q, qper, nsplit, s)
-        const int nf = wgrad1x1_nf(H * W);
-        CF_W1(1, 1, 2); CF_W1(1, 2, 2); CF_W1(2, 1, 2); CF_W1(2, 2, 2); CF_W1(2, 4, 2); CF_W1(4, 1, 2); CF_W1(4, 2, 2);
-        CF_W1(1, 1, 1); CF_W1(1, 2, 1); CF_W1(2, 1, 1); CF_W1(2, 2, 1); CF_W1(2, 4, 1); CF_W1(4, 1, 1); CF_W1(4, 2, 1); CF_W1(4, 4, 1);
-        CF_W1(4, 8, 1); CF_W1(8, 2, 1);
-#undef CF_W1
-        if (rc == 0) {
-            g_wgrad_last_S = nsplit;
-            const int nw = MR * NR;
-            if (!g_wgrad_defer) k_wgrad_reduce<<<dim3((nw + MR + 63) / 64), dim3(256), 0, s>>>(w, gw, gbias, nw, nw + MR, nsplit);
-            CF_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-#define CF_W(HH, WW) rc = taps == 9 ? dispatch_nt<HH, WW, 9>(A, Bm, gw, gbias, w, B, MR, NR, s, bsB, sqB) : dispatch_nt<HH, WW, 1>(A, Bm, gw, gbias, w, B, MR, NR, s, bsB, sqB)
-    if (H == 16 && W == 16) CF_W(16, 16);
-    else if (H == 8 && W == 8) CF_W(8, 8);
-    else if (H == 4 && W == 4) CF_W(4, 4);
-    else { cf_set_error("cf_wgrad: image %dx%d unsupported", H, W); return CF_ERR_UNSUPPORTED; }
-#undef CF_W
-    if (rc) return rc;
-    CF_LAUNCH_CHECK();
-    return 0;
+    return S * a.per() * 4;
 }
 
 int cf_wgrad(const float* A, const float* Bm, float* gw, float* gbias, void* ws, int B, int MR, int NR, int H, int W,
              int taps, cf_stream_t stream) {
-    return wgrad_impl(A, Bm, gw, gbias, ws, B, MR, NR, H, W, taps, (int64_t)NR * H * W, 0, stream);
+    return wgrad_single(A, Bm, gw, gbias, ws, B, MR, NR, H, W, taps, WgForm::Env, stream);
 }
 
 // The four weight gradients of one flow step - NN.4 (s_gh x t_h2), NN.2 (3x3: s_gh2 x t_h1), NN.0 (s_gh1 x t_y0), the
@@ -876,9 +886,10 @@ int64_t cf_step_wgrads_ws_bytes(int B, int C, int H, int W) {
            cf_wgrad_ws_bytes(B, HID, HALF, H, W, 1) + cf_wgrad_ws_bytes(B, C, C, H, W, 1);
 }
 
-// n steps of one shape: per product ONE launch over all steps (blockIdx.z) - the Conv1x1 product once per (stride, layout) of
-// the step inputs: the first step of a level reads the tensor in front of its Squeeze - and ONE reduce launch.  Each step's
-// workspace is laid out as cf_step_wgrads' (cf_step_wgrads_ws_bytes); results bit for bit those of n cf_step_wgrads calls.
+// n steps of one shape: per product ONE launch over all steps whose plans are equal (blockIdx.z; the Conv1x1 product differs by
+// the stride / layout of the step inputs: the first step of a level reads the tensor in front of its Squeeze) and ONE reduce
+// launch.  Each step's workspace is laid out as cf_step_wgrads' (cf_step_wgrads_ws_bytes); results bit for bit those of n
+// cf_step_wgrads calls.
 static int step_wgrads_impl(int n, const float* const* s_gh, const float* const* s_gh2, const float* const* s_gh1,
                             const float* const* s_gy, const float* const* t_h2, const float* const* t_h1, const float* const* t_y0,
                             const float* const* xs, float* const* gw3, float* const* gb3, float* const* gw2, float* const* gb2,
@@ -895,38 +906,33 @@ static int step_wgrads_impl(int n, const float* const* s_gh, const float* const*
     for (int i = 0; i < n; ++i)
         for (int q = 0; q < 4; ++q) CF_REQUIRE(As[q][i] && Bs[q][i] && gws[q][i] && gbs[q][i] && ws[i]);
     WgReduce4B db{};
-    int64_t woff = 0;
-    int nmax = 0;
+    int64_t woff = 0, nmax = 0;
     for (int q = 0; q < 4; ++q) {
-        // steps that share the operand layout of this product go into one launch
+        const int MR = MRs[q], NR = NRs[q], taps = tps[q];
+        WgPlan plan[kWgBatch];
+        for (int i = 0; i < n; ++i) {
+            const int64_t bsB = q == 3 ? xs_bstride[i] : (int64_t)NR * H * W;
+            const bool sqB = q == 3 && xs_unsqueezed[i] != 0;
+            plan[i] = wg_plan(B, MR, NR, H, W, taps, wg_aligned(As[q][i], Bs[q][i]), bsB, sqB, WgForm::Env);
+        }
         bool done[kWgBatch] = {};
         for (int i0 = 0; i0 < n; ++i0) {
             if (done[i0]) continue;
             WgBatch wb{};
-            int idx[kWgBatch], m = 0;
+            int m = 0;
             for (int i = i0; i < n; ++i) {
-                if (done[i] || (q == 3 && (xs_bstride[i] != xs_bstride[i0] || (xs_unsqueezed[i] != 0) != (xs_unsqueezed[i0] != 0)))) continue;
-                // (alignment decides the kernel inside wgrad_impl: only steps whose operands agree with the leader's share a launch)
-                if ((((reinterpret_cast<uintptr_t>(As[q][i]) | reinterpret_cast<uintptr_t>(Bs[q][i])) & 15) == 0) !=
-                    (((reinterpret_cast<uintptr_t>(As[q][i0]) | reinterpret_cast<uintptr_t>(Bs[q][i0])) & 15) == 0)) continue;
-                done[i] = true; idx[m] = i;
+                if (done[i] || !wg_same_launch(plan[i], plan[i0])) continue;
+                done[i] = true;
                 wb.A[m] = As[q][i]; wb.Bm[m] = Bs[q][i]; wb.part[m] = (float*)((char*)ws[i] + woff);
+                WgReduce4& d = db.d[i];
+                d.part[q] = wb.part[m]; d.out0[q] = gws[q][i]; d.out1[q] = gbs[q][i];
+                d.n0[q] = (int)plan[i].per() - MR; d.n[q] = (int)plan[i].per(); d.S[q] = plan[i].S; d.taps[q] = taps;
                 ++m;
             }
-            g_wgrad_defer = true; g_wgrad_batch = &wb; g_wgrad_nb = m;
-            const int rc = wgrad_impl(wb.A[0], wb.Bm[0], gws[q][idx[0]], gbs[q][idx[0]], wb.part[0], B, MRs[q], NRs[q], H, W, tps[q],
-                                      q == 3 ? xs_bstride[i0] : (int64_t)NRs[q] * H * W, q == 3 && xs_unsqueezed[i0] != 0, stream);
-            g_wgrad_defer = false; g_wgrad_batch = nullptr; g_wgrad_nb = 1;
-            if (rc) return rc;
-            const int nw = tps[q] * MRs[q] * NRs[q];
-            for (int j = 0; j < m; ++j) {
-                WgReduce4& d = db.d[idx[j]];
-                d.part[q] = wb.part[j]; d.out0[q] = gws[q][idx[j]]; d.out1[q] = gbs[q][idx[j]];
-                d.n0[q] = nw; d.n[q] = nw + MRs[q]; d.S[q] = g_wgrad_last_S; d.taps[q] = tps[q];
-            }
-            nmax = nw + MRs[q] > nmax ? nw + MRs[q] : nmax;
+            if (int rc = wgrad_launch(plan[i0], wb, m, cf_s(stream))) return rc;
         }
-        woff += cf_wgrad_ws_bytes(B, MRs[q], NRs[q], H, W, tps[q]);
+        nmax = plan[0].per() > nmax ? plan[0].per() : nmax;
+        woff += cf_wgrad_ws_bytes(B, MR, NR, H, W, taps);
     }
     k_wgrad_reduce4<<<dim3((nmax + 63) / 64, 4, n), dim3(256), 0, cf_s(stream)>>>(db);
     CF_LAUNCH_CHECK();
@@ -960,20 +966,16 @@ int cf_step_wgrads_batch(int n, const float* const* s_gh, const float* const* s_
 }
 
 // multiply-adds per sample the matrix pipe executes for the four weight gradients of a step (bench.py): direct 40 C^2 HW;
-// the Winograd form F(3x3, 2x2) of the 3x3 (launch_form: every shape but 16x16 with 128 columns) runs 16 instead of 36 C^2
+// the Winograd form F(3x3, 2x2) of the 3x3 (wg_plan: every shape but 16x16 with 128 columns) runs 16 instead of 36 C^2
 int64_t cf_step_wgrads_macs(int B, int C, int H, int W) {
-    (void)B;
-    const bool wino = !wgrad_direct_only() && !(H * W == 256 && 2 * C > 64);
-    return (wino ? 20ll : 40ll) * C * C * H * W;
+    const WgPlan p = wg_plan(B, 2 * C, 2 * C, H, W, 9, true, (int64_t)2 * C * H * W, false, WgForm::Env);
+    return (p.kernel == WgKernel::Wino ? 20ll : 40ll) * C * C * H * W;
 }
 
 // test hook (not part of the public header): cf_wgrad with the form of the 3x3 chosen by the caller (0 direct, 1 Winograd)
 int cf_wgrad_form(const float* A, const float* Bm, float* gw, float* gbias, void* ws, int B, int MR, int NR, int H, int W,
                   int taps, int form, cf_stream_t stream) {
-    g_wgrad_form = form ? 1 : 0;
-    const int rc = cf_wgrad(A, Bm, gw, gbias, ws, B, MR, NR, H, W, taps, stream);
-    g_wgrad_form = -1;
-    return rc;
+    return wgrad_single(A, Bm, gw, gbias, ws, B, MR, NR, H, W, taps, form ? WgForm::Wino : WgForm::Direct, stream);
 }
 
 }  // extern "C"

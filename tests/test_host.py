@@ -135,6 +135,90 @@ def test_step_dispatch_breakpoints(built, setting):
         assert lines[20] == "7c2a86c3ec00086a32d855de78c909fd1fc4e762fe67234ccf36ecf20a48c0cf"
 
 
+# ---- the weight-gradient launch plan as the size queries and the flop accounting see it ----------------------------------------
+# Recorded from the library as it was BEFORE cf_wgrad.hip got its one wg_plan (commit 46e84f8).  (H, MR, NR, taps): the shapes of
+# tools/wgrad_bench.py, the mnist level, ragged ones.
+WGRAD_WS_SHAPES = [(16, 32, 32, 9), (8, 64, 64, 9), (4, 128, 128, 9), (16, 16, 32, 1), (16, 32, 8, 1), (16, 16, 16, 1),
+                   (8, 32, 64, 1), (8, 64, 16, 1), (8, 32, 32, 1), (4, 64, 128, 1), (4, 128, 32, 1), (4, 64, 64, 1),
+                   (16, 8, 16, 1), (16, 16, 4, 1), (16, 8, 8, 1), (16, 16, 16, 9),
+                   (4, 24, 40, 1), (4, 72, 100, 9), (16, 128, 128, 9)]
+WGRAD_WS_SHA = "255337f9dfc253e38616005e0da80ea26bdfbc4508e8990b66266213533a5a1d"        # 19 shapes x B = 0..8192, ascending
+WGRAD_STEP_WS_SHA = "3b8d2fe8ab4f4dd0cea04a09f783784756a771756d78e5bbd7d2d85071b86b02"   # SHAPES x B = 0..8192
+# where the slope of the partial count over B changes: the count's change points as arithmetic runs (first B, spacing, step,
+# how many).  Staged 3x3 at 4x4: a split per 4 chunks of 4 samples up to 512 / 4 row tiles; the skinny 1x1: one partial per four
+# waves of qper units, qper growing by one every 1024 / 2048 samples (each time the count falls back)
+WGRAD_WS_RUNS = {
+    (4, 128, 128, 9): [(29, 16, 1, 127)],
+    (8, 32, 64, 1): [(3, 2, 1, 511), (1025, 0, -255, 1), (1029, 4, 1, 255)],
+    (4, 24, 40, 1): [(5, 4, 1, 511), (2049, 0, -255, 1), (2057, 8, 1, 255), (4097, 0, -170, 1), (4105, 12, 1, 170),
+                     (6145, 0, -127, 1), (6161, 16, 1, 127)],
+}
+
+
+def _runs(S):
+    out = []
+    for B in range(1, len(S)):
+        d = S[B] - S[B - 1]
+        if d == 0:
+            continue
+        if out:
+            first, gap, step, n = out[-1]
+            if step == d and (n == 1 or B == first + n * gap):
+                out[-1] = (first, B - first if n == 1 else gap, step, n + 1)
+                continue
+        out.append((B, 0, d, 1))
+    return out
+
+
+def test_wgrad_workspace_sizes(built):
+    """cf_wgrad_ws_bytes / cf_step_wgrads_ws_bytes for every batch 0..8192, exactly: pins wgrad_splits at its 512-workgroup target
+    and the skinny 1x1 kernel's split rule at every batch.  NOT pinned here: the Winograd form's split count (256 workgroups to aim
+    for) - the workspace is sized for the direct form's, which is never smaller; the GPU digests of tests/test_gpu_parity.py pin it
+    at their batches."""
+    import hashlib
+    from contextflow_amd.layers import _hip
+    L = _hip.lib()
+    h = hashlib.sha256()
+    for shape in WGRAD_WS_SHAPES:
+        H, MR, NR, taps = shape
+        v = [L.cf_wgrad_ws_bytes(B, MR, NR, H, H, taps) for B in range(8193)]
+        for x in v:
+            h.update(str(x).encode())
+        if shape in WGRAD_WS_RUNS:
+            per = 4 * (taps * MR * NR + MR)
+            assert all(x % per == 0 for x in v) and v[0] == per, shape
+            assert _runs([x // per for x in v]) == WGRAD_WS_RUNS[shape], shape
+    assert h.hexdigest() == WGRAD_WS_SHA
+    h = hashlib.sha256()
+    for C, H, W in SHAPES:
+        for B in range(8193):
+            h.update(str(L.cf_step_wgrads_ws_bytes(B, C, H, W)).encode())
+    assert h.hexdigest() == WGRAD_STEP_WS_SHA
+
+
+WGRAD_MACS_SCRIPT = """
+import sys
+sys.path.insert(0, %r)
+from contextflow_amd.layers import _hip
+L = _hip.lib()
+print([L.cf_step_wgrads_macs(B, C, H, W) // (C * C * H * W) for C, H, W in %r for B in (1, 256, 8192)])
+"""
+
+
+@pytest.mark.parametrize("setting,want", [("", [20, 20, 20, 20, 40]), ("CONTEXTFLOW_DIRECT_CONV=1", [40] * 5)])
+def test_step_wgrads_macs(built, setting, want):
+    """cf_step_wgrads_macs in units of C^2 HW: the 3x3 in the Winograd form (16 of 36) everywhere but at C = 64 on 16x16 (128
+    columns keep the direct form), and nowhere under CONTEXTFLOW_DIRECT_CONV=1 (a child process: the switch is read once)."""
+    import ast
+    env = {k: v for k, v in os.environ.items() if not k.startswith("CONTEXTFLOW_")}
+    if setting:
+        env.update([setting.split("=")])
+    shapes = SHAPES + ((64, 16, 16),)
+    r = subprocess.run([sys.executable, "-c", WGRAD_MACS_SCRIPT % (ROOT, shapes)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert ast.literal_eval(r.stdout.strip()) == [w for w in want for _ in range(3)]
+
+
 def test_gfx950_code_object(built):
     out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "--offloading", built], capture_output=True, text=True)
     blob = out.stdout + out.stderr

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Times cf_wgrad (split-K MFMA weight-gradient GEMM) on the shapes of the cifar10 conv flow.  usage: wgrad_bench.py [B]"""
+"""Times cf_wgrad (split-K MFMA weight-gradient GEMM) on the shapes of the cifar10 conv flow.  usage: wgrad_bench.py [B] [timed iterations, default 10]"""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch
 from contextflow_amd.layers import _hip
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 8192
+iters = int(sys.argv[2]) if len(sys.argv) > 2 else 10
 dev = "cuda"
 L = _hip.lib()
 for (H, MR, NR, taps) in [(16, 32, 32, 9), (8, 64, 64, 9), (4, 128, 128, 9), (16, 16, 32, 1), (16, 32, 8, 1), (16, 16, 16, 1),
@@ -20,10 +21,10 @@ for (H, MR, NR, taps) in [(16, 32, 32, 9), (8, 64, 64, 9), (4, 128, 128, 9), (16
         run()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize(); e0.record()
-    for _ in range(10):
+    for _ in range(iters):
         run()
     e1.record(); torch.cuda.synchronize()
-    us = e0.elapsed_time(e1) * 100
+    us = e0.elapsed_time(e1) * 1000 / iters
     fl = 2.0 * MR * NR * taps * H * H * B
     by = 4.0 * (MR + NR) * H * H * B
     print("H=%2d MR=%3d NR=%3d taps=%d: %7.1f us  %6.1f TFLOP/s  %5.2f TB/s (operands)" % (H, MR, NR, taps, us, fl / us / 1e6, by / us / 1e6))
