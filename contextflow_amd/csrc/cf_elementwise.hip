@@ -419,6 +419,43 @@ int launch_postprocess_inv(const float* z, float* x, int B, int n_keep, int64_t 
     return 0;
 }
 
+// Backward of the fused pre-processing (k_sample<1> / k_preprocess_rng) from its OUTPUT alone: with v = sigmoid(y),
+// dy/dv = 1 / (v (1 - v)) = 2 + e^y + e^-y and d ldj/dv = -1/v + 1/(1 - v) = e^y - e^-y, dv/dx = 1 / (s1 s2), so
+//   gx[b, i] = (gy[b, i] (2 + e^y + e^-y) + gld[b] (e^y - e^-y)) / (s1 s2),   i < n (the image elements of the row);
+// the dequantisation noise is inside y and is neither redrawn nor stored, the Augment channels behind the n elements get no
+// gradient (their noise does not depend on x).  gx is dense (B, n).
+template <int V>
+__global__ __launch_bounds__(256) void k_preprocess_bwd(const float* __restrict__ y, const float* __restrict__ gy,
+                                                        const float* __restrict__ gld, float* __restrict__ gx, int64_t n_items,
+                                                        int per_sample, int64_t ybs, int64_t gybs, float s12) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_items; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / per_sample;
+        const int j = (int)(i - b * per_sample);
+        float r[V], g[V];
+        vload<V>(y + b * ybs + (int64_t)j * V, r);
+        vload<V>(gy + b * gybs + (int64_t)j * V, g);
+        const float gl = gld[b];
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            const float ep = expf(r[e]), em = expf(-r[e]);
+            r[e] = (g[e] * (2.0f + ep + em) + gl * (ep - em)) / s12;
+        }
+        vstore<V>(gx + i * V, r);
+    }
+}
+
+int launch_preprocess_bwd(const float* y, const float* gy, const float* gld, float* gx, int B, int N, int64_t ybs, int64_t gybs,
+                          float s12, hipStream_t s) {
+    const bool vec = N % 4 == 0 && ybs % 4 == 0 && gybs % 4 == 0 && aligned16(y) && aligned16(gy) && aligned16(gx);
+    const int per = vec ? N / 4 : N;
+    const int64_t items = (int64_t)B * per;
+    int64_t blocks = (items + 255) / 256;
+    if (blocks > 16384) blocks = 16384;
+    if (vec) k_preprocess_bwd<4><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(y, gy, gld, gx, items, per, ybs, gybs, s12);
+    else k_preprocess_bwd<1><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(y, gy, gld, gx, items, per, ybs, gybs, s12);
+    return 0;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -512,6 +549,15 @@ int cf_preprocess_rng_fwd(const float* x, float* y, float* ldj, uint64_t* rng_st
                                                                   (unsigned long long)seed, N / 4, aug_n / 4, N, y_bstride,
                                                                   t1, s1, t2, s2, ldj_const);
     if (advance) k_rng_advance<<<dim3(1), dim3(1), 0, cf_s(stream)>>>((unsigned long long*)rng_state);
+    CF_LAUNCH_CHECK();
+    return 0;
+}
+
+int cf_preprocess_bwd(const float* y, const float* gy, const float* gld, float* gx, int B, int N, int64_t y_bstride,
+                      int64_t gy_bstride, float s1, float s2, cf_stream_t stream) {
+    if (B == 0) return 0;                       // empty batch: nothing to do (pointers may be null)
+    CF_REQUIRE(y && gy && gld && gx && B >= 0 && N > 0 && y_bstride >= N && gy_bstride >= N);
+    launch_preprocess_bwd(y, gy, gld, gx, B, N, y_bstride, gy_bstride, s1 * s2, cf_s(stream));
     CF_LAUNCH_CHECK();
     return 0;
 }

@@ -237,7 +237,10 @@ __device__ __forceinline__ void adj_axis(int c, int d, int N, int (&src)[2], boo
 // generalist's weights are frozen in that mode, so of the operand planes of the weight-gradient GEMMs only s_gh is written
 // (156 of 172 KB per sample at C = 16 are not).
 // Neither form touches s_y0 / s_h1 / s_h2: they stay in the argument list that the two entry points share.
-template <class G, bool CTX>
+// DATA = true (cf_flow_step_bwd_data: the input gradient of log p(x) with frozen weights): none of the four operand planes of
+// the weight-gradient GEMMs is written (s_gh, s_gh2, s_gh1, s_gy may be null: 6 C HW of the 7 C HW floats the kernel stores per
+// sample); everything that leads to g_x is the same instruction stream, so g_x is bit for bit the training form's.
+template <class G, bool CTX, bool DATA = false>
 __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
     const float* __restrict__ x, const float* __restrict__ gz, const float* __restrict__ gld,
     const float* __restrict__ ws, const float* __restrict__ wsb, float* __restrict__ gx,
@@ -446,8 +449,8 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
                 }
             }
         }
-        rows_store_t<G, C, C>(s_gh, GH, b0, B, wave, lane);
-        if constexpr (!CTX) rows_store_t<G, HALF, C>(s_gy + HALF * HW, Y0, b0, B, wave, lane);   // g_y1 rows of the g_y plane
+        if constexpr (!DATA) rows_store_t<G, C, C>(s_gh, GH, b0, B, wave, lane);
+        if constexpr (!CTX && !DATA) rows_store_t<G, HALF, C>(s_gy + HALF * HW, Y0, b0, B, wave, lane);   // g_y1 rows of the g_y plane
         // g_h2 = (NN.4^T g_h) * [h2 > 0]
         f32x16 acc[RT1][PTW];
 #pragma unroll
@@ -465,7 +468,7 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
                 for (int r = 0; r < 16; ++r)
                     if (!((m2[rt][q] >> r) & 1u)) acc[rt][q][r] = 0.f;
         tiles_to_plane<G, RT1>(acc, H1, HID, pix, lk);       // g_h2 plane over the whole H region (own columns)
-        if constexpr (!CTX) rows_store_t<G, HID, HID>(s_gh2, H1, b0, B, wave, lane);   // weight-gradient operand plane
+        if constexpr (!CTX && !DATA) rows_store_t<G, HID, HID>(s_gh2, H1, b0, B, wave, lane);   // weight-gradient operand plane
     }
     // g_z0, the start value of the g_y0 accumulators two phases on (rows of that single tile = channels 0..31 in natural
     // order; 128 contiguous bytes per row and half wave): in flight during the transposed 3x3
@@ -603,7 +606,7 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
                 for (int r = 0; r < 16; ++r)
                     if (!((m1[rt][q] >> r) & 1u)) acc[rt][q][r] = 0.f;
         tiles_to_plane<G, RT1>(acc, H1, HID, pix, lk);       // g_h1 plane
-        if constexpr (!CTX) rows_store_t<G, HID, HID>(s_gh1, H1, b0, B, wave, lane);   // weight-gradient operand plane
+        if constexpr (!CTX && !DATA) rows_store_t<G, HID, HID>(s_gh1, H1, b0, B, wave, lane);   // weight-gradient operand plane
     }
     {   // g_y0 = NN.0^T g_h1 + g_z0: the accumulators start from g_z0 (requested before the transposed 3x3)
         f32x16 (&acc)[1][PTW] = accy;
@@ -618,7 +621,7 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
                 const int row = tile_row(r, lk);
                 if (row < HALF) H1[row * RS + pix[q]] = acc[0][q][r];
             }
-        if constexpr (!CTX) rows_store_t<G, HALF, C>(s_gy, H1, b0, B, wave, lane);   // g_y0 rows (weight-gradient operand plane)
+        if constexpr (!CTX && !DATA) rows_store_t<G, HALF, C>(s_gy, H1, b0, B, wave, lane);   // g_y0 rows (weight-gradient operand plane)
         // g_x = (e^{-logs} Wm)^T g_y
         f32x16 ax[Bw::RTI][PTW];
 #pragma unroll
@@ -645,8 +648,9 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
 // row dy the three planes  GA[dx][co][s] = sum over { p : reflect(p + d) = s } of g_h2[co][p]  are formed once (two row reads,
 // one fold of a float4 per dx), after which a tap is a plain product.  TAPED form only (log-scale, y1 and the ReLU mask words
 // of the tape in the layout of the 32x32x2 kernels: one word holds the four rows of a lane's accumulator).
+// DATA = true: as in k_flow_step_bwd, the weight-gradient operand planes are not written (their pointers may be null).
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-template <class G>
+template <class G, bool DATA = false>
 __global__ __launch_bounds__(256) void k_flow_step_bwd_rs16(const float* __restrict__ gz, const float* __restrict__ gld,
                                                             const float* __restrict__ wsb, float* __restrict__ gx,
                                                             float* __restrict__ s_gh, float* __restrict__ s_gh2,
@@ -715,8 +719,10 @@ __global__ __launch_bounds__(256) void k_flow_step_bwd_rs16(const float* __restr
     auto plane_out = [&](float* __restrict__ dst, const float* __restrict__ src, int floats) {
         for (int e = 4 * tid; e < floats; e += 1024) *reinterpret_cast<float4*>(dst + e) = *reinterpret_cast<const float4*>(src + e);
     };
-    plane_out(s_gh + (int64_t)b * C * HW, GH, C * P);
-    plane_out(s_gy + (int64_t)b * C * HW + HALF * HW, GY + HALF * P, HALF * P);
+    if constexpr (!DATA) {
+        plane_out(s_gh + (int64_t)b * C * HW, GH, C * P);
+        plane_out(s_gy + (int64_t)b * C * HW + HALF * HW, GY + HALF * P, HALF * P);
+    }
     // ---- g_h2 = (NN.4^T g_h) * [h2 > 0]: row tiles 2 w, 2 w + 1
     {
         f32x4 a[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
@@ -732,7 +738,7 @@ __global__ __launch_bounds__(256) void k_flow_step_bwd_rs16(const float* __restr
             for (int r = 0; r < 4; ++r) H2[(16 * (2 * w + t) + 4 * g + r) * P + col] = ((mw2[t] >> r) & 1u) ? a[t][r] : 0.f;
     }
     __syncthreads();
-    plane_out(s_gh2 + (int64_t)b * HID * HW, H2, HID * P);
+    if constexpr (!DATA) plane_out(s_gh2 + (int64_t)b * HID * HW, H2, HID * P);
     // ---- g_h1 = (NN.2^T (*) g_h2) * [h1 > 0]
     f32x4 a2[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll 1
@@ -787,7 +793,7 @@ __global__ __launch_bounds__(256) void k_flow_step_bwd_rs16(const float* __restr
 #pragma unroll
         for (int r = 0; r < 4; ++r) H2[(16 * (2 * w + t) + 4 * g + r) * P + col] = ((mw1[t] >> r) & 1u) ? a2[t][r] : 0.f;
     __syncthreads();
-    plane_out(s_gh1 + (int64_t)b * HID * HW, H2, HID * P);
+    if constexpr (!DATA) plane_out(s_gh1 + (int64_t)b * HID * HW, H2, HID * P);
     // ---- g_y0 = NN.0^T g_h1 + g_z0: row tile w & 1, K half w >> 1; the halves meet in the (dead) gathered planes
     {
         f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -803,7 +809,7 @@ __global__ __launch_bounds__(256) void k_flow_step_bwd_rs16(const float* __restr
         const int e = tid + 256 * i;
         const float v = GA[e] + GA[HALF * P + e] + gz0[i];
         GY[e] = v;
-        s_gy[(int64_t)b * C * HW + e] = v;
+        if constexpr (!DATA) s_gy[(int64_t)b * C * HW + e] = v;
     }
     __syncthreads();
     // ---- g_x = (e^{-logs} Wm)^T g_y: row tile w
@@ -843,16 +849,16 @@ int launch_prepare_bwd(const StepPackBwdBatch& pb, int n, hipStream_t s) {
     return 0;
 }
 
-template <class G, bool CTX>
+template <class G, bool CTX, bool DATA = false>
 int launch_step_bwd(const float* x, const float* gz, const float* gld, const float* ws, const float* wsb, float* gx,
                     float* s_y0, float* s_h1, float* s_h2, float* s_gh, float* s_gh2, float* s_gh1, float* s_gy, int B,
                     int64_t xbs, hipStream_t s, const float* sb = nullptr, StepTape tp = kNoTape, int gx_unsq = 0) {
     constexpr size_t lds_bytes = (size_t)G::LDS_FLOATS * sizeof(float);
     if (lds_bytes > 64 * 1024) {
         static std::atomic<uint64_t> raised{0};
-        if (int rc_ = cf_raise_dynamic_lds((const void*)k_flow_step_bwd<G, CTX>, 160 * 1024, raised, __func__)) return rc_;
+        if (int rc_ = cf_raise_dynamic_lds((const void*)k_flow_step_bwd<G, CTX, DATA>, 160 * 1024, raised, __func__)) return rc_;
     }
-    k_flow_step_bwd<G, CTX><<<dim3((B + G::SPW - 1) / G::SPW), dim3(256), lds_bytes, s>>>(
+    k_flow_step_bwd<G, CTX, DATA><<<dim3((B + G::SPW - 1) / G::SPW), dim3(256), lds_bytes, s>>>(
         x, gz, gld, ws, wsb, gx, s_y0, s_h1, s_h2, s_gh, s_gh2, s_gh1, s_gy, B, xbs, sb, tp, gx_unsq);
     return 0;
 }
@@ -937,6 +943,37 @@ int cf_flow_step_bwd_taped(const float* gz, const float* gld, const void* wsb, c
         default: cf_set_error("cf_flow_step_bwd_taped: shape (%d,%d,%d) unsupported", C, H, W); return CF_ERR_UNSUPPORTED;
     }
 #undef CF_BWDT
+    if (rc) return rc;
+    CF_LAUNCH_CHECK();
+    return 0;
+}
+
+// the data-gradient chain of cf_flow_step_bwd_taped alone (d log p(x) / d x with frozen weights: FlowSequential.score): the same
+// kernels with the stores of the four weight-gradient operand planes compiled out, the same dispatch - gx is bitwise equal.
+int cf_flow_step_bwd_data(const float* gz, const float* gld, const void* wsb, const void* t_aux, float* gx, int B, int C, int H,
+                          int W, int gx_unsqueezed, cf_stream_t stream) {
+    if (B == 0) return 0;
+    CF_REQUIRE(gz && gld && wsb && t_aux && gx && (!gx_unsqueezed || C % 4 == 0));
+    CF_REQUIRE((reinterpret_cast<uintptr_t>(gz) & 15) == 0 && (reinterpret_cast<uintptr_t>(gx) & 15) == 0 &&
+               (reinterpret_cast<uintptr_t>(t_aux) & 15) == 0);
+    const float* wb = (const float*)wsb;
+    const StepTape tp = make_tape(nullptr, nullptr, nullptr, const_cast<void*>(t_aux), B, C, H, W);
+    int rc = 0;
+#define CF_BWDD(G) rc = launch_step_bwd<G, false, true>(nullptr, gz, gld, nullptr, wb, gx, nullptr, nullptr, nullptr, nullptr, nullptr, \
+                                                      nullptr, nullptr, B, (int64_t)C * H * W, cf_s(stream), nullptr, tp, gx_unsqueezed != 0)
+    switch (shape_id(C, H, W)) {
+        case 0: CF_BWDD(B8); break;
+        case 1: CF_BWDD(B16); break;
+        case 2: CF_BWDD(B32); break;
+        case 3:
+            if (B <= CF_BWD_RS16_MAXB)      // one sample per workgroup, as cf_flow_step_bwd_taped
+                k_flow_step_bwd_rs16<B64, true><<<dim3(B), dim3(256), 0, cf_s(stream)>>>(gz, gld, wb, gx, nullptr, nullptr, nullptr, nullptr, B,
+                                                                                        tp, gx_unsqueezed != 0);
+            else CF_BWDD(B64);
+            break;
+        default: cf_set_error("cf_flow_step_bwd_data: shape (%d,%d,%d) unsupported", C, H, W); return CF_ERR_UNSUPPORTED;
+    }
+#undef CF_BWDD
     if (rc) return rc;
     CF_LAUNCH_CHECK();
     return 0;

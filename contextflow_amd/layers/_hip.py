@@ -30,6 +30,7 @@ SIGNATURES = {
     "cf_clamp": (_c_int, [_c_p, _c_p, _c_i64, _c_f, _c_f, _c_p]),
     "cf_preprocess_fwd": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_i64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p]),
     "cf_preprocess_rng_fwd": (_c_int, [_c_p] * 4 + [ctypes.c_uint64, _c_int, _c_int, _c_int, _c_i64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_int, _c_p]),
+    "cf_preprocess_bwd": (_c_int, [_c_p] * 4 + [_c_int, _c_int, _c_i64, _c_i64, _c_f, _c_f, _c_p]),
     "cf_std_normal_nll": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_i64, _c_p]),
     "cf_squeeze": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_int, _c_p]),
     "cf_conv1x1_fwd": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_p]),
@@ -81,6 +82,7 @@ SIGNATURES = {
     "cf_step_wgrads_macs": (_c_i64, [_c_int] * 4),
     "cf_flow_step_tape_aux_bytes": (_c_i64, [_c_int] * 4),
     "cf_flow_step_bwd_taped": (_c_int, [_c_p] * 9 + [_c_int] * 5 + [_c_p]),
+    "cf_flow_step_bwd_data": (_c_int, [_c_p] * 5 + [_c_int] * 5 + [_c_p]),
     "cf_flow_step_fwd_taped": (_c_int, [_c_p] * 8 + [_c_int] * 4 + [_c_i64, _c_int, _c_p]),
     "cf_step_param_grads": (_c_int, [_c_p] * 7 + [_c_int] + [_c_p] * 3 + [_c_int, _c_p]),
     "cf_bf16_split": (_c_int, [_c_int]),

@@ -18,8 +18,13 @@ def step_tape(B, C, H, W, dev):
 
 
 class Pre(NamedTuple):
-    """pre-processing: nothing trainable at or above it"""
+    """pre-processing: nothing trainable at or above it; its backward (cf_preprocess_bwd, only when the input needs a
+    gradient) reads the forward output alone"""
     kind = "pre"
+    y: Any = None            # forward output (B, C + aug, H, W): the tensor the next record reads anyway
+    n: int = 0               # image elements per sample (the Augment channels behind them get no gradient)
+    s1: float = 1.0          # scales of the two Normalizations
+    s2: float = 1.0
 
 
 class Step(NamedTuple):
@@ -35,6 +40,7 @@ class Step(NamedTuple):
     winv: Any = None         # Wm^-1
     planes: Any = None       # step_tape(...) of the forward, or None = rebuilt from x at backward time
     wsb: Any = None          # packed backward tables
+    aux: Any = None          # data-only walk (input gradient with frozen weights): the tape's aux buffer, all that is kept of the step
 
 
 class VStep(NamedTuple):

@@ -18,12 +18,19 @@ Conv1x1 / ActNorm of other shapes, Augment: the SMAP topology) go through autogr
 The tape is a list of the named records of _tape.py.  A record's backward has a data half (the chain to the record before, on
 the main stream) and a parameter half (at small batches on a side stream).  The parameter half of a conv step is ONE function
 over n steps (_step_param_part_batch: the steps of a resolution level at small batches, a single step otherwise), fed by named
-items (StepWork); the Conv1x1 / ActNorm chain that closes it is shared with the transformer steps (_affine_param_grads)."""
+items (StepWork); the Conv1x1 / ActNorm chain that closes it is shared with the transformer steps (_affine_param_grads).
+
+d log p(x) / d x: when the input needs a gradient the walk goes one record further, through the pre-processing
+(pre_backward: cf_preprocess_bwd, from the forward output alone).  With no trainable parameter - and always in
+FlowSequential.score - it is the data-only walk (input_gradient): the data halves alone, every conv step through
+cf_flow_step_bwd_data (no weight-gradient operand planes), no side streams, no bucket, no StepWork items; the tape then keeps
+of a conv step only the aux buffer (_tape.Step.aux)."""
 import contextlib
 import ctypes
 from collections import namedtuple
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _hip
 from ._tape import step_tape
@@ -43,9 +50,9 @@ def _param_part_on(side, keep, alive, fn, dev):
 
 
 # ------------------------------------------------------------------------------------------------ GMM prior
-def gmm_backward(x, dist, prepared, g, gcol=None, side=None, keep=None, sink=None):
+def gmm_backward(x, dist, prepared, g, gcol=None, side=None, keep=None, sink=None, params=True):
     """x: (B, D...) possibly a channel slice; g: (B, M) upstream; gcol: its column sums (M,) if the caller has them (the
-    priors of one backward pass share g).  Returns (gx like x, {param: grad})."""
+    priors of one backward pass share g).  Returns (gx like x, {param: grad}); params=False: the data half alone, (gx, None)."""
     a, nm, cst, M, K, D = prepared
     xv, xbs = _hip.bview(x)
     B = xv.shape[0]
@@ -68,6 +75,8 @@ def gmm_backward(x, dist, prepared, g, gcol=None, side=None, keep=None, sink=Non
     # parameter sums over the batch: S1 = r^T x, S2 = r^T x^2 (MK x D) and S0 = column sums of r, as split-K MFMA GEMMs
     # over the samples (cf_linear_wgrad: the bias-gradient column gives S0; x is squared while it is staged for S2)
     # (small batches: on the side stream - the chain to the previous layer needs gx only)
+    if not params:
+        return gx.view(xv.shape), None
     return gx.view(xv.shape), _param_part_on(side, keep, (xv, r, a, nm, gcol),
                                              lambda: _gmm_param_part(xv, xbs, r, dist, a, nm, g, gcol, B, M, K, D, dev, sink), dev)
 
@@ -174,6 +183,60 @@ def step_backward(rec, gz, gld, gsum=None, side=None, keep=None, sink=None, coll
     return gx, _param_part_on(side, keep, (work, gsum), lambda: _step_param_part_batch([work], gsum, gld, B, dev, sink), dev)[0]
 
 
+def step_backward_data(rec, gz, gld):
+    """The data half of step_backward alone (cf_flow_step_bwd_data: the kernels of cf_flow_step_bwd_taped without the stores of
+    the four weight-gradient operand planes; dL/dx bitwise equal), from the aux buffer of the taping forward (rec.aux)."""
+    C, H, W = rec.shape
+    gzc = _hip.f32(gz)
+    B, dev = gzc.shape[0], gzc.device
+    gx = torch.empty((B, C // 4, 2 * H, 2 * W) if rec.squeeze else (B, C, H, W), device=dev, dtype=torch.float32)
+    _hip.call("cf_flow_step_bwd_data", _hip.p(gzc), _hip.p(_hip.f32(gld)), _hip.p(rec.wsb), _hip.p(rec.aux), _hip.p(gx), B, C, H, W,
+              int(bool(rec.squeeze)), _hip.stream())
+    return gx
+
+
+def pre_backward(rec, gz, gld):
+    """Through the fused pre-processing (rec: _tape.Pre): dL/dx (B, n) from dL/dy (gz, in y's layout), dL/d ld1 (gld) and the
+    forward output y alone - cf_preprocess_bwd; the Augment channels of y carry no gradient to x."""
+    yv, ybs = _hip.bview(rec.y)
+    gv, gbs = _hip.bview(gz)
+    B = yv.shape[0]
+    gx = torch.empty(B, rec.n, device=yv.device, dtype=torch.float32)
+    _hip.call("cf_preprocess_bwd", _hip.p(yv), _hip.p(gv), _hip.p(_hip.f32(gld)), _hip.p(gx), B, rec.n, ybs, gbs, rec.s1, rec.s2,
+              _hip.stream())
+    return gx
+
+
+def input_gradient(tape, glogp):
+    """The data-only walk: d sum(glogp * logp) / d (flow input) from a tape, fp32, flat or in the layout of the first record's
+    input.  Only the data half of every record is launched, on the current stream; no parameter gradient is computed."""
+    glogp = _hip.f32(glogp)
+    if glogp.shape[0] == 0:          # empty batch: nothing to launch
+        return glogp.new_zeros(0)
+    gld = glogp.sum(1).contiguous()
+    gz = None
+    for rec in reversed(tape):
+        kind = rec.kind
+        if kind == "prior":
+            gz = gmm_backward(rec.x, rec.dist, rec.prepared, glogp, params=False)[0]
+        elif kind == "split":
+            c = rec.x.shape[1] // 2
+            gz = torch.cat([gz, gmm_backward(rec.x[:, c:], rec.dist, rec.prepared, glogp, params=False)[0]], dim=1)
+        elif kind == "step":
+            gz = step_backward_data(rec, gz, gld)
+        elif kind == "vstep":
+            gz = vstep_backward(rec, gz, gld, params=False)[0]
+        elif kind == "squeeze":
+            gz = squeeze_op(gz, rec.p, True)
+        elif kind == "pre":
+            return pre_backward(rec, gz, gld)
+        elif kind == "layer":
+            gz = layer_backward(rec.module, rec.x, gz, gld, params=False)[0]
+        else:
+            raise NotImplementedError("no backward for tape record %r" % (kind,))
+    return gz
+
+
 def _affine_param_grads(affs, gWps, gbps, HW, gsum, gld, dev, sink=None):
     """Chain to the Conv1x1 / ActNorm parameters of n steps of one width from the gradients of their folded matrix / bias
     (W' = diag(s) Wm, b' = -t s, s = exp(-logs); gWps[i] (C, C), gbps[i] (C,), dense): one launch, one workgroup per step
@@ -265,12 +328,12 @@ def wgrad_group(members, dev, dests=None):
     return res
 
 
-def vstep_backward(rec, gz, gld, gsum=None, side=None, keep=None, sink=None):
+def vstep_backward(rec, gz, gld, gsum=None, side=None, keep=None, sink=None, params=True):
     """Conv1x1 -> ActNorm -> TransCoupling (one fused step of the transformer flows, tape record _tape.VStep) backwards: ONE
     kernel re-runs the step from its input and walks back (cf_vit_step_bwd), ONE grouped launch contracts the 26
     weight-gradient operand pairs it leaves (cf_linear_wgrad_group), the LayerNorm gradients are column sums of its
     per-workgroup partials, and the Conv1x1 / ActNorm chain is _affine_param_grads - as for the conv flows.
-    Returns (dL/dx, {param: grad})."""
+    Returns (dL/dx, {param: grad}); params=False: the kernel alone, (dL/dx, None)."""
     conv, act, cpl, ws, xtape, wsb = rec.conv, rec.act, rec.cpl, rec.ws, rec.xtape, rec.wsb
     xv, xbs = _hip.bview(rec.x)
     B, C = xv.shape[0], xv.shape[1]
@@ -298,6 +361,8 @@ def vstep_backward(rec, gz, gld, gsum=None, side=None, keep=None, sink=None):
                   depth, xbs, st)
     # ---- weight gradients: the planes as (rows, width) matrices (layout: include/contextflow_hip.h, cf_vit_step_bwd)
     # (small batches: on the side stream, as in step_backward)
+    if not params:
+        return gx, None
     HWv = xv.shape[2] * xv.shape[3]
     aff = Affine(conv, act, Wm, t, logs, rec.winv)
     return gx, _param_part_on(side, keep, (planes, lnp, xv, ws, wsb, gsum, aff),
@@ -352,20 +417,33 @@ def _vstep_param_part(aff, vit, depth, planes, lnp, nwg, C, HW, gsum, gld, dev, 
 
 # ------------------------------------------------------------------------------------------------ the Function
 class FlowLogProb(torch.autograd.Function):
-    """logp (B,M) of a FlowSequential with parameter gradients.  `params` are passed positionally only so that autograd
-    tracks them; the arithmetic reads them from the modules."""
+    """logp (B,M) of a FlowSequential with parameter gradients and, when x requires one, the input gradient.  `params` (the
+    trainable ones) are passed positionally only so that autograd tracks them; the arithmetic reads them from the modules.
+    No trainable parameter: the forward keeps the lean tape and the backward is the data-only walk (input_gradient)."""
 
     @staticmethod
     def forward(ctx, flow, x, *params):
         tape = []
-        z, logp = flow._forward_fused(x, None, tape=tape)
+        ctx.data_only = ctx.needs_input_grad[1] and not params
+        z, logp = flow._forward_fused(x, None, tape=tape, data_only=ctx.data_only)
         ctx.flow, ctx.tape, ctx.params = flow, tape, params
+        ctx.x_like = (x.shape, x.dtype)
         ctx.mark_non_differentiable(z)
         return z, logp
 
     @staticmethod
+    def _as_input(ctx, g):
+        shape, dtype = ctx.x_like
+        return g.reshape(shape).to(dtype)
+
+    @staticmethod
+    @once_differentiable
     def backward(ctx, _gz_unused, glogp):
         flow, tape, params = ctx.flow, ctx.tape, ctx.params
+        need_x = ctx.needs_input_grad[1]
+        if ctx.data_only:
+            return (None, FlowLogProb._as_input(ctx, input_gradient(tape, glogp)))
+        gx_in = None
         glogp = _hip.f32(glogp)
         gld = glogp.sum(1).contiguous()                     # d/d ld1[b]: logp = ldM + ld1[:, None]
         gsum = gld.sum().reshape(1)                         # shared by the parameter chains of all steps
@@ -468,6 +546,8 @@ class FlowLogProb(torch.autograd.Function):
             elif kind == "squeeze":
                 gz = squeeze_op(gz, rec.p, True)
             elif kind == "pre":
+                if need_x:
+                    gx_in = pre_backward(rec, gz, gld)
                 break                                        # nothing trainable upstream of the pre-processing
             elif kind == "layer":
                 gz, gp = layer_backward(rec.module, rec.x, gz, gld)
@@ -489,7 +569,9 @@ class FlowLogProb(torch.autograd.Function):
                 v = bucket.view(p)
                 if v is not None:
                     p.grad = v                               # (assigned, not accumulated: one backward per optimizer step)
-        return (None, None) + tuple(acc.get(p) for p in params)
+        if need_x:               # (a flow without a pre-processing record: the walk has ended at the input)
+            gx_in = FlowLogProb._as_input(ctx, gx_in if gx_in is not None else gz)
+        return (None, gx_in) + tuple(acc.get(p) for p in params)
 
 
 SEGMENT_MIN_BYTES = 1 << 20      # data-parallel bucket: a segment is closed at the first record boundary past this size, and at every SplitPrior

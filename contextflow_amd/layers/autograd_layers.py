@@ -4,6 +4,8 @@ not cover (the SMAP topology: 26 channels, 8x1 windows; reference training step 
 
 Each `*_backward(module, x_in, gz, gld)` takes the layer's saved input, the gradient w.r.t. its output and the
 gradient w.r.t. the per-sample log-det (B,), and returns (gradient w.r.t. the input, {parameter: gradient}).
+params=False (the input gradient of log p(x) with frozen weights): the same data-gradient launches, no parameter-gradient
+launch, an empty dict.
 Nothing but the layer input is kept from the forward: the conditioner is recomputed (token-major, with its
 intermediates) inside the backward.  Elementwise / normalisation / attention pieces are HIP kernels
 (csrc/cf_layers_bwd.hip); the Linear layers' two backward products are plain library GEMMs."""
@@ -127,7 +129,7 @@ def vit_backward(vit, tape, gh, grads):
 
 
 # ------------------------------------------------------------------------------------------------ layers
-def transcoupling_backward(m, x_in, gz, gld):
+def transcoupling_backward(m, x_in, gz, gld, params=True):
     """TransCoupling (coupling.py:123-155): z = [x0 | x1 exp(log_s) + t], ldj = sum log_s, [t | raw] = ViT(x0)."""
     x, xbs = _hip.bview(x_in)
     gzv, gzbs = _hip.bview(gz)
@@ -138,10 +140,10 @@ def transcoupling_backward(m, x_in, gz, gld):
     ghd = _new(B, C, H, W, like=x)
     _hip.call("cf_coupling_apply_bwd", _hip.p(x), _hip.p(h), _hip.p(gzv), _hip.p(_hip.f32(gld)), _hip.p(gx), _hip.p(ghd),
               B, C, H * W, xbs, gzbs, _hip.stream())
-    grads = {}
+    grads = {} if params else None
     gx0 = vit_backward(m.NN[0], tape, ghd, grads)
     gx[:, :half] += gx0
-    return gx, grads
+    return gx, grads or {}
 
 
 def _relu_mask(act, gy):
@@ -189,7 +191,7 @@ def conv_backward(x_in, conv, gy, grads, need_gx=True):
     return gx
 
 
-def coupling_conv_backward(m, x_in, gz, gld):
+def coupling_conv_backward(m, x_in, gz, gld, params=True):
     """Coupling with a conv conditioner of any shape (coupling.py:39-66; the fused step kernels cover only the image
     shapes): the conditioner is re-run layer by layer with its activations kept, then the chain back."""
     from .coupling import conv2d_reflect
@@ -205,14 +207,14 @@ def coupling_conv_backward(m, x_in, gz, gld):
     gx, gh = _new(B, C, H, W, like=x), _new(B, C, H, W, like=x)
     _hip.call("cf_coupling_apply_bwd", _hip.p(x), _hip.p(h), _hip.p(gzv), _hip.p(_hip.f32(gld)), _hip.p(gx), _hip.p(gh),
               B, C, H * W, xbs, gzbs, _hip.stream())
-    grads = {}
+    grads = {} if params else None
     g2 = _relu_mask(a2, conv_backward(a2, c3, gh, grads))
     g1 = _relu_mask(a1, conv_backward(a1, c2, g2, grads))
     gx[:, :half] += conv_backward(x0, c1, g1, grads)
-    return gx, grads
+    return gx, grads or {}
 
 
-def masked_coupling_backward(m, x_in, gz, gld):
+def masked_coupling_backward(m, x_in, gz, gld, params=True):
     """MaskedCoupling (ar.py:33-57): z = x exp(log_s) + t with [t ; raw] = conv3(relu(conv2(relu(conv1(relu x))))) + [x ; x].
     The weights are masked in place by the forward (masked_conv_2d.py:22), so - as under torch.autograd in the reference -
     the weight gradients are the plain convolution gradients (entries at masked positions are wiped by the next forward)."""
@@ -234,15 +236,15 @@ def masked_coupling_backward(m, x_in, gz, gld):
     gxx, gh = _new(B, 2 * D, H, W, like=x), _new(B, 2 * D, H, W, like=x)
     _hip.call("cf_coupling_apply_bwd", _hip.p(xx), _hip.p(h), _hip.p(gzz), _hip.p(_hip.f32(gld)), _hip.p(gxx), _hip.p(gh),
               B, 2 * D, H * W, 2 * D * H * W, 2 * D * H * W, _hip.stream())
-    grads = {}
+    grads = {} if params else None
     g2 = _relu_mask(a2, conv_backward(a2, nn_.conv3, gh, grads))
     g1 = _relu_mask(a1, conv_backward(a1, nn_.conv2, g2, grads))
     g0 = _relu_mask(x, conv_backward(a0, nn_.conv1, g1, grads))
     gx = gxx[:, D:] + g0 + gh[:, :D] + gh[:, D:]                       # through x * s, the residual block, and + [x ; x]
-    return gx.contiguous(), grads
+    return gx.contiguous(), grads or {}
 
 
-def conv1x1_backward(m, x_in, gz, gld):
+def conv1x1_backward(m, x_in, gz, gld, params=True):
     """Conv1x1 (conv1x1.py:52-57): z = W x per pixel, ldj = H W log|det W|."""
     x = _hip.f32(x_in)
     B, C, H, W = x.shape
@@ -251,6 +253,8 @@ def conv1x1_backward(m, x_in, gz, gld):
     gx = torch.empty_like(gzc)
     _hip.call("cf_conv1x1_fwd", _hip.p(gzc), _hip.p(Wm.t().contiguous()), None, _hip.p(gx), B, C, H * W, C * H * W, C * H * W,
               _hip.stream())
+    if not params:
+        return gx, {}
     lad = _new(1, like=gzc)
     winv = _new(C, C, like=gzc)
     _hip.call("cf_slogdet_inverse", _hip.p(Wm), C, _hip.p(lad), _hip.p(winv), _hip.stream())
@@ -266,13 +270,15 @@ def conv1x1_backward(m, x_in, gz, gld):
     return gx, {m.NN: gW}
 
 
-def actnorm_backward(m, x_in, gz, gld):
+def actnorm_backward(m, x_in, gz, gld, params=True):
     """ActNorm (actnorm.py:53-60): z = (x - t) exp(-logs), ldj = +sum(logs) (reference quirk: no H W factor)."""
     x = _hip.f32(x_in).contiguous()
     B, C, H, W = x.shape
     t, logs = _hip.f32(m.NN_t.detach()), _hip.f32(m.NN_logs.detach())
     gzc = _hip.f32(gz).contiguous()
     st = _hip.stream()
+    if not params:
+        return gzc * torch.exp(-logs).view(1, C, 1, 1), {}
     z = _new(B, C, H, W, like=gzc)
     _hip.call("cf_actnorm", _hip.p(x), _hip.p(t), _hip.p(logs), _hip.p(z), None, B, C, H * W, 0, st)
     sums = _new(2 * C, like=gzc)
@@ -283,7 +289,7 @@ def actnorm_backward(m, x_in, gz, gld):
     return gx, {m.NN_t: -s * sums[:C], m.NN_logs: gld.sum() - sums[C:]}
 
 
-def layer_backward(m, x_in, gz, gld):
+def layer_backward(m, x_in, gz, gld, params=True):
     """Dispatch on the layer type; raises for layers without a hand-written backward."""
     from .actnorm import ActNorm
     from .augment import Augment
@@ -292,15 +298,15 @@ def layer_backward(m, x_in, gz, gld):
     from .coupling import Coupling, TransCoupling
     from .permute_axes import PermuteAxes
     if isinstance(m, TransCoupling):
-        return transcoupling_backward(m, x_in, gz, gld)
+        return transcoupling_backward(m, x_in, gz, gld, params)
     if type(m) is Coupling and not m.context_net:
-        return coupling_conv_backward(m, x_in, gz, gld)
+        return coupling_conv_backward(m, x_in, gz, gld, params)
     if isinstance(m, MaskedCoupling):
-        return masked_coupling_backward(m, x_in, gz, gld)
+        return masked_coupling_backward(m, x_in, gz, gld, params)
     if type(m) is Conv1x1:
-        return conv1x1_backward(m, x_in, gz, gld)
+        return conv1x1_backward(m, x_in, gz, gld, params)
     if type(m) is ActNorm:
-        return actnorm_backward(m, x_in, gz, gld)
+        return actnorm_backward(m, x_in, gz, gld, params)
     if isinstance(m, Augment) and m.split_dim == 1:
         return gz[:, : x_in.shape[1]], {}
     if isinstance(m, PermuteAxes):

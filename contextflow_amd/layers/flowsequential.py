@@ -328,7 +328,7 @@ class FlowSequential(nn.Module):
         _hip.call("cf_flow_step_bwd_prepare_batch", n, A(cols[0]), A(cols[2]), A(cols[3]), A(cols[5]), A(cols[7]), A(wsb), C, H, W, _hip.stream())
         return list(zip(ws, winv, wsb))
 
-    def _tables(self, plan, key, B, dev, main, tape):
+    def _tables(self, plan, key, B, dev, main, tape, data_only=False):
         """The parameter transforms of a fused call: kept from the previous call while the parameters they derive from are
         unchanged (evaluation); otherwise rebuilt on the side stream, overlapping the main stream's kernels.  Returns
         (prepared: plan index -> (buffers, producer's event | None), prior tables, their event | None, fresh: the entries built
@@ -340,9 +340,12 @@ class FlowSequential(nn.Module):
         cache up before it captures, and its graph then holds no prepare launches.  Tables built DURING a capture live in the
         graph's private pool and their events belong to the capture: they must not outlive it as cache entries (a later eager
         call would wait on a captured event and read buffers that only exist after a replay), so a user-side capture with a
-        cold cache simply rebuilds the tables inside its graph."""
+        cold cache simply rebuilds the tables inside its graph.
+        data_only (the input gradient with frozen weights: `score`, a frozen model under autograd): the training form of the
+        step tables - with the backward kernel's fragments - is kept the same way, in slots of its own."""
         prepared, todo, vkey = {}, [], {}
-        cache_ok = tape is None
+        cache_ok = tape is None or data_only
+        slot = lambda k, op: (key, k, vkey.get(k)) + (("train",) if tape is not None and op[0] in ("step", "vstep") else ())
         capturing = torch.cuda.is_current_stream_capturing()
         store_ok = cache_ok and not capturing
         for k, op in enumerate(plan):
@@ -356,7 +359,7 @@ class FlowSequential(nn.Module):
             else:
                 continue
             ver = _derived.key(srcs, dev.index)
-            hit = self._prep.get((key, k, vkey.get(k))) if cache_ok else None
+            hit = self._prep.get(slot(k, op)) if cache_ok else None
             if hit is not None and hit[0] == ver:
                 prepared[k] = (hit[1], None if capturing else hit[2])      # the producer's event stays with the entry: a later call on ANOTHER
             else:                                    # stream is ordered against the side stream that wrote the buffers
@@ -412,7 +415,7 @@ class FlowSequential(nn.Module):
                 prepared[k] = (buf, ev)
                 fresh.add(k)
                 if store_ok:
-                    self._prep[(key, k, vkey.get(k))] = (ver, buf, ev)
+                    self._prep[slot(k, op)] = (ver, buf, ev)
             if prior is None:
                 prior = self.dist.prepared()
                 ev_prior = torch.cuda.Event()
@@ -436,15 +439,17 @@ class FlowSequential(nn.Module):
             for buf in bufs(prior if k == "prior" else prepared[k][0]):
                 buf.record_stream(main)
 
-    def _forward_fused(self, x, context, tape=None, halves=None):
-        """halves, if a list, receives the channel slice every SplitPrior's mixture kernel scores, in forward order (`encode`)."""
+    def _forward_fused(self, x, context, tape=None, halves=None, data_only=False):
+        """halves, if a list, receives the channel slice every SplitPrior's mixture kernel scores, in forward order (`encode`).
+        tape, if a list, receives the records of layers/_tape.py (the taping kernels run); data_only: the tape is for the
+        data-only walk (autograd.input_gradient) - of a conv step it keeps the aux buffer alone, neither planes nor input."""
         B, M, dev = x.shape[0], self.mixtures, x.device
         key = tuple(x.shape[1:])
         plan = self._plans.get(key)
         if plan is None:
             plan = self._plans[key] = self._build_plan(key)
         main = torch.cuda.current_stream(dev)
-        prepared, prior, ev_prior, fresh = self._tables(plan, key, B, dev, main, tape)
+        prepared, prior, ev_prior, fresh = self._tables(plan, key, B, dev, main, tape, data_only)
 
         def chain_run(k, ws, nmax, joins):
             """Plan indices and tables of the run of at most nmax steps that starts at step k (tables ws) and goes on while
@@ -473,14 +478,14 @@ class FlowSequential(nn.Module):
             if k in chained:
                 continue
             if kind == "pre":
-                if tape is not None:
-                    tape.append(_tape.Pre())
                 _, deq, n1, n2, aug = op
                 xin = _hip.f32(x)
                 C, H, W = xin.shape[1:]
                 N = C * H * W
                 ca = aug.aug_size if aug is not None else 0
                 y = torch.empty(B, C + ca, H, W, device=dev, dtype=torch.float32)
+                if tape is not None:
+                    tape.append(_tape.Pre(y, N, n1._s, n2._s))
                 cst = -N * math.log(n1._s) - N * math.log(n2._s)      # normalize.py:42-49, twice
                 ldp = ld1 if k == 0 else torch.empty_like(ld1)         # the kernel assigns its per-sample ldj
                 if (deq.dist.fixed_noise is None and (aug is None or aug.distribution.fixed_noise is None)
@@ -518,7 +523,12 @@ class FlowSequential(nn.Module):
                     # backward uses are bit for bit those of the forward that produced the loss.
                     keep = TAPE_PLANES and 18 * B * C * H * W <= torch.cuda.get_device_properties(dev).total_memory // 64
                     planes = step_tape(B, C, H, W, dev)
-                    tape.append(_tape.Step(conv, act, cpl, (C, H, W), sq, x, ws, winv, planes if keep else None, wsb))
+                    if data_only:
+                        # the y0 / h1 / h2 planes are scratch here (handed back to the allocator behind the launch: the next
+                        # step of the shape gets the same blocks); the walk back reads the aux buffer alone
+                        tape.append(_tape.Step(conv, act, cpl, (C, H, W), sq, wsb=wsb, aux=planes[3]))
+                    else:
+                        tape.append(_tape.Step(conv, act, cpl, (C, H, W), sq, x, ws, winv, planes if keep else None, wsb))
                     x, xbs = _hip.bview(x)
                     z = torch.empty(B, C, H, W, device=dev, dtype=torch.float32)
                     _hip.call("cf_flow_step_fwd_taped", _hip.p(x), _hip.p(z), _hip.p(ld1), _hip.p(ws), _hip.p(planes[0]),
@@ -650,7 +660,9 @@ class FlowSequential(nn.Module):
             if params and not self._fusable() and self._needs_only_init():
                 with torch.no_grad():        # first training call: the ActNorm data-dependent init (actnorm.py:28-35)
                     self._forward_layers(input, context)
-            if params and self._fusable():   # training: same kernels + a tape, hand-written backward (autograd.py)
+            # training: same kernels + a tape, hand-written backward (autograd.py); an input that requires a gradient gets
+            # d logp / d x the same way - also from a frozen or eval() model (the data-only walk)
+            if (params or input.requires_grad) and self._fusable():
                 from .autograd import FlowLogProb
                 return FlowLogProb.apply(self, input, *params)
         with torch.no_grad():
@@ -755,6 +767,42 @@ class FlowSequential(nn.Module):
 
     def log_prob(self, input, context=None):
         return self.forward(input, context)[1]
+
+    def score(self, x, labels=None, weights=None):
+        """(grad, logp): grad = d/dx sum_m w[b, m] logp[b, m], fp32 in the shape of x, and the (B, M) log-densities.
+        weights: the (B, M) tensor w, used as given.  labels: an int or B class indices - one-hot rows (checked as `sample`
+        checks them: ValueError for host values outside [0, M) or a wrong length).  Neither: the score of the marginal,
+        d/dx log sum_m p(x | m), i.e. w = softmax(logp, dim=1) of the returned logp.  Both: ValueError.
+        Always the data-only walk (the kernels of `forward`, a tape of the steps' aux buffers, the data halves of the backward:
+        layers/autograd.input_gradient), whatever the parameters' requires_grad; works under no_grad and touches no .grad
+        and no requires_grad.  Generalist flows on the fused plan only: NotImplementedError otherwise."""
+        _hip.require_device(x)
+        if labels is not None and weights is not None:
+            raise ValueError("score: give labels or weights, not both")
+        self._refresh_generation()
+        if self._has_context_nets():
+            raise NotImplementedError("score of a context-conditioned (specialist) flow")
+        if not self._fusable():
+            raise NotImplementedError("score needs the fused plan: a mixture prior, initialised ActNorms (run one forward first) and fused = True")
+        from .autograd import input_gradient
+        B, M = x.shape[0], self.mixtures
+        xd = x.detach()
+        if labels is not None:
+            lab, m = self.dist._class_labels(labels, B)
+            if lab is None:
+                lab = torch.full((B,), m, device=xd.device, dtype=torch.int64)
+            weights = torch.nn.functional.one_hot(lab.to(torch.int64).clamp(0, M - 1), M).to(torch.float32)
+        elif weights is not None:
+            if tuple(weights.shape) != (B, M):
+                raise ValueError("score: weights of shape %s, (%d, %d) expected" % (tuple(weights.shape), B, M))
+            weights = weights.detach().to(device=xd.device)
+        with torch.no_grad():
+            tape = []
+            _, logp = self._forward_fused(xd, None, tape=tape, data_only=True)
+            if weights is None:
+                weights = torch.softmax(logp, dim=1)
+            grad = input_gradient(tape, weights).reshape(x.shape)
+        return grad, logp
 
     def capture(self, example_input):
         """Capture the fused forward for inputs of this exact shape into a HIP graph; returns a callable

@@ -73,6 +73,12 @@ int cf_preprocess_fwd(const float* x, const float* u, float* y, float* ldj, int 
 int cf_preprocess_rng_fwd(const float* x, float* y, float* ldj, uint64_t* rng_state, uint64_t seed, int B, int N,
                           int aug_n, int64_t y_bstride, float t1, float s1, float t2, float s2, float ldj_const,
                           int advance, cf_stream_t stream);
+/* backward of cf_preprocess_fwd / cf_preprocess_rng_fwd from the forward OUTPUT y alone (the noise is neither redrawn nor
+ * stored): gx[b,i] = (gy[b,i] (2 + e^y + e^-y) + gld[b] (e^y - e^-y)) / (s1 s2) for the first N elements of every row; y rows have
+ * stride y_bstride, gy rows gy_bstride (the Augment channels behind the N elements get no gradient), gx is dense (B, N);
+ * gld (B) = dL / d ldj.                                                                               */
+int cf_preprocess_bwd(const float* y, const float* gy, const float* gld, float* gx, int B, int N, int64_t y_bstride,
+                      int64_t gy_bstride, float s1, float s2, cf_stream_t stream);
 /* out[b] = 0.5*sum(eps^2) + 0.5*N*log(2 pi)  = -log N(eps;0,I)  Augment ldj (augment.py:14-18,
  * distributions/gaussian.py:50-54); eps rows have stride eps_bstride.                              */
 int cf_std_normal_nll(const float* eps, float* out, int B, int N, int64_t eps_bstride, cf_stream_t stream);
@@ -329,6 +335,10 @@ int cf_flow_step_fwd_ctx_taped(const float* x, float* z, float* ldj_acc, const v
 int cf_flow_step_bwd_taped(const float* gz, const float* gld, const void* wsb, const void* t_aux, float* gx, float* s_gh,
                            float* s_gh2, float* s_gh1, float* s_gy, int B, int C, int H, int W, int gx_unsqueezed,
                            cf_stream_t stream);
+/* cf_flow_step_bwd_taped without its four weight-gradient operand planes (the input gradient of log p(x) with frozen
+ * weights): the same kernels and dispatch with those stores compiled out, gx bitwise equal; per sample 6 C HW floats less. */
+int cf_flow_step_bwd_data(const float* gz, const float* gld, const void* wsb, const void* t_aux, float* gx, int B, int C, int H,
+                          int W, int gx_unsqueezed, cf_stream_t stream);
 
 /* Conv1x1 / ActNorm parameter gradients of a fused step from the gradients of its folded matrix / bias (gWp (C,C) and
  * gbp (C) = the wgrad of the g_y plane against the step input): gNN = diag(s) gWp + G H W Wm^-T, gt = -s gbp,
