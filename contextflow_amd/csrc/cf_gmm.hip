@@ -266,51 +266,6 @@ __global__ __launch_bounds__(256, 2) void k_gmm_logprob_levels(GmmLevels L, floa
                                       MKtot, K, L.D[l], dlo, min(L.D[l], dlo + L.dsplit[l]), L.xbs[l], 0, Mtot);
 }
 
-// one thread per (b, component) as in k_gmm_finish; out[b, m] = (ldM[b, m] +) sum_levels logsumexp_k(...) (+ ld1[b])
-__global__ __launch_bounds__(256) void k_gmm_finish_levels(const float* __restrict__ q, GmmLevels L,
-                                                           const float* __restrict__ ldM, const float* __restrict__ ld1,
-                                                           float* __restrict__ out, int B, int M, int K) {
-    __shared__ float l[256];
-    const int MK = M * K, spb = blockDim.x / MK;
-    const int sl = threadIdx.x / MK, mk = threadIdx.x - sl * MK;
-    const int b = blockIdx.x * spb + sl;
-    const bool live = b < B && sl < spb;
-    const bool head = live && mk % K == 0;
-    const int64_t e = (int64_t)b * M + mk / K;
-    float r = 0.f;
-    bool first = true;
-    if (head && ldM) { r = ldM[e]; first = false; }
-    for (int lev = 0; lev < L.n; ++lev) {
-        float s = 0.f;
-        if (live) {
-            const float* qp = q + (int64_t)b * MK + mk;
-            const int64_t zs = (int64_t)B * MK;
-            int z = L.z0[lev];
-            const int zend = L.z0[lev + 1];
-            for (; z + 8 <= zend; z += 8) {
-                float v[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = qp[(z + j) * zs];
-                s += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-            }
-            for (; z < zend; ++z) s += qp[z * zs];
-        }
-        __syncthreads();
-        l[threadIdx.x] = live ? L.cst[lev][mk] - 0.5f * s : 0.f;
-        __syncthreads();
-        if (head) {
-            const float* lp = l + threadIdx.x;
-            float mx = -INFINITY;
-            for (int k = 0; k < K; ++k) mx = fmaxf(mx, lp[k]);
-            float sum = 0.f;
-            for (int k = 0; k < K; ++k) sum += expf(lp[k] - mx);
-            const float v = mx + logf(sum);
-            r = first ? v : r + v;
-            first = false;
-        }
-    }
-    if (head) out[e] = ld1 ? r + ld1[b] : r;
-}
 
 // Context-shifted mixtures whose shifts are embedding lookups (model.py:157,162: CatEmbeddings + EyeSampling): a sample's
 // mixture is one of Um x Us parameter sets - means mu + cm[km], scales softplus(sG + cs[ks]) - chosen by its context.
@@ -332,162 +287,154 @@ __global__ __launch_bounds__(256, 2) void k_gmm_logprob_keyed(const float* __res
                                             xbs, 0, Mtot, order + tl.z, tl.w);
 }
 
-// k_gmm_finish with the constant row chosen by the sample's scale key
-__global__ __launch_bounds__(256) void k_gmm_finish_keyed(const float* __restrict__ q, const float* __restrict__ cst_tab,
-                                                          const int* __restrict__ key, float* __restrict__ out, int B, int M,
-                                                          int K, int nsplit, int accumulate) {
-    __shared__ float l[256];
-    const int MK = M * K, spb = blockDim.x / MK;
+// ---- finishing kernels of the D-split form: sum the partials over the d-slices, then the logsumexp over the K components of
+// every (sample, mixture).  Three pieces, shared by all six kernels (five sources).
+// One thread per (b, component): the partial sums of one sample are read as runs of MK consecutive floats; the K log-joints
+// of a mixture meet in LDS.  A block holds SPB = blockDim / MK whole samples (small batches are latency-bound: the
+// one-thread-per-(b, m) form with its 2 K nsplit strided loads per thread took longer than the main kernel).
+struct GmmSlot {
+    int mk, b;
+    bool live;
+};
+__device__ __forceinline__ GmmSlot gmm_slot(int B, int MK) {
+    const int spb = blockDim.x / MK;
     const int sl = threadIdx.x / MK, mk = threadIdx.x - sl * MK;
     const int b = blockIdx.x * spb + sl;
-    const bool live = b < B && sl < spb;
-    float s = 0.f;
-    if (live) {
-        const float* qp = q + (int64_t)b * MK + mk;
-        const int64_t zs = (int64_t)B * MK;
-        for (int z = 0; z < nsplit; ++z) s += qp[z * zs];
-    }
-    l[threadIdx.x] = live ? cst_tab[(int64_t)key[b] * MK + mk] - 0.5f * s : 0.f;
-    __syncthreads();
-    if (live && mk % K == 0) {
-        const float* lp = l + threadIdx.x;
-        float mx = -INFINITY;
-        for (int k = 0; k < K; ++k) mx = fmaxf(mx, lp[k]);
-        float sum = 0.f;
-        for (int k = 0; k < K; ++k) sum += expf(lp[k] - mx);
-        const float r = mx + logf(sum);
-        const int64_t e = (int64_t)b * M + mk / K;
-        out[e] = accumulate ? out[e] + r : r;
-    }
+    return GmmSlot{mk, b, b < B && sl < spb};
 }
 
-// finishing kernel for the D-split form: sum partials, logsumexp.  One thread per (b, component): the partial sums of
-// one sample are read as runs of MK consecutive floats; the K log-joints of a mixture meet in LDS.  A block holds
-// SPB = blockDim / MK whole samples (small batches are latency-bound: the one-thread-per-(b, m) form with its
-// 2 K nsplit strided loads per thread took longer than the main kernel).
-__global__ __launch_bounds__(256) void k_gmm_finish(const float* __restrict__ q, const float* __restrict__ cst,
-                                                    float* __restrict__ out, int B, int M, int K, int nsplit,
-                                                    int accumulate) {
-    __shared__ float l[256];
-    const int MK = M * K, spb = blockDim.x / MK;
-    const int sl = threadIdx.x / MK, mk = threadIdx.x - sl * MK;
-    const int b = blockIdx.x * spb + sl;
-    const bool live = b < B && sl < spb;
+// sum over the d-slices [z0, z1) of one (b, component): qp = its partial in slice 0, the slices lie zs = B MK floats apart.
+// TREE: 8 independent loads in flight (the partials sit 4 B MK bytes apart), summed as a tree, then a serial tail; otherwise
+// serial throughout.  The two forms round differently from 8 slices on, and each kernel keeps the one it was written with -
+// tree: k_gmm_finish<true>, k_gmm_finish_levels, k_gmm_resp_finish_mk; serial: k_gmm_finish<false> (the keyed form) and the two
+// kernels for more than 256 components - because the bits of every entry point are pinned (GMM_SHA in tests/test_gpu_parity.py).  Moving a kernel to
+// the other form is a change of results (and, for the serial ones, of speed), not a clean-up.
+template <bool TREE>
+__device__ __forceinline__ float gmm_partial_sum(const float* __restrict__ qp, int64_t zs, int z0, int z1) {
     float s = 0.f;
-    if (live) {
-        const float* qp = q + (int64_t)b * MK + mk;
-        const int64_t zs = (int64_t)B * MK;
-        int z = 0;
-        for (; z + 8 <= nsplit; z += 8) {              // 8 independent loads in flight (the partials sit 4 B MK bytes apart)
+    int z = z0;
+    if (TREE) {
+        for (; z + 8 <= z1; z += 8) {
             float v[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = qp[(z + j) * zs];
             s += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
         }
-        for (; z < nsplit; ++z) s += qp[z * zs];
     }
-    l[threadIdx.x] = live ? cst[mk] - 0.5f * s : 0.f;
+    for (; z < z1; ++z) s += qp[z * zs];
+    return s;
+}
+
+// logsumexp over K consecutive log-joints, as its two parts: the forward finishes take mx + logf(sum), the responsibility
+// finishes expf(lj - mx) * (g / sum)
+__device__ __forceinline__ void gmm_lse(const float* lp, int K, float& mx, float& sum) {
+    mx = -INFINITY;
+    for (int k = 0; k < K; ++k) mx = fmaxf(mx, lp[k]);
+    sum = 0.f;
+    for (int k = 0; k < K; ++k) sum += expf(lp[k] - mx);
+}
+
+// out[b, m] (+)= logsumexp_k(cst[mk] - 1/2 sum of the partials); key != nullptr: the constant row is chosen by the sample's
+// scale key (cf_gmm_logprob_keyed).  TREE = true for cf_gmm_logprob, false for the keyed form (gmm_partial_sum).  One source,
+// two kernels: the null test costs nothing measurable (profiles/gmm_plan_ab.txt); sending cf_gmm_logprob through
+// k_gmm_finish_levels with one level does - 0.6 us per call at a batch of 256 - so that kernel stays on its own.
+template <bool TREE>
+__global__ __launch_bounds__(256) void k_gmm_finish(const float* __restrict__ q, const float* __restrict__ cst_tab,
+                                                    const int* __restrict__ key, float* __restrict__ out, int B, int M, int K,
+                                                    int nsplit, int accumulate) {
+    __shared__ float l[256];
+    const int MK = M * K;
+    const GmmSlot t = gmm_slot(B, MK);
+    l[threadIdx.x] = t.live ? cst_tab[(key ? (int64_t)key[t.b] * MK : 0) + t.mk] -
+                                  0.5f * gmm_partial_sum<TREE>(q + (int64_t)t.b * MK + t.mk, (int64_t)B * MK, 0, nsplit)
+                            : 0.f;
     __syncthreads();
-    if (live && mk % K == 0) {
-        const float* lp = l + threadIdx.x;
-        float mx = -INFINITY;
-        for (int k = 0; k < K; ++k) mx = fmaxf(mx, lp[k]);
-        float sum = 0.f;
-        for (int k = 0; k < K; ++k) sum += expf(lp[k] - mx);
+    if (t.live && t.mk % K == 0) {
+        float mx, sum;
+        gmm_lse(l + threadIdx.x, K, mx, sum);
         const float r = mx + logf(sum);
-        const int64_t e = (int64_t)b * M + mk / K;
+        const int64_t e = (int64_t)t.b * M + t.mk / K;
         out[e] = accumulate ? out[e] + r : r;
     }
 }
 
-// same for mixtures with more than 256 components in all: one thread per (b, m)
+// all levels of cf_gmm_logprob_levels: out[b, m] = (ldM[b, m] +) sum_levels logsumexp_k(...) (+ ld1[b])
+__global__ __launch_bounds__(256) void k_gmm_finish_levels(const float* __restrict__ q, GmmLevels L,
+                                                           const float* __restrict__ ldM, const float* __restrict__ ld1,
+                                                           float* __restrict__ out, int B, int M, int K) {
+    __shared__ float l[256];
+    const int MK = M * K;
+    const GmmSlot t = gmm_slot(B, MK);
+    const bool head = t.live && t.mk % K == 0;
+    const int64_t e = (int64_t)t.b * M + t.mk / K;
+    float r = 0.f;
+    bool first = true;
+    if (head && ldM) { r = ldM[e]; first = false; }
+    for (int lev = 0; lev < L.n; ++lev) {
+        const float s = t.live ? gmm_partial_sum<true>(q + (int64_t)t.b * MK + t.mk, (int64_t)B * MK, L.z0[lev], L.z0[lev + 1]) : 0.f;
+        __syncthreads();
+        l[threadIdx.x] = t.live ? L.cst[lev][t.mk] - 0.5f * s : 0.f;
+        __syncthreads();
+        if (head) {
+            float mx, sum;
+            gmm_lse(l + threadIdx.x, K, mx, sum);
+            const float v = mx + logf(sum);
+            r = first ? v : r + v;
+            first = false;
+        }
+    }
+    if (head) out[e] = ld1 ? r + ld1[t.b] : r;
+}
+
+// finishing kernel of the backward: r[b, mk] = softmax_k(cst - q/2)[mk] * g[b, m] (responsibilities times the upstream
+// gradient).  One thread per (b, m, k) as in k_gmm_finish - the partial sums are nsplit loads per thread, 8 in flight, instead
+// of K nsplit serial ones (small batches: 53 -> 8 us at B = 256); every thread normalises its own component.
+__global__ __launch_bounds__(256) void k_gmm_resp_finish_mk(const float* __restrict__ q, const float* __restrict__ cst,
+                                                            const float* __restrict__ g, float* __restrict__ r, int B, int M,
+                                                            int K, int nsplit) {
+    __shared__ float l[256];
+    const int MK = M * K;
+    const GmmSlot t = gmm_slot(B, MK);
+    const float lj = t.live ? cst[t.mk] - 0.5f * gmm_partial_sum<true>(q + (int64_t)t.b * MK + t.mk, (int64_t)B * MK, 0, nsplit) : 0.f;
+    l[threadIdx.x] = lj;
+    __syncthreads();
+    if (t.live) {
+        const int m = t.mk / K;
+        float mx, sum;
+        gmm_lse(l + threadIdx.x - (t.mk - m * K), K, mx, sum);
+        r[(int64_t)t.b * MK + t.mk] = expf(lj - mx) * (g[(int64_t)t.b * M + m] / sum);
+    }
+}
+
+// mixtures with more than 256 components in all: one thread per (b, m), its K log-joints in registers (K <= 16)
+__device__ __forceinline__ void gmm_logjoints_bm(const float* __restrict__ q, const float* __restrict__ cst, float (&lj)[16],
+                                                 int64_t b, int m, int B, int MK, int K, int nsplit) {
+    for (int k = 0; k < K; ++k)
+        lj[k] = cst[m * K + k] - 0.5f * gmm_partial_sum<false>(q + b * MK + m * K + k, (int64_t)B * MK, 0, nsplit);
+}
+
 __global__ __launch_bounds__(256) void k_gmm_finish_bm(const float* __restrict__ q, const float* __restrict__ cst,
                                                        float* __restrict__ out, int B, int M, int K, int nsplit,
                                                        int accumulate) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= (int64_t)B * M) return;
-    const int b = (int)(e / M), m = (int)(e - (int64_t)b * M);
-    const int MK = M * K;
-    float lj[16];
-    float mx = -INFINITY;
-    for (int k = 0; k < K; ++k) {
-        float s = 0.f;
-        for (int z = 0; z < nsplit; ++z) s += q[((int64_t)z * B + b) * MK + m * K + k];
-        lj[k] = cst[m * K + k] - 0.5f * s;
-        mx = fmaxf(mx, lj[k]);
-    }
-    float sum = 0.f;
-    for (int k = 0; k < K; ++k) sum += expf(lj[k] - mx);
+    float lj[16], mx, sum;
+    gmm_logjoints_bm(q, cst, lj, e / M, (int)(e % M), B, M * K, K, nsplit);
+    gmm_lse(lj, K, mx, sum);
     const float r = mx + logf(sum);
     out[e] = accumulate ? out[e] + r : r;
 }
 
-// finishing kernel of the backward: sum the D-split partials, r[b, mk] = softmax_k(cst - q/2)[mk] * g[b, m]
-// (responsibilities times the upstream gradient).  One thread per (b, m, k) as in k_gmm_finish - the partial sums are
-// nsplit loads per thread, 8 in flight, instead of K nsplit serial ones (small batches: 53 -> 8 us at B = 256); the K
-// log-joints of a mixture meet in LDS and every thread normalises its own component.
-__global__ __launch_bounds__(256) void k_gmm_resp_finish_mk(const float* __restrict__ q, const float* __restrict__ cst,
-                                                            const float* __restrict__ g, float* __restrict__ r, int B, int M,
-                                                            int K, int nsplit) {
-    __shared__ float l[256];
-    const int MK = M * K, spb = blockDim.x / MK;
-    const int sl = threadIdx.x / MK, mk = threadIdx.x - sl * MK;
-    const int b = blockIdx.x * spb + sl;
-    const bool live = b < B && sl < spb;
-    float s = 0.f;
-    if (live) {
-        const float* qp = q + (int64_t)b * MK + mk;
-        const int64_t zs = (int64_t)B * MK;
-        int z = 0;
-        for (; z + 8 <= nsplit; z += 8) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = qp[(z + j) * zs];
-            s += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-        }
-        for (; z < nsplit; ++z) s += qp[z * zs];
-    }
-    const float lj = live ? cst[mk] - 0.5f * s : 0.f;
-    l[threadIdx.x] = lj;
-    __syncthreads();
-    if (live) {
-        const int m = mk / K;
-        const float* lp = l + threadIdx.x - (mk - m * K);
-        float mx = -INFINITY;
-        for (int k = 0; k < K; ++k) mx = fmaxf(mx, lp[k]);
-        float sum = 0.f;
-        for (int k = 0; k < K; ++k) sum += expf(lp[k] - mx);
-        r[(int64_t)b * MK + mk] = expf(lj - mx) * (g[(int64_t)b * M + m] / sum);
-    }
-}
-
-// same for mixtures with more than 256 components in all: one thread per (b, m)
 __global__ __launch_bounds__(256) void k_gmm_resp_finish(const float* __restrict__ q, const float* __restrict__ cst,
                                                          const float* __restrict__ g, float* __restrict__ r, int B, int M,
                                                          int K, int nsplit) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= (int64_t)B * M) return;
-    const int b = (int)(e / M), m = (int)(e - (int64_t)b * M);
-    const int MK = M * K;
-    float l[16];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        if (k < K) {
-            float s = 0.f;
-            for (int z = 0; z < nsplit; ++z) s += q[((int64_t)z * B + b) * MK + m * K + k];
-            l[k] = cst[m * K + k] - 0.5f * s;
-            mx = fmaxf(mx, l[k]);
-        }
-    }
-    float sum = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < K) { l[k] = expf(l[k] - mx); sum += l[k]; }
+    float lj[16], mx, sum;
+    gmm_logjoints_bm(q, cst, lj, e / M, (int)(e % M), B, M * K, K, nsplit);
+    gmm_lse(lj, K, mx, sum);
     const float sc = g[e] / sum;
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < K) r[(int64_t)b * MK + m * K + k] = l[k] * sc;
+    for (int k = 0; k < K; ++k) r[e * K + k] = expf(lj[k] - mx) * sc;
 }
 
 // ---- elementwise pieces of the mixture backward (autograd.py gmm_backward), one launch each instead of a chain of
@@ -664,7 +611,6 @@ __global__ __launch_bounds__(256) void k_gmm_draw(const float* __restrict__ mG, 
     }
 }
 
-// D-split heuristic: enough workgroups to cover the chip (~2 per CU), chunks stay multiples of DC
 // ---- parameter sums of the mixture backward: S0[mk] = sum_b r[b][mk], S1[mk][d] = sum_b r[b][mk] x[b][d],
 // S2[mk][d] = sum_b r[b][mk] x[b][d]^2 - one (MK x B)(B x D) product with two right-hand sides.  MK = 80 rows are five
 // 16-row tiles of v_mfma_f32_16x16x4_f32 exactly (no padding rows); a WAVE owns 32 columns of d and one slice of the batch:
@@ -784,12 +730,72 @@ void gmm_sums_split(int B, int D, int& nsp, int& spb) {
     nsp = (B + spb - 1) / spb;
 }
 
-int choose_nsplit(int B, int MK, int D) {
-    const int mkb = MK <= 16 ? 16 : 80;
-    const int64_t base = (int64_t)((B + TB - 1) / TB) * ((MK + mkb - 1) / mkb);
+// ---- the launch plan of the register-tiled kernel: the one place that decides the component tile and the D split.  Pure in its
+// arguments; every *_ws_bytes query and every launch reads it, so a query and its launch cannot disagree, and the levels form
+// uses per level literally the plan of the cf_gmm_logprob call it replaces.
+struct GmmPlan {
+    int mkt, mkb;        // components per thread (1 | 5) and per workgroup (16 mkt)
+    int ns, dsplit;      // d-slices launched (blockIdx.z) and their width: a multiple of DC, or D when ns == 1
+    int ns_cap;          // the split count before the slices were rounded to DC (>= ns): what the workspace queries of
+                         // cf_gmm_logprob, cf_gmm_resp and cf_gmm_logprob_keyed have always reported (768 columns: 16 for 12 slices)
+    int64_t ws_bytes(int B, int MK, int slices) const { return (int64_t)slices * B * MK * (int64_t)sizeof(float); }
+};
+
+// tiles: workgroups along the samples (ceil(B / TB), or the tile count of the keyed form).  D-split heuristic: enough workgroups
+// to cover the chip (~2 per CU), slices stay multiples of DC.
+GmmPlan gmm_plan(int tiles, int MK, int D, bool split_allowed) {
+    GmmPlan p;
+    p.mkt = MK <= 16 ? 1 : 5;
+    p.mkb = 16 * p.mkt;
+    const int64_t base = (int64_t)tiles * ((MK + p.mkb - 1) / p.mkb);
     int ns = 1;
-    while (base * ns < 512 && ns < 64 && D / (ns * 2) >= DC) ns *= 2;
-    return ns;
+    while (split_allowed && base * ns < 512 && ns < 64 && D / (ns * 2) >= DC) ns *= 2;
+    p.ns_cap = p.ns = ns;
+    p.dsplit = D;
+    if (ns > 1) {
+        p.dsplit = ((D + ns - 1) / ns + DC - 1) / DC * DC;
+        p.ns = (D + p.dsplit - 1) / p.dsplit;
+    }
+    return p;
+}
+inline int gmm_tiles(int B) { return (B + TB - 1) / TB; }
+
+// 16-byte vector loads are legal: every row of x, a and nm and every slice of it starts on a 16-byte boundary
+bool gmm_vec_ok(const float* x, const float* a, const float* nm, int D, int64_t x_bstride, int dsplit) {
+    return D % 4 == 0 && x_bstride % 4 == 0 && dsplit % 4 == 0 &&
+           ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(nm)) & 15) == 0;
+}
+
+// k_gmm_logprob as the plan says: grid (tiles, component blocks, slices).  SPLIT: partial sums to q [ns][B][MK], else the
+// in-body epilogue writes out.
+struct GmmOperands {
+    const float *x, *a, *nm, *cst;
+    float *out, *q;
+    int B, M, K, D;
+    int64_t x_bstride;
+    int accumulate;
+};
+int gmm_launch(const GmmPlan& p, const GmmOperands& o, bool split, hipStream_t s) {
+    const int MK = o.M * o.K;
+    const bool vec = gmm_vec_ok(o.x, o.a, o.nm, o.D, o.x_bstride, p.dsplit);
+    void (*k)(const float*, const float*, const float*, const float*, float*, float*, int, int, int, int, int, int64_t, int, int) = nullptr;
+    switch (p.mkt * 4 + (vec ? 2 : 0) + (split ? 1 : 0)) {
+        case 1 * 4 + 0: k = k_gmm_logprob<1, false, false>; break;
+        case 1 * 4 + 1: k = k_gmm_logprob<1, false, true>; break;
+        case 1 * 4 + 2: k = k_gmm_logprob<1, true, false>; break;
+        case 1 * 4 + 3: k = k_gmm_logprob<1, true, true>; break;
+        case 5 * 4 + 0: k = k_gmm_logprob<5, false, false>; break;
+        case 5 * 4 + 1: k = k_gmm_logprob<5, false, true>; break;
+        case 5 * 4 + 2: k = k_gmm_logprob<5, true, false>; break;
+        case 5 * 4 + 3: k = k_gmm_logprob<5, true, true>; break;
+    }
+    if (!k) {
+        cf_set_error("cf_gmm: no k_gmm_logprob with %d components per thread", p.mkt);
+        return CF_ERR_UNSUPPORTED;
+    }
+    k<<<dim3(gmm_tiles(o.B), (MK + p.mkb - 1) / p.mkb, p.ns), dim3(256), 0, s>>>(o.x, o.a, o.nm, o.cst, o.out, o.q, o.B, MK, o.K, o.D, p.dsplit,
+                                                                              o.x_bstride, o.accumulate, o.M);
+    return 0;
 }
 
 }  // namespace
@@ -800,26 +806,6 @@ int cf_gmm_prepare(const float* mG, const float* sG, const float* wG, float* a, 
                    int D, cf_stream_t stream) {
     CF_REQUIRE(mG && sG && wG && a && nm && cst && M > 0 && K > 0 && D > 0);
     k_gmm_prepare<<<dim3(M * K), dim3(256), 0, cf_s(stream)>>>(mG, sG, wG, a, nm, cst, K, D);
-    CF_LAUNCH_CHECK();
-    return 0;
-}
-
-// q[b, mk] = sum_d ((x[b,d] + nm[mk,d]) * a[mk,d])^2 — the quadratic forms alone (used by the backward pass to rebuild
-// the component responsibilities)
-int cf_gmm_quad(const float* x, const float* a, const float* nm, float* q, int B, int M, int K, int D, int64_t x_bstride,
-                cf_stream_t stream) {
-    if (B == 0) return 0;                       // empty batch: nothing to do (pointers may be null)
-    CF_REQUIRE(x && a && nm && q && M > 0 && K > 0 && K <= 16 && D > 0 && x_bstride >= D);
-    const int MK = M * K;
-    const bool small = MK <= 16;
-    const bool vec = (D % 4 == 0) && (x_bstride % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) &&
-                     ((reinterpret_cast<uintptr_t>(a) & 15) == 0) && ((reinterpret_cast<uintptr_t>(nm) & 15) == 0);
-    const int mkb = small ? 16 : 80;
-    dim3 grid((B + TB - 1) / TB, (MK + mkb - 1) / mkb, 1);
-#define CF_GO(MKT, V) k_gmm_logprob<MKT, V, true><<<grid, dim3(256), 0, cf_s(stream)>>>(x, a, nm, nullptr, nullptr, q, B, MK, K, D, D, x_bstride, 0, M)
-    if (small) { if (vec) CF_GO(1, true); else CF_GO(1, false); }
-    else       { if (vec) CF_GO(5, true); else CF_GO(5, false); }
-#undef CF_GO
     CF_LAUNCH_CHECK();
     return 0;
 }
@@ -872,43 +858,28 @@ int cf_gmm_draw(const float* mG, const float* sG, const float* cdf, const int32_
 }
 
 int64_t cf_gmm_ws_bytes(int B, int M, int K, int D) {
-    const int ns = choose_nsplit(B, M * K, D);
-    return ns > 1 ? (int64_t)ns * B * M * K * sizeof(float) : 0;
+    const GmmPlan p = gmm_plan(gmm_tiles(B), M * K, D, true);
+    return p.ns_cap > 1 ? p.ws_bytes(B, M * K, p.ns_cap) : 0;
 }
 
 int cf_gmm_logprob(const float* x, const float* a, const float* nm, const float* cst, float* out, void* ws,
                    int B, int M, int K, int D, int64_t x_bstride, int accumulate, cf_stream_t stream) {
     if (B == 0) return 0;                       // empty batch: nothing to do (pointers may be null)
     CF_REQUIRE(x && a && nm && cst && out && B >= 0 && M > 0 && K > 0 && K <= 16 && D > 0 && x_bstride >= D);
-    if (B == 0) return 0;
     const int MK = M * K;
-    const bool small = MK <= 16;
-    CF_REQUIRE(small ? (16 % K == 0 || M == 1) : (80 % K == 0));
-    int ns = ws ? choose_nsplit(B, MK, D) : 1;
-    int dsplit = D;
-    if (ns > 1) { dsplit = ((D + ns - 1) / ns + DC - 1) / DC * DC; ns = (D + dsplit - 1) / dsplit; }
-    const bool vec = (D % 4 == 0) && (x_bstride % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) &&
-                     ((reinterpret_cast<uintptr_t>(a) & 15) == 0) && ((reinterpret_cast<uintptr_t>(nm) & 15) == 0) &&
-                     (dsplit % 4 == 0);
-    const int mkb = small ? 16 : 80;
-    dim3 grid((B + TB - 1) / TB, (MK + mkb - 1) / mkb, ns);
+    CF_REQUIRE(MK <= 16 ? (16 % K == 0 || M == 1) : (80 % K == 0));
+    const GmmPlan p = gmm_plan(gmm_tiles(B), MK, D, ws != nullptr);
     float* q = (float*)ws;
-#define CF_GO(MKT, V, S) k_gmm_logprob<MKT, V, S><<<grid, dim3(256), 0, cf_s(stream)>>>(x, a, nm, cst, out, q, B, MK, K, D, dsplit, x_bstride, accumulate, M)
-    if (ns > 1) {
-        if (small) { if (vec) CF_GO(1, true, true); else CF_GO(1, false, true); }
-        else       { if (vec) CF_GO(5, true, true); else CF_GO(5, false, true); }
+    if (int rc = gmm_launch(p, GmmOperands{x, a, nm, cst, out, q, B, M, K, D, x_bstride, accumulate}, p.ns > 1, cf_s(stream))) return rc;
+    if (p.ns > 1) {
         const int spb = 256 / MK;
         if (spb >= 1) {
-            k_gmm_finish<<<dim3((unsigned)((B + spb - 1) / spb)), dim3(spb * MK), 0, cf_s(stream)>>>(q, cst, out, B, M, K, ns, accumulate);
+            k_gmm_finish<true><<<dim3((unsigned)((B + spb - 1) / spb)), dim3(spb * MK), 0, cf_s(stream)>>>(q, cst, nullptr, out, B, M, K, p.ns, accumulate);
         } else {
             const int64_t n = (int64_t)B * M;
-            k_gmm_finish_bm<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, cf_s(stream)>>>(q, cst, out, B, M, K, ns, accumulate);
+            k_gmm_finish_bm<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, cf_s(stream)>>>(q, cst, out, B, M, K, p.ns, accumulate);
         }
-    } else {
-        if (small) { if (vec) CF_GO(1, true, false); else CF_GO(1, false, false); }
-        else       { if (vec) CF_GO(5, true, false); else CF_GO(5, false, false); }
     }
-#undef CF_GO
     CF_LAUNCH_CHECK();
     return 0;
 }
@@ -917,15 +888,11 @@ int cf_gmm_logprob(const float* x, const float* a, const float* nm, const float*
 // its prepared tables a[l], nm[l] (M*K, D[l]) and cst[l] (M*K).  out[b, m] = (ldM[b, m] +) sum_l log p_l(x_l[b] | m) (+ ld1[b]);
 // ldM and ld1 may be null.  The levels are summed in order, each with the D split cf_gmm_logprob would choose: the result
 // equals the chain of cf_gmm_logprob(..., accumulate) calls + cf_logdet_combine bit for bit.
-// Requires n <= 4, M*K <= 256, D[l] % 4 == 0, x_bstride[l] % 4 == 0, 16-byte aligned x[l] / a[l] / nm[l].
+// Requires n <= 4, M*K <= 256 and vector loads on every level (gmm_vec_ok).
 int64_t cf_gmm_levels_ws_bytes(int n, const int* D, int B, int M, int K) {
     if (n < 1 || n > GMM_MAX_LEVELS || !D) return -1;
     int64_t z = 0;
-    for (int l = 0; l < n; ++l) {
-        int ns = choose_nsplit(B, M * K, D[l]);
-        if (ns > 1) { const int ds = ((D[l] + ns - 1) / ns + DC - 1) / DC * DC; ns = (D[l] + ds - 1) / ds; }
-        z += ns;
-    }
+    for (int l = 0; l < n; ++l) z += gmm_plan(gmm_tiles(B), M * K, D[l], true).ns;
     return z * B * M * K * (int64_t)sizeof(float);
 }
 
@@ -936,28 +903,26 @@ int cf_gmm_logprob_levels(int n, const float* const* x, const float* const* a, c
     CF_REQUIRE(n >= 1 && n <= GMM_MAX_LEVELS && x && a && nm && cst && D && x_bstride && out && ws && B >= 0 && M > 0 &&
                K > 0 && K <= 16 && M * K <= 256);
     const int MK = M * K;
-    const bool small = MK <= 16;
-    CF_REQUIRE(small ? (16 % K == 0 || M == 1) : (80 % K == 0));
+    CF_REQUIRE(MK <= 16 ? (16 % K == 0 || M == 1) : (80 % K == 0));
+    GmmPlan p{};
     GmmLevels L;
     L.n = n;
     int z = 0;
     for (int l = 0; l < GMM_MAX_LEVELS; ++l) {
         const int s = l < n ? l : n - 1;
-        CF_REQUIRE(x[s] && a[s] && nm[s] && cst[s] && D[s] > 0 && D[s] % 4 == 0 && x_bstride[s] >= D[s] && x_bstride[s] % 4 == 0);
-        CF_REQUIRE(((reinterpret_cast<uintptr_t>(x[s]) | reinterpret_cast<uintptr_t>(a[s]) | reinterpret_cast<uintptr_t>(nm[s])) & 15) == 0);
+        CF_REQUIRE(x[s] && a[s] && nm[s] && cst[s] && D[s] > 0 && x_bstride[s] >= D[s]);
+        p = gmm_plan(gmm_tiles(B), MK, D[s], true);
+        CF_REQUIRE(gmm_vec_ok(x[s], a[s], nm[s], D[s], x_bstride[s], p.dsplit));
         L.x[l] = x[s]; L.a[l] = a[s]; L.nm[l] = nm[s]; L.cst[l] = cst[s]; L.xbs[l] = x_bstride[s]; L.D[l] = D[s];
-        int ns = choose_nsplit(B, MK, D[s]), ds = D[s];
-        if (ns > 1) { ds = ((D[s] + ns - 1) / ns + DC - 1) / DC * DC; ns = (D[s] + ds - 1) / ds; }
-        L.dsplit[l] = ds;
+        L.dsplit[l] = p.dsplit;
         L.z0[l] = z;
-        if (l < n) z += ns;
+        if (l < n) z += p.ns;
     }
     L.z0[GMM_MAX_LEVELS] = z;
     for (int l = n; l < GMM_MAX_LEVELS; ++l) L.z0[l] = z;
-    const int mkb = small ? 16 : 80;
-    dim3 grid((B + TB - 1) / TB, (MK + mkb - 1) / mkb, z);
+    dim3 grid(gmm_tiles(B), (MK + p.mkb - 1) / p.mkb, z);
     float* q = (float*)ws;
-    if (small) k_gmm_logprob_levels<1><<<grid, dim3(256), 0, cf_s(stream)>>>(L, q, B, MK, K, M);
+    if (p.mkt == 1) k_gmm_logprob_levels<1><<<grid, dim3(256), 0, cf_s(stream)>>>(L, q, B, MK, K, M);
     else k_gmm_logprob_levels<5><<<grid, dim3(256), 0, cf_s(stream)>>>(L, q, B, MK, K, M);
     const int spb = 256 / MK;
     k_gmm_finish_levels<<<dim3((unsigned)((B + spb - 1) / spb)), dim3(spb * MK), 0, cf_s(stream)>>>(q, L, ldM, ld1, out, B, M, K);
@@ -970,16 +935,11 @@ int cf_gmm_logprob_levels(int n, const float* const* x, const float* const* a, c
 // per mean key, cst_tab (Us, M*K), key_s (B): every sample's scale key.  order (B): the sample indices grouped by
 // (scale key, mean key); tiles (T, 4) int32 rows [ks, km, first position in order, count <= 128 (0 = unused tile)].
 // out[b, m] (+)= logsumexp_k(cst_tab[key_s[b]] - 1/2 sum_d ((x + nm) a)^2).  M*K <= 256 and a multiple of 80 / K as for
-// cf_gmm_logprob with M*K > 16; D % 4 == 0, x_bstride % 4 == 0, 16-byte aligned x and tables.
-static int keyed_nsplit(int T, int MK, int D) {
-    const int64_t base = (int64_t)T * ((MK + 79) / 80);
-    int ns = 1;
-    while (base * ns < 512 && ns < 64 && D / (ns * 2) >= DC) ns *= 2;
-    return ns;
-}
-
+// cf_gmm_logprob with M*K > 16; vector loads (gmm_vec_ok), 16-byte aligned tiles.  The plan is cf_gmm_logprob's with the T tiles
+// in place of ceil(B / 128).
 int64_t cf_gmm_keyed_ws_bytes(int T, int B, int M, int K, int D) {
-    return (int64_t)keyed_nsplit(T, M * K, D) * B * M * K * (int64_t)sizeof(float);
+    const GmmPlan p = gmm_plan(T, M * K, D, true);
+    return p.ws_bytes(B, M * K, p.ns_cap);
 }
 
 int cf_gmm_logprob_keyed(const float* x, const float* a_tab, const float* nm_tab, const float* cst_tab, const int* key_s,
@@ -987,18 +947,16 @@ int cf_gmm_logprob_keyed(const float* x, const float* a_tab, const float* nm_tab
                          int64_t x_bstride, int accumulate, cf_stream_t stream) {
     if (B == 0) return 0;
     CF_REQUIRE(x && a_tab && nm_tab && cst_tab && key_s && tiles && order && out && ws && T > 0 && B > 0 && M > 0 && K > 0 &&
-               K <= 16 && M * K > 16 && M * K <= 256 && 80 % K == 0 && D > 0 && D % 4 == 0 && x_bstride >= D && x_bstride % 4 == 0);
-    CF_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(a_tab) | reinterpret_cast<uintptr_t>(nm_tab) |
-                 reinterpret_cast<uintptr_t>(tiles)) & 15) == 0);
+               K <= 16 && M * K > 16 && M * K <= 256 && 80 % K == 0 && D > 0 && x_bstride >= D);
     const int MK = M * K;
-    int ns = keyed_nsplit(T, MK, D), dsplit = D;
-    if (ns > 1) { dsplit = ((D + ns - 1) / ns + DC - 1) / DC * DC; ns = (D + dsplit - 1) / dsplit; }
+    const GmmPlan p = gmm_plan(T, MK, D, true);                  // (M K > 16: mkt = 5, the one keyed instantiation)
+    CF_REQUIRE(gmm_vec_ok(x, a_tab, nm_tab, D, x_bstride, p.dsplit) && (reinterpret_cast<uintptr_t>(tiles) & 15) == 0);
     float* q = (float*)ws;
-    k_gmm_logprob_keyed<5><<<dim3(T, (MK + 79) / 80, ns), dim3(256), 0, cf_s(stream)>>>(x, a_tab, nm_tab, tiles, order, q, B, MK,
-                                                                                       K, D, dsplit, x_bstride, M);
+    k_gmm_logprob_keyed<5><<<dim3(T, (MK + p.mkb - 1) / p.mkb, p.ns), dim3(256), 0, cf_s(stream)>>>(x, a_tab, nm_tab, tiles, order, q, B,
+                                                                                                   MK, K, D, p.dsplit, x_bstride, M);
     const int spb = 256 / MK;
-    k_gmm_finish_keyed<<<dim3((unsigned)((B + spb - 1) / spb)), dim3(spb * MK), 0, cf_s(stream)>>>(q, cst_tab, key_s, out, B, M, K,
-                                                                                                 ns, accumulate);
+    k_gmm_finish<false><<<dim3((unsigned)((B + spb - 1) / spb)), dim3(spb * MK), 0, cf_s(stream)>>>(q, cst_tab, key_s, out, B, M, K,
+                                                                                                 p.ns, accumulate);
     CF_LAUNCH_CHECK();
     return 0;
 }
@@ -1006,8 +964,8 @@ int cf_gmm_logprob_keyed(const float* x, const float* a_tab, const float* nm_tab
 // backward of the mixture prior, first half: r (B, M*K) = responsibilities x upstream gradient g (B, M), D split over
 // blockIdx.z when the batch alone does not fill the chip.  ws: cf_gmm_resp_ws_bytes(...) bytes.
 int64_t cf_gmm_resp_ws_bytes(int B, int M, int K, int D) {
-    const int ns = choose_nsplit(B, M * K, D);
-    return (int64_t)ns * B * M * K * sizeof(float);
+    const GmmPlan p = gmm_plan(gmm_tiles(B), M * K, D, true);
+    return p.ws_bytes(B, M * K, p.ns_cap);
 }
 
 int cf_gmm_resp(const float* x, const float* a, const float* nm, const float* cst, const float* g, float* r, void* ws, int B,
@@ -1015,26 +973,15 @@ int cf_gmm_resp(const float* x, const float* a, const float* nm, const float* cs
     if (B == 0) return 0;
     CF_REQUIRE(x && a && nm && cst && g && r && ws && M > 0 && K > 0 && K <= 16 && D > 0 && x_bstride >= D);
     const int MK = M * K;
-    const bool small = MK <= 16;
-    int ns = choose_nsplit(B, MK, D);
-    int dsplit = D;
-    if (ns > 1) { dsplit = ((D + ns - 1) / ns + DC - 1) / DC * DC; ns = (D + dsplit - 1) / dsplit; }
-    const bool vec = (D % 4 == 0) && (x_bstride % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) &&
-                     ((reinterpret_cast<uintptr_t>(a) & 15) == 0) && ((reinterpret_cast<uintptr_t>(nm) & 15) == 0) &&
-                     (dsplit % 4 == 0);
-    const int mkb = small ? 16 : 80;
-    dim3 grid((B + TB - 1) / TB, (MK + mkb - 1) / mkb, ns);
+    const GmmPlan p = gmm_plan(gmm_tiles(B), MK, D, true);
     float* q = (float*)ws;
-#define CF_GO(MKT, V) k_gmm_logprob<MKT, V, true><<<grid, dim3(256), 0, cf_s(stream)>>>(x, a, nm, nullptr, nullptr, q, B, MK, K, D, dsplit, x_bstride, 0, M)
-    if (small) { if (vec) CF_GO(1, true); else CF_GO(1, false); }
-    else       { if (vec) CF_GO(5, true); else CF_GO(5, false); }
-#undef CF_GO
+    if (int rc = gmm_launch(p, GmmOperands{x, a, nm, nullptr, nullptr, q, B, M, K, D, x_bstride, 0}, true, cf_s(stream))) return rc;
     if (MK <= 256) {
         const int spb = 256 / MK;
-        k_gmm_resp_finish_mk<<<dim3((unsigned)((B + spb - 1) / spb)), dim3(256), 0, cf_s(stream)>>>(q, cst, g, r, B, M, K, ns);
+        k_gmm_resp_finish_mk<<<dim3((unsigned)((B + spb - 1) / spb)), dim3(256), 0, cf_s(stream)>>>(q, cst, g, r, B, M, K, p.ns);
     } else {
         const int64_t n = (int64_t)B * M;
-        k_gmm_resp_finish<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, cf_s(stream)>>>(q, cst, g, r, B, M, K, ns);
+        k_gmm_resp_finish<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, cf_s(stream)>>>(q, cst, g, r, B, M, K, p.ns);
     }
     CF_LAUNCH_CHECK();
     return 0;

@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CONTEXTFLOW_HIP_LIB: developer override (A/B builds, probe builds of tools/dev); the default is the in-tree library
 LIB_PATH = os.environ.get("CONTEXTFLOW_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "libcontextflow_hip.so")
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 _c_int, _c_i64, _c_f, _c_p = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -73,7 +73,6 @@ SIGNATURES = {
     "cf_gmm_bwd_params_w": (_c_int, [_c_p] * 11 + [_c_int] * 3 + [_c_p]),
     "cf_gmm_resp_ws_bytes": (_c_i64, [_c_int] * 4),
     "cf_gmm_resp": (_c_int, [_c_p] * 7 + [_c_int] * 4 + [_c_i64, _c_p]),
-    "cf_gmm_quad": (_c_int, [_c_p] * 4 + [_c_int] * 4 + [_c_i64, _c_p]),
     "cf_flow_step_bwd_ws_bytes": (_c_i64, [_c_int] * 3),
     "cf_flow_step_bwd_prepare": (_c_int, [_c_p] * 6 + [_c_int] * 3 + [_c_p]),
     "cf_flow_step_macs": (_c_i64, [_c_int] * 5),

@@ -27,8 +27,9 @@ extern "C" {
 #endif
 
 /* Version 13 also covers the entry points added after it that only ADD symbols (cf_adamw_step_batch_dev, cf_grad_norm_partials,
- * cf_grad_norm_batch, cf_grad_scale_batch): no existing signature or behaviour moved, so no caller of version 13 breaks. */
-#define CF_ABI_VERSION 13
+ * cf_grad_norm_batch, cf_grad_scale_batch): no existing signature or behaviour moved, so no caller of version 13 breaks.
+ * Version 14: cf_gmm_quad (no caller; cf_gmm_resp feeds the backward) left the ABI. */
+#define CF_ABI_VERSION 14
 #define CF_ERR_ARG (-1)          /* bad argument (shape, null pointer, unsupported size) */
 #define CF_ERR_UNSUPPORTED (-2)  /* shape not covered by this kernel; caller uses the generic path */
 
@@ -174,10 +175,6 @@ int cf_gmm_logprob_keyed(const float* x, const float* a_tab, const float* nm_tab
                          const int* tiles, const int* order, float* out, void* ws, int T, int B, int M, int K, int D,
                          int64_t x_bstride, int accumulate, cf_stream_t stream);
 
-/* q[b, m*K+k] = sum_d ((x[b,d] + nm)*a)^2 only (B x M*K, dense): the backward pass rebuilds the responsibilities
- * softmax_k(cst - q/2) from it.                                                                        */
-int cf_gmm_quad(const float* x, const float* a, const float* nm, float* q, int B, int M, int K, int D,
-                int64_t x_bstride, cf_stream_t stream);
 /* backward, first half in one call: r (B, M*K) = softmax_k(cst - q/2) * g[b, m] - the component responsibilities times the
  * upstream gradient g (B, M); the reduction over D is split over workgroups when B alone does not fill the chip.
  * ws: cf_gmm_resp_ws_bytes(...) bytes.                                                                          */

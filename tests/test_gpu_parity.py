@@ -174,6 +174,7 @@ def test_gmm_levels_entry_equals_the_chain_of_calls(L, B, with_ldM):
     want = torch.empty(B, M, device=DEV)
     _hip.call("cf_logdet_combine", _hip.p(ldM), _hip.p(ld1), _hip.p(want), B, M, _hip.stream())
     assert torch.equal(got, want)
+    _gmm_bits("levels", (B, with_ldM), [got])
     tot = sum(ref) + ld1.cpu()[:, None] + (ldM0.cpu() if with_ldM else 0)
     close(got, tot, tol=3e-6)
     assert not gmm_levels_ok([(levels[0][0][:, 1:], levels[0][1])])          # misaligned / wrong width: refused, not copied
@@ -224,6 +225,198 @@ def test_keyed_mixture_kernel_against_the_formula_and_the_per_sample_kernel(L, B
     with torch.no_grad():
         got2 = dist.log_prob(x.flip(0).contiguous(), context2)
     assert torch.equal(got2, got.flip(0)) or (got2 - got.flip(0)).abs().max().item() < 2e-6 * scale
+
+
+# ---- bits of the mixture entry points ---------------------------------------------------------------------------------------
+# sha256 over the output bytes, recorded on an MI355X from the library as it was BEFORE cf_gmm.hip got its one launch plan and its
+# shared finishing pieces (commit bbf7a47; two processes, equal digests: profiles/gmm_plan_parity.txt).  The inputs come from
+# seeded CPU generators and every sum in these kernels has a fixed order, so the digests hold from run to run.
+GMM_SHA = {
+    "logprob": {
+        (10, 8, 768, 70, 1536): "77934101c51abbd204c34251d8e4c4aaf6664a40fb134fba2363429dce2f24f5",
+        (10, 8, 1536, 1, 1536): "7c88875179c50c45f862861794034169f077607367a29de9388f7476e2925032",
+        (10, 8, 100, 300, 100): "bded5adbbfe0feb3d34194c64a15c43caee903c03aaad241ed076da0c7fa8506",
+        (10, 8, 99, 131, 99): "15817742310d377904170dc53681d87160d84c797a53de24a1cae8c380eb38d2",
+        (10, 8, 48, 257, 48): "0db8de9c4d6d5bd4099a542431dffd6d3427ec0c3df0b651e6929120cab6dbbb",
+        (2, 8, 768, 70, 768): "99c08f5f577aeb724657e02eb8491b8677e6b1d3c52eb5101b226eb8f078f7f3",
+        (1, 5, 64, 5, 64): "5c6f315e706b575a1e3bed0db94aae60c450c85fa8ccc8368a5ba277a027ba78",
+        (5, 8, 768, 70, 768): "c836f5f4af851522593b785d7d513e90b4c9a1340e63b27f6789326552f96180",
+        (33, 8, 256, 40, 256): "7e63de3ca7f5d9ad597469255e9d7f41d256fc686db257276587b6e4bd68507d",
+    },
+    "accumulate": {
+        (10, 8, 768, 70, 1536): "995cea89ed0ef89e0a45bfed5275229460d0594d363b5650e1dd44cf730fa34f",
+    },
+    "single": {
+        (10, 8, 768, 70, 1536): "d71f533187992e98fe9f991d8ee0b30596382050246b45c5e67c6642d9779b1b",
+    },
+    "resp": {
+        (10, 8, 768, 70, 1536): "4f65b8d911cfe20700270b102ca8397a5359ae8d7153b81f98fd4c72f78926e6",
+        (10, 8, 1536, 1, 1536): "81fc844ac62b1e2b2cd3b39b1d277971dde074b333a5f3084f143bfa7b99609d",
+        (10, 8, 100, 300, 100): "b2fc3621175050f00fc329949f548ce8215838b9213c0a45014d3eed2d3a62d9",
+        (10, 8, 99, 131, 99): "3c52e911c188bc996680dc9a587912461be7226f8ac1159f6fc8e3f0c2203099",
+        (10, 8, 48, 257, 48): "12e17e28685b1a4575644afb3e10122904fb675ca624e48e70c0f16cb9e7b755",
+        (2, 8, 768, 70, 768): "6e3ed5d687c03f941370279b54c05b3df8d072250ab4238b290d599a2137979d",
+        (1, 5, 64, 5, 64): "f7b6a358e9b5873d952f4840603ea63ac7c11f8890261c54690d7d350e5bf173",
+        (5, 8, 768, 70, 768): "c04acf449d22fa0bc1dd2fcc03f871cb4302d8b18f9fbb303a7f68957787fa85",
+        (33, 8, 256, 40, 256): "15eac2d5e39e0606cb6a4b6b7410c5b78286ce09fbc4ad361c584bbd26db54c9",
+    },
+    "levels": {
+        (1, False): "8ceb26d274eb67637034070f6bd3d754c5fbfc091f0286a7ded9e158188c2c6b",
+        (70, True): "951d56c77db4c33db934c7e90a3a102d930314698671c0da44aa62c65aad1052",
+        (256, False): "d44d040acb7c962025c6649377a70497980e3dd205ca37f246aafdaa4ae407f9",
+        (1000, True): "81b1c9a16c112388025ef75f812c748929fe2997fbf5cb23fbf38c293fe2cfce",
+    },
+    "keyed": {
+        (300, 0): "e9e9d963b011d3b1ed8da6cac7dbf19a5de3b76113c819dbfeceb23c5aeb0353",
+        (300, 1): "54977e558b5d52a5ed19e5373339c5192c6d152739ce5c65f4328b673e6af415",
+    },
+}
+
+
+def _gmm_bits(test, key, tensors):
+    import hashlib
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(t.detach().cpu().contiguous().numpy().tobytes())
+    print("GMM_SHA %s %r %s" % (test, key, h.hexdigest()))
+    assert GMM_SHA[test].get(key) == h.hexdigest(), (test, key, h.hexdigest())
+
+
+# (M, K, D, B, row stride of x, d-slices launched): the smallest shapes that reach each branch of gmm_plan / gmm_launch and each
+# finishing kernel.  768 columns off a channel slice in 12 slices (a tree group of 8 + a tail of 4); 24 slices for one sample;
+# a ragged last chunk (second slice 36 wide); D % 4 != 0 (scalar loads); D < 64: no split, the in-body epilogue with a ragged
+# sample tile; M K = 16 (one component per thread); M = 1 with 16 % K != 0; M K = 40: a ragged component block, 240-thread finish
+# blocks; M K = 264 > 256: four component blocks, the last ragged, and the one-thread-per-(b, m) finishing kernels.
+GMM_CASES = [(10, 8, 768, 70, 1536, 12), (10, 8, 1536, 1, 1536, 24), (10, 8, 100, 300, 100, 2), (10, 8, 99, 131, 99, 2),
+             (10, 8, 48, 257, 48, 1), (2, 8, 768, 70, 768, 12), (1, 5, 64, 5, 64, 2), (5, 8, 768, 70, 768, 12),
+             (33, 8, 256, 40, 256, 8)]
+GMM_IDS = ["-".join(map(str, c[:5])) for c in GMM_CASES]
+_gmm_case_cache = {}
+
+
+def _gmm_case(case):
+    """Seeded CPU inputs of a GMM_CASES entry, its prepared tables on the device and the oracle's log-probabilities (computed
+    once, shared by the tests below, never written to)."""
+    from contextflow_amd.layers.distributions.gaussian import gmm_prepare
+    if case not in _gmm_case_cache:
+        M, K, D, B, stride, _ = case
+        g = torch.Generator().manual_seed(1000 * D + B)
+        mG, sG, wG = torch.randn(M, K, D, generator=g), 1 + 0.2 * torch.randn(M, K, D, generator=g), torch.randn(M, K, generator=g)
+        xw = torch.randn(B, stride, generator=g)
+        out0, gup = torch.randn(B, M, generator=g), torch.randn(B, M, generator=g)
+        x = xw.to(DEV)[:, stride - D:]                                        # a channel slice where stride > D
+        ref = fo.gmm_logprob(xw[:, stride - D:], mG, sG, wG)
+        _gmm_case_cache[case] = (x, gmm_prepare(mG.to(DEV), sG.to(DEV), wG.to(DEV)), out0, gup, ref)
+    return _gmm_case_cache[case]
+
+
+def _gmm_slices_launched(case):
+    """The slice count of the case as the library reports it: cf_gmm_levels_ws_bytes of the one level is the launched count x B M K
+    floats (the plan of the cf_gmm_logprob call, literally); cf_gmm_ws_bytes and cf_gmm_resp_ws_bytes cover it (they report the
+    count before the slices were rounded to 32 columns) and the former is 0 without a split."""
+    from contextflow_amd.layers import _hip
+    M, K, D, B, _, ns = case
+    lib, per = _hip.lib(), B * M * K * 4
+    assert lib.cf_gmm_levels_ws_bytes(1, (ctypes.c_int * 1)(D), B, M, K) == ns * per, case
+    nb, nr = lib.cf_gmm_ws_bytes(B, M, K, D), lib.cf_gmm_resp_ws_bytes(B, M, K, D)
+    assert (nb == 0 if ns == 1 else nb >= ns * per) and nr >= ns * per and nr == max(nb, per), case
+    return nb, nr
+
+
+@pytest.mark.parametrize("case", GMM_CASES, ids=GMM_IDS)
+def test_gmm_logprob_bits_and_oracle(L, case):
+    """cf_gmm_logprob at every branch of its plan: the recorded bits, and the oracle at 2e-6 (a wrong recording cannot hide a wrong
+    kernel).  The first case also accumulating onto a seeded out and, without a workspace, through the single-pass epilogue."""
+    from contextflow_amd.layers import _hip
+    M, K, D, B, stride, ns = case
+    x, (a, nm, cst, _, _, _), out0, _, ref = _gmm_case(case)
+    nbytes, _ = _gmm_slices_launched(case)
+    ws = torch.empty(nbytes, device=DEV, dtype=torch.uint8) if nbytes else None
+
+    def run(out, ws, accumulate):
+        _hip.call("cf_gmm_logprob", _hip.p(x), _hip.p(a), _hip.p(nm), _hip.p(cst), _hip.p(out), _hip.p(ws), B, M, K, D, stride,
+                  accumulate, _hip.stream())
+        return out
+    out = run(torch.empty(B, M, device=DEV), ws, 0)
+    _gmm_bits("logprob", case[:5], [out])
+    close(out, ref, tol=2e-6)
+    if case == GMM_CASES[0]:
+        acc = run(out0.to(DEV), ws, 1)
+        _gmm_bits("accumulate", case[:5], [acc])
+        close(acc, out0 + ref, tol=2e-6)
+        single = run(torch.empty(B, M, device=DEV), None, 0)
+        _gmm_bits("single", case[:5], [single])
+        close(single, ref, tol=2e-6)
+
+
+@pytest.mark.parametrize("case", GMM_CASES, ids=GMM_IDS)
+def test_gmm_resp_bits(L, case):
+    """cf_gmm_resp (responsibilities x upstream gradient) on the same shapes: the recorded bits; the responsibilities of a mixture
+    sum to one (K roundings of a value <= 1: 1e-5 of the gradient's scale)."""
+    from contextflow_amd.layers import _hip
+    M, K, D, B, stride, ns = case
+    x, (a, nm, cst, _, _, _), _, gup, _ = _gmm_case(case)
+    _, nbytes = _gmm_slices_launched(case)
+    ws = torch.empty(nbytes, device=DEV, dtype=torch.uint8)
+    g = gup.to(DEV)
+    r = torch.empty(B, M * K, device=DEV)
+    _hip.call("cf_gmm_resp", _hip.p(x), _hip.p(a), _hip.p(nm), _hip.p(cst), _hip.p(g), _hip.p(r), _hip.p(ws), B, M, K, D, stride,
+              _hip.stream())
+    _gmm_bits("resp", case[:5], [r])
+    close(r.view(B, M, K).sum(-1), gup, tol=1e-5)
+
+
+def test_gmm_keyed_entry_with_host_built_tiles(L):
+    """cf_gmm_logprob_keyed called directly: two scale keys x three mean keys (one pair without samples), seven tiles - two of one
+    bucket (128 + 22 samples), one unused - over 768 columns, i.e. 12 slices: a serial sum of more than eight partials in
+    the keyed finishing kernel, where the tree form would round differently.  Against gaussian.py:142-158 in fp64; the recorded bits."""
+    from contextflow_amd.layers.distributions.gaussian import gmm_prepare
+    from contextflow_amd.layers import _hip
+    M, K, D, B, Us, Um = 10, 8, 768, 300, 2, 3
+    MK = M * K
+    g = torch.Generator().manual_seed(768300)
+    mG, sG, wG = torch.randn(M, K, D, generator=g), 1 + 0.2 * torch.randn(M, K, D, generator=g), torch.randn(M, K, generator=g)
+    cs, cm = 0.3 * torch.randn(Us, M, K, D, generator=g), 0.3 * torch.randn(Um, M, K, D, generator=g)
+    x, out0 = torch.randn(B, D, generator=g), torch.randn(B, M, generator=g)
+    perm = torch.randperm(B, generator=g)
+    counts = {(0, 0): 150, (0, 1): 40, (0, 2): 0, (1, 0): 30, (1, 1): 50, (1, 2): 30}
+    key_s, key_m = torch.zeros(B, dtype=torch.int32), torch.zeros(B, dtype=torch.int32)
+    tiles, pos = [], 0
+    for (ks, km), n in counts.items():                                     # order = perm: the samples grouped by (ks, km)
+        key_s[perm[pos:pos + n]], key_m[perm[pos:pos + n]] = ks, km
+        tiles += [[ks, km, pos + j, min(128, n - j)] for j in range(0, n, 128)]
+        pos += n
+    tiles.insert(3, [1, 2, 0, 0])                                          # an unused tile in the middle
+    T = len(tiles)
+    assert pos == B and T == 7 and sorted(t[3] for t in tiles)[:2] == [0, 22]
+    preps = [gmm_prepare(mG.to(DEV), (sG + cs[ks]).to(DEV), wG.to(DEV)) for ks in range(Us)]
+    a_tab = torch.stack([p[0] for p in preps]).contiguous()
+    cst_tab = torch.stack([p[2] for p in preps]).contiguous()
+    nm_tab = (-(mG.unsqueeze(0) + cm)).reshape(Um, MK, D).to(DEV)
+    nbytes = _hip.lib().cf_gmm_keyed_ws_bytes(T, B, M, K, D)
+    assert nbytes == 16 * B * MK * 4                                       # 16 slices of 48 columns asked for: 12 of 64 launched
+    ws = torch.empty(nbytes, device=DEV, dtype=torch.uint8)
+    xd, ks_d, tiles_d = x.to(DEV), key_s.to(DEV), torch.tensor(tiles, dtype=torch.int32).to(DEV)
+    order_d = perm.to(torch.int32).to(DEV)
+
+    def run(out, accumulate):
+        _hip.call("cf_gmm_logprob_keyed", _hip.p(xd), _hip.p(a_tab), _hip.p(nm_tab), _hip.p(cst_tab), _hip.p(ks_d), _hip.p(tiles_d),
+                  _hip.p(order_d), _hip.p(out), _hip.p(ws), T, B, M, K, D, D, accumulate, _hip.stream())
+        return out
+    ref = torch.empty(B, M, dtype=torch.float64)
+    logw = torch.log_softmax(wG.double(), -1)
+    for (ks, km), n in counts.items():
+        idx = (key_s == ks) & (key_m == km)
+        mu, sig = (mG + cm[km]).double(), torch.nn.functional.softplus((sG + cs[ks]).double())
+        lp = (-0.5 * ((x[idx].double().view(-1, 1, 1, D) - mu) / sig) ** 2 - torch.log(sig) - 0.5 * math.log(2 * math.pi)).sum(-1)
+        ref[idx] = torch.logsumexp(lp + logw, -1)
+    scale = ref.abs().max().item()
+    got = run(torch.empty(B, M, device=DEV), 0)
+    _gmm_bits("keyed", (B, 0), [got])
+    assert (got.cpu().double() - ref).abs().max().item() < 2e-6 * scale
+    acc = run(out0.to(DEV), 1)
+    _gmm_bits("keyed", (B, 1), [acc])
+    assert (acc.cpu().double() - (out0.double() + ref)).abs().max().item() < 2e-6 * scale
 
 
 @pytest.mark.parametrize("B,D,wide", [(1003, 768, 1536), (70, 1536, 1536), (4, 96, 128), (16384, 768, 768)])

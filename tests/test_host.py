@@ -33,7 +33,7 @@ def test_library_exports_every_declared_symbol(built):
     for s in syms:
         assert hasattr(lib, s), "header declares %s but the library does not export it" % s
     assert sorted(_hip.SIGNATURES) == syms, set(_hip.SIGNATURES) ^ set(syms)
-    assert _hip.lib().cf_abi_version() == _hip.ABI_VERSION == 13
+    assert _hip.lib().cf_abi_version() == _hip.ABI_VERSION == 14
     # pure host-side queries work without a GPU
     assert _hip.lib().cf_flow_step_supported(64, 4, 4, 3, 3) == 1
     assert _hip.lib().cf_flow_step_supported(26, 8, 1, 3, 1) == 0
@@ -194,6 +194,44 @@ def test_wgrad_workspace_sizes(built):
         for B in range(8193):
             h.update(str(L.cf_step_wgrads_ws_bytes(B, C, H, W)).encode())
     assert h.hexdigest() == WGRAD_STEP_WS_SHA
+
+
+# ---- the mixture launch plan as the size queries see it ---------------------------------------------------------------------------
+# Recorded from the library as it was BEFORE cf_gmm.hip got its one gmm_plan (commit bbf7a47).  M K x D: the component tiles (16 |
+# 80 wide, ragged, more than 256 components) x widths below one chunk pair, ragged, not a multiple of 4, and the flows' levels.
+GMM_WS_MK = (16, 40, 80, 160, 264)                        # K = 8
+GMM_WS_D = (48, 64, 96, 99, 100, 768, 1536, 3072)
+GMM_WS_LEVELS = ((1536, 768, 768), (2048,), (1024, 1024))  # cifar10; mnist as preset and with split priors
+GMM_WS_SHA = "51099e5ed70a874abf875cebea92b6b42471e3ff4ccc6bc143b8e0448a561750"
+
+
+def test_gmm_workspace_sizes(built):
+    """cf_gmm_ws_bytes, cf_gmm_resp_ws_bytes, cf_gmm_keyed_ws_bytes and cf_gmm_levels_ws_bytes for every batch 0..8192, exactly:
+    pins the D split of gmm_plan (512 workgroups to aim for, slices of at least one 32-column chunk, at most 64) as each of the
+    four queries reports it.  The keyed query runs over T = 1..64 tiles as B advances and once more, all 64, at B = 8192."""
+    import ctypes
+    import hashlib
+    from contextflow_amd.layers import _hip
+    L = _hip.lib()
+    arr = lambda v: (ctypes.c_int * len(v))(*v)
+    levels = [arr(v) for v in GMM_WS_LEVELS]
+    h = hashlib.sha256()
+    for MK in GMM_WS_MK:
+        M, K = MK // 8, 8
+        for D in GMM_WS_D:
+            for B in range(8193):
+                h.update(("%d %d %d " % (L.cf_gmm_ws_bytes(B, M, K, D), L.cf_gmm_resp_ws_bytes(B, M, K, D),
+                                         L.cf_gmm_keyed_ws_bytes(1 + B % 64, B, M, K, D))).encode())
+            for T in range(1, 65):
+                h.update(("%d " % L.cf_gmm_keyed_ws_bytes(T, 8192, M, K, D)).encode())
+        for B in range(8193):
+            for v in levels:
+                h.update(("%d " % L.cf_gmm_levels_ws_bytes(len(v), v, B, M, K)).encode())
+    assert h.hexdigest() == GMM_WS_SHA
+    five = arr([64] * 5)
+    assert L.cf_gmm_levels_ws_bytes(0, five, 256, 10, 8) == -1 and L.cf_gmm_levels_ws_bytes(5, five, 256, 10, 8) == -1
+    # the one-level queries report the split count before the slices are rounded to 32 columns, the levels query the launched one
+    assert L.cf_gmm_ws_bytes(70, 10, 8, 768) == 16 * 70 * 80 * 4 and L.cf_gmm_levels_ws_bytes(1, arr([768]), 70, 10, 8) == 12 * 70 * 80 * 4
 
 
 WGRAD_MACS_SCRIPT = """
