@@ -77,6 +77,23 @@ def bpd(logp, name):
     return -torch.logsumexp(logp.double(), dim=-1) / (D * math.log(2.0))
 
 
+def gmm_resp_closed_form(x, mG, sG, wG, g, chunk=64):
+    """What cf_gmm_resp returns, written out in the dtype of its arguments: r[b, m k] = softmax_k(log-joint + log_softmax(wG))
+    * g[b, m] with log-joint = sum_d log N(x[b, d]; mG[m, k, d], softplus(sG[m, k, d])) (gaussian.py:138-161).  x (B, D), mG / sG
+    (M, K, D), wG (M, K), g (B, M); returns (B, M K).  Samples go in chunks: the (chunk, M, K, D) broadcast is the only large
+    intermediate."""
+    M, K = wG.shape
+    sig = torch.nn.functional.softplus(sG)
+    cst = -torch.log(sig) - 0.5 * math.log(2.0 * math.pi)
+    logw = torch.log_softmax(wG, dim=-1)
+    out = []
+    for b0 in range(0, x.shape[0], chunk):
+        xv = x[b0:b0 + chunk].reshape(-1, 1, 1, x.shape[1])
+        lj = (-0.5 * ((xv - mG) / sig) ** 2 + cst).sum(-1) + logw
+        out.append((torch.softmax(lj, dim=-1) * g[b0:b0 + chunk].unsqueeze(-1)).reshape(-1, M * K))
+    return torch.cat(out, 0)
+
+
 SPECIALIST = {
     # fixture: (dataset, ctx description) — see tests/golden/make_golden_specialist.py
     "mnist_eye_cf": ("mnist", dict(contexts=[64], enc_emb="eye", contextflow=True)),

@@ -13,7 +13,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import flow_oracle as fo                     # noqa: E402
-from tests.helpers import load_e2e, pre_init_params, e2e_inputs, unit, bpd, stress_tolerance   # noqa: E402
+from tests.helpers import load_e2e, pre_init_params, e2e_inputs, unit, bpd, stress_tolerance, gmm_resp_closed_form   # noqa: E402
 
 BPD_TOL = 1e-5
 DEV = "cuda:0"
@@ -291,7 +291,7 @@ GMM_CASES = [(10, 8, 768, 70, 1536, 12), (10, 8, 1536, 1, 1536, 24), (10, 8, 100
              (10, 8, 48, 257, 48, 1), (2, 8, 768, 70, 768, 12), (1, 5, 64, 5, 64, 2), (5, 8, 768, 70, 768, 12),
              (33, 8, 256, 40, 256, 8)]
 GMM_IDS = ["-".join(map(str, c[:5])) for c in GMM_CASES]
-_gmm_case_cache = {}
+_gmm_case_cache, _gmm_case_cpu, _gmm_resp_cache = {}, {}, {}
 
 
 def _gmm_case(case):
@@ -307,7 +307,21 @@ def _gmm_case(case):
         x = xw.to(DEV)[:, stride - D:]                                        # a channel slice where stride > D
         ref = fo.gmm_logprob(xw[:, stride - D:], mG, sG, wG)
         _gmm_case_cache[case] = (x, gmm_prepare(mG.to(DEV), sG.to(DEV), wG.to(DEV)), out0, gup, ref)
+        _gmm_case_cpu[case] = (xw[:, stride - D:], mG, sG, wG)
     return _gmm_case_cache[case]
+
+
+def _gmm_case_resp(case):
+    """cf_gmm_resp's result for the case by the closed form (tests/helpers.py) in fp64, and the relative error the same form makes
+    in fp32 on these inputs - computed once."""
+    if case not in _gmm_resp_cache:
+        _, _, _, gup, _ = _gmm_case(case)
+        xs, mG, sG, wG = _gmm_case_cpu[case]
+        r64 = gmm_resp_closed_form(xs.double(), mG.double(), sG.double(), wG.double(), gup.double())
+        r32 = gmm_resp_closed_form(xs, mG, sG, wG, gup)
+        scale = max(r64.abs().max().item(), 1e-3)
+        _gmm_resp_cache[case] = (r64, scale, (r32.double() - r64).abs().max().item() / scale)
+    return _gmm_resp_cache[case]
 
 
 def _gmm_slices_launched(case):
@@ -352,7 +366,8 @@ def test_gmm_logprob_bits_and_oracle(L, case):
 @pytest.mark.parametrize("case", GMM_CASES, ids=GMM_IDS)
 def test_gmm_resp_bits(L, case):
     """cf_gmm_resp (responsibilities x upstream gradient) on the same shapes: the recorded bits; the responsibilities of a mixture
-    sum to one (K roundings of a value <= 1: 1e-5 of the gradient's scale)."""
+    sum to one (K roundings of a value <= 1: 1e-5 of the gradient's scale); r against softmax_k(log-joint + log-weight) * g in fp64,
+    below max(1e-4, 3 x the error of the same form in fp32)."""
     from contextflow_amd.layers import _hip
     M, K, D, B, stride, ns = case
     x, (a, nm, cst, _, _, _), _, gup, _ = _gmm_case(case)
@@ -364,6 +379,12 @@ def test_gmm_resp_bits(L, case):
               _hip.stream())
     _gmm_bits("resp", case[:5], [r])
     close(r.view(B, M, K).sum(-1), gup, tol=1e-5)
+    # ... and the values themselves, under the rule of tests/test_gmm_backward.py (recorded bits say "unchanged", not "right")
+    r64, scale, floor = _gmm_case_resp(case)
+    err = (r.cpu().double() - r64).abs().max().item() / scale
+    tol = max(1e-4, 3.0 * floor)
+    print("GMM_BWD resp_bits %s r: relative error %.3e, fp32 floor %.3e, bar %.3e" % ("-".join(map(str, case[:5])), err, floor, tol))
+    assert err < tol, "r: relative error %.3e (fp32 floor %.3e, bar %.1e)" % (err, floor, tol)
 
 
 def test_gmm_keyed_entry_with_host_built_tiles(L):
