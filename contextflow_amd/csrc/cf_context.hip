@@ -725,6 +725,227 @@ __global__ __launch_bounds__(256) void k_actnorm_ctx_bwd(const float* __restrict
     }
 }
 
+// ---- the data-only backward of the Conv1x1 + ActNorm pair (the input gradient of log p(x | c): FlowSequential.score with a
+// context).  Adjoint of cf_affine_ctx_fwd with respect to x alone:
+//   gx[b] = W_b^T (gz[b] (.) exp(-l_b)),   W_b as in k_conv1x1_ctx (m1 == NULL: the identity),
+//   l_b = m2[b, C:2C] [+ logs] (m2 == NULL: no scale)
+// Neither log-det depends on x, so neither x, t nor gld is read, and none of the C x C / 2C parameter gradients of
+// k_conv1x1_ctx_bwd / k_actnorm_ctx_bwd is formed.  USQ: gx is stored in the (C/4, 2H, 2W) layout in front of a Squeeze((2,2)).
+__device__ __forceinline__ int unsqueezed_index(int c, int p, int W, int HW) {
+    const int yy = p / W, xx = p - yy * W;
+    return (c >> 2) * 4 * HW + (2 * yy + ((c >> 1) & 1)) * 2 * W + 2 * xx + (c & 1);
+}
+
+// Any shape, any alignment: one workgroup per sample, W_b with exp(-l_b) folded into its rows (row stride CP) and gz (row
+// stride HWP, odd) in LDS, as k_conv1x1_ctx_bwd without its xs plane and G products; a thread owns a pixel and 8 input channels.
+template <bool USQ>
+__global__ __launch_bounds__(256) void k_affine_ctx_bwd_data(const float* __restrict__ gz, const float* __restrict__ m1,
+                                                             const float* __restrict__ Wm, const float* __restrict__ m2,
+                                                             const float* __restrict__ logs, float* __restrict__ gx, int C,
+                                                             int H, int W, int64_t gzbs) {
+    extern __shared__ __align__(16) float dyn[];
+    const int CP = (C + 7) & ~7, HW = H * W, HWP = HW | 1;
+    float* sb = dyn;                                  // [C] exp(-l_b)
+    float* Wb = dyn + ((C + 3) & ~3);                 // Wb[o][i] = W_b[o][i] exp(-l_b[o]), row stride CP (zero padded)
+    float* gs = Wb + C * CP;                          // [C][HWP]
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* gb = gz + (int64_t)b * gzbs;
+    float* gxb = gx + (int64_t)b * C * HW;
+    for (int c = tid; c < C; c += 256) {
+        float lv = 0.f;
+        if (m2 != nullptr) { lv = m2[(int64_t)b * 2 * C + C + c]; if (logs != nullptr) lv += logs[c]; }
+        sb[c] = m2 != nullptr ? expf(-lv) : 1.f;
+    }
+    __syncthreads();
+    if (m1 == nullptr) {                              // ActNorm alone: a scale per channel
+        for (int e0 = tid; e0 < C * HW; e0 += 4 * 256) {
+            float gv[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) gv[i] = gb[min(e0 + i * 256, C * HW - 1)];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int e = e0 + i * 256;
+                if (e < C * HW) { const int c = e / HW, p = e - c * HW; gxb[USQ ? unsqueezed_index(c, p, W, HW) : e] = gv[i] * sb[c]; }
+            }
+        }
+        return;
+    }
+    const float* mb = m1 + (int64_t)b * C * C;
+    for (int e0 = tid; e0 < C * HW; e0 += 8 * 256) {   // batches of independent loads (padded rows: scalar stores)
+        float gv[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) gv[i] = gb[min(e0 + i * 256, C * HW - 1)];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int e = e0 + i * 256;
+            if (e < C * HW) { const int c = e / HW, p = e - c * HW; gs[c * HWP + p] = gv[i]; }
+        }
+    }
+    for (int e0 = tid; e0 < C * CP; e0 += 8 * 256) {
+        float mv[8], wm[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int e = min(e0 + k * 256, C * CP - 1), o = e / CP, i = min(e - o * CP, C - 1);
+            mv[k] = mb[o * C + i];
+            wm[k] = Wm != nullptr ? Wm[o * C + i] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int e = e0 + k * 256;
+            if (e < C * CP) {
+                const int o = e / CP, i = e - o * CP;
+                float w = 0.f;
+                if (i < C) {
+                    w = o > i ? mv[k] : (o == i ? expf(mv[k]) : 0.f);
+                    if (Wm != nullptr) w += wm[k] - (o == i ? 1.f : 0.f);
+                    w *= sb[o];
+                }
+                Wb[e] = w;
+            }
+        }
+    }
+    __syncthreads();
+    const int nib = CP >> 3;
+    for (int e = tid; e < nib * HW; e += 256) {       // gx = W_b^T (s gz): a pixel and 8 input channels per thread
+        const int ib = e / HW, p = e - ib * HW, i0 = ib * 8;
+        float acc[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k] = 0.f;
+        for (int o = 0; o < C; ++o) {
+            const float gv = gs[o * HWP + p];
+            const float4 w0 = *reinterpret_cast<const float4*>(&Wb[o * CP + i0]);
+            const float4 w1 = *reinterpret_cast<const float4*>(&Wb[o * CP + i0 + 4]);
+            acc[0] = fmaf(w0.x, gv, acc[0]); acc[1] = fmaf(w0.y, gv, acc[1]);
+            acc[2] = fmaf(w0.z, gv, acc[2]); acc[3] = fmaf(w0.w, gv, acc[3]);
+            acc[4] = fmaf(w1.x, gv, acc[4]); acc[5] = fmaf(w1.y, gv, acc[5]);
+            acc[6] = fmaf(w1.z, gv, acc[6]); acc[7] = fmaf(w1.w, gv, acc[7]);
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (i0 + k < C) gxb[USQ ? unsqueezed_index(i0 + k, p, W, HW) : (i0 + k) * HW + p] = acc[k];
+    }
+}
+
+// The three levels of the image flows: k_affine_ctx_wave transposed - one wave per sample, no LDS, no barrier, 64
+// v_mfma_f32_16x16x4_f32 per sample, every operand read from global memory once.
+//   A (W_b^T with exp(-l_b) folded into its columns; 16 rows i x 4 k = o per instruction): lane (n, kk) holds
+//     W_b[o = 16 g + 4 kk + e][i = 16 it + n] exp(-l_b[o]), e = 0..3, for four successive k-steps - a column walk of the row-major
+//     m1 (dwords, 64-byte runs over n); blocks g < it hold NN alone.  The scale costs C^2 / 64 multiplies per lane, not C HW.
+//   B (gz): for those k-steps lane (n, kk) needs gz[o = 16 g + 4 kk + e][pixel of column n] - exactly the forward's x loads.
+//   D: lane (n, kk) holds rows i = 16 it + 4 kk + r: float4 stores over the four column tiles; USQ: the four rows are the four
+//     phases of ONE channel q = 4 it + kk of the un-squeezed tensor (the mirror of the forward's SQ loads).
+// The k-step loop runs over the row tiles / column tiles innermost: successive MFMAs never share an accumulator (the fp32
+// 16x16x4 form issues every 32 cycles and returns after 40).
+template <int C, int W, bool USQ>
+__global__ __launch_bounds__(256) void k_affine_ctx_bwd_wave(const float* __restrict__ gz, const float* __restrict__ m1,
+                                                             const float* __restrict__ Wm, const float* __restrict__ m2,
+                                                             const float* __restrict__ logs, float* __restrict__ gx, int B,
+                                                             int64_t gzbs) {
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    constexpr int HW = W * W, RT = C / 16, NG = C / 16, WIDE = HW >= 64, NT = WIDE ? HW / 64 : 1, NJ = WIDE ? 4 : 1;
+    const int lane = threadIdx.x & 63, n = lane & 15, kk = lane >> 4;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;                                // a whole wave: the kernel has no barrier
+    const float* mb = m1 + (int64_t)b * C * C;
+    const float* gb = gz + (int64_t)b * gzbs;
+    float4 a[RT][NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        const int o0 = 16 * g + 4 * kk;
+        float ss[4] = {1.f, 1.f, 1.f, 1.f};
+        if (m2 != nullptr) {
+            float4 lv = *reinterpret_cast<const float4*>(m2 + (int64_t)b * 2 * C + C + o0);
+            if (logs != nullptr) {
+                const float4 l0 = *reinterpret_cast<const float4*>(logs + o0);
+                lv.x += l0.x; lv.y += l0.y; lv.z += l0.z; lv.w += l0.w;
+            }
+            ss[0] = expf(-lv.x); ss[1] = expf(-lv.y); ss[2] = expf(-lv.z); ss[3] = expf(-lv.w);
+        }
+#pragma unroll
+        for (int it = 0; it < RT; ++it) {
+            const int i = 16 * it + n;
+            float v[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = g >= it ? mb[(o0 + e) * C + i] : 0.f;
+            if (g == it) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int o = o0 + e;
+                    const float ex = expf(v[e]) - (Wm != nullptr ? 1.f : 0.f);
+                    v[e] = o > i ? v[e] : (o == i ? ex : 0.f);
+                }
+            }
+            if (Wm != nullptr) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] += Wm[(o0 + e) * C + i];
+            }
+            a[it][g] = make_float4(v[0] * ss[0], v[1] * ss[1], v[2] * ss[2], v[3] * ss[3]);
+        }
+    }
+    float* gxb = gx + (int64_t)b * C * HW;
+#pragma unroll
+    for (int T = 0; T < NT; ++T) {
+        f32x4 acc[RT][NJ];
+#pragma unroll
+        for (int it = 0; it < RT; ++it)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) acc[it][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            float gv[4][NJ];                           // [k-step e][column tile j]
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if constexpr (WIDE) {
+                    const float4 v = *reinterpret_cast<const float4*>(gb + (16 * g + 4 * kk + e) * HW + 64 * T + 4 * n);
+                    gv[e][0] = v.x; gv[e][1] = v.y; gv[e][2] = v.z; gv[e][3] = v.w;
+                } else {
+                    gv[e][0] = gb[(16 * g + 4 * kk + e) * HW + n];
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int it = 0; it < RT; ++it) {
+                    const float av = e == 0 ? a[it][g].x : (e == 1 ? a[it][g].y : (e == 2 ? a[it][g].z : a[it][g].w));
+#pragma unroll
+                    for (int j = 0; j < NJ; ++j) acc[it][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, gv[e][j], acc[it][j], 0, 0, 0);
+                }
+        }
+#pragma unroll
+        for (int it = 0; it < RT; ++it) {
+            if constexpr (!USQ) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int i = 16 * it + 4 * kk + r;
+                    if constexpr (WIDE)
+                        *reinterpret_cast<float4*>(gxb + i * HW + 64 * T + 4 * n) =
+                            make_float4(acc[it][0][r], acc[it][1][r], acc[it][2][r], acc[it][3][r]);
+                    else
+                        gxb[i * HW + n] = acc[it][0][r];
+                }
+            } else {
+                float* qb = gxb + (4 * it + kk) * 4 * HW;      // channel q of the (C/4, 2W, 2W) sample
+                if constexpr (WIDE) {
+                    const int p0 = 64 * T + 4 * n, yy = p0 / W, xx = p0 - yy * W;       // 4 pixels of one image row (W >= 4)
+#pragma unroll
+                    for (int dy = 0; dy < 2; ++dy) {
+                        float* row = qb + (2 * yy + dy) * 2 * W + 2 * xx;
+                        *reinterpret_cast<float4*>(row) =
+                            make_float4(acc[it][0][2 * dy], acc[it][0][2 * dy + 1], acc[it][1][2 * dy], acc[it][1][2 * dy + 1]);
+                        *reinterpret_cast<float4*>(row + 4) =
+                            make_float4(acc[it][2][2 * dy], acc[it][2][2 * dy + 1], acc[it][3][2 * dy], acc[it][3][2 * dy + 1]);
+                    }
+                } else {
+                    const int yy = n / W, xx = n - yy * W;
+#pragma unroll
+                    for (int dy = 0; dy < 2; ++dy)
+                        *reinterpret_cast<float2*>(qb + (2 * yy + dy) * 2 * W + 2 * xx) = make_float2(acc[it][0][2 * dy], acc[it][0][2 * dy + 1]);
+                }
+            }
+        }
+    }
+}
+
 // out[b, c] = sum_p a[b, c, p]      (d/d of a per-sample bias: row sums of a gradient plane)
 __global__ __launch_bounds__(256) void k_sample_channel_sums(const float* __restrict__ a, float* __restrict__ out, int HW,
                                                              int64_t rows) {
@@ -753,7 +974,10 @@ __global__ __launch_bounds__(256) void k_relu_bwd(const float* __restrict__ x, c
 // component loop inside, gx accumulates in registers (PIT pixels per lane and sample) and the (component, channel)
 // sums are segmented shuffle reductions over the SEG lanes of the channel.  lp_in (optional): the log-joints kept by
 // the forward; without it they are recomputed first.
-template <int S, bool TAB>
+// DATA = true (cf_gmm_ctx_bwd_data: the input gradient alone, FlowSequential.score with a context): no dsig reads, no a0 / a1
+// sums, no segmented reductions and no gc stores (gc may be null); the gx accumulation is the same instruction stream, so gx is
+// bit for bit the training form's.
+template <int S, bool TAB, bool DATA = false>
 __global__ __launch_bounds__(256) void k_gmm_ctx_bwd(const float* __restrict__ x, const float* __restrict__ mG,
                                                      const float* __restrict__ sG, const float* __restrict__ logw,
                                                      const float* __restrict__ c, const float* __restrict__ g,
@@ -814,7 +1038,7 @@ __global__ __launch_bounds__(256) void k_gmm_ctx_bwd(const float* __restrict__ x
                 for (int s = 0; s < S; ++s) {
                     r[s] = rr[s * MK + mk];
                     cm[s] = dok ? c[co[s] + mk * D + d] : 0.f;
-                    cs[s] = dok ? c[co[s] + (MK + mk) * D + d] : 0.f;
+                    cs[s] = (dok && !(TAB && DATA)) ? c[co[s] + (MK + mk) * D + d] : 0.f;
                     a0[s] = 0.f;
                     a1[s] = 0.f;
                 }
@@ -828,30 +1052,34 @@ __global__ __launch_bounds__(256) void k_gmm_ctx_bwd(const float* __restrict__ x
                         if constexpr (!TAB) sv = sg[e];
 #pragma unroll
                         for (int s = 0; s < S; ++s) {
-                            float inv, dsig;
+                            float inv, dsig = 0.f;
                             if constexpr (TAB) {
                                 inv = tb.inv[io[s] + (int64_t)mk * N + e];
-                                dsig = tb.dsig[io[s] + (int64_t)mk * N + e];
+                                if constexpr (!DATA) dsig = tb.dsig[io[s] + (int64_t)mk * N + e];
                             } else {
                                 const float t = sv + cs[s];
                                 inv = __frcp_rn(softplus_fast(t));
-                                dsig = t > 20.f ? 1.f : __frcp_rn(1.0f + __expf(-t));           // softplus'
+                                if constexpr (!DATA) dsig = t > 20.f ? 1.f : __frcp_rn(1.0f + __expf(-t));   // softplus'
                             }
                             const float dd = xs[s * N + e] - m - cm[s];
                             const float q = dd * inv * inv;                                  // d / sig^2
                             gxa[s][it] = fmaf(-r[s], q, gxa[s][it]);
-                            a0[s] += q;
-                            a1[s] += (dd * q * inv - inv) * dsig;
+                            if constexpr (!DATA) {
+                                a0[s] += q;
+                                a1[s] += (dd * q * inv - inv) * dsig;
+                            }
                         }
                     }
                 }
+                if constexpr (!DATA) {
 #pragma unroll
-                for (int s = 0; s < S; ++s) {
-                    for (int o = L.SEG >> 1; o > 0; o >>= 1) { a0[s] += __shfl_xor(a0[s], o, 64); a1[s] += __shfl_xor(a1[s], o, 64); }
-                    if (L.pl == 0 && dok && live[s]) {
-                        float* gcb = gc + co[s];
-                        if (p0 == 0) { gcb[mk * D + d] = r[s] * a0[s]; gcb[(MK + mk) * D + d] = r[s] * a1[s]; }
-                        else { gcb[mk * D + d] += r[s] * a0[s]; gcb[(MK + mk) * D + d] += r[s] * a1[s]; }
+                    for (int s = 0; s < S; ++s) {
+                        for (int o = L.SEG >> 1; o > 0; o >>= 1) { a0[s] += __shfl_xor(a0[s], o, 64); a1[s] += __shfl_xor(a1[s], o, 64); }
+                        if (L.pl == 0 && dok && live[s]) {
+                            float* gcb = gc + co[s];
+                            if (p0 == 0) { gcb[mk * D + d] = r[s] * a0[s]; gcb[(MK + mk) * D + d] = r[s] * a1[s]; }
+                            else { gcb[mk * D + d] += r[s] * a0[s]; gcb[(MK + mk) * D + d] += r[s] * a1[s]; }
+                        }
                     }
                 }
             }
@@ -932,7 +1160,7 @@ static int gmm_ctx_fwd_launch(const char* who, const float* x, const float* mG, 
     return 0;
 }
 
-template <bool TAB>
+template <bool TAB, bool DATA = false>
 static int gmm_ctx_bwd_launch(const char* who, const float* x, const float* mG, const float* sG, const float* logw, const float* c,
                               const float* g, const float* lp, float* gx, float* gc, int B, int M, int K, int D, int HW,
                               int64_t xbs, GmmTab tb, hipStream_t st) {
@@ -941,12 +1169,12 @@ static int gmm_ctx_bwd_launch(const char* who, const float* x, const float* mG, 
     if (S == 0) { cf_set_error("%s: D*HW=%d needs %zu B of LDS", who, D * HW, lds); return CF_ERR_UNSUPPORTED; }
     if (lds > 64 * 1024) {
         static std::atomic<uint64_t> raised{0};
-        if (int rc_ = cf_raise_dynamic_lds((const void*)k_gmm_ctx_bwd<1, TAB>, 160 * 1024, raised, __func__)) return rc_;
+        if (int rc_ = cf_raise_dynamic_lds((const void*)k_gmm_ctx_bwd<1, TAB, DATA>, 160 * 1024, raised, __func__)) return rc_;
     }
     const dim3 grid((B + S - 1) / S);
-    if (S == 4) k_gmm_ctx_bwd<4, TAB><<<grid, dim3(256), lds, st>>>(x, mG, sG, logw, c, g, lp, gx, gc, B, M, K, D, HW, xbs, tb);
-    else if (S == 2) k_gmm_ctx_bwd<2, TAB><<<grid, dim3(256), lds, st>>>(x, mG, sG, logw, c, g, lp, gx, gc, B, M, K, D, HW, xbs, tb);
-    else k_gmm_ctx_bwd<1, TAB><<<grid, dim3(256), lds, st>>>(x, mG, sG, logw, c, g, lp, gx, gc, B, M, K, D, HW, xbs, tb);
+    if (S == 4) k_gmm_ctx_bwd<4, TAB, DATA><<<grid, dim3(256), lds, st>>>(x, mG, sG, logw, c, g, lp, gx, gc, B, M, K, D, HW, xbs, tb);
+    else if (S == 2) k_gmm_ctx_bwd<2, TAB, DATA><<<grid, dim3(256), lds, st>>>(x, mG, sG, logw, c, g, lp, gx, gc, B, M, K, D, HW, xbs, tb);
+    else k_gmm_ctx_bwd<1, TAB, DATA><<<grid, dim3(256), lds, st>>>(x, mG, sG, logw, c, g, lp, gx, gc, B, M, K, D, HW, xbs, tb);
     return 0;
 }
 
@@ -1116,6 +1344,37 @@ int cf_actnorm_ctx_bwd(const float* x, const float* m, const float* t, const flo
     return 0;
 }
 
+// the input gradient through [Squeeze(2,2) ->] Conv1x1(c) -> ActNorm(c') in one launch; m1 / m2 NULL: a lone ActNorm / Conv1x1
+int cf_affine_ctx_bwd_data(const float* gz, const float* m1, const float* Wm, const float* m2, const float* logs, float* gx,
+                           int B, int C, int H, int W, int64_t gz_bstride, int out_unsqueeze, cf_stream_t stream) {
+    if (B == 0) return 0;
+    CF_REQUIRE(gz && gx && B >= 0 && C > 0 && C <= 256 && H > 0 && W > 0 && (m1 || !Wm) && (m2 || !logs) &&
+               gz_bstride >= (int64_t)C * H * W && (!out_unsqueeze || C % 4 == 0));
+    const bool al = ((reinterpret_cast<uintptr_t>(gz) | reinterpret_cast<uintptr_t>(m1) | reinterpret_cast<uintptr_t>(Wm) |
+                      reinterpret_cast<uintptr_t>(m2) | reinterpret_cast<uintptr_t>(logs) | reinterpret_cast<uintptr_t>(gx)) & 15) == 0 &&
+                    gz_bstride % 4 == 0;
+    if (al && m1 && H == W && ((C == 16 && W == 16) || (C == 32 && W == 8) || (C == 64 && W == 4))) {
+        const dim3 grid((B + 3) / 4), blk(256);
+#define CF_AFFB(CC, WW) do { if (out_unsqueeze) k_affine_ctx_bwd_wave<CC, WW, true><<<grid, blk, 0, cf_s(stream)>>>(gz, m1, Wm, m2, logs, gx, B, gz_bstride); \
+                             else k_affine_ctx_bwd_wave<CC, WW, false><<<grid, blk, 0, cf_s(stream)>>>(gz, m1, Wm, m2, logs, gx, B, gz_bstride); } while (0)
+        if (C == 16) CF_AFFB(16, 16); else if (C == 32) CF_AFFB(32, 8); else CF_AFFB(64, 4);
+#undef CF_AFFB
+        CF_LAUNCH_CHECK();
+        return 0;
+    }
+    const size_t lds = (size_t)(((C + 3) & ~3) + (m1 ? C * ((C + 7) & ~7) + C * ((H * W) | 1) : 0)) * sizeof(float);
+    if (lds > 160 * 1024) { cf_set_error("cf_affine_ctx_bwd_data: C=%d, H*W=%d need %zu B of LDS", C, H * W, lds); return CF_ERR_UNSUPPORTED; }
+    if (lds > 64 * 1024) {
+        static std::atomic<uint64_t> raised0{0}, raised1{0};
+        if (int rc_ = out_unsqueeze ? cf_raise_dynamic_lds((const void*)k_affine_ctx_bwd_data<true>, 160 * 1024, raised1, __func__)
+                                    : cf_raise_dynamic_lds((const void*)k_affine_ctx_bwd_data<false>, 160 * 1024, raised0, __func__)) return rc_;
+    }
+    if (out_unsqueeze) k_affine_ctx_bwd_data<true><<<dim3(B), dim3(256), lds, cf_s(stream)>>>(gz, m1, Wm, m2, logs, gx, C, H, W, gz_bstride);
+    else k_affine_ctx_bwd_data<false><<<dim3(B), dim3(256), lds, cf_s(stream)>>>(gz, m1, Wm, m2, logs, gx, C, H, W, gz_bstride);
+    CF_LAUNCH_CHECK();
+    return 0;
+}
+
 int cf_sample_channel_sums(const float* a, float* out, int B, int C, int HW, cf_stream_t stream) {
     if (B == 0) return 0;
     CF_REQUIRE(a && out && B >= 0 && C > 0 && HW > 0);
@@ -1154,6 +1413,24 @@ int cf_gmm_ctx_bwd_tab(const float* x, const float* mG, const float* inv_sig, co
     CF_REQUIRE(x && mG && inv_sig && dsig && lsum && logw && c && key && g && gx && gc && B >= 0 && M > 0 && K > 0 && D > 0 && HW > 0);
     int rc = gmm_ctx_bwd_launch<true>("cf_gmm_ctx_bwd_tab", x, mG, nullptr, logw, c, g, lp, gx, gc, B, M, K, D, HW, x_bstride,
                                       GmmTab{inv_sig, dsig, lsum, key, nullptr}, cf_s(stream));
+    if (rc) return rc;
+    CF_LAUNCH_CHECK();
+    return 0;
+}
+
+// d/dx alone of either form (FlowSequential.score with a context): inv_sig / lsum / key select the table form, sG the direct
+// one; the kernels of cf_gmm_ctx_bwd / cf_gmm_ctx_bwd_tab with everything that leads to gc compiled out - gx is bitwise equal.
+int cf_gmm_ctx_bwd_data(const float* x, const float* mG, const float* sG, const float* inv_sig, const float* lsum,
+                        const float* logw, const float* c, const int* key, const float* g, const float* lp, float* gx, int B,
+                        int M, int K, int D, int HW, int64_t x_bstride, cf_stream_t stream) {
+    if (B == 0) return 0;
+    const bool tab = inv_sig != nullptr || lsum != nullptr || key != nullptr;
+    CF_REQUIRE(x && mG && logw && c && g && gx && B >= 0 && M > 0 && K > 0 && D > 0 && HW > 0 &&
+               (tab ? (inv_sig && lsum && key) : sG != nullptr));
+    int rc = tab ? gmm_ctx_bwd_launch<true, true>("cf_gmm_ctx_bwd_data", x, mG, nullptr, logw, c, g, lp, gx, nullptr, B, M, K, D, HW,
+                                                  x_bstride, GmmTab{inv_sig, nullptr, lsum, key, nullptr}, cf_s(stream))
+                 : gmm_ctx_bwd_launch<false, true>("cf_gmm_ctx_bwd_data", x, mG, sG, logw, c, g, lp, gx, nullptr, B, M, K, D, HW,
+                                                   x_bstride, GmmTab{nullptr, nullptr, nullptr, nullptr, nullptr}, cf_s(stream));
     if (rc) return rc;
     CF_LAUNCH_CHECK();
     return 0;

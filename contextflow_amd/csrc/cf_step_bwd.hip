@@ -1005,4 +1005,30 @@ int cf_flow_step_bwd_ctx(const float* x, const float* gz, const float* gld, cons
     return 0;
 }
 
+// the data-gradient chain of cf_flow_step_bwd_ctx alone (d log p(x | c) / d x: FlowSequential.score with a context): the same
+// kernel and dispatch with the store of the s_gh plane compiled out - gx is bitwise equal.
+int cf_flow_step_bwd_ctx_data(const float* x, const float* gz, const float* gld, const void* ws, const void* wsb,
+                              const float* sbias, float* gx, int B, int C, int H, int W, int64_t x_bstride, cf_stream_t stream) {
+    if (B == 0) return 0;
+    CF_REQUIRE(x && gz && gld && ws && wsb && sbias && gx);
+    CF_REQUIRE(x_bstride >= (int64_t)C * H * W && x_bstride % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
+               (reinterpret_cast<uintptr_t>(gz) & 15) == 0 && (reinterpret_cast<uintptr_t>(gx) & 15) == 0);
+    const float* w = (const float*)ws;
+    const float* wb = (const float*)wsb;
+    int rc = 0;
+#define CF_BWDCD(G) rc = launch_step_bwd<G, true, true>(x, gz, gld, w, wb, gx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, \
+                                                       nullptr, B, x_bstride, cf_s(stream), sbias)
+    switch (shape_id(C, H, W)) {
+        case 0: CF_BWDCD(B8); break;
+        case 1: CF_BWDCD(B16); break;
+        case 2: CF_BWDCD(B32); break;
+        case 3: CF_BWDCD(B64); break;
+        default: cf_set_error("cf_flow_step_bwd_ctx_data: shape (%d,%d,%d) unsupported", C, H, W); return CF_ERR_UNSUPPORTED;
+    }
+#undef CF_BWDCD
+    if (rc) return rc;
+    CF_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // extern "C"

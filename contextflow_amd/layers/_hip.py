@@ -157,6 +157,9 @@ SIGNATURES = {
     "cf_gmm_ctx_bwd_tab": (_c_int, [_c_p] * 12 + [_c_int] * 5 + [_c_i64, _c_p]),
     "cf_gmm_ctx_pgrad_tab": (_c_int, [_c_p] * 9 + [_c_int] * 5 + [_c_i64, _c_int, _c_p]),
     "cf_gmm_ctx_bwd": (_c_int, [_c_p] * 9 + [_c_int] * 5 + [_c_i64, _c_p]),
+    "cf_affine_ctx_bwd_data": (_c_int, [_c_p] * 6 + [_c_int] * 4 + [_c_i64, _c_int, _c_p]),
+    "cf_flow_step_bwd_ctx_data": (_c_int, [_c_p] * 7 + [_c_int] * 4 + [_c_i64, _c_p]),
+    "cf_gmm_ctx_bwd_data": (_c_int, [_c_p] * 11 + [_c_int] * 5 + [_c_i64, _c_p]),
     "cf_add_repeat": (_c_int, [_c_p] * 2 + [_c_int] * 4 + [_c_p]),
     "cf_cond_gauss_sample": (_c_int, [_c_p] * 4 + [_c_int, _c_int, _c_p]),
     "cf_activation": (_c_int, [_c_p] * 3 + [_c_i64, _c_int, _c_int, _c_f, _c_f, _c_p, _c_int, _c_p]),

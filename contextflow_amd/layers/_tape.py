@@ -19,10 +19,12 @@ def step_tape(B, C, H, W, dev):
 
 class Pre(NamedTuple):
     """pre-processing: nothing trainable at or above it; its backward (cf_preprocess_bwd, only when the input needs a
-    gradient) reads the forward output alone"""
+    gradient) reads the forward output alone.  The specialist tape (autograd_ctx.taped_forward) also writes it for the time-series
+    flows, which have no transform in front ([Augment] alone): y stays None there and the backward is a channel slice; n = 0
+    marks a prefix the input gradient is not built for."""
     kind = "pre"
     y: Any = None            # forward output (B, C + aug, H, W): the tensor the next record reads anyway
-    n: int = 0               # image elements per sample (the Augment channels behind them get no gradient)
+    n: int = 0               # data elements per sample (the Augment channels behind them get no gradient)
     s1: float = 1.0          # scales of the two Normalizations
     s2: float = 1.0
 
@@ -137,3 +139,21 @@ class CtxMixture(NamedTuple):
     context: Any
     lp: Any                  # per-component log-joints of the forward
     tab: Any                 # (key, inv, dsig, lsum) scale tables of the embedding-lookup form, or None
+
+
+def data_only(rec):
+    """A specialist record with only what the data-only walk (autograd_ctx.input_gradient_ctx) reads: no layer input where the
+    backward kernel does not need it, no code, CN activations or encoder noise - and of a mode-2 coupling the aux buffer alone
+    (its y0 / h1 / h2 planes, operands of the weight gradients, go back to the allocator with this call)."""
+    kind = rec.kind
+    if kind == "ctx_affine":
+        return rec._replace(x=None, c=None, eps=None)
+    if kind == "ctx_coupling":
+        if rec.mode == 1:
+            return rec._replace(c=None, a1=None, a2=None, eps=None)
+        return rec._replace(x=None, c=None, a1=None, a2=None, cn=None, ws=None, planes=(None, None, None, rec.planes[3]), eps=None)
+    if kind == "ctx_transcoupling":
+        return rec._replace(c=None, a1=None, a2=None, eps=None)
+    if kind == "ctx_mixture":
+        return rec._replace(context=None)
+    return rec

@@ -7,7 +7,12 @@ context-encoder output; the backward runs the data-gradient chain with HIP kerne
 cf_actnorm_ctx_bwd, the fused MFMA step-backward kernel with the per-sample CN(c) bias for the Coupling layers,
 cf_gmm_ctx_bwd) and turns the per-sample parameter gradients into CN / embedding gradients with library GEMMs.
 Built for the conv couplings with the encoders that have no trainable parameters of their own (eye | onehot + uniform)
-and for embedding lookups (embed + eyesample)."""
+and for embedding lookups (embed + eyesample).
+
+The same tape gives the input gradient of log p(x | c): the training walk goes on through the pre-processing when x requires a
+gradient, and with no trainable parameter (a frozen specialist, FlowSequential.score) input_gradient_ctx walks the data halves
+alone - cf_affine_ctx_bwd_data, cf_flow_step_bwd_ctx_data, cf_gmm_ctx_bwd_data - and forms no parameter gradient."""
+import math
 import os
 from typing import Any, NamedTuple
 
@@ -15,14 +20,19 @@ import torch
 
 from . import _derived, _hip, _tape
 from .actnorm import ActNorm
+from .augment import Augment
 from .autograd_layers import _new, _relu_mask
 from .context import (ArgmaxCatDequantization, CatEmbeddings, EyeSampling, ProbSampling, UniformCatDequantization,
                       VariationalCatDequantization)
 from .conv1x1 import Conv1x1
 from .coupling import Coupling, TransCoupling
+from .dequantize import Dequantization
+from .distributions.uniform import UniformDistribution
+from .normalize import Normalization
 from .permute_axes import PermuteAxes
 from .splitprior import SplitPrior
 from .squeeze import Squeeze, squeeze_op
+from .transforms import LogitTransform
 
 TRAINABLE_ENCODERS = (UniformCatDequantization, EyeSampling, VariationalCatDequantization, ArgmaxCatDequantization, ProbSampling)
 
@@ -262,6 +272,24 @@ def _cn_chain_backward(rec, gcn, ldscale, bw):
     _cn_input_backward(rec, CN[0], ga1, ldscale, bw)
 
 
+def _coupling_wsb(rec, C, H, W, dev):
+    """Transposed fragments of the step-backward kernel for a coupling record (identity 1x1 / ActNorm in front): kept while the
+    three weights are unchanged (frozen under contextflow)."""
+    m, f, pp = rec.module, _hip.f32, _hip.p
+    c1, c2, c3 = m.NN[0], m.NN[2], m.NN[4]
+
+    def build():
+        eye = torch.eye(C, device=dev, dtype=torch.float32)
+        zero = torch.zeros(C, device=dev, dtype=torch.float32)
+        wsb = torch.empty(_hip.lib().cf_flow_step_bwd_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
+        w1 = f(c1.weight.detach())
+        w1x = w1 if rec.mode == 1 else w1[:, :C // 2].contiguous()
+        _hip.call("cf_flow_step_bwd_prepare", pp(eye), pp(zero), pp(w1x), pp(f(c2.weight.detach())),
+                  pp(f(c3.weight.detach())), pp(wsb), C, H, W, _hip.stream())
+        return wsb
+    return _derived.get(m, "ctx_wsb", _derived.key((c1.weight, c2.weight, c3.weight), rec.mode, C, H, W, str(dev)), build, dev)
+
+
 def coupling_ctx_backward(rec, gz, bw):
     """Coupling with a context net through the fused step-backward kernel (identity 1x1 / ActNorm in front).
     contextflow (mode 1): the conditioner is frozen, CN(c) is a bias on its output - d/d CN(c) = per-sample row sums of the
@@ -275,16 +303,7 @@ def coupling_ctx_backward(rec, gz, bw):
     dev, st, f, pp, L = x.device, _hip.stream(), _hip.f32, _hip.p, _hip.lib()
     c1, c2, c3 = m.NN[0], m.NN[2], m.NN[4]
     w1 = f(c1.weight.detach())
-    # transposed fragments of the backward kernel: kept while the three weights are unchanged (frozen under contextflow)
-    def build():
-        eye = torch.eye(C, device=dev, dtype=torch.float32)
-        zero = torch.zeros(C, device=dev, dtype=torch.float32)
-        wsb = torch.empty(L.cf_flow_step_bwd_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
-        w1x = w1 if rec.mode == 1 else w1[:, :D].contiguous()
-        _hip.call("cf_flow_step_bwd_prepare", pp(eye), pp(zero), pp(w1x), pp(f(c2.weight.detach())),
-                  pp(f(c3.weight.detach())), pp(wsb), C, H, W, st)
-        return wsb
-    wsb = _derived.get(m, "ctx_wsb", _derived.key((c1.weight, c2.weight, c3.weight), rec.mode, C, H, W, str(dev)), build, dev)
+    wsb = _coupling_wsb(rec, C, H, W, dev)
     gx = torch.empty(B, C, H, W, device=dev, dtype=torch.float32)
     s_gh = torch.empty(B, C, HW, device=dev, dtype=torch.float32)
     gzc = f(gz).contiguous()
@@ -350,6 +369,9 @@ def transcoupling_ctx_backward(rec, gz, bw):
     ghd = _new(B, C, H, W, like=x)
     _hip.call("cf_coupling_apply_bwd", _hip.p(x), _hip.p(h), _hip.p(gzv), _hip.p(_hip.f32(gld)), _hip.p(gx), _hip.p(ghd),
               B, C, H * W, xbs, gzbs, st)
+    if bw.by_param is None:                                           # the data-only walk: host wiring of the same kernels
+        gx[:, :half] += vit_backward(m.NN[0] if m.contextflow else m.NN, vtape, ghd, None)[:, :half]
+        return gx
     if m.contextflow:
         gcn = _new(B, C, like=x)
         _hip.call("cf_sample_channel_sums", _hip.p(ghd), _hip.p(gcn), B, C, H * W, st)
@@ -402,11 +424,82 @@ def gmm_ctx_backward(rec, g, grads):
     return gx
 
 
-# What SpecialistLogProb.forward and the layers' training forwards (_forward_ctx, _log_prob_ctx) append to the tape, and the
+# ---- the data-only walk: d sum(glogp * logp) / dx alone (FlowSequential.score with a context, log_prob of a frozen specialist
+# with x.requires_grad).  One launch per record, on the current stream; nothing below forms a parameter gradient.
+def affine_ctx_backward_data(conv, act, gz, unsqueeze):
+    """[Squeeze(2,2) <-] Conv1x1(c) <- ActNorm(c') in one cf_affine_ctx_bwd_data launch: gx = W_b^T (gz exp(-l_b)).  conv / act:
+    the two CtxAffine records (either may be None); unsqueeze: gx leaves in the layout in front of the Squeeze."""
+    gzv, gzbs = _hip.bview(gz)
+    B, C, H, W = gzv.shape
+    gx = torch.empty((B, C // 4, 2 * H, 2 * W) if unsqueeze else (B, C, H, W), device=gzv.device, dtype=torch.float32)
+    cm, am = conv and conv.module, act and act.module
+    _hip.call("cf_affine_ctx_bwd_data", _hip.p(gzv), _hip.p(conv.m if conv else None),
+              _hip.p(_hip.f32(cm.NN.detach()) if conv and cm.contextflow else None), _hip.p(act.m if act else None),
+              _hip.p(_hip.f32(am.NN_logs.detach()) if act and am.contextflow else None), _hip.p(gx), B, C, H, W, gzbs,
+              int(unsqueeze), _hip.stream())
+    return gx
+
+
+def coupling_ctx_backward_data(rec, gz, bw):
+    """Mode 1: cf_flow_step_bwd_ctx_data (the recompute from x, no s_gh plane); mode 2: the generalist's cf_flow_step_bwd_data on
+    the aux buffer the taping forward left."""
+    gzc = _hip.f32(gz)
+    B, C, H, W = gzc.shape
+    wsb = _coupling_wsb(rec, C, H, W, gzc.device)
+    gx = torch.empty(B, C, H, W, device=gzc.device, dtype=torch.float32)
+    if rec.mode == 1:
+        x, xbs = _hip.bview(rec.x)
+        _hip.call("cf_flow_step_bwd_ctx_data", _hip.p(x), _hip.p(gzc), _hip.p(bw.gld), _hip.p(rec.ws), _hip.p(wsb), _hip.p(rec.cn),
+                  _hip.p(gx), B, C, H, W, xbs, _hip.stream())
+    else:
+        _hip.call("cf_flow_step_bwd_data", _hip.p(gzc), _hip.p(bw.gld), _hip.p(wsb), _hip.p(rec.planes[3]), _hip.p(gx), B, C, H, W, 0,
+                  _hip.stream())
+    return gx
+
+
+def gmm_ctx_backward_data(rec, g):
+    """d/dx of the context-shifted mixture alone (cf_gmm_ctx_bwd_data, either form of the scale shifts)."""
+    dist = rec.dist
+    x, xbs = _hip.bview(rec.x)
+    B, D, H, W = x.shape
+    gx = _new(B, D, H, W, like=x)
+    key, inv, _, lsum = rec.tab if rec.tab is not None else (None,) * 4
+    _hip.call("cf_gmm_ctx_bwd_data", _hip.p(x), _hip.p(_hip.f32(dist.mG.detach())),
+              _hip.p(_hip.f32(dist.sG.detach()) if rec.tab is None else None), _hip.p(inv), _hip.p(lsum), _hip.p(rec.logw),
+              _hip.p(rec.c), _hip.p(key), _hip.p(_hip.f32(g)), _hip.p(rec.lp), _hip.p(gx), B, dist.M, dist.K, D, H * W, xbs,
+              _hip.stream())
+    return gx
+
+
+def pre_ctx_backward(rec, gz, bw):
+    """Through whatever ran in front of the first record: the fused pre-processing backward of the image flows
+    (autograd.pre_backward), the leading data channels for the time-series flows."""
+    if rec.n <= 0:
+        raise NotImplementedError("input gradient of a specialist flow: no backward through the layers in front of its first context layer")
+    if rec.y is not None:
+        from .autograd import pre_backward
+        return pre_backward(rec, gz, bw.gld)
+    return gz[:, :rec.n // math.prod(gz.shape[2:])].contiguous()
+
+
+def _pre_record(prefix, x_in, y):
+    """The Pre record of a specialist tape from the modules that ran in front of its first record (x_in -> y)."""
+    n = math.prod(x_in.shape[1:])
+    kinds = [type(m) for m in prefix]
+    if kinds and kinds[-1] is Augment and prefix[-1].split_dim == 1:       # its channels sit behind the data and get no gradient
+        kinds = kinds[:-1]
+    if not kinds:                                                           # the time-series flows: nothing transforms x
+        return _tape.Pre(None, n)
+    if kinds == [Dequantization, Normalization, Normalization, LogitTransform] and isinstance(prefix[0].dist, UniformDistribution):
+        return _tape.Pre(y, n, prefix[1]._s, prefix[2]._s)
+    return _tape.Pre()                                                      # n = 0: pre_ctx_backward raises
+
+
+# What taped_forward and the layers' training forwards (_forward_ctx, _log_prob_ctx) append to the tape, and the
 # backward of each kind: (record, d/d of the layer's output, the pass) -> d/d of its input
 RECORDS = (_tape.Pre, _tape.Squeeze, _tape.Permute, _tape.CtxAffine, _tape.CtxCoupling, _tape.CtxTransCoupling, _tape.CtxMixture)
 BACKWARD = {
-    "pre": None,                                         # ends the walk: nothing trainable at or above the pre-processing
+    "pre": pre_ctx_backward,                             # only when the input needs a gradient: nothing trainable at or above it
     "squeeze": lambda rec, gz, bw: squeeze_op(gz, rec.p, True),
     "permute": lambda rec, gz, bw: gz.permute(rec.inverse).contiguous(),
     "ctx_affine": affine_ctx_backward,
@@ -414,55 +507,123 @@ BACKWARD = {
     "ctx_transcoupling": transcoupling_ctx_backward,
     "ctx_mixture": lambda rec, gz, bw: torch.cat([gz, gmm_ctx_backward(rec, bw.glogp, bw.by_param)], dim=1),   # a SplitPrior's
 }
+# ... of the data-only walk (input_gradient_ctx pairs the ctx_affine records itself)
+BACKWARD_DATA = {
+    "pre": pre_ctx_backward,
+    "squeeze": BACKWARD["squeeze"],
+    "permute": BACKWARD["permute"],
+    "ctx_coupling": coupling_ctx_backward_data,
+    "ctx_transcoupling": transcoupling_ctx_backward,     # by_param = None: the ViT's data gradient alone
+    "ctx_mixture": lambda rec, gz, bw: torch.cat([gz, gmm_ctx_backward_data(rec, bw.glogp)], dim=1),
+}
+
+
+def input_gradient_ctx(tape, glogp):
+    """The data-only walk of a specialist tape (taped_forward: the final prior's record last): d sum(glogp * logp) / d (flow
+    input), fp32, flat or in the layout of the first record's input.  Adjacent Conv1x1 / ActNorm records - and a Squeeze((2,2))
+    in front of them - leave in one launch."""
+    glogp = _hip.f32(glogp)
+    if glogp.shape[0] == 0:          # empty batch: nothing to launch
+        return glogp.new_zeros(0)
+    bw = _Pass(None, glogp, glogp.sum(1).contiguous(), None, None)
+    gz = gmm_ctx_backward_data(tape[-1], glogp)
+    i = len(tape) - 2
+    while i >= 0:
+        rec = tape[i]
+        i -= 1
+        if rec.kind != "ctx_affine":
+            gz = BACKWARD_DATA[rec.kind](rec, gz, bw)
+            continue
+        conv, act = (rec, None) if isinstance(rec.module, Conv1x1) else (None, rec)
+        if conv is None and i >= 0 and tape[i].kind == "ctx_affine" and isinstance(tape[i].module, Conv1x1):
+            conv = tape[i]
+            i -= 1
+        unsq = i >= 0 and tape[i].kind == "squeeze" and tuple(tape[i].p) == (2, 2) and gz.shape[1] % 4 == 0
+        if unsq:
+            i -= 1
+        gz = affine_ctx_backward_data(conv, act, gz, unsq)
+    return gz
+
+
+def taped_forward(flow, x, context, data_only=False):
+    """(z, logp, tape) of a specialist flow with the tape of its layers, the final prior's record last.  data_only: the records
+    keep only what input_gradient_ctx reads (_tape.data_only)."""
+    B, M = x.shape[0], flow.mixtures
+    x_in = x
+    tape, prefix = [None], []                            # tape[0]: the Pre record, written in front of the first other one
+    keep = _tape.data_only if data_only else (lambda rec: rec)
+    logdet = torch.zeros(B, M, device=x.device, dtype=torch.float32)
+    # everything the CN nets compute from the context alone, for all layers at once (the uniform encoders' codes are formed
+    # inside the first grouped launch and kept for the backward): 36 encodings + 60 Linears one by one otherwise
+    from . import specialist
+    specialist._draw_encoder_noise(flow, B, x.device)
+    pre = specialist._front_end(flow, context, B, x.device, train=True)
+
+    def first_record():
+        if tape[0] is None:
+            tape[0] = _pre_record(prefix, x_in, x)
+    for mod in flow.sequence_modules:
+        if isinstance(mod, (Conv1x1, ActNorm, Coupling, TransCoupling)) and mod.context_net:
+            first_record()
+            x, ldj = mod._forward_ctx(x, context, tape, pre.get(id(mod)))
+            tape[-1] = keep(tape[-1])
+        elif isinstance(mod, SplitPrior) and getattr(mod.dist, "context_net", None):
+            first_record()
+            c = x.shape[1] // 2
+            ldj = mod.dist._log_prob_ctx(x[:, c:], context, tape)
+            tape[-1] = keep(tape[-1])
+            x = x[:, :c]
+        else:
+            if any(p.requires_grad for p in mod.parameters()):
+                raise NotImplementedError("specialist training: %s has trainable parameters" % type(mod).__name__)
+            if isinstance(mod, Squeeze):
+                first_record()
+                tape.append(_tape.Squeeze(tuple(mod.p)))
+            elif isinstance(mod, PermuteAxes):
+                first_record()
+                tape.append(_tape.Permute(tuple(mod.inverse_permutation)))
+            elif len(tape) > 1:
+                raise NotImplementedError("specialist training: no backward through %s behind the pre-processing" % type(mod).__name__)
+            else:
+                prefix.append(mod)
+            x, ldj = mod(x, context)
+        logdet += ldj if ldj.dim() == 2 else ldj.unsqueeze(-1)
+    first_record()
+    logp = flow.dist._log_prob_ctx(x, context, tape) + logdet
+    tape[-1] = keep(tape[-1])
+    return x, logp, tape
 
 
 class SpecialistLogProb(torch.autograd.Function):
-    """logp (B, M) of a specialist FlowSequential with gradients for its trainable (context) parameters."""
+    """logp (B, M) of a specialist FlowSequential with gradients for its trainable (context) parameters and, when x requires
+    one, the input gradient.  No trainable parameter: the forward keeps the lean tape and the backward is the data-only walk
+    (input_gradient_ctx)."""
 
     @staticmethod
     def forward(ctx, flow, x, context, *params):
-        B, M = x.shape[0], flow.mixtures
-        tape = [_tape.Pre()]                             # whatever runs before the first record below is pre-processing
-        logdet = torch.zeros(B, M, device=x.device, dtype=torch.float32)
-        # everything the CN nets compute from the context alone, for all layers at once (the uniform encoders' codes are formed
-        # inside the first grouped launch and kept for the backward): 36 encodings + 60 Linears one by one otherwise
-        from . import specialist
-        specialist._draw_encoder_noise(flow, B, x.device)
-        pre = specialist._front_end(flow, context, B, x.device, train=True)
-        for mod in flow.sequence_modules:
-            if isinstance(mod, (Conv1x1, ActNorm, Coupling, TransCoupling)) and mod.context_net:
-                x, ldj = mod._forward_ctx(x, context, tape, pre.get(id(mod)))
-            elif isinstance(mod, SplitPrior) and getattr(mod.dist, "context_net", None):
-                c = x.shape[1] // 2
-                ldj = mod.dist._log_prob_ctx(x[:, c:], context, tape)
-                x = x[:, :c]
-            else:
-                if any(p.requires_grad for p in mod.parameters()):
-                    raise NotImplementedError("specialist training: %s has trainable parameters" % type(mod).__name__)
-                if isinstance(mod, Squeeze):
-                    tape.append(_tape.Squeeze(tuple(mod.p)))
-                elif isinstance(mod, PermuteAxes):
-                    tape.append(_tape.Permute(tuple(mod.inverse_permutation)))
-                elif len(tape) > 1:
-                    raise NotImplementedError("specialist training: no backward through %s behind the pre-processing" % type(mod).__name__)
-                x, ldj = mod(x, context)
-            logdet += ldj if ldj.dim() == 2 else ldj.unsqueeze(-1)
-        logp = flow.dist._log_prob_ctx(x, context, tape) + logdet
+        ctx.data_only = ctx.needs_input_grad[1] and not params
+        z, logp, tape = taped_forward(flow, x, context, ctx.data_only)
         ctx.prior = tape.pop()                           # the final prior's record: the backward starts from it
         ctx.tape, ctx.params, ctx.context = tape, params, context
-        ctx.mark_non_differentiable(x)
-        return x, logp
+        ctx.x_like = (x.shape, x.dtype)
+        ctx.mark_non_differentiable(z)
+        return z, logp
 
     @staticmethod
     def backward(ctx, _gz_unused, glogp):
+        shape, dtype = ctx.x_like
+        if ctx.data_only:
+            return (None, input_gradient_ctx(ctx.tape + [ctx.prior], glogp).reshape(shape).to(dtype), None)
         glogp = _hip.f32(glogp)
         gld = glogp.sum(1).contiguous()
         bw = _Pass(ctx.context, glogp, gld, {}, [] if DEFER_LINEAR_WGRADS else None)
         gz = gmm_ctx_backward(ctx.prior, glogp, bw.by_param)
+        gx = None
         for rec in reversed(ctx.tape):
-            bwd = BACKWARD[rec.kind]
-            if bwd is None:
+            if rec.kind == "pre":                        # nothing trainable at or above the pre-processing
+                if ctx.needs_input_grad[1]:
+                    gx = pre_ctx_backward(rec, gz, bw).reshape(shape).to(dtype)
                 break
-            gz = bwd(rec, gz, bw)
+            gz = BACKWARD[rec.kind](rec, gz, bw)
         _flush_linear_wgrads(bw, glogp.device)
-        return (None, None, None) + tuple(bw.by_param.get(p) for p in ctx.params)
+        return (None, gx, None) + tuple(bw.by_param.get(p) for p in ctx.params)

@@ -648,8 +648,10 @@ class FlowSequential(nn.Module):
         if torch.is_grad_enabled() and self._specialist():
             from .autograd_ctx import trainable as _trainable
             params = self._trainable_params()
-            if params and _trainable(self):  # specialist training under contextflow (autograd_ctx.py); other
-                                             # specialist models evaluate only: they fall through to the no_grad path
+            # specialist training under contextflow (autograd_ctx.py), and d logp / d x for an input that requires a gradient - also
+            # from a frozen or eval() specialist (the data-only walk); other specialist models evaluate only: they fall through
+            # to the no_grad path
+            if (params or (input.requires_grad and context is not None)) and _trainable(self):
                 if any(isinstance(m, ActNorm) and m.contextflow and not m.is_initialized() for m in self.sequence_modules):
                     with torch.no_grad():    # first call: the ActNorm data-dependent init
                         self._forward_layers(input, context)
@@ -768,25 +770,36 @@ class FlowSequential(nn.Module):
     def log_prob(self, input, context=None):
         return self.forward(input, context)[1]
 
-    def score(self, x, labels=None, weights=None):
+    def score(self, x, labels=None, weights=None, context=None):
         """(grad, logp): grad = d/dx sum_m w[b, m] logp[b, m], fp32 in the shape of x, and the (B, M) log-densities.
         weights: the (B, M) tensor w, used as given.  labels: an int or B class indices - one-hot rows (checked as `sample`
         checks them: ValueError for host values outside [0, M) or a wrong length).  Neither: the score of the marginal,
         d/dx log sum_m p(x | m), i.e. w = softmax(logp, dim=1) of the returned logp.  Both: ValueError.
         Always the data-only walk (the kernels of `forward`, a tape of the steps' aux buffers, the data halves of the backward:
         layers/autograd.input_gradient), whatever the parameters' requires_grad; works under no_grad and touches no .grad
-        and no requires_grad.  Generalist flows on the fused plan only: NotImplementedError otherwise."""
+        and no requires_grad.  Generalist flows on the fused plan; specialist flows with their `context` (the (B, nctx) integer
+        tensor `forward` takes) through autograd_ctx.taped_forward / input_gradient_ctx - the context encoders draw their noise as
+        `forward` does, it is a constant of the gradient and its log-density enters logp alone.  NotImplementedError otherwise."""
         _hip.require_device(x)
         if labels is not None and weights is not None:
             raise ValueError("score: give labels or weights, not both")
         self._refresh_generation()
-        if self._has_context_nets():
-            raise NotImplementedError("score of a context-conditioned (specialist) flow")
-        if not self._fusable():
+        specialist = self._has_context_nets()
+        if specialist:
+            from . import autograd_ctx
+            if context is None:
+                raise NotImplementedError("score of a context-conditioned (specialist) flow needs its context")
+            if not self._specialist() or not autograd_ctx.trainable(self):
+                raise NotImplementedError("score of a specialist flow: a context encoder or layout the taped forward is not built for")
+            if any(isinstance(m, ActNorm) and m.contextflow and not m.is_initialized() for m in self.sequence_modules):
+                raise NotImplementedError("score needs initialised ActNorms (run one forward first)")
+        elif not self._fusable():
             raise NotImplementedError("score needs the fused plan: a mixture prior, initialised ActNorms (run one forward first) and fused = True")
         from .autograd import input_gradient
         B, M = x.shape[0], self.mixtures
         xd = x.detach()
+        if specialist and B == 0:        # empty batch: nothing to launch
+            return xd.new_zeros(x.shape, dtype=torch.float32), xd.new_zeros((0, M), dtype=torch.float32)
         if labels is not None:
             lab, m = self.dist._class_labels(labels, B)
             if lab is None:
@@ -797,11 +810,14 @@ class FlowSequential(nn.Module):
                 raise ValueError("score: weights of shape %s, (%d, %d) expected" % (tuple(weights.shape), B, M))
             weights = weights.detach().to(device=xd.device)
         with torch.no_grad():
-            tape = []
-            _, logp = self._forward_fused(xd, None, tape=tape, data_only=True)
+            if specialist:
+                _, logp, tape = autograd_ctx.taped_forward(self, xd, context, data_only=True)
+            else:
+                tape = []
+                _, logp = self._forward_fused(xd, None, tape=tape, data_only=True)
             if weights is None:
                 weights = torch.softmax(logp, dim=1)
-            grad = input_gradient(tape, weights).reshape(x.shape)
+            grad = (autograd_ctx.input_gradient_ctx if specialist else input_gradient)(tape, weights).reshape(x.shape)
         return grad, logp
 
     def capture(self, example_input):

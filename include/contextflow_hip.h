@@ -655,6 +655,23 @@ int cf_gmm_ctx_pgrad_tab(const float* x, const float* mG, const float* inv_sig, 
                           const int* key, const float* r, float* pgm, float* pgs, int B, int M, int K, int D, int HW,
                           int64_t x_bstride, int slab, cf_stream_t stream);
 
+/* ---- the input gradient of log p(x | c) of a specialist flow (FlowSequential.score with a context): the data halves of the
+ * kernels above alone - no parameter gradient is formed, whatever trains.
+ * [Squeeze(2,2) ->] Conv1x1(c) -> ActNorm(c') backward w.r.t. the data: gx[b] = W_b^T (gz[b] * exp(-l_b)), W_b from m1 (B,C*C)
+ * [+ Wm - I] as cf_conv1x1_ctx (m1 NULL: the identity), l_b = m2[b, C:2C] [+ logs] (m2 NULL: no scale).  out_unsqueeze: gx in
+ * the (B, C/4, 2H, 2W) layout.  One wave per sample on the matrix pipe at (16,16,16) / (32,8,8) / (64,4,4) with 16-byte
+ * aligned operands, one workgroup per sample (LDS) elsewhere.                                                     */
+int cf_affine_ctx_bwd_data(const float* gz, const float* m1, const float* Wm, const float* m2, const float* logs, float* gx,
+                           int B, int C, int H, int W, int64_t gz_bstride, int out_unsqueeze, cf_stream_t stream);
+/* cf_flow_step_bwd_ctx without its operand planes: s_gh is not written either, gx is bitwise the same.           */
+int cf_flow_step_bwd_ctx_data(const float* x, const float* gz, const float* gld, const void* ws, const void* wsb,
+                              const float* sbias, float* gx, int B, int C, int H, int W, int64_t x_bstride, cf_stream_t stream);
+/* cf_gmm_ctx_bwd / cf_gmm_ctx_bwd_tab without gc: inv_sig / lsum / key non-NULL select the table form, sG the direct one;
+ * gx is bitwise the same.                                                                                         */
+int cf_gmm_ctx_bwd_data(const float* x, const float* mG, const float* sG, const float* inv_sig, const float* lsum,
+                        const float* logw, const float* c, const int* key, const float* g, const float* lp, float* gx, int B,
+                        int M, int K, int D, int HW, int64_t x_bstride, cf_stream_t stream);
+
 /* h[b,c2,:] += x[b, c2 % C, :] in place: identity branch of MaskedResidualBlock2d (`--coupling maf`,
  * layers/autoregressive/masked_conv_2d.py:93-98)                                                                */
 int cf_add_repeat(float* h, const float* x, int B, int C2, int C, int HW, cf_stream_t stream);
