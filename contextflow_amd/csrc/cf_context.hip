@@ -6,6 +6,8 @@
 // One workgroup owns one sample in the three per-sample kernels, so the per-sample parameters live in LDS / registers.
 #include "cf_common.h"
 #include <math.h>
+#include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -38,10 +40,6 @@ __global__ __launch_bounds__(256) void k_ctx_encode(const int64_t* __restrict__ 
     out[e] = (x + u[e]) / qbins[j];
 }
 
-// Conv1x1 with a context net (conv1x1.py:34-50): m = CN(c) reshaped (C, C) per sample;
-//   W_b = tril(m, -1) + diag(exp(diag m))            [+ NN - I under contextflow]
-//   z[b] = W_b x[b] per pixel;  ldj[b] = H W sum(diag m)   (the caller adds H W log|det NN| under contextflow -
-//   the reference's own expression, not the log-det of W_b).
 // row stride of the transposed per-sample matrix in LDS: C rounded up to 8 (16-byte rows for the float4 reads), plus 4
 // when that is a multiple of 32 (the transposed writes would otherwise all land in one bank)
 __host__ __device__ inline int conv1x1_ctx_cp(int C) {
@@ -77,25 +75,38 @@ __device__ __forceinline__ void stage_copy(float* __restrict__ dst, const float*
     }
 }
 
-// One workgroup per sample: W_b^T (row stride CP = C rounded up to 8, zero padded) and x in LDS; a thread owns one
-// pixel and 8 output channels at a time - per input channel one x read and two 16-byte (broadcast) reads of W_b^T.
-__global__ __launch_bounds__(256) void k_conv1x1_ctx(const float* __restrict__ x, const float* __restrict__ m,
-                                                     const float* __restrict__ Wm, float* __restrict__ z,
-                                                     float* __restrict__ ldj, int C, int HW, int64_t xbs) {
-    extern __shared__ __align__(16) float dyn[];
-    const int CP = conv1x1_ctx_cp(C);
-    float* Wt = dyn;                                  // Wt[i][o] = W_b[o][i], row stride CP
-    float* xs = dyn + C * CP;                         // [C][HW]
-    float* scr = xs + C * HW;                         // [4] (inside the dynamic block: no static LDS next to a 160 KiB request)
-    float* ms = scr + 4;                              // [C*C] this sample's CN(c) output, staged before the transposed read
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const float* mb = m + (int64_t)b * C * C;
-    const float* xb = x + (int64_t)b * xbs;
-    stage_copy(ms, mb, C * C, tid);
-    __syncthreads();
-    float dsum = 0.f;
-    // lanes walk i: ms read without bank conflicts, Wt written at stride CP; the shared NN matrix is fetched in batches of
-    // independent loads (a load inside the element loop costs one full memory latency per element)
+// ---- the per-sample matrix: element (o, i) of W_b = tril(m, -1) + diag(exp(diag m)) [+ NN - I] from v = m[o][i] and
+// wm = NN[o][i] (nn: under contextflow).  Two arithmetic families that round differently ON PURPOSE - every kernel keeps the bits
+// it has always produced, so the two orders must not be unified:
+//   LDS kernels:  base + (wm - delta)          base = v | exp(v) | 0 below / on / above the diagonal, delta = (o == i)
+//   wave kernels: (exp(v) - 1) + wm on the diagonal, v + wm elsewhere.  wb_element_wave is the first term, for the fragments on
+//                 the block diagonal; the fragments below it hold m as it is, those above 0, and the caller adds NN to all.
+//                 It also adds the diagonal's v to dsum (the log-det term of the forward; the backward has no use for it)
+__device__ __forceinline__ float wb_element(float v, float wm, bool nn, int o, int i) {
+    float w = o > i ? v : (o == i ? expf(v) : 0.f);
+    if (nn) w += wm - (o == i ? 1.f : 0.f);
+    return w;
+}
+__device__ __forceinline__ float wb_element_wave(float v, bool nn, int o, int i, float& dsum) {
+    const float ex = expf(v) - (nn ? 1.f : 0.f);
+    if (o == i) dsum += v;
+    return o > i ? v : (o == i ? ex : 0.f);
+}
+
+// Squeeze((2,2)) (squeeze.py:10-11): offset of (channel c, pixel p) of the squeezed (C, H, W) sample inside the un-squeezed
+// (C/4, 2H, 2W) one - the reads of a fused Squeeze in front of the pair, the writes of its adjoint
+__device__ __forceinline__ int squeeze_index(int c, int p, int W, int HW) {
+    const int yy = p / W, xx = p - yy * W;
+    return (c >> 2) * 4 * HW + (2 * yy + ((c >> 1) & 1)) * 2 * W + 2 * xx + (c & 1);
+}
+
+// The two LDS forms of W_b, built by the 256 threads of a workgroup.  Both fetch what they read from global memory in batches
+// of 8 independent loads at a clamped index (see stage_copy: a load inside the element loop costs one full memory latency per
+// element) and zero the padding up to CP.
+// Forward: Wt[i * CP + o] = W_b[o][i] from this sample's m staged in LDS (ms).  Lanes walk i: ms read without bank conflicts,
+// Wt written at stride CP.  Returns dsum + weight * (this lane's share of sum diag m).
+__device__ __forceinline__ float build_wb_transposed(float* Wt, const float* ms, const float* Wm, int C, int CP, float weight,
+                                                     float dsum, int tid) {
     for (int e0 = tid; e0 < CP * C; e0 += 8 * 256) {
         float wm[8];
 #pragma unroll
@@ -108,28 +119,58 @@ __global__ __launch_bounds__(256) void k_conv1x1_ctx(const float* __restrict__ x
                 float w = 0.f;
                 if (o < C) {
                     const float v = ms[e];
-                    w = o > i ? v : (o == i ? expf(v) : 0.f);
-                    if (o == i) dsum += v;
-                    if (Wm != nullptr) w += wm[k] - (o == i ? 1.f : 0.f);
+                    w = wb_element(v, wm[k], Wm != nullptr, o, i);
+                    if (o == i) dsum = fmaf(weight, v, dsum);
                 }
                 Wt[i * CP + o] = w;
             }
         }
     }
-    stage_copy(xs, xb, C * HW, tid);                  // xs is 16-byte aligned: C * CP is a multiple of 8
-    dsum = cf_block_sum<4>(dsum, scr);                // also the barrier that publishes Wt / xs
-    if (tid == 0) ldj[b] = dsum * (float)HW;
-    float* zb = z + (int64_t)b * C * HW;
-    const int nob = CP >> 3;
-    for (int e = tid; e < nob * HW; e += 256) {
-        const int ob = e / HW, p = e - ob * HW, o0 = ob * 8;
+    return dsum;
+}
+// Backward: Wb[o * CP + i] = W_b[o][i] [* rowscale[o] (SCALE)] from this sample's m in global memory (mb).
+template <bool SCALE>
+__device__ __forceinline__ void build_wb_rowmajor(float* Wb, const float* mb, const float* Wm, const float* rowscale, int C, int CP,
+                                                  int tid) {
+    for (int e0 = tid; e0 < C * CP; e0 += 8 * 256) {
+        float mv[8], wm[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int e = min(e0 + k * 256, C * CP - 1), o = e / CP, i = min(e - o * CP, C - 1);
+            mv[k] = mb[o * C + i];
+            wm[k] = Wm != nullptr ? Wm[o * C + i] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int e = e0 + k * 256;
+            if (e < C * CP) {
+                const int o = e / CP, i = e - o * CP;
+                float w = 0.f;
+                if (i < C) {
+                    w = wb_element(mv[k], wm[k], Wm != nullptr, o, i);
+                    if constexpr (SCALE) w *= rowscale[o];
+                }
+                Wb[e] = w;
+            }
+        }
+    }
+}
+
+// The product of all four LDS kernels: out[c][p] = sum_k A[k * CP + c] v[k * vs + p], k < C.  A thread owns one pixel p and 8
+// channels c0 .. c0 + 7 at a time - per k one read of v and two 16-byte (broadcast) reads of A - and hands each of its
+// sums to epi(c, p, acc).
+template <class Epi>
+__device__ __forceinline__ void pixel8_product(const float* A, const float* v, int C, int CP, int vs, int HW, int tid, Epi epi) {
+    const int ncb = CP >> 3;
+    for (int e = tid; e < ncb * HW; e += 256) {
+        const int cb = e / HW, p = e - cb * HW, c0 = cb * 8;
         float acc[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc[k] = 0.f;
-        for (int i = 0; i < C; ++i) {
-            const float xv = xs[i * HW + p];
-            const float4 w0 = *reinterpret_cast<const float4*>(&Wt[i * CP + o0]);
-            const float4 w1 = *reinterpret_cast<const float4*>(&Wt[i * CP + o0 + 4]);
+        for (int k = 0; k < C; ++k) {
+            const float xv = v[k * vs + p];
+            const float4 w0 = *reinterpret_cast<const float4*>(&A[k * CP + c0]);
+            const float4 w1 = *reinterpret_cast<const float4*>(&A[k * CP + c0 + 4]);
             acc[0] = fmaf(w0.x, xv, acc[0]); acc[1] = fmaf(w0.y, xv, acc[1]);
             acc[2] = fmaf(w0.z, xv, acc[2]); acc[3] = fmaf(w0.w, xv, acc[3]);
             acc[4] = fmaf(w1.x, xv, acc[4]); acc[5] = fmaf(w1.y, xv, acc[5]);
@@ -137,8 +178,61 @@ __global__ __launch_bounds__(256) void k_conv1x1_ctx(const float* __restrict__ x
         }
 #pragma unroll
         for (int k = 0; k < 8; ++k)
-            if (o0 + k < C) zb[(int64_t)(o0 + k) * HW + p] = acc[k];
+            if (c0 + k < C) epi(c0 + k, p, acc[k]);
     }
+}
+
+// ActNorm with a context net: t_b, exp(-l_b) and l_b of channel c of sample b from m = CN(c) = [t_b | logs_b] per sample, plus
+// the shared NN_t / NN_logs under contextflow (both given or neither).  WITH_T = false: the data backward has no use for t_b and
+// no t to read.
+struct ActNormCtxTerms { float t, s, l; };
+template <bool WITH_T = true>
+__device__ __forceinline__ ActNormCtxTerms actnorm_ctx_terms(const float* m, int b, const float* t, const float* logs, int C, int c) {
+    float tv = 0.f;
+    if constexpr (WITH_T) tv = m[(int64_t)b * 2 * C + c];
+    float lv = m[(int64_t)b * 2 * C + C + c];
+    if ((WITH_T ? t : logs) != nullptr) {
+        if constexpr (WITH_T) tv += t[c];
+        lv += logs[c];
+    }
+    return {tv, expf(-lv), lv};
+}
+
+// dyn[] of the two forward LDS kernels: the arrays in their order, sizes in floats.  The kernel carves dyn[] with these
+// sizes (on dyn itself: the compiler must see LDS addresses), the launcher requests floats().  NACT = C with the ActNorm
+// terms of k_affine_ctx, 0 without.  scr lies inside the dynamic block: no static LDS next to a 160 KiB request.
+struct CtxFwdLds {
+    int CP;
+    int nWt;      // Wt[i][o] = W_b[o][i], row stride CP
+    int nxs;      // xs[C][HW]  (16-byte aligned: C * CP is a multiple of 4)
+    int nact;     // after scr[nscr]: tb[NACT] = t_b, sb[NACT] = exp(-logs_b)
+    int nms;      // ms[C*C] this sample's CN(c) output, staged before the transposed read
+    __host__ __device__ CtxFwdLds(int C, int HW, int NACT) : CP(conv1x1_ctx_cp(C)), nWt(C * CP), nxs(C * HW), nact(NACT), nms(C * C) {}
+    static constexpr int nscr = 4;
+    __host__ __device__ int floats() const { return nWt + nxs + nscr + 2 * nact + nms; }
+};
+
+// Conv1x1 with a context net (conv1x1.py:34-50): m = CN(c) reshaped (C, C) per sample;
+//   W_b = tril(m, -1) + diag(exp(diag m))            [+ NN - I under contextflow]
+//   z[b] = W_b x[b] per pixel;  ldj[b] = H W sum(diag m)   (the caller adds H W log|det NN| under contextflow -
+//   the reference's own expression, not the log-det of W_b).
+// One workgroup per sample: W_b^T (row stride CP = C rounded up to 8, zero padded) and x in LDS, then pixel8_product over the
+// output channels.
+__global__ __launch_bounds__(256) void k_conv1x1_ctx(const float* __restrict__ x, const float* __restrict__ m,
+                                                     const float* __restrict__ Wm, float* __restrict__ z,
+                                                     float* __restrict__ ldj, int C, int HW, int64_t xbs) {
+    extern __shared__ __align__(16) float dyn[];
+    const CtxFwdLds L(C, HW, 0);
+    float *Wt = dyn, *xs = Wt + L.nWt, *scr = xs + L.nxs, *ms = scr + L.nscr;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    stage_copy(ms, m + (int64_t)b * C * C, C * C, tid);
+    __syncthreads();
+    float dsum = build_wb_transposed(Wt, ms, Wm, C, L.CP, 1.f, 0.f, tid);
+    stage_copy(xs, x + (int64_t)b * xbs, C * HW, tid);
+    dsum = cf_block_sum<4>(dsum, scr);                // also the barrier that publishes Wt / xs
+    if (tid == 0) ldj[b] = dsum * (float)HW;
+    float* zb = z + (int64_t)b * C * HW;
+    pixel8_product(Wt, xs, C, L.CP, HW, HW, tid, [=](int o, int p, float acc) { zb[(int64_t)o * HW + p] = acc; });
 }
 
 // ActNorm with a context net (actnorm.py:40-60): m = CN(c) = [t_b | logs_b] per sample (+ the shared NN_t / NN_logs
@@ -152,10 +246,9 @@ __global__ __launch_bounds__(256) void k_actnorm_ctx(const float* __restrict__ x
     const int b = blockIdx.x, tid = threadIdx.x;
     float lsum = 0.f;
     if (tid < C) {
-        float tv = m[(int64_t)b * 2 * C + tid], lv = m[(int64_t)b * 2 * C + C + tid];
-        if (t != nullptr) { tv += t[tid]; lv += logs[tid]; }
-        tb[tid] = tv; sb[tid] = expf(-lv);
-        lsum = lv;
+        const ActNormCtxTerms a = actnorm_ctx_terms(m, b, t, logs, C, tid);
+        tb[tid] = a.t; sb[tid] = a.s;
+        lsum = a.l;
     }
     lsum = cf_block_sum<4>(lsum, scr);
     if (tid == 0) ldj[b] = lsum;
@@ -177,32 +270,27 @@ __global__ __launch_bounds__(256) void k_affine_ctx(const float* __restrict__ x,
                                                     const float* __restrict__ lad, float cadd, float* __restrict__ z,
                                                     float* __restrict__ ldj, int C, int H, int W, int64_t xbs, int accumulate) {
     extern __shared__ __align__(16) float dyn[];
-    const int CP = conv1x1_ctx_cp(C), HW = H * W;
-    float* Wt = dyn;                                  // Wt[i][o] = W_b[o][i], row stride CP
-    float* xs = dyn + C * CP;                         // [C][HW]
-    float* scr = xs + C * HW;                         // [4]
-    float* tb = scr + 4;                              // [C]  t_b
-    float* sb = tb + C;                               // [C]  exp(-logs_b)
-    float* ms = sb + C;                               // [C*C] this sample's Conv1x1.CN(c), staged before the transposed read
+    const int HW = H * W;
+    const CtxFwdLds L(C, HW, C);
+    float *Wt = dyn, *xs = Wt + L.nWt, *scr = xs + L.nxs, *tb = scr + L.nscr, *sb = tb + L.nact, *ms = sb + L.nact;
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* xb = x + (int64_t)b * xbs;
     stage_copy(ms, m1 + (int64_t)b * C * C, C * C, tid);
     float dsum = 0.f;
     if (tid < C) {
-        float tv = m2[(int64_t)b * 2 * C + tid], lv = m2[(int64_t)b * 2 * C + C + tid];
-        if (t != nullptr) { tv += t[tid]; lv += logs[tid]; }
-        tb[tid] = tv; sb[tid] = expf(-lv);
-        dsum = lv;                                    // joins the block sum below with weight 1 (the diagonal gets H W)
+        const ActNormCtxTerms a = actnorm_ctx_terms(m2, b, t, logs, C, tid);
+        tb[tid] = a.t; sb[tid] = a.s;
+        dsum = a.l;                                  // joins the block sum below with weight 1 (the diagonal gets H W)
     }
     if constexpr (!SQ) {
-        stage_copy(xs, xb, C * HW, tid);              // xs is 16-byte aligned: C * CP is a multiple of 4
+        stage_copy(xs, xb, C * HW, tid);
     } else {
         for (int e0 = tid; e0 < C * HW; e0 += 8 * 256) {
             float v[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                const int e = min(e0 + k * 256, C * HW - 1), c = e / HW, p = e - c * HW, yy = p / W, xx = p - yy * W;
-                v[k] = xb[(c >> 2) * 4 * HW + (2 * yy + ((c >> 1) & 1)) * 2 * W + 2 * xx + (c & 1)];
+                const int e = min(e0 + k * 256, C * HW - 1), c = e / HW;
+                v[k] = xb[squeeze_index(c, e - c * HW, W, HW)];
             }
 #pragma unroll
             for (int k = 0; k < 8; ++k)
@@ -211,52 +299,47 @@ __global__ __launch_bounds__(256) void k_affine_ctx(const float* __restrict__ x,
     }
     __syncthreads();
     const float hw = (float)HW;
-    for (int e0 = tid; e0 < CP * C; e0 += 8 * 256) {
-        float wm[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) wm[k] = Wm != nullptr ? Wm[min(e0 + k * 256, C * C - 1)] : 0.f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int e = e0 + k * 256;
-            if (e < CP * C) {
-                const int o = e / C, i = e - o * C;
-                float w = 0.f;
-                if (o < C) {
-                    const float v = ms[e];
-                    w = o > i ? v : (o == i ? expf(v) : 0.f);
-                    if (o == i) dsum = fmaf(hw, v, dsum);
-                    if (Wm != nullptr) w += wm[k] - (o == i ? 1.f : 0.f);
-                }
-                Wt[i * CP + o] = w;
-            }
-        }
-    }
+    dsum = build_wb_transposed(Wt, ms, Wm, C, L.CP, hw, dsum, tid);
     dsum = cf_block_sum<4>(dsum, scr);                // also the barrier that publishes Wt
     if (tid == 0) {
         const float v = dsum + (lad != nullptr ? hw * lad[0] : 0.f) + cadd;
         ldj[b] = accumulate ? ldj[b] + v : v;
     }
     float* zb = z + (int64_t)b * C * HW;
-    const int nob = CP >> 3;
-    for (int e = tid; e < nob * HW; e += 256) {
-        const int ob = e / HW, p = e - ob * HW, o0 = ob * 8;
-        float acc[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) acc[k] = 0.f;
-        for (int i = 0; i < C; ++i) {
-            const float xv = xs[i * HW + p];
-            const float4 w0 = *reinterpret_cast<const float4*>(&Wt[i * CP + o0]);
-            const float4 w1 = *reinterpret_cast<const float4*>(&Wt[i * CP + o0 + 4]);
-            acc[0] = fmaf(w0.x, xv, acc[0]); acc[1] = fmaf(w0.y, xv, acc[1]);
-            acc[2] = fmaf(w0.z, xv, acc[2]); acc[3] = fmaf(w0.w, xv, acc[3]);
-            acc[4] = fmaf(w1.x, xv, acc[4]); acc[5] = fmaf(w1.y, xv, acc[5]);
-            acc[6] = fmaf(w1.z, xv, acc[6]); acc[7] = fmaf(w1.w, xv, acc[7]);
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (o0 + k < C) zb[(int64_t)(o0 + k) * HW + p] = (acc[k] - tb[o0 + k]) * sb[o0 + k];
-    }
+    pixel8_product(Wt, xs, C, L.CP, HW, HW, tid, [=](int o, int p, float acc) { zb[(int64_t)o * HW + p] = (acc - tb[o]) * sb[o]; });
 }
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// What k_affine_ctx_wave and its transpose k_affine_ctx_bwd_wave (below) share: the fragment grid of a (C, W, W) level, the
+// rows of a fused Squeeze((2,2)) and the ActNorm terms in the layout of the D rows.  Lane (n = lane & 15, kk = lane >> 4).
+template <int C, int W>
+struct AffineWave {
+    static constexpr int HW = W * W, RT = C / 16, NG = C / 16, WIDE = HW >= 64, NT = WIDE ? HW / 64 : 1, NJ = WIDE ? 4 : 1;
+    // the pixel of column n of pixel tile T; WIDE: the first of 4 pixels of one image row (W >= 4), one per column tile
+    static __device__ __forceinline__ int pixel0(int T, int n) { return WIDE ? 64 * T + 4 * n : n; }
+    // un-squeezed (C/4, 2W, 2W) sample: where row 2 yy + dy of channel q meets squeezed pixel (yy, xx) - the 2 floats there
+    // are its phases (dy, dx = 0 | 1), squeezed channels 4 q + 2 dy + dx; WIDE: 8 floats, pixels (yy, xx .. xx + 3)
+    template <class P>
+    static __device__ __forceinline__ P phase_row(P sample, int q, int dy, int yy, int xx) {
+        return sample + q * 4 * HW + (2 * yy + dy) * 2 * W + 2 * xx;
+    }
+    // t_b and l_b of rows o0 .. o0 + 3 of sample b, as actnorm_ctx_terms
+    template <bool WITH_T = true>
+    static __device__ __forceinline__ void actnorm_rows(const float* m2, int b, const float* t, const float* logs, int o0, float4& tv,
+                                                        float4& lv) {
+        if constexpr (WITH_T) tv = *reinterpret_cast<const float4*>(m2 + (int64_t)b * 2 * C + o0);
+        lv = *reinterpret_cast<const float4*>(m2 + (int64_t)b * 2 * C + C + o0);
+        if ((WITH_T ? t : logs) != nullptr) {
+            if constexpr (WITH_T) {
+                const float4 t0 = *reinterpret_cast<const float4*>(t + o0);
+                tv.x += t0.x; tv.y += t0.y; tv.z += t0.z; tv.w += t0.w;
+            }
+            const float4 l0 = *reinterpret_cast<const float4*>(logs + o0);
+            lv.x += l0.x; lv.y += l0.y; lv.z += l0.z; lv.w += l0.w;
+        }
+    }
+};
 
 // The same on the matrix pipe for the three levels of the image flows, ONE WAVE per sample and no LDS: per sample the
 // product is (C x C) (C x HW) = 64 v_mfma_f32_16x16x4_f32 whatever the level, and every operand is read from global memory
@@ -278,12 +361,12 @@ __global__ __launch_bounds__(256) void k_affine_ctx_wave(const float* __restrict
                                                          const float* __restrict__ t, const float* __restrict__ logs,
                                                          const float* __restrict__ lad, float cadd, float* __restrict__ z,
                                                          float* __restrict__ ldj, int B, int64_t xbs, int accumulate) {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    constexpr int HW = W * W, RT = C / 16, NG = C / 16, WIDE = HW >= 64, NT = WIDE ? HW / 64 : 1;
+    using G = AffineWave<C, W>;
+    constexpr int HW = G::HW, RT = G::RT, NG = G::NG, WIDE = G::WIDE, NT = G::NT, NJ = G::NJ;
     const int lane = threadIdx.x & 63, n = lane & 15, kk = lane >> 4;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;                                // a whole wave: the kernel has no barrier
-    constexpr int NBLK = (C / 16) * (C / 16 + 1) / 2;
+    constexpr int NBLK = RT * (RT + 1) / 2;
     const float* mb = m1 + (int64_t)b * (BLK ? NBLK * 256 : C * C);
     const float* xb = x + (int64_t)b * xbs;
     // ---- A fragments.  W_b is block lower triangular on the 16 x 16 grid of fragments: blocks above the diagonal hold NN alone
@@ -305,12 +388,7 @@ __global__ __launch_bounds__(256) void k_affine_ctx_wave(const float* __restrict
             float v[4] = {a[rt][g].x, a[rt][g].y, a[rt][g].z, a[rt][g].w};
             if (g == rt) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int i = i0 + e;
-                    const float ex = expf(v[e]) - (Wm != nullptr ? 1.f : 0.f);
-                    if (o == i) dsum += v[e];
-                    v[e] = o > i ? v[e] : (o == i ? ex : 0.f);
-                }
+                for (int e = 0; e < 4; ++e) v[e] = wb_element_wave(v[e], Wm != nullptr, o, i0 + e, dsum);
             }
             if (Wm != nullptr) {
                 const float4 wv = *reinterpret_cast<const float4*>(Wm + o * C + i0);
@@ -319,18 +397,18 @@ __global__ __launch_bounds__(256) void k_affine_ctx_wave(const float* __restrict
             a[rt][g] = make_float4(v[0], v[1], v[2], v[3]);
         }
     // ---- the product
-    f32x4 acc[RT][NT][WIDE ? 4 : 1];
+    f32x4 acc[RT][NT][NJ];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
         for (int T = 0; T < NT; ++T)
 #pragma unroll
-            for (int j = 0; j < (WIDE ? 4 : 1); ++j) acc[rt][T][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < NJ; ++j) acc[rt][T][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int T = 0; T < NT; ++T)
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
-            float xv[4][WIDE ? 4 : 1];                 // [k-step e][column tile j]
+            float xv[4][NJ];                           // [k-step e][column tile j]
             if constexpr (WIDE) {
                 if constexpr (!SQ) {
 #pragma unroll
@@ -339,10 +417,10 @@ __global__ __launch_bounds__(256) void k_affine_ctx_wave(const float* __restrict
                         xv[e][0] = v.x; xv[e][1] = v.y; xv[e][2] = v.z; xv[e][3] = v.w;
                     }
                 } else {
-                    const int p0 = 64 * T + 4 * n, yy = p0 / W, xx = p0 - yy * W;       // 4 pixels of one image row (W >= 4)
+                    const int p0 = G::pixel0(T, n), yy = p0 / W, xx = p0 - yy * W;
 #pragma unroll
                     for (int dy = 0; dy < 2; ++dy) {
-                        const float* row = xb + (4 * g + kk) * 4 * HW + (2 * yy + dy) * 2 * W + 2 * xx;
+                        const float* row = G::phase_row(xb, 4 * g + kk, dy, yy, xx);
                         const float4 u0 = *reinterpret_cast<const float4*>(row), u1 = *reinterpret_cast<const float4*>(row + 4);
                         xv[2 * dy][0] = u0.x; xv[2 * dy][1] = u0.z; xv[2 * dy][2] = u1.x; xv[2 * dy][3] = u1.z;
                         xv[2 * dy + 1][0] = u0.y; xv[2 * dy + 1][1] = u0.w; xv[2 * dy + 1][2] = u1.y; xv[2 * dy + 1][3] = u1.w;
@@ -353,10 +431,10 @@ __global__ __launch_bounds__(256) void k_affine_ctx_wave(const float* __restrict
 #pragma unroll
                     for (int e = 0; e < 4; ++e) xv[e][0] = xb[(16 * g + 4 * kk + e) * HW + n];
                 } else {
-                    const int yy = n / W, xx = n - yy * W;
+                    const int p0 = G::pixel0(T, n), yy = p0 / W, xx = p0 - yy * W;
 #pragma unroll
                     for (int dy = 0; dy < 2; ++dy) {
-                        const float2 u = *reinterpret_cast<const float2*>(xb + (4 * g + kk) * 4 * HW + (2 * yy + dy) * 2 * W + 2 * xx);
+                        const float2 u = *reinterpret_cast<const float2*>(G::phase_row(xb, 4 * g + kk, dy, yy, xx));
                         xv[2 * dy][0] = u.x; xv[2 * dy + 1][0] = u.y;
                     }
                 }
@@ -367,7 +445,7 @@ __global__ __launch_bounds__(256) void k_affine_ctx_wave(const float* __restrict
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
 #pragma unroll
-                    for (int j = 0; j < (WIDE ? 4 : 1); ++j)
+                    for (int j = 0; j < NJ; ++j)
                         acc[rt][T][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], xv[e][j], acc[rt][T][j], 0, 0, 0);
             }
         }
@@ -377,13 +455,8 @@ __global__ __launch_bounds__(256) void k_affine_ctx_wave(const float* __restrict
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
         const int o0 = 16 * rt + 4 * kk;
-        float4 tv = *reinterpret_cast<const float4*>(m2 + (int64_t)b * 2 * C + o0);
-        float4 lv = *reinterpret_cast<const float4*>(m2 + (int64_t)b * 2 * C + C + o0);
-        if (t != nullptr) {
-            const float4 t0 = *reinterpret_cast<const float4*>(t + o0), l0 = *reinterpret_cast<const float4*>(logs + o0);
-            tv.x += t0.x; tv.y += t0.y; tv.z += t0.z; tv.w += t0.w;
-            lv.x += l0.x; lv.y += l0.y; lv.z += l0.z; lv.w += l0.w;
-        }
+        float4 tv, lv;
+        G::actnorm_rows(m2, b, t, logs, o0, tv, lv);
         if (n == 0) lsum += (lv.x + lv.y) + (lv.z + lv.w);
         const float tt[4] = {tv.x, tv.y, tv.z, tv.w};
         const float ss[4] = {expf(-lv.x), expf(-lv.y), expf(-lv.z), expf(-lv.w)};
@@ -608,6 +681,20 @@ __global__ __launch_bounds__(64) void k_sigmoid_ldj(const float* __restrict__ x,
 // ---- backward of the context branches (specialist training under contextflow: the CN nets and the priors' embedding
 // tables are the trainable parameters; the generalist's own parameters are frozen, model.py / coupling.py:36) ------
 
+// dyn[] of the two backward LDS kernels, as CtxFwdLds.  NSB = C with the exp(-l_b) row of k_affine_ctx_bwd_data, 0 without;
+// XPLANE: the x plane of k_conv1x1_ctx_bwd; MATRIX = false: sb alone (the lone ActNorm of k_affine_ctx_bwd_data).
+struct CtxBwdLds {
+    int CP, HWP;
+    int nsb;      // sb[NSB] exp(-l_b), rounded up to 16 bytes
+    int nWb;      // Wb[o][i], row stride CP (zero padded)
+    int nxs;      // xs[C][HWP] if XPLANE
+    int ngs;      // gs[C][HWP]
+    __host__ __device__ CtxBwdLds(int C, int HW, int NSB, bool XPLANE, bool MATRIX = true)
+        : CP((C + 7) & ~7), HWP(HW | 1), nsb((NSB + 3) & ~3), nWb(MATRIX ? C * CP : 0), nxs(MATRIX && XPLANE ? C * HWP : 0),
+          ngs(MATRIX ? C * HWP : 0) {}
+    __host__ __device__ int floats() const { return nsb + nWb + nxs + ngs; }
+};
+
 // Conv1x1 with a context net, backward: gx[b] = W_b^T gz[b];  G = sum_p gz[b][:,p] x[b][:,p]^T;
 // gm[b][o][i] = G[o][i] (o > i) | G[i][i] exp(m_ii) + H W gld[b] (o == i) | 0 (o < i)      (d/d CN(c) output)
 // One workgroup per sample; W_b (row stride CP), x and gz (row stride HWP = odd: the (o, i) products below walk rows
@@ -617,10 +704,9 @@ __global__ __launch_bounds__(256) void k_conv1x1_ctx_bwd(const float* __restrict
                                                          const float* __restrict__ gld, float* __restrict__ gx,
                                                          float* __restrict__ gm, int C, int HW, int64_t xbs, int64_t gzbs) {
     extern __shared__ __align__(16) float dyn[];
-    const int CP = (C + 7) & ~7, HWP = HW | 1;
-    float* Wb = dyn;                                  // Wb[o][i], row stride CP (zero padded)
-    float* xs = dyn + C * CP;                         // [C][HWP]
-    float* gs = xs + C * HWP;                         // [C][HWP]
+    const CtxBwdLds L(C, HW, 0, true);
+    const int CP = L.CP, HWP = L.HWP;
+    float *Wb = dyn, *xs = Wb + L.nWb, *gs = xs + L.nxs;
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* mb = m + (int64_t)b * C * C;
     const float* xb = x + (int64_t)b * xbs;
@@ -635,49 +721,11 @@ __global__ __launch_bounds__(256) void k_conv1x1_ctx_bwd(const float* __restrict
             if (e < C * HW) { const int c = e / HW, p = e - c * HW; xs[c * HWP + p] = xv[i]; gs[c * HWP + p] = gv[i]; }
         }
     }
-    for (int e0 = tid; e0 < C * CP; e0 += 8 * 256) {   // batches of independent loads (see k_conv1x1_ctx)
-        float mv[8], wm[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int e = min(e0 + k * 256, C * CP - 1), o = e / CP, i = min(e - o * CP, C - 1);
-            mv[k] = mb[o * C + i];
-            wm[k] = Wm != nullptr ? Wm[o * C + i] : 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int e = e0 + k * 256;
-            if (e < C * CP) {
-                const int o = e / CP, i = e - o * CP;
-                float w = 0.f;
-                if (i < C) {
-                    w = o > i ? mv[k] : (o == i ? expf(mv[k]) : 0.f);
-                    if (Wm != nullptr) w += wm[k] - (o == i ? 1.f : 0.f);
-                }
-                Wb[e] = w;
-            }
-        }
-    }
+    build_wb_rowmajor<false>(Wb, mb, Wm, nullptr, C, CP, tid);
     __syncthreads();
     float* gxb = gx + (int64_t)b * C * HW;
-    const int nib = CP >> 3;
-    for (int e = tid; e < nib * HW; e += 256) {       // gx = W_b^T gz: a pixel and 8 input channels per thread
-        const int ib = e / HW, p = e - ib * HW, i0 = ib * 8;
-        float acc[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) acc[k] = 0.f;
-        for (int o = 0; o < C; ++o) {
-            const float gv = gs[o * HWP + p];
-            const float4 w0 = *reinterpret_cast<const float4*>(&Wb[o * CP + i0]);
-            const float4 w1 = *reinterpret_cast<const float4*>(&Wb[o * CP + i0 + 4]);
-            acc[0] = fmaf(w0.x, gv, acc[0]); acc[1] = fmaf(w0.y, gv, acc[1]);
-            acc[2] = fmaf(w0.z, gv, acc[2]); acc[3] = fmaf(w0.w, gv, acc[3]);
-            acc[4] = fmaf(w1.x, gv, acc[4]); acc[5] = fmaf(w1.y, gv, acc[5]);
-            acc[6] = fmaf(w1.z, gv, acc[6]); acc[7] = fmaf(w1.w, gv, acc[7]);
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (i0 + k < C) gxb[(int64_t)(i0 + k) * HW + p] = acc[k];
-    }
+    // gx = W_b^T gz over the input channels
+    pixel8_product(Wb, gs, C, CP, HWP, HW, tid, [=](int i, int p, float acc) { gxb[(int64_t)i * HW + p] = acc; });
     float* gmb = gm + (int64_t)b * C * C;
     const float gl = gld[b] * (float)HW;
     for (int e = tid; e < C * C; e += 256) {          // lanes walk i (rows of xs: odd stride), o is shared
@@ -708,9 +756,8 @@ __global__ __launch_bounds__(256) void k_actnorm_ctx_bwd(const float* __restrict
     const float* gb = gz + (int64_t)b * gzbs;
     float* gxb = gx + (int64_t)b * C * HW;
     for (int c = wave; c < C; c += 4) {               // a wave owns a channel at a time
-        float tv = m[(int64_t)b * 2 * C + c], lv = m[(int64_t)b * 2 * C + C + c];
-        if (t != nullptr) { tv += t[c]; lv += logs[c]; }
-        const float s = expf(-lv);
+        const ActNormCtxTerms a = actnorm_ctx_terms(m, b, t, logs, C, c);
+        const float tv = a.t, s = a.s;
         float s0 = 0.f, s1 = 0.f;
         for (int p = lane; p < HW; p += 64) {
             const float g = gb[(int64_t)c * HW + p], z = (xb[(int64_t)c * HW + p] - tv) * s;
@@ -731,11 +778,6 @@ __global__ __launch_bounds__(256) void k_actnorm_ctx_bwd(const float* __restrict
 //   l_b = m2[b, C:2C] [+ logs] (m2 == NULL: no scale)
 // Neither log-det depends on x, so neither x, t nor gld is read, and none of the C x C / 2C parameter gradients of
 // k_conv1x1_ctx_bwd / k_actnorm_ctx_bwd is formed.  USQ: gx is stored in the (C/4, 2H, 2W) layout in front of a Squeeze((2,2)).
-__device__ __forceinline__ int unsqueezed_index(int c, int p, int W, int HW) {
-    const int yy = p / W, xx = p - yy * W;
-    return (c >> 2) * 4 * HW + (2 * yy + ((c >> 1) & 1)) * 2 * W + 2 * xx + (c & 1);
-}
-
 // Any shape, any alignment: one workgroup per sample, W_b with exp(-l_b) folded into its rows (row stride CP) and gz (row
 // stride HWP, odd) in LDS, as k_conv1x1_ctx_bwd without its xs plane and G products; a thread owns a pixel and 8 input channels.
 template <bool USQ>
@@ -744,18 +786,15 @@ __global__ __launch_bounds__(256) void k_affine_ctx_bwd_data(const float* __rest
                                                              const float* __restrict__ logs, float* __restrict__ gx, int C,
                                                              int H, int W, int64_t gzbs) {
     extern __shared__ __align__(16) float dyn[];
-    const int CP = (C + 7) & ~7, HW = H * W, HWP = HW | 1;
-    float* sb = dyn;                                  // [C] exp(-l_b)
-    float* Wb = dyn + ((C + 3) & ~3);                 // Wb[o][i] = W_b[o][i] exp(-l_b[o]), row stride CP (zero padded)
-    float* gs = Wb + C * CP;                          // [C][HWP]
+    const int HW = H * W;
+    const CtxBwdLds L(C, HW, C, false);
+    const int CP = L.CP, HWP = L.HWP;
+    float *sb = dyn, *Wb = sb + L.nsb, *gs = Wb + L.nWb;          // Wb[o][i] = W_b[o][i] exp(-l_b[o])
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* gb = gz + (int64_t)b * gzbs;
     float* gxb = gx + (int64_t)b * C * HW;
-    for (int c = tid; c < C; c += 256) {
-        float lv = 0.f;
-        if (m2 != nullptr) { lv = m2[(int64_t)b * 2 * C + C + c]; if (logs != nullptr) lv += logs[c]; }
-        sb[c] = m2 != nullptr ? expf(-lv) : 1.f;
-    }
+    for (int c = tid; c < C; c += 256)
+        sb[c] = m2 != nullptr ? actnorm_ctx_terms<false>(m2, b, nullptr, logs, C, c).s : 1.f;
     __syncthreads();
     if (m1 == nullptr) {                              // ActNorm alone: a scale per channel
         for (int e0 = tid; e0 < C * HW; e0 += 4 * 256) {
@@ -765,7 +804,7 @@ __global__ __launch_bounds__(256) void k_affine_ctx_bwd_data(const float* __rest
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int e = e0 + i * 256;
-                if (e < C * HW) { const int c = e / HW, p = e - c * HW; gxb[USQ ? unsqueezed_index(c, p, W, HW) : e] = gv[i] * sb[c]; }
+                if (e < C * HW) { const int c = e / HW, p = e - c * HW; gxb[USQ ? squeeze_index(c, p, W, HW) : e] = gv[i] * sb[c]; }
             }
         }
         return;
@@ -781,49 +820,10 @@ __global__ __launch_bounds__(256) void k_affine_ctx_bwd_data(const float* __rest
             if (e < C * HW) { const int c = e / HW, p = e - c * HW; gs[c * HWP + p] = gv[i]; }
         }
     }
-    for (int e0 = tid; e0 < C * CP; e0 += 8 * 256) {
-        float mv[8], wm[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int e = min(e0 + k * 256, C * CP - 1), o = e / CP, i = min(e - o * CP, C - 1);
-            mv[k] = mb[o * C + i];
-            wm[k] = Wm != nullptr ? Wm[o * C + i] : 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int e = e0 + k * 256;
-            if (e < C * CP) {
-                const int o = e / CP, i = e - o * CP;
-                float w = 0.f;
-                if (i < C) {
-                    w = o > i ? mv[k] : (o == i ? expf(mv[k]) : 0.f);
-                    if (Wm != nullptr) w += wm[k] - (o == i ? 1.f : 0.f);
-                    w *= sb[o];
-                }
-                Wb[e] = w;
-            }
-        }
-    }
+    build_wb_rowmajor<true>(Wb, mb, Wm, sb, C, CP, tid);
     __syncthreads();
-    const int nib = CP >> 3;
-    for (int e = tid; e < nib * HW; e += 256) {       // gx = W_b^T (s gz): a pixel and 8 input channels per thread
-        const int ib = e / HW, p = e - ib * HW, i0 = ib * 8;
-        float acc[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) acc[k] = 0.f;
-        for (int o = 0; o < C; ++o) {
-            const float gv = gs[o * HWP + p];
-            const float4 w0 = *reinterpret_cast<const float4*>(&Wb[o * CP + i0]);
-            const float4 w1 = *reinterpret_cast<const float4*>(&Wb[o * CP + i0 + 4]);
-            acc[0] = fmaf(w0.x, gv, acc[0]); acc[1] = fmaf(w0.y, gv, acc[1]);
-            acc[2] = fmaf(w0.z, gv, acc[2]); acc[3] = fmaf(w0.w, gv, acc[3]);
-            acc[4] = fmaf(w1.x, gv, acc[4]); acc[5] = fmaf(w1.y, gv, acc[5]);
-            acc[6] = fmaf(w1.z, gv, acc[6]); acc[7] = fmaf(w1.w, gv, acc[7]);
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (i0 + k < C) gxb[USQ ? unsqueezed_index(i0 + k, p, W, HW) : (i0 + k) * HW + p] = acc[k];
-    }
+    // gx = W_b^T (s gz) over the input channels
+    pixel8_product(Wb, gs, C, CP, HWP, HW, tid, [=](int i, int p, float acc) { gxb[USQ ? squeeze_index(i, p, W, HW) : i * HW + p] = acc; });
 }
 
 // The three levels of the image flows: k_affine_ctx_wave transposed - one wave per sample, no LDS, no barrier, 64
@@ -841,24 +841,22 @@ __global__ __launch_bounds__(256) void k_affine_ctx_bwd_wave(const float* __rest
                                                              const float* __restrict__ Wm, const float* __restrict__ m2,
                                                              const float* __restrict__ logs, float* __restrict__ gx, int B,
                                                              int64_t gzbs) {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    constexpr int HW = W * W, RT = C / 16, NG = C / 16, WIDE = HW >= 64, NT = WIDE ? HW / 64 : 1, NJ = WIDE ? 4 : 1;
+    using G = AffineWave<C, W>;
+    constexpr int HW = G::HW, RT = G::RT, NG = G::NG, WIDE = G::WIDE, NT = G::NT, NJ = G::NJ;
     const int lane = threadIdx.x & 63, n = lane & 15, kk = lane >> 4;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;                                // a whole wave: the kernel has no barrier
     const float* mb = m1 + (int64_t)b * C * C;
     const float* gb = gz + (int64_t)b * gzbs;
     float4 a[RT][NG];
+    float dsum = 0.f;                                  // (the diagonal sum wb_element_wave keeps: not used here)
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
         const int o0 = 16 * g + 4 * kk;
         float ss[4] = {1.f, 1.f, 1.f, 1.f};
         if (m2 != nullptr) {
-            float4 lv = *reinterpret_cast<const float4*>(m2 + (int64_t)b * 2 * C + C + o0);
-            if (logs != nullptr) {
-                const float4 l0 = *reinterpret_cast<const float4*>(logs + o0);
-                lv.x += l0.x; lv.y += l0.y; lv.z += l0.z; lv.w += l0.w;
-            }
+            float4 tv, lv;                             // (tv: not formed)
+            G::template actnorm_rows<false>(m2, b, nullptr, logs, o0, tv, lv);
             ss[0] = expf(-lv.x); ss[1] = expf(-lv.y); ss[2] = expf(-lv.z); ss[3] = expf(-lv.w);
         }
 #pragma unroll
@@ -869,11 +867,7 @@ __global__ __launch_bounds__(256) void k_affine_ctx_bwd_wave(const float* __rest
             for (int e = 0; e < 4; ++e) v[e] = g >= it ? mb[(o0 + e) * C + i] : 0.f;
             if (g == it) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int o = o0 + e;
-                    const float ex = expf(v[e]) - (Wm != nullptr ? 1.f : 0.f);
-                    v[e] = o > i ? v[e] : (o == i ? ex : 0.f);
-                }
+                for (int e = 0; e < 4; ++e) v[e] = wb_element_wave(v[e], Wm != nullptr, o0 + e, i, dsum);
             }
             if (Wm != nullptr) {
 #pragma unroll
@@ -924,22 +918,18 @@ __global__ __launch_bounds__(256) void k_affine_ctx_bwd_wave(const float* __rest
                         gxb[i * HW + n] = acc[it][0][r];
                 }
             } else {
-                float* qb = gxb + (4 * it + kk) * 4 * HW;      // channel q of the (C/4, 2W, 2W) sample
-                if constexpr (WIDE) {
-                    const int p0 = 64 * T + 4 * n, yy = p0 / W, xx = p0 - yy * W;       // 4 pixels of one image row (W >= 4)
+                const int p0 = G::pixel0(T, n), yy = p0 / W, xx = p0 - yy * W;
 #pragma unroll
-                    for (int dy = 0; dy < 2; ++dy) {
-                        float* row = qb + (2 * yy + dy) * 2 * W + 2 * xx;
+                for (int dy = 0; dy < 2; ++dy) {                // rows r = 2 dy + dx: the phases of channel q = 4 it + kk
+                    float* row = G::phase_row(gxb, 4 * it + kk, dy, yy, xx);
+                    if constexpr (WIDE) {
                         *reinterpret_cast<float4*>(row) =
                             make_float4(acc[it][0][2 * dy], acc[it][0][2 * dy + 1], acc[it][1][2 * dy], acc[it][1][2 * dy + 1]);
                         *reinterpret_cast<float4*>(row + 4) =
                             make_float4(acc[it][2][2 * dy], acc[it][2][2 * dy + 1], acc[it][3][2 * dy], acc[it][3][2 * dy + 1]);
+                    } else {
+                        *reinterpret_cast<float2*>(row) = make_float2(acc[it][0][2 * dy], acc[it][0][2 * dy + 1]);
                     }
-                } else {
-                    const int yy = n / W, xx = n - yy * W;
-#pragma unroll
-                    for (int dy = 0; dy < 2; ++dy)
-                        *reinterpret_cast<float2*>(qb + (2 * yy + dy) * 2 * W + 2 * xx) = make_float2(acc[it][0][2 * dy], acc[it][0][2 * dy + 1]);
                 }
             }
         }
@@ -1142,41 +1132,68 @@ static int gmm_ctx_group(int N, int MK, size_t* lds) {
     return *lds <= 160 * 1024 ? 1 : 0;
 }
 
+// The launch of a context-GMM kernel family K<S> (a generic functor: K(std::integral_constant<int, S>) is the kernel for S
+// samples per workgroup): S as gmm_ctx_group says, K<1> alone can need more than 64 KiB.
+template <class K, class... A>
+static int gmm_ctx_launch(const char* who, const char* func, std::atomic<uint64_t>& raised, K kernel, int B, int D, int HW, int MK,
+                          hipStream_t st, A... args) {
+    size_t lds;
+    const int S = gmm_ctx_group(D * HW, MK, &lds);
+    if (S == 0) { cf_set_error("%s: D*HW=%d needs %zu B of LDS", who, D * HW, lds); return CF_ERR_UNSUPPORTED; }
+    if (lds > 64 * 1024)
+        if (int rc_ = cf_raise_dynamic_lds((const void*)kernel(std::integral_constant<int, 1>{}), 160 * 1024, raised, func)) return rc_;
+    const dim3 grid((B + S - 1) / S);
+    if (S == 4) kernel(std::integral_constant<int, 4>{})<<<grid, dim3(256), lds, st>>>(args...);
+    else if (S == 2) kernel(std::integral_constant<int, 2>{})<<<grid, dim3(256), lds, st>>>(args...);
+    else kernel(std::integral_constant<int, 1>{})<<<grid, dim3(256), lds, st>>>(args...);
+    return 0;
+}
+
 template <bool TAB>
 static int gmm_ctx_fwd_launch(const char* who, const float* x, const float* mG, const float* sG, const float* logw, const float* c,
                               float* out, float* lp_out, int B, int M, int K, int D, int HW, int64_t xbs, int accumulate,
                               GmmTab tb, hipStream_t st) {
-    size_t lds;
-    const int S = gmm_ctx_group(D * HW, M * K, &lds);
-    if (S == 0) { cf_set_error("%s: D*HW=%d needs %zu B of LDS", who, D * HW, lds); return CF_ERR_UNSUPPORTED; }
-    if (lds > 64 * 1024) {
-        static std::atomic<uint64_t> raised{0};
-        if (int rc_ = cf_raise_dynamic_lds((const void*)k_gmm_ctx<1, TAB>, 160 * 1024, raised, __func__)) return rc_;
-    }
-    const dim3 grid((B + S - 1) / S);
-    if (S == 4) k_gmm_ctx<4, TAB><<<grid, dim3(256), lds, st>>>(x, mG, sG, logw, c, out, lp_out, B, M, K, D, HW, xbs, accumulate, tb);
-    else if (S == 2) k_gmm_ctx<2, TAB><<<grid, dim3(256), lds, st>>>(x, mG, sG, logw, c, out, lp_out, B, M, K, D, HW, xbs, accumulate, tb);
-    else k_gmm_ctx<1, TAB><<<grid, dim3(256), lds, st>>>(x, mG, sG, logw, c, out, lp_out, B, M, K, D, HW, xbs, accumulate, tb);
-    return 0;
+    static std::atomic<uint64_t> raised{0};
+    return gmm_ctx_launch(who, __func__, raised, [](auto s) { return k_gmm_ctx<decltype(s)::value, TAB>; }, B, D, HW, M * K, st,
+                          x, mG, sG, logw, c, out, lp_out, B, M, K, D, HW, xbs, accumulate, tb);
 }
 
 template <bool TAB, bool DATA = false>
 static int gmm_ctx_bwd_launch(const char* who, const float* x, const float* mG, const float* sG, const float* logw, const float* c,
                               const float* g, const float* lp, float* gx, float* gc, int B, int M, int K, int D, int HW,
                               int64_t xbs, GmmTab tb, hipStream_t st) {
-    size_t lds;
-    const int S = gmm_ctx_group(D * HW, M * K, &lds);
-    if (S == 0) { cf_set_error("%s: D*HW=%d needs %zu B of LDS", who, D * HW, lds); return CF_ERR_UNSUPPORTED; }
+    static std::atomic<uint64_t> raised{0};
+    return gmm_ctx_launch(who, __func__, raised, [](auto s) { return k_gmm_ctx_bwd<decltype(s)::value, TAB, DATA>; }, B, D, HW, M * K, st,
+                          x, mG, sG, logw, c, g, lp, gx, gc, B, M, K, D, HW, xbs, tb);
+}
+
+// ---- host side of the Conv1x1 / ActNorm kernels
+
+// the three levels of the image flows, which k_affine_ctx_wave / k_affine_ctx_bwd_wave are instantiated for
+static bool affine_wave_shape(int C, int H, int W) {
+    return H == W && ((C == 16 && W == 16) || (C == 32 && W == 8) || (C == 64 && W == 4));
+}
+
+// every pointer 16-byte aligned (NULL counts as aligned)
+template <class... P>
+static bool aligned16(const P*... p) { return ((... | reinterpret_cast<uintptr_t>(p)) & 15) == 0; }
+
+// One workgroup of 256 threads per sample with `floats` of dynamic LDS, for the per-sample LDS kernels: refused above the
+// 160 KiB of a CU, the limit of the kernel raised above 64 KiB (once per kernel and device: `raised` is per instantiation).
+template <auto Kernel, class... A>
+static int launch_per_sample(const char* who, int B, int C, int HW, int floats, hipStream_t st, A... args) {
+    const size_t lds = (size_t)floats * sizeof(float);
+    if (lds > 160 * 1024) { cf_set_error("%s: C=%d, H*W=%d need %zu B of LDS", who, C, HW, lds); return CF_ERR_UNSUPPORTED; }
     if (lds > 64 * 1024) {
         static std::atomic<uint64_t> raised{0};
-        if (int rc_ = cf_raise_dynamic_lds((const void*)k_gmm_ctx_bwd<1, TAB, DATA>, 160 * 1024, raised, __func__)) return rc_;
+        if (int rc_ = cf_raise_dynamic_lds((const void*)Kernel, 160 * 1024, raised, who)) return rc_;
     }
-    const dim3 grid((B + S - 1) / S);
-    if (S == 4) k_gmm_ctx_bwd<4, TAB, DATA><<<grid, dim3(256), lds, st>>>(x, mG, sG, logw, c, g, lp, gx, gc, B, M, K, D, HW, xbs, tb);
-    else if (S == 2) k_gmm_ctx_bwd<2, TAB, DATA><<<grid, dim3(256), lds, st>>>(x, mG, sG, logw, c, g, lp, gx, gc, B, M, K, D, HW, xbs, tb);
-    else k_gmm_ctx_bwd<1, TAB, DATA><<<grid, dim3(256), lds, st>>>(x, mG, sG, logw, c, g, lp, gx, gc, B, M, K, D, HW, xbs, tb);
+    Kernel<<<dim3(B), dim3(256), lds, st>>>(args...);
     return 0;
 }
+
+// grid of the grid-stride elementwise kernels (256 threads) over n elements
+static dim3 grid_stride_blocks(int64_t n) { return dim3((unsigned)std::min<int64_t>((n + 255) / 256, 16384)); }
 
 }  // namespace
 
@@ -1197,21 +1214,15 @@ int cf_conv1x1_ctx(const float* x, const float* m, const float* Wm, float* z, fl
                    int64_t x_bstride, cf_stream_t stream) {
     if (B == 0) return 0;
     CF_REQUIRE(x && m && z && ldj && B >= 0 && C > 0 && HW > 0);
-    const size_t lds = (size_t)(C * conv1x1_ctx_cp(C) + C * HW + 4 + C * C) * sizeof(float);
-    if (lds > 160 * 1024) { cf_set_error("cf_conv1x1_ctx: C=%d, H*W=%d need %zu B of LDS", C, HW, lds); return CF_ERR_UNSUPPORTED; }
-    if (lds > 64 * 1024) {
-        static std::atomic<uint64_t> raised{0};
-        if (int rc_ = cf_raise_dynamic_lds((const void*)k_conv1x1_ctx, 160 * 1024, raised, __func__)) return rc_;
-    }
-    k_conv1x1_ctx<<<dim3(B), dim3(256), lds, cf_s(stream)>>>(x, m, Wm, z, ldj, C, HW, x_bstride);
+    if (int rc = launch_per_sample<k_conv1x1_ctx>(__func__, B, C, HW, CtxFwdLds(C, HW, 0).floats(), cf_s(stream), x, m, Wm, z, ldj, C, HW,
+                                                  x_bstride)) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }
 
 // number of floats per sample of the blocked form of m1 (cf_affine_ctx_fwd, m1_blocked != 0), 0 where it is not offered
 int cf_affine_ctx_blocked_floats(int C, int H, int W) {
-    const bool wave = H == W && ((C == 16 && W == 16) || (C == 32 && W == 8) || (C == 64 && W == 4));
-    return wave ? (C / 16) * (C / 16 + 1) / 2 * 256 : 0;
+    return affine_wave_shape(C, H, W) ? (C / 16) * (C / 16 + 1) / 2 * 256 : 0;
 }
 
 int cf_affine_ctx_fwd(const float* x, const float* m1, const float* Wm, const float* m2, const float* t, const float* logs,
@@ -1222,10 +1233,7 @@ int cf_affine_ctx_fwd(const float* x, const float* m1, const float* Wm, const fl
     CF_REQUIRE(x && m1 && m2 && z && ldj && B >= 0 && C > 0 && C <= 256 && H > 0 && W > 0 && ((t == nullptr) == (logs == nullptr)) &&
                x_bstride >= (int64_t)C * H * W && (!in_squeeze || C % 4 == 0));
     // the image flows' three levels: one wave per sample on the matrix pipe, operands straight from global memory
-    const bool al = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(m1) | reinterpret_cast<uintptr_t>(m2) |
-                      reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(Wm) | reinterpret_cast<uintptr_t>(t) |
-                      reinterpret_cast<uintptr_t>(logs)) & 15) == 0 && x_bstride % 4 == 0;
-    if (al && H == W && ((C == 16 && W == 16) || (C == 32 && W == 8) || (C == 64 && W == 4))) {
+    if (affine_wave_shape(C, H, W) && aligned16(x, m1, m2, z, Wm, t, logs) && x_bstride % 4 == 0) {
         const dim3 grid((B + 3) / 4), blk(256);
 #define CF_AFF2(CC, WW, SQV, BLV) k_affine_ctx_wave<CC, WW, SQV, BLV><<<grid, blk, 0, cf_s(stream)>>>(x, m1, Wm, m2, t, logs, lad, cadd, z, ldj, B, x_bstride, accumulate)
 #define CF_AFF(CC, WW) do { if (in_squeeze) { if (m1_blocked) CF_AFF2(CC, WW, true, true); else CF_AFF2(CC, WW, true, false); } \
@@ -1237,15 +1245,11 @@ int cf_affine_ctx_fwd(const float* x, const float* m1, const float* Wm, const fl
         return 0;
     }
     CF_REQUIRE(!m1_blocked);                             // (the blocked form exists for the wave kernel's shapes and needs their alignment)
-    const size_t lds = (size_t)(C * conv1x1_ctx_cp(C) + C * H * W + 4 + 2 * C + C * C) * sizeof(float);
-    if (lds > 160 * 1024) { cf_set_error("cf_affine_ctx_fwd: C=%d, H*W=%d need %zu B of LDS", C, H * W, lds); return CF_ERR_UNSUPPORTED; }
-    if (lds > 64 * 1024) {
-        static std::atomic<uint64_t> raised0{0}, raised1{0};
-        if (int rc_ = in_squeeze ? cf_raise_dynamic_lds((const void*)k_affine_ctx<true>, 160 * 1024, raised1, __func__)
-                                 : cf_raise_dynamic_lds((const void*)k_affine_ctx<false>, 160 * 1024, raised0, __func__)) return rc_;
-    }
-    if (in_squeeze) k_affine_ctx<true><<<dim3(B), dim3(256), lds, cf_s(stream)>>>(x, m1, Wm, m2, t, logs, lad, cadd, z, ldj, C, H, W, x_bstride, accumulate);
-    else k_affine_ctx<false><<<dim3(B), dim3(256), lds, cf_s(stream)>>>(x, m1, Wm, m2, t, logs, lad, cadd, z, ldj, C, H, W, x_bstride, accumulate);
+    const int floats = CtxFwdLds(C, H * W, C).floats();
+    if (int rc = in_squeeze ? launch_per_sample<k_affine_ctx<true>>(__func__, B, C, H * W, floats, cf_s(stream), x, m1, Wm, m2, t, logs, lad,
+                                                                    cadd, z, ldj, C, H, W, x_bstride, accumulate)
+                            : launch_per_sample<k_affine_ctx<false>>(__func__, B, C, H * W, floats, cf_s(stream), x, m1, Wm, m2, t, logs, lad,
+                                                                     cadd, z, ldj, C, H, W, x_bstride, accumulate)) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }
@@ -1264,9 +1268,7 @@ int cf_add_sample_bias(float* h, const float* bias, int B, int C, int HW, int re
     if (B == 0) return 0;
     CF_REQUIRE(h && bias && B >= 0 && C > 0 && HW > 0);
     const int64_t total = (int64_t)B * C * HW;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    k_add_sample_bias<<<dim3((unsigned)blocks), dim3(256), 0, cf_s(stream)>>>(h, bias, HW, total, relu);
+    k_add_sample_bias<<<grid_stride_blocks(total), dim3(256), 0, cf_s(stream)>>>(h, bias, HW, total, relu);
     CF_LAUNCH_CHECK();
     return 0;
 }
@@ -1324,13 +1326,8 @@ int cf_conv1x1_ctx_bwd(const float* x, const float* m, const float* Wm, const fl
                        float* gm, int B, int C, int HW, int64_t x_bstride, int64_t gz_bstride, cf_stream_t stream) {
     if (B == 0) return 0;
     CF_REQUIRE(x && m && gz && gld && gx && gm && B >= 0 && C > 0 && HW > 0);
-    const size_t lds = (size_t)(C * ((C + 7) & ~7) + 2 * C * (HW | 1)) * sizeof(float);
-    if (lds > 160 * 1024) { cf_set_error("cf_conv1x1_ctx_bwd: C=%d, H*W=%d need %zu B of LDS", C, HW, lds); return CF_ERR_UNSUPPORTED; }
-    if (lds > 64 * 1024) {
-        static std::atomic<uint64_t> raised{0};
-        if (int rc_ = cf_raise_dynamic_lds((const void*)k_conv1x1_ctx_bwd, 160 * 1024, raised, __func__)) return rc_;
-    }
-    k_conv1x1_ctx_bwd<<<dim3(B), dim3(256), lds, cf_s(stream)>>>(x, m, Wm, gz, gld, gx, gm, C, HW, x_bstride, gz_bstride);
+    if (int rc = launch_per_sample<k_conv1x1_ctx_bwd>(__func__, B, C, HW, CtxBwdLds(C, HW, 0, true).floats(), cf_s(stream), x, m, Wm, gz, gld,
+                                                      gx, gm, C, HW, x_bstride, gz_bstride)) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }
@@ -1350,10 +1347,7 @@ int cf_affine_ctx_bwd_data(const float* gz, const float* m1, const float* Wm, co
     if (B == 0) return 0;
     CF_REQUIRE(gz && gx && B >= 0 && C > 0 && C <= 256 && H > 0 && W > 0 && (m1 || !Wm) && (m2 || !logs) &&
                gz_bstride >= (int64_t)C * H * W && (!out_unsqueeze || C % 4 == 0));
-    const bool al = ((reinterpret_cast<uintptr_t>(gz) | reinterpret_cast<uintptr_t>(m1) | reinterpret_cast<uintptr_t>(Wm) |
-                      reinterpret_cast<uintptr_t>(m2) | reinterpret_cast<uintptr_t>(logs) | reinterpret_cast<uintptr_t>(gx)) & 15) == 0 &&
-                    gz_bstride % 4 == 0;
-    if (al && m1 && H == W && ((C == 16 && W == 16) || (C == 32 && W == 8) || (C == 64 && W == 4))) {
+    if (m1 && affine_wave_shape(C, H, W) && aligned16(gz, m1, Wm, m2, logs, gx) && gz_bstride % 4 == 0) {
         const dim3 grid((B + 3) / 4), blk(256);
 #define CF_AFFB(CC, WW) do { if (out_unsqueeze) k_affine_ctx_bwd_wave<CC, WW, true><<<grid, blk, 0, cf_s(stream)>>>(gz, m1, Wm, m2, logs, gx, B, gz_bstride); \
                              else k_affine_ctx_bwd_wave<CC, WW, false><<<grid, blk, 0, cf_s(stream)>>>(gz, m1, Wm, m2, logs, gx, B, gz_bstride); } while (0)
@@ -1362,15 +1356,11 @@ int cf_affine_ctx_bwd_data(const float* gz, const float* m1, const float* Wm, co
         CF_LAUNCH_CHECK();
         return 0;
     }
-    const size_t lds = (size_t)(((C + 3) & ~3) + (m1 ? C * ((C + 7) & ~7) + C * ((H * W) | 1) : 0)) * sizeof(float);
-    if (lds > 160 * 1024) { cf_set_error("cf_affine_ctx_bwd_data: C=%d, H*W=%d need %zu B of LDS", C, H * W, lds); return CF_ERR_UNSUPPORTED; }
-    if (lds > 64 * 1024) {
-        static std::atomic<uint64_t> raised0{0}, raised1{0};
-        if (int rc_ = out_unsqueeze ? cf_raise_dynamic_lds((const void*)k_affine_ctx_bwd_data<true>, 160 * 1024, raised1, __func__)
-                                    : cf_raise_dynamic_lds((const void*)k_affine_ctx_bwd_data<false>, 160 * 1024, raised0, __func__)) return rc_;
-    }
-    if (out_unsqueeze) k_affine_ctx_bwd_data<true><<<dim3(B), dim3(256), lds, cf_s(stream)>>>(gz, m1, Wm, m2, logs, gx, C, H, W, gz_bstride);
-    else k_affine_ctx_bwd_data<false><<<dim3(B), dim3(256), lds, cf_s(stream)>>>(gz, m1, Wm, m2, logs, gx, C, H, W, gz_bstride);
+    const int floats = CtxBwdLds(C, H * W, C, false, m1 != nullptr).floats();
+    if (int rc = out_unsqueeze ? launch_per_sample<k_affine_ctx_bwd_data<true>>(__func__, B, C, H * W, floats, cf_s(stream), gz, m1, Wm, m2,
+                                                                                logs, gx, C, H, W, gz_bstride)
+                               : launch_per_sample<k_affine_ctx_bwd_data<false>>(__func__, B, C, H * W, floats, cf_s(stream), gz, m1, Wm, m2,
+                                                                                 logs, gx, C, H, W, gz_bstride)) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }
@@ -1387,9 +1377,7 @@ int cf_sample_channel_sums(const float* a, float* out, int B, int C, int HW, cf_
 int cf_relu_bwd(const float* x, const float* gy, float* out, int64_t n, cf_stream_t stream) {
     if (n == 0) return 0;
     CF_REQUIRE(x && gy && out && n >= 0);
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    k_relu_bwd<<<dim3((unsigned)blocks), dim3(256), 0, cf_s(stream)>>>(x, gy, out, n);
+    k_relu_bwd<<<grid_stride_blocks(n), dim3(256), 0, cf_s(stream)>>>(x, gy, out, n);
     CF_LAUNCH_CHECK();
     return 0;
 }
@@ -1453,9 +1441,7 @@ int cf_add_repeat(float* h, const float* x, int B, int C2, int C, int HW, cf_str
     if (B == 0) return 0;
     CF_REQUIRE(h && x && B >= 0 && C2 > 0 && C > 0 && HW > 0);
     const int64_t total = (int64_t)B * C2 * HW;
-    int64_t blocks = (total + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    k_add_repeat<<<dim3((unsigned)blocks), dim3(256), 0, cf_s(stream)>>>(h, x, C2, C, HW, total);
+    k_add_repeat<<<grid_stride_blocks(total), dim3(256), 0, cf_s(stream)>>>(h, x, C2, C, HW, total);
     CF_LAUNCH_CHECK();
     return 0;
 }

@@ -507,7 +507,8 @@ def test_grouped_linears_with_the_context_code_formed_in_the_kernel(L, onehot, K
 
 @pytest.mark.parametrize("C,H,W,B,cf,sq", [(16, 16, 16, 5, True, False), (16, 16, 16, 3, True, True), (32, 8, 8, 37, False, False),
                                             (32, 8, 8, 9, True, True), (64, 4, 4, 130, True, False), (64, 4, 4, 6, False, True),
-                                            (8, 6, 6, 7, True, False), (12, 4, 4, 5, False, True)])
+                                            (8, 6, 6, 7, True, False), (12, 4, 4, 5, False, True),
+                                            (76, 9, 8, 3, True, False), (76, 9, 8, 3, False, True)])      # > 64 KiB of LDS
 def test_fused_specialist_affine_equals_its_two_layers(L, C, H, W, B, cf, sq):
     """cf_affine_ctx_fwd (per-sample Conv1x1 + per-sample ActNorm [+ Squeeze] in one pass; the one-wave-per-sample MFMA form at
     the three image-flow levels, the LDS form elsewhere) against Squeeze -> cf_conv1x1_ctx -> cf_actnorm_ctx and against

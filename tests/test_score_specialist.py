@@ -175,7 +175,8 @@ def _affine_ref(gz, m1, Wm, m2, logs):
     return g.reshape(gz.shape)
 
 
-@pytest.mark.parametrize("C,H,W", [(16, 16, 16), (32, 8, 8), (64, 4, 4), (8, 16, 16), (26, 8, 1), (76, 18, 1)])
+@pytest.mark.parametrize("C,H,W", [(16, 16, 16), (32, 8, 8), (64, 4, 4), (8, 16, 16), (26, 8, 1), (76, 18, 1),
+                                     (76, 12, 12)])                                       # > 64 KiB of LDS
 def test_affine_ctx_bwd_data_against_fp64(L, C, H, W):
     """cf_affine_ctx_bwd_data: gx = W_b^T (gz exp(-l_b)) against the fp64 formula at the three wave shapes, mnist's level, SMAP's
     26 and ATM's 76 channels; B in {1, 5, 9}; with and without Wm / logs; m1 = NULL; m2 = NULL; out_unsqueeze where C % 4 == 0
