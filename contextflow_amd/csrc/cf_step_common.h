@@ -931,6 +931,11 @@ template <class G> __device__ __forceinline__ int w24_pix(int s, int y, int x, i
     else return w24_row<G>(s, y, kq) + w24_col<G>(x, kq);
 }
 
+// CF_W24_SPREAD (A/B builds of tools/dev/make_abl.py): 1 = the 8x8 level issues the patch reads of the next k-group one patch column
+// per nu step, 0 = as one burst behind the vertical sums, as the 4x4 level does either way
+#ifndef CF_W24_SPREAD
+#define CF_W24_SPREAD 1
+#endif
 template <class G>
 __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const float* __restrict__ wsl, ws_rsrc_t rs, int lane,
                                                   int wave) {
@@ -944,6 +949,9 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
     // nu order inside a group: 0 and 5 first, so that A0 / A5 die early and A1 .. A4 live on as P, Q, R, D
     constexpr int NU[6] = {0, 5, 1, 2, 3, 4};
     typedef float f32x2w __attribute__((ext_vector_type(2)));
+    // 8x8 only: at 4x4 two of the six patch columns repeat another one's words, hipcc merges those reads inside a burst (32 values,
+    // not 48), and the burst measured faster there
+    constexpr bool SPREAD = CF_W24_SPREAD && H == 8;
     const int rt0 = __builtin_amdgcn_readfirstlane((NCT == 1 ? wave : wave / NCT) * RTW);
     float* H1 = lds + HALF * PIX;
     const int l15 = lane & 15, lg = lane >> 4;
@@ -993,11 +1001,12 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
     };
     struct Raw { f32x2w d[2][6][2]; };                    // [row r1 / r2][patch column][k-step pair]
     struct WFrag { float4 a[RTW]; };
-    auto load_raw = [&](const int (&o)[2][6], int kk, Raw& r) {
+    // patch columns [c0, c1) of k-group kk (both patch rows, both k-step pairs: 8 values per column)
+    auto load_raw_cols = [&](const int (&o)[2][6], int kk, Raw& r, int c0, int c1) {
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
-            for (int c = 0; c < 6; ++c)
+            for (int c = c0; c < c1; ++c)
 #pragma unroll
                 for (int e2 = 0; e2 < 2; ++e2) {
                     const char* q0 = reinterpret_cast<const char*>(lds) + (16 * kk + 8 * e2) * PIX * 4;      // k-steps 4 kk + 2 e2 (+1)
@@ -1005,6 +1014,7 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
                     r.d[h][c][e2] = f32x2w{*reinterpret_cast<const float*>(q0 + o[h][c]), *reinterpret_cast<const float*>(q1 + o[h][c])};
                 }
     };
+    auto load_raw = [&](const int (&o)[2][6], int kk, Raw& r) { load_raw_cols(o, kk, r, 0, 6); };
     auto load_w = [&](int xi, int s, WFrag& f) {          // step s = kk * 6 + (index of nu in NU) of vertical index xi
         const int kk = s / 6, nu = NU[s % 6];
         const int fr = G::OFF_AW24 + (((xi * 6 + nu) * RT16 + rt0) * KG4 + kk) * 256;
@@ -1035,21 +1045,18 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
             for (int c = 0; c < 6; ++c)
 #pragma unroll
                 for (int e2 = 0; e2 < 2; ++e2) A[c][e2] = raw.d[0][c][e2] + sigma * raw.d[1][c][e2];
-            if (kk + 1 < KG4) {
-                load_raw(o, kk + 1, raw);
-            } else {                                      // first group of the next xi: its operand addresses replace this xi's
-                addrs(xn, o);
-                load_raw(o, 0, raw);
-            }
-#pragma unroll
-            for (int t = 0; t < 6; ++t) {
-                const int s = kk * 6 + t, nu = NU[t];
-                if (s + 1 < NS) load_w(xi, s + 1, wf[(s + 1) & 1]);
-                else load_w(xn, 0, wf[0]);
-                __builtin_amdgcn_sched_barrier(0);
-                // horizontal transform B4^T row nu:  nu 0: A0/4 - 5/4 A2 + A4;  1, 2: P +- Q (P = A4 - A2/4, Q = A3 - A1/4);
-                // 3, 4: R +- (A3 - A1)/2 (R = A4 - A2);  5: A1/4 - 5/4 A3 + A5
-                f32x2w v[2];
+            // the 48 patch values of the next k-group: as ONE burst here the reads fill the wave's LDS queue and hold its
+            // instruction issue - MFMAs included - until they return; SPREAD: one patch column (8 values) goes out with each of
+            // the six steps, into the same registers (raw is dead once A is formed)
+            if (kk + 1 == KG4) addrs(xn, o);              // first group of the next xi: its operand addresses replace this xi's
+            const int kn = kk + 1 < KG4 ? kk + 1 : 0;
+            if constexpr (!SPREAD) load_raw(o, kn, raw);
+            // horizontal transform B4^T row nu:  nu 0: A0/4 - 5/4 A2 + A4;  1, 2: P +- Q (P = A4 - A2/4, Q = A3 - A1/4);
+            // 3, 4: R +- (A3 - A1)/2 (R = A4 - A2);  5: A1/4 - 5/4 A3 + A5
+            // (One lambda, called per step: written out inside the step loop, with the operand addresses of the next xi formed in
+            // the burst's branch, the same arithmetic compiled to scalar halves - 4x4: 505 v_fma_f32 beside 263 v_pk_fma_f32,
+            // now 31 beside 532, and 64 hazard s_nop instead of 216.  Why hipcc packs this form and not that one is not known.)
+            auto operand = [&](const int nu, f32x2w (&v)[2]) {
 #pragma unroll
                 for (int e2 = 0; e2 < 2; ++e2) {
                     const f32x2w a0 = A[0][e2], a1 = A[1][e2], a2 = A[2][e2], a3 = A[3][e2], a4 = A[4][e2], a5 = A[5][e2];
@@ -1060,6 +1067,16 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
                     else if (nu == 4) v[e2] = (a4 - a2) - 0.5f * (a3 - a1);
                     else v[e2] = 0.25f * a1 + (a5 - 1.25f * a3);
                 }
+            };
+#pragma unroll
+            for (int t = 0; t < 6; ++t) {
+                const int s = kk * 6 + t, nu = NU[t];
+                if (s + 1 < NS) load_w(xi, s + 1, wf[(s + 1) & 1]);
+                else load_w(xn, 0, wf[0]);
+                if constexpr (SPREAD) load_raw_cols(o, kn, raw, t, t + 1);
+                __builtin_amdgcn_sched_barrier(0);
+                f32x2w v[2];
+                operand(nu, v);
                 const WFrag& f = wf[s & 1];
 #pragma unroll
                 for (int e = 0; e < 4; ++e)

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Print the top kernels of a rocprofv3 --kernel-trace --stats output directory.  usage: kstats.py DIR [N] [filter]"""
+"""Print the top kernels of a rocprofv3 --kernel-trace --stats --output-format csv output directory (the default output format
+of newer rocprofv3 is a database, not CSV).  usage: kstats.py DIR [N] [filter]"""
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + '/**/*kernel_stats.csv', recursive=True)[0]
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 25
