@@ -113,8 +113,10 @@ class FlowSequential(nn.Module):
 
     def invalidate_caches(self):
         """Drop everything derived from parameter VALUES (packed step workspaces, mixture tables, captured graphs).  Needed
-        only after writes that bypass the version counters (`param.data.copy_(...)`); optimizer steps, `load_state_dict`,
-        `.to()` are noticed without it."""
+        only after writes that bypass the version counters: `param.data.copy_(...)`, a kernel that writes a parameter through its
+        raw pointer, and the replay of a captured graph that updates parameters (`GraphedTrainStep` calls this itself after every
+        replay).  Eager optimizer steps - torch's, and `optim.FusedAdamW.step()`, which advances the counters of what its
+        kernels wrote - `load_state_dict` and `.to()` are noticed without it."""
         self._prep.clear()
         self._graphs.clear()
         self._graph_policy.clear()                   # the replay-vs-eager verdicts are measured again

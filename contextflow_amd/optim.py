@@ -23,6 +23,19 @@ device-rate form under capture.  With `max_grad_norm`, ALWAYS the device-rate fo
 only there; such an eager `step()` calls `push_hyperparameters()` itself first.  The two forms give the same bits for the same
 rate (`test_device_learning_rate_equals_host_learning_rate`).
 `clip_grad_norm_` below is the eager drop-in for the reference's line, on the same kernels.
+
+What torch sees of a step.  The kernels write parameters and moments through raw pointers, so `step()` advances the `_version`
+counter of every tensor it wrote (the parameters that had a gradient, their `exp_avg` and `exp_avg_sq`) itself, in both kernel
+forms, eager and under capture: everything keyed on the counters - the parameter-derived tables of layers/_derived.py, the
+auto-captured evaluation graphs - follows an eager training loop as it follows torch.optim.AdamW.  The REPLAY of a captured step
+runs no Python and moves no counter: `GraphedTrainStep` calls `invalidate_caches()` after every replay for that reason.
+
+The update count.  `state[p]["step"]` of every parameter of a group is a view of ONE device scalar per group, advanced once per
+`step()` in which at least one parameter of the group had a gradient.  A parameter that sits a step out (`grad is None`) keeps its
+parameter and moments but its bias corrections use the group's count from then on - torch.optim.AdamW counts per parameter.  The
+flows here give every trainable parameter a gradient in every step, where the two agree.  `load_state_dict` takes the count of the
+group's last parameter that carries one.  The moments are allocated at construction for the parameters that require a gradient
+then: a parameter unfrozen later has none, and `step()` raises instead of skipping or guessing - build a new optimizer.
 """
 import ctypes
 
@@ -226,13 +239,15 @@ class FusedAdamW(torch.optim.Optimizer):
                 loss = closure()
         work = []
         for group, flat, slot in zip(self.param_groups, self._flats, self._lr_dev):
-            if flat is None:
-                continue
             ps = [p for p in group["params"] if p.requires_grad and p.grad is not None]
             if not ps:
                 continue
             gs = []
             for p in ps:
+                if flat is None or "exp_avg" not in self.state.get(p, ()):
+                    raise RuntimeError("FusedAdamW: a parameter of shape %s has a gradient but no moments - it did not require a gradient "
+                                       "when the optimizer was built.  The moments are allocated at construction (one flat buffer per "
+                                       "group): build a new FusedAdamW after unfreezing parameters" % (tuple(p.shape),))
                 g = p.grad
                 if g.is_sparse or g.dtype != torch.float32 or g.device != p.device:
                     raise RuntimeError("FusedAdamW: dense fp32 gradients on the parameter's device")
@@ -257,18 +272,22 @@ class FusedAdamW(torch.optim.Optimizer):
             A = _hip.ptr_array
             beta1, beta2 = group["betas"]
             lr = _check_lr(group["lr"])
+            ms, vs = [self.state[p]["exp_avg"] for p in ps], [self.state[p]["exp_avg_sq"] for p in ps]
             if capturing or rec is not None:
                 # rate from the device scalar.  Under capture a fill would be baked into the graph: the scalar must be current
                 if capturing and lr != slot[1]:
                     raise RuntimeError("FusedAdamW: param_group['lr'] changed since the last push_hyperparameters(); call it "
                                        "before capturing a step (capture_train_step does)")
-                _hip.call("cf_adamw_step_batch_dev", n, A(ps), A(gs), A([self.state[p]["exp_avg"] for p in ps]),
-                          A([self.state[p]["exp_avg_sq"] for p in ps]), ctypes.cast(numel, ctypes.c_void_p), _hip.p(flat[2]),
+                _hip.call("cf_adamw_step_batch_dev", n, A(ps), A(gs), A(ms), A(vs), ctypes.cast(numel, ctypes.c_void_p), _hip.p(flat[2]),
                           _hip.p(slot[0]), _hip.p(rec), float(beta1), float(beta2), float(group["eps"]),
                           float(group["weight_decay"]), int(group["maximize"]), _hip.stream())
-                continue
-            _hip.call("cf_adamw_step_batch", n, A(ps), A(gs), A([self.state[p]["exp_avg"] for p in ps]),
-                      A([self.state[p]["exp_avg_sq"] for p in ps]), ctypes.cast(numel, ctypes.c_void_p), _hip.p(flat[2]),
-                      lr, float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]),
-                      int(group["maximize"]), _hip.stream())
+            else:
+                _hip.call("cf_adamw_step_batch", n, A(ps), A(gs), A(ms), A(vs), ctypes.cast(numel, ctypes.c_void_p), _hip.p(flat[2]),
+                          lr, float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]),
+                          int(group["maximize"]), _hip.stream())
+            # the kernel wrote through raw pointers: tell torch, so that everything keyed on `_version` (layers/_derived.py, the
+            # auto-captured evaluation graphs) sees the update.  Host-only, also under capture; ONE call for the list (571 single
+            # calls cost 0.5 ms of host time for the smap flow, the list 45 us).  The moment views share the counter of their flat buffer
+            torch.autograd.graph.increment_version(ps)
+            torch.autograd.graph.increment_version((flat[0], flat[1]))
         return loss
