@@ -826,6 +826,168 @@ __global__ __launch_bounds__(256) void k_affine_ctx_bwd_data(const float* __rest
     pixel8_product(Wb, gs, C, CP, HWP, HW, tid, [=](int i, int p, float acc) { gxb[USQ ? squeeze_index(i, p, W, HW) : i * HW + p] = acc; });
 }
 
+// ---- the pair backwards (FlowSequential.inverse / decode / sample with a context): the inverse of cf_affine_ctx_fwd,
+//   x[b] = W_b^-1 (z[b] (.) exp(l_b) + t_b) per pixel,   W_b as in k_conv1x1_ctx (m1 == NULL: the identity - a streaming pass),
+//   [t_b | l_b] = m2[b] [+ t | logs] (m2 == NULL: y = z).
+// It inverts the map z = W_b x the forward applies: under contextflow W_b is a full matrix (whatever log-det the forward reports).
+// dyn[] of the kernel, as CtxFwdLds: MATRIX = false is the lone ActNorm.
+struct CtxInvLds {
+    int CP, S;
+    int nAt;      // At[k][c] = W_b^-1[c][k], row stride CP (zero padded): the operand of pixel8_product
+    int nys;      // ys[C][HW] = z exp(l_b) + t_b
+    int nxs;      // xs[C][HW]: the first solution x0 = W_b^-1 y, kept for the refinement step
+    int nA;       // A[C][S]: W_b, inverted in place, then W_b again; S = C + 1 (the column walks of the elimination meet no bank twice)
+    int nc;       // tb[C] = t_b, eb[C] = exp(l_b), colk[C], rowk[C], rowo[C], piv[C] (int), rounded up to 4 floats each
+    __host__ __device__ CtxInvLds(int C, int HW, bool MATRIX)
+        : CP((C + 7) & ~7), S(C + 1), nAt(MATRIX ? C * CP : 0), nys(MATRIX ? C * HW : 0), nxs(nys), nA(MATRIX ? C * (C + 1) : 0),
+          nc((C + 3) & ~3) {}
+    __host__ __device__ int floats() const { return nAt + nys + nxs + nA + (nA ? 6 : 2) * nc; }
+};
+
+// One workgroup per sample.  W_b (build_wb_rowmajor: the LDS family's rounding) is inverted in place by fp32 Gauss-Jordan with
+// partial (row) pivoting - the arithmetic of k_inverse_lds (cf_linalg.hip): per pivot a search, a row swap, the scaled pivot row and
+// one rank-1 update of the C x C block; the column swaps that undo the row pivoting run at the end - and its transpose
+// multiplies the staged y.  Every loop is bounded by C: a zero pivot gives a non-finite x, never a hang.  C^3 / 256 FMAs per thread
+// for the inverse next to C^2 HW / 256 for the product.
+// One step of iterative refinement follows: x = x0 + W_b^-1 (y - W_b x0) with the residual accumulated in fp64.  An fp32 inverse
+// times y errs by cond(W_b) eps - 1e-4 of scale at the condition numbers of 1e3 .. 1e4 that trained contextflow layers reach, and
+// up to 20 x what an fp32 LU solve loses on the lower triangular W_b without contextflow - and the chain multiplies such steps;
+// the refined x is within eps + (cond eps)^2 of the exact one.  It costs two more products over data that is in LDS already.
+template <bool USQ>
+__global__ __launch_bounds__(256) void k_affine_ctx_inv(const float* __restrict__ z, const float* __restrict__ m1,
+                                                        const float* __restrict__ Wm, const float* __restrict__ m2,
+                                                        const float* __restrict__ t, const float* __restrict__ logs,
+                                                        float* __restrict__ x, int C, int H, int W, int64_t zbs) {
+    extern __shared__ __align__(16) float dyn[];
+    const int HW = H * W;
+    const CtxInvLds L(C, HW, m1 != nullptr);
+    const int CP = L.CP, S = L.S;
+    float *At = dyn, *ys = At + L.nAt, *xs = ys + L.nys, *A = xs + L.nxs, *tb = A + L.nA, *eb = tb + L.nc;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const float* zb = z + (int64_t)b * zbs;
+    float* xb = x + (int64_t)b * C * HW;
+    for (int c = tid; c < C; c += 256) {
+        float tv = 0.f, ev = 1.f;
+        if (m2 != nullptr) {
+            const ActNormCtxTerms a = actnorm_ctx_terms(m2, b, t, logs, C, c);
+            tv = a.t; ev = expf(a.l);
+        }
+        tb[c] = tv; eb[c] = ev;
+    }
+    __syncthreads();
+    if (m1 == nullptr) {                              // ActNorm alone: a scale and a shift per channel
+        for (int e0 = tid; e0 < C * HW; e0 += 4 * 256) {
+            float zv[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) zv[i] = zb[min(e0 + i * 256, C * HW - 1)];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int e = e0 + i * 256;
+                if (e < C * HW) { const int c = e / HW, p = e - c * HW; xb[USQ ? squeeze_index(c, p, W, HW) : e] = fmaf(zv[i], eb[c], tb[c]); }
+            }
+        }
+        return;
+    }
+    float* colk = eb + L.nc;                           // per pivot: column k of the matrix as it was (0 at the pivot row)
+    float* rowk = colk + L.nc;                         // ... the new pivot row: row p / pivot, 1 / pivot at column k
+    float* rowo = rowk + L.nc;                         // ... the old row k (column k zeroed): it moves to row p
+    int* piv = reinterpret_cast<int*>(rowo + L.nc);
+    // y = z exp(l_b) + t_b -> LDS (batches of independent loads, in flight while the matrix is built)
+    for (int e0 = tid; e0 < C * HW; e0 += 8 * 256) {
+        float zv[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) zv[i] = zb[min(e0 + i * 256, C * HW - 1)];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int e = e0 + i * 256;
+            if (e < C * HW) { const int c = e / HW; ys[e] = fmaf(zv[i], eb[c], tb[c]); }
+        }
+    }
+    build_wb_rowmajor<false>(A, m1 + (int64_t)b * C * C, Wm, nullptr, C, S, tid);
+    __syncthreads();
+    // this thread's walk over the C x C block in steps of 256 elements: (row, column) of its first element and the step
+    const int r0 = tid / C, c0 = tid - r0 * C, dr = 256 / C, dc = 256 - dr * C;
+    // The elimination is bound by the vector instructions it issues (C^3 / 256 element updates per thread), so a thread owns ONE
+    // column c0 and the block of rows [ra, rb) - row group r0 of the 256 / C groups - and an update is a read, a select, an FMA
+    // and a write at addresses one row stride apart.  Two barriers per pivot: every wave finds the pivot row for itself, what the
+    // rank-1 update reads of the old matrix is staged - its column k and the rows k and p, the swap folded in - and every element
+    // is then updated from the staged vectors alone; the rows k and p are put right by their owners behind the sweep.
+    const int RG = (C + dr - 1) / dr, ra = min(r0 * RG, C), rb = r0 < dr ? min(ra + RG, C) : ra;
+    for (int k = 0; k < C; ++k) {
+        // pivot search over rows k .. C-1 of column k: key = (bits of |a|, ~row), so the maximum is the largest |a| at the lowest row
+        unsigned long long key = 0ull;
+        for (int r = k + lane; r < C; r += 64) {
+            const unsigned long long kv = ((unsigned long long)__float_as_uint(fabsf(A[r * S + k])) << 32) | (0xFFFFFFFFu - (unsigned)r);
+            key = kv > key ? kv : key;
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long ok = __shfl_xor(key, o, 64);
+            key = ok > key ? ok : key;
+        }
+        const int p = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
+        if (tid == 0) piv[k] = p;
+        const float d = 1.0f / A[p * S + k], akk = A[k * S + k];
+        for (int c = tid; c < C; c += 256) {
+            const float ap = A[p * S + c], ak = A[k * S + c], ac = A[c * S + k];
+            rowk[c] = (c == k ? 1.0f : ap) * d;
+            rowo[c] = c == k ? 0.f : ak;
+            colk[c] = (c == k || c == p) ? 0.f : ac;            // (rows k and p: written behind the sweep)
+        }
+        __syncthreads();
+        const float rk = rowk[c0];
+        const bool zc = c0 == k;
+        float* col = A + c0;
+        for (int r = ra; r < rb; r += 8) {
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = col[min(r + j, rb - 1) * S];
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (r + j < rb) col[(r + j) * S] = fmaf(-colk[r + j], rk, zc ? 0.f : v[j]);
+        }
+        if (p != k && p >= ra && p < rb) col[p * S] = fmaf(-akk, rk, rowo[c0]);
+        if (k >= ra && k < rb) col[k * S] = rk;
+        __syncthreads();
+    }
+    for (int k = C - 1; k >= 0; --k) {
+        const int p = piv[k];                         // (the same for every thread: the barrier is uniform)
+        if (p != k) {
+            for (int r = tid; r < C; r += 256) { const float v = A[r * S + k]; A[r * S + k] = A[r * S + p]; A[r * S + p] = v; }
+            __syncthreads();
+        }
+    }
+    // At[k][c] = W_b^-1[c][k]: lanes walk c (A at stride S, At contiguous), padding columns zero
+    for (int kk = r0, c = c0; kk < C;) {
+        At[kk * CP + c] = A[c * S + kk];
+        kk += dr; c += dc;
+        if (c >= C) { c -= C; ++kk; }
+    }
+    for (int e = tid; e < C * (CP - C); e += 256) { const int kk = e / (CP - C); At[kk * CP + C + (e - kk * (CP - C))] = 0.f; }
+    __syncthreads();
+    build_wb_rowmajor<false>(A, m1 + (int64_t)b * C * C, Wm, nullptr, C, S, tid);          // W_b again, for the residual
+    pixel8_product(At, ys, C, CP, HW, HW, tid, [=](int c, int p, float acc) { xs[c * HW + p] = acc; });
+    __syncthreads();
+    // ys <- y - W_b x0 in fp64: a thread owns a pixel and 8 rows of W_b, and is the only reader of the y it replaces
+    for (int e = tid; e < (CP >> 3) * HW; e += 256) {
+        const int cb = e / HW, p = e - cb * HW, c0 = cb * 8;
+        double acc[8];
+        int row[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { row[k] = min(c0 + k, C - 1) * S; acc[k] = (double)ys[min(c0 + k, C - 1) * HW + p]; }
+        for (int i = 0; i < C; ++i) {
+            const double xv = (double)xs[i * HW + p];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) acc[k] = fma(-(double)A[row[k] + i], xv, acc[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (c0 + k < C) ys[(c0 + k) * HW + p] = (float)acc[k];
+    }
+    __syncthreads();
+    pixel8_product(At, ys, C, CP, HW, HW, tid,
+                   [=](int c, int p, float acc) { xb[USQ ? squeeze_index(c, p, W, HW) : c * HW + p] = xs[c * HW + p] + acc; });
+}
+
 // The three levels of the image flows: k_affine_ctx_wave transposed - one wave per sample, no LDS, no barrier, 64
 // v_mfma_f32_16x16x4_f32 per sample, every operand read from global memory once.
 //   A (W_b^T with exp(-l_b) folded into its columns; 16 rows i x 4 k = o per instruction): lane (n, kk) holds
@@ -1361,6 +1523,21 @@ int cf_affine_ctx_bwd_data(const float* gz, const float* m1, const float* Wm, co
                                                                                 logs, gx, C, H, W, gz_bstride)
                                : launch_per_sample<k_affine_ctx_bwd_data<false>>(__func__, B, C, H * W, floats, cf_s(stream), gz, m1, Wm, m2,
                                                                                  logs, gx, C, H, W, gz_bstride)) return rc;
+    CF_LAUNCH_CHECK();
+    return 0;
+}
+
+// [Squeeze(2,2) <-] Conv1x1(c) <- ActNorm(c') backwards in one launch; m1 / m2 NULL: a lone ActNorm / Conv1x1 inverse
+int cf_affine_ctx_inv(const float* z, const float* m1, const float* Wm, const float* m2, const float* t, const float* logs,
+                      float* x_out, int B, int C, int H, int W, int64_t z_bstride, int out_unsqueeze, cf_stream_t stream) {
+    if (B == 0) return 0;
+    CF_REQUIRE(z && x_out && (m1 || m2) && B >= 0 && C > 0 && C <= 256 && H > 0 && W > 0 && (m1 || !Wm) && (m2 || !logs) &&
+               ((t == nullptr) == (logs == nullptr)) && z_bstride >= (int64_t)C * H * W && (!out_unsqueeze || C % 4 == 0));
+    const int floats = CtxInvLds(C, H * W, m1 != nullptr).floats();
+    if (int rc = out_unsqueeze ? launch_per_sample<k_affine_ctx_inv<true>>(__func__, B, C, H * W, floats, cf_s(stream), z, m1, Wm, m2, t, logs,
+                                                                           x_out, C, H, W, z_bstride)
+                               : launch_per_sample<k_affine_ctx_inv<false>>(__func__, B, C, H * W, floats, cf_s(stream), z, m1, Wm, m2, t, logs,
+                                                                            x_out, C, H, W, z_bstride)) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }

@@ -529,13 +529,17 @@ __global__ __launch_bounds__(256) void k_gmm_sample4(const float* __restrict__ m
 // cf_normal4 and keeps one of its four results: both forms give the same bits for every (seed, state, b, d).  (That is a whole
 // Philox call and two Box-Muller pairs per ELEMENT in the scalar form, four times the vector form's arithmetic: the price of the
 // fallback for ragged D / misaligned operands; the flows' levels all take the vector form.)
-template <bool VEC>
+// CTX (cf_gmm_ctx_draw): the per-sample shifts of a prior with a context net (gaussian.py:146-158), c (B, 2, M, K, Dch) constant
+// over the HW pixels of a channel: mean mG + cm_b, scale softplus(sG + cs_b).  The CTX = false instantiations are the kernel as it
+// was (no shift is read or added).
+template <bool VEC, bool CTX>
 __global__ __launch_bounds__(256) void k_gmm_draw(const float* __restrict__ mG, const float* __restrict__ sG,
                                                   const float* __restrict__ cdf, const int32_t* __restrict__ labels, int label0,
                                                   const float* __restrict__ u, const float* __restrict__ eps,
                                                   const unsigned long long* __restrict__ state, unsigned long long seed,
                                                   const float* __restrict__ z1, int64_t z1_bstride, int D1,
-                                                  float* __restrict__ out, int B, int M, int K, int D, float temperature, int TL) {
+                                                  float* __restrict__ out, int B, int M, int K, int D, float temperature, int TL,
+                                                  const float* __restrict__ c, int HW) {
     const int tpr = 1 << TL;
     const int64_t b = (int64_t)blockIdx.x * (256 >> TL) + (threadIdx.x >> TL);
     const int lane = threadIdx.x & (tpr - 1);
@@ -563,6 +567,9 @@ __global__ __launch_bounds__(256) void k_gmm_draw(const float* __restrict__ mG, 
     const float* zr = z1 + b * z1_bstride;           // (read only where D1 > 0)
     const float* er = eps + b * (int64_t)D;          // (read only in the explicit mode)
     float* orow = out + b * ((int64_t)D1 + D);
+    const int Dch = CTX ? D / HW : 0;
+    const float* cmr = CTX ? c + (b * 2 * M * K + (int64_t)m * K + k) * Dch : nullptr;     // cm_b of (m, k); cs_b lies M K Dch behind
+    const int64_t cso = (int64_t)M * K * Dch;
     if (VEC) {
         const int n1 = D1 >> 2, n = n1 + (D >> 2);
         for (int i = lane; i < n; i += tpr) {
@@ -583,8 +590,18 @@ __global__ __launch_bounds__(256) void k_gmm_draw(const float* __restrict__ mG, 
                 e[0] = ev.x; e[1] = ev.y; e[2] = ev.z; e[3] = ev.w;
             }
             float4 o;
-            o.x = fmaf(temperature * softplus_ref(sg.x), e[0], mu.x); o.y = fmaf(temperature * softplus_ref(sg.y), e[1], mu.y);
-            o.z = fmaf(temperature * softplus_ref(sg.z), e[2], mu.z); o.w = fmaf(temperature * softplus_ref(sg.w), e[3], mu.w);
+            if constexpr (CTX) {
+                float mv[4] = {mu.x, mu.y, mu.z, mu.w}, sv[4] = {sg.x, sg.y, sg.z, sg.w}, ov[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int ch = (4 * g + j) / HW;
+                    ov[j] = fmaf(temperature * softplus_ref(sv[j] + cmr[cso + ch]), e[j], mv[j] + cmr[ch]);
+                }
+                o = make_float4(ov[0], ov[1], ov[2], ov[3]);
+            } else {
+                o.x = fmaf(temperature * softplus_ref(sg.x), e[0], mu.x); o.y = fmaf(temperature * softplus_ref(sg.y), e[1], mu.y);
+                o.z = fmaf(temperature * softplus_ref(sg.z), e[2], mu.z); o.w = fmaf(temperature * softplus_ref(sg.w), e[3], mu.w);
+            }
             reinterpret_cast<float4*>(orow)[i] = o;
         }
     } else {
@@ -606,7 +623,11 @@ __global__ __launch_bounds__(256) void k_gmm_draw(const float* __restrict__ mG, 
                 ev = j == 0 ? e[0] : j == 1 ? e[1] : j == 2 ? e[2] : e[3];
             } else
                 ev = er[d];
-            orow[i] = fmaf(temperature * softplus_ref(sr[d]), ev, mr[d]);
+            if constexpr (CTX) {
+                const int ch = d / HW;
+                orow[i] = fmaf(temperature * softplus_ref(sr[d] + cmr[cso + ch]), ev, mr[d] + cmr[ch]);
+            } else
+                orow[i] = fmaf(temperature * softplus_ref(sr[d]), ev, mr[d]);
         }
     }
 }
@@ -831,11 +852,14 @@ int cf_gmm_sample(const float* mG, const float* sG, const int64_t* rows, const f
     return 0;
 }
 
-int cf_gmm_draw(const float* mG, const float* sG, const float* cdf, const int32_t* labels, int label0, const float* u,
-                const float* eps, const unsigned long long* state, unsigned long long seed, const float* z1,
-                int64_t z1_bstride, int D1, float* out, int B, int M, int K, int D, float temperature, cf_stream_t stream) {
+// cf_gmm_draw (c == NULL, HW unused) and cf_gmm_ctx_draw (c (B, 2 M K D / HW): the per-sample shifts)
+static int gmm_draw(const float* mG, const float* sG, const float* cdf, const int32_t* labels, int label0, const float* u,
+                    const float* eps, const unsigned long long* state, unsigned long long seed, const float* z1,
+                    int64_t z1_bstride, int D1, float* out, int B, int M, int K, int D, float temperature, const float* c, int HW,
+                    cf_stream_t stream) {
     if (B == 0) return 0;                       // empty batch: nothing to do (pointers may be null)
     CF_REQUIRE(mG && sG && cdf && out && B > 0 && M > 0 && K > 0 && K <= 16 && D > 0 && D1 >= 0);
+    CF_REQUIRE(c == nullptr || (HW > 0 && D % HW == 0));
     CF_REQUIRE((u == nullptr) == (eps == nullptr));          // explicit noise: both; Philox: neither
     CF_REQUIRE(eps != nullptr || state != nullptr);
     CF_REQUIRE(D1 == 0 || (z1 != nullptr && z1_bstride >= D1));
@@ -849,12 +873,27 @@ int cf_gmm_draw(const float* mG, const float* sG, const float* cdf, const int32_
     const int rows = 256 >> tl;                 // samples per workgroup
     const int64_t blocks = ((int64_t)B + rows - 1) / rows;
     const float* z = D1 ? z1 : nullptr;
-#define CF_GO(V) k_gmm_draw<V><<<dim3((unsigned)blocks), dim3(256), 0, cf_s(stream)>>>(mG, sG, cdf, labels, label0, u, eps, state, seed, \
-                                                                                       z, z1_bstride, D1, out, B, M, K, D, temperature, tl)
-    if (vec) CF_GO(true); else CF_GO(false);
+#define CF_GO(V, X) k_gmm_draw<V, X><<<dim3((unsigned)blocks), dim3(256), 0, cf_s(stream)>>>(mG, sG, cdf, labels, label0, u, eps, state, seed, \
+                                                                                             z, z1_bstride, D1, out, B, M, K, D, temperature, tl, c, HW)
+    if (c != nullptr) { if (vec) CF_GO(true, true); else CF_GO(false, true); }
+    else { if (vec) CF_GO(true, false); else CF_GO(false, false); }
 #undef CF_GO
     CF_LAUNCH_CHECK();
     return 0;
+}
+
+int cf_gmm_draw(const float* mG, const float* sG, const float* cdf, const int32_t* labels, int label0, const float* u,
+                const float* eps, const unsigned long long* state, unsigned long long seed, const float* z1,
+                int64_t z1_bstride, int D1, float* out, int B, int M, int K, int D, float temperature, cf_stream_t stream) {
+    return gmm_draw(mG, sG, cdf, labels, label0, u, eps, state, seed, z1, z1_bstride, D1, out, B, M, K, D, temperature, nullptr, 0, stream);
+}
+
+int cf_gmm_ctx_draw(const float* mG, const float* sG, const float* cdf, const float* c, const int32_t* labels, int label0,
+                    const float* u, const float* eps, const unsigned long long* state, unsigned long long seed, const float* z1,
+                    int64_t z1_bstride, int D1, float* out, int B, int M, int K, int D, int HW, float temperature, cf_stream_t stream) {
+    if (B == 0) return 0;
+    CF_REQUIRE(c != nullptr);
+    return gmm_draw(mG, sG, cdf, labels, label0, u, eps, state, seed, z1, z1_bstride, D1, out, B, M, K, D, temperature, c, HW, stream);
 }
 
 int64_t cf_gmm_ws_bytes(int B, int M, int K, int D) {

@@ -105,7 +105,10 @@ class ActNorm(FlowLayer):
 
     def reverse(self, z, context=None):
         if self.context_net:
-            raise NotImplementedError("ActNorm.reverse with a context net (the reference's own is marked 'to update')")
+            # by specification (the reference's own is marked 'to update'): x = z exp(l_b) + t_b, one streaming cf_affine_ctx_inv pass
+            from .conv1x1 import affine_ctx_inverse
+            _hip.require_device(z, self.NN_t)
+            return affine_ctx_inverse(z, act=self, context=context)
         assert self._init_done
         return self._run(z, True)[0]
 

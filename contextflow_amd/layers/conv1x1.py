@@ -26,6 +26,33 @@ def conv1x1_apply(x, W, bias=None):
     return out
 
 
+def affine_ctx_inverse(z, conv=None, act=None, context=None, unsqueeze=False):
+    """[Squeeze(2,2) <-] Conv1x1(c) <- ActNorm(c') backwards in one cf_affine_ctx_inv launch: x = W_b^-1 (z exp(l_b) + t_b).  conv /
+    act: the layers (either may be None: the other one alone); each forms its code through cn_linear, exactly as its forward
+    does.  NotImplementedError where the per-sample matrix and the sample do not fit the LDS of a CU."""
+    zv, zbs = _hip.bview(z)
+    B, C, H, W = zv.shape
+    m1 = Wm = m2 = t = logs = None
+    if act is not None:
+        if act.contextflow and not act.is_initialized():
+            raise RuntimeError("ActNorm.reverse with a context net under contextflow needs an initialised layer (run one forward first)")
+        m2 = cn_linear(act, context).m
+        if act.contextflow:
+            t, logs = _hip.f32(act.NN_t.detach()), _hip.f32(act.NN_logs.detach())
+    if conv is not None:
+        m1 = cn_linear(conv, context).m
+        Wm = _hip.f32(conv.NN.detach()) if conv.contextflow else None
+    x = torch.empty((B, C // 4, 2 * H, 2 * W) if unsqueeze else (B, C, H, W), device=zv.device, dtype=torch.float32)
+    try:
+        _hip.call("cf_affine_ctx_inv", _hip.p(zv), _hip.p(m1), _hip.p(Wm), _hip.p(m2), _hip.p(t), _hip.p(logs), _hip.p(x), B, C, H, W, zbs,
+                  int(unsqueeze), _hip.stream())
+    except RuntimeError as e:
+        if "(code -2)" in str(e):              # CF_ERR_UNSUPPORTED: the shape needs more LDS than a CU has
+            raise NotImplementedError(str(e)) from None
+        raise
+    return x
+
+
 class Conv1x1(FlowLayer):
     def __init__(self, data_size, context_net=None, contextflow=False):
         super().__init__()
@@ -75,7 +102,8 @@ class Conv1x1(FlowLayer):
     def reverse(self, z, context=None):
         _hip.require_device(z, self.NN)
         if self.context_net:
-            raise NotImplementedError("Conv1x1.reverse with a context net (the reference's own is marked 'to update')")
+            # by specification (the reference's own is marked 'to update'): the inverse of the map z = W_b x the forward applies
+            return affine_ctx_inverse(z, conv=self, context=context)
         # W^-1 follows NN's version counter and storage (`sample` inverts every layer's matrix per call otherwise)
         inv = _derived.get(self, "winv", _derived.key((self.NN,), str(z.device)),
                            lambda: slogdet_inverse(_hip.f32(self.NN.detach()), True)[1], z.device)

@@ -383,14 +383,17 @@ class GaussianMixtureDistribution(nn.Module):
             raise ValueError("labels: values outside [0, %d)" % M)
         return _ClassLabels(t.to(device=self.mG.device, dtype=torch.int32).contiguous(), 0)
 
-    def draw(self, n_samples, labels=None, temperature=1.0, z1=None):
+    def draw(self, n_samples, labels=None, temperature=1.0, z1=None, context=None):
         """One cf_gmm_draw launch: per sample the class-mixture of `labels` (see _class_labels), a component by its weight,
         mG + temperature * softplus(sG) * eps - noise from the in-kernel Philox stream, positioned by torch's CUDA generator
         (`_hip.noise_nonce`) - written behind the channels of z1 (B, C1, H, W), if given: the draw and the concatenate of
-        SplitPrior.reverse in one pass.  Returns (n, C1 + C, H, W)."""
+        SplitPrior.reverse in one pass.  Returns (n, C1 + C, H, W).
+        A prior with a context net takes `context` ((n, nctx) integers): the rows of shifts c = context_net(context) (B, 2 M K C) are
+        gathered and cf_gmm_ctx_draw draws from (mG + cm_b) + temperature * softplus(sG + cs_b) * eps - the density `log_prob(.,
+        context)` scores (the reference's own `sample` ignores the shifts: `sample` below keeps that behaviour)."""
         _hip.require_device(self.mG, z1)
-        if self.context_net:
-            raise NotImplementedError("class-conditional / tempered sampling of a mixture with a context net")
+        if self.context_net and context is None:
+            raise ValueError("draw: a mixture with a context net needs its context")
         temperature = float(temperature)
         if not (temperature >= 0.0 and math.isfinite(temperature)):
             raise ValueError("temperature must be finite and >= 0, got %r" % temperature)
@@ -405,8 +408,22 @@ class GaussianMixtureDistribution(nn.Module):
                 raise ValueError("draw: kept half of shape %s for %d samples of a prior over %s" % (tuple(z1.shape), n_samples, (C, H, W)))
             C1 = z1.shape[1]
             D1 = C1 * H * W
+        shifts = None
+        if self.context_net:
+            if isinstance(context, list):
+                context = context[0]
+            if context.shape[0] != n_samples:
+                raise ValueError("draw: a context of %d rows for %d samples" % (context.shape[0], n_samples))
+            shifts = _hip.f32(self.context_net(context)[0])
+            if tuple(shifts.shape) != (n_samples, 2 * self.M * self.K * C):
+                raise ValueError("draw: context net output of shape %s, (%d, %d) expected" % (tuple(shifts.shape), n_samples, 2 * self.M * self.K * C))
         key, nonce = _hip.noise_nonce(dev)
         out = torch.empty(n_samples, C1 + C, H, W, device=dev, dtype=torch.float32)
+        if shifts is not None:
+            _hip.call("cf_gmm_ctx_draw", _hip.p(_hip.f32(self.mG.detach())), _hip.p(_hip.f32(self.sG.detach())), _hip.p(self.component_cdf()),
+                      _hip.p(shifts), _hip.p(lab), label0, None, None, _hip.p(nonce), key, _hip.p(z1 if D1 else None), zbs, D1, _hip.p(out),
+                      n_samples, self.M, self.K, D, H * W, temperature, _hip.stream())
+            return out
         _hip.call("cf_gmm_draw", _hip.p(_hip.f32(self.mG.detach())), _hip.p(_hip.f32(self.sG.detach())), _hip.p(self.component_cdf()),
                   _hip.p(lab), label0, None, None, _hip.p(nonce), key, _hip.p(z1 if D1 else None), zbs, D1, _hip.p(out), n_samples,
                   self.M, self.K, D, temperature, _hip.stream())

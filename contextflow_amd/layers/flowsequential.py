@@ -22,7 +22,7 @@ from . import _derived, _hip, _tape
 from ._tape import step_tape
 from .actnorm import ActNorm
 from .augment import Augment
-from .conv1x1 import Conv1x1
+from .conv1x1 import Conv1x1, affine_ctx_inverse
 from . import coupling as _cpl
 from .coupling import Coupling, TransCoupling
 from .dequantize import Dequantization
@@ -57,6 +57,20 @@ def _on_parameter_registration(module, name, param):
 
 
 torch.nn.modules.module.register_module_parameter_registration_hook(_on_parameter_registration)
+
+
+class ContextNoise:
+    """The noise of the stochastic context encoders of one flow for one batch (FlowSequential.context_noise): `tensors`, one per
+    encoder in `flow.modules()` order."""
+
+    def __init__(self, tensors):
+        self.tensors = list(tensors)
+
+    def __len__(self):
+        return len(self.tensors)
+
+    def __iter__(self):
+        return iter(self.tensors)
 
 
 class FlowSequential(nn.Module):
@@ -179,9 +193,13 @@ class FlowSequential(nn.Module):
         return bool(getattr(self.dist, "context_net", None))
 
     def _has_context_nets(self):
-        """True when the prior, a layer or a layer's prior carries a context net (a specialist flow)."""
-        return bool(getattr(self.dist, "context_net", None)) or any(
-            getattr(m, "context_net", None) or getattr(getattr(m, "dist", None), "context_net", None) for m in self.sequence_modules)
+        """True when the prior, a layer or a layer's prior carries a context net (a specialist flow).  The answer is kept until a
+        parameter is registered somewhere (the generalist `sample` / `encode` / `decode` ask per call)."""
+        hit = self.__dict__.get("_ctx_nets")
+        if hit is None or hit[0] != _PARAM_GENERATION[0]:
+            hit = self.__dict__["_ctx_nets"] = (_PARAM_GENERATION[0], bool(getattr(self.dist, "context_net", None)) or any(
+                getattr(m, "context_net", None) or getattr(getattr(m, "dist", None), "context_net", None) for m in self.sequence_modules))
+        return hit[1]
 
     def _needs_only_init(self):
         """True when the fused plan is blocked only by ActNorm layers that have not seen their first batch yet."""
@@ -857,10 +875,65 @@ class FlowSequential(nn.Module):
             events.append((e0, e1, B, C, H * W))
         return x
 
-    def inverse(self, z, context=None):
+    # ------------------------------------------------------------------ the stochastic context encoders, pinned
+    def _stochastic_encoders(self):
+        """Every module of the flow that draws noise when it encodes a context, in `modules()` order."""
+        from .context import ConditionalGaussianDistribution, UniformCatDequantization
+        return [m for m in self.modules() if isinstance(m, (UniformCatDequantization, ConditionalGaussianDistribution))]
+
+    def context_noise(self, context):
+        """One noise tensor per stochastic context encoder of the flow - every UniformCatDequantization ((B, width) uniforms) and
+        every ConditionalGaussianDistribution ((B, D) normals), in `modules()` order, in the shapes those encoders draw, from
+        torch's device generator - as a ContextNoise.  Passed as `noise=` to encode / decode / inverse / sample it makes both
+        directions see the same codes: every layer of a specialist flow draws its own noise otherwise, and `decode(encode(x, c), c)`
+        would not be a round trip."""
+        from .context import UniformCatDequantization
+        B = int(context.shape[0])
+        dev = next(self.parameters()).device
+        _hip.require_device(next(self.parameters()))
+        out = []
+        for e in self._stochastic_encoders():
+            draw = torch.rand if isinstance(e, UniformCatDequantization) else torch.randn
+            out.append(draw((B, e.D), device=dev, dtype=torch.float32))
+        return ContextNoise(out)
+
+    def _pinned(self, noise, context):
+        """Context manager: every stochastic encoder reads its tensor of `noise` (a ContextNoise, or a sequence of tensors in
+        the same order) for the duration of the block; an encoder whose `fixed_noise` is already set keeps it.  None: nothing."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def pin():
+            encs = self._stochastic_encoders()
+            tensors = list(noise.tensors if isinstance(noise, ContextNoise) else noise)
+            if len(tensors) != len(encs):
+                raise ValueError("noise: %d tensors for a flow with %d stochastic context encoders" % (len(tensors), len(encs)))
+            B = None if context is None else int(context.shape[0])
+            for e, t in zip(encs, tensors):
+                if t.dim() != 2 or t.shape[1] != e.D or (B is not None and t.shape[0] != B):
+                    raise ValueError("noise: a tensor of shape %s for an encoder that draws (%s, %d)" % (tuple(t.shape), B, e.D))
+            mine = [(e, t) for e, t in zip(encs, tensors) if e.fixed_noise is None]
+            try:
+                for e, t in mine:
+                    e.fixed_noise = t
+                yield
+            finally:
+                for e, _ in mine:
+                    e.fixed_noise = None
+        return contextlib.nullcontext() if noise is None else pin()
+
+    def _need_context(self, what, context):
+        if context is None and self._has_context_nets():
+            raise ValueError("%s: a context-conditioned (specialist) flow needs its context" % what)
+
+    def inverse(self, z, context=None, noise=None):
         """Run every layer's `reverse` from the last to the first (the loop of flowsequential.py:35-37); groups
-        Coupling <- ActNorm <- Conv1x1 of a supported shape run as one fused kernel."""
-        return self._inverse(z, context, None)
+        Coupling <- ActNorm <- Conv1x1 of a supported shape run as one fused kernel.  A specialist flow takes its `context`
+        (ValueError without): ActNorm(c) <- Conv1x1(c) pairs, with the Squeeze((2,2)) in front of them, run as one
+        cf_affine_ctx_inv launch, the couplings layer by layer; noise (`context_noise`): the codes the encoders form."""
+        self._need_context("inverse", context)
+        with self._pinned(noise, context):
+            return self._inverse(z, context, None)
 
     def _pixel_range(self):
         """(0, bins - 1) of the image flows - Dequantization followed by Normalization(0, bins) (model.py:97-98) - else None."""
@@ -869,19 +942,28 @@ class FlowSequential(nn.Module):
             return 0.0, mods[1]._s - 1.0
         return None
 
-    def _inverse(self, z, context, clamp, latents=None, labels=None, temperature=1.0):
+    def _inverse(self, z, context, clamp, latents=None, labels=None, temperature=1.0, ctx_draw=False):
         """`inverse`; clamp = (lo, hi): the output of the leading Dequantization's reverse is projected into that range.
         latents: the split-off halves in forward order, put back by the SplitPriors instead of fresh draws (`decode`);
-        labels / temperature: passed to every SplitPrior's draw (`sample`).  All at their defaults: the plain chain."""
+        labels / temperature: passed to every SplitPrior's draw (`sample`).  All at their defaults: the plain chain.
+        A specialist flow (context nets, a context given): every ActNorm(c) <- Conv1x1(c) pair - with the Squeeze((2,2)) in front of
+        it - is one cf_affine_ctx_inv launch, everything else its own reverse(z, context); ctx_draw: the SplitPriors draw from the
+        context-shifted mixtures (`sample` under a context)."""
         if latents is not None:
             latents = list(latents)
         _hip.require_device(z)
         mods = self.sequence_modules
         i = len(mods) - 1
+        spec = context is not None and self._has_context_nets()
         with torch.no_grad():
             while i >= 0:
                 m = mods[i]
-                if (self.fused and i >= 2 and z.dim() == 4 and isinstance(mods[i - 1], ActNorm)
+                if (spec and isinstance(m, ActNorm) and m.context_net and i >= 1 and z.dim() == 4 and isinstance(mods[i - 1], Conv1x1)
+                        and mods[i - 1].context_net and mods[i - 1].D == z.shape[1]):
+                    sq = i >= 2 and isinstance(mods[i - 2], Squeeze) and tuple(mods[i - 2].p) == (2, 2) and z.shape[1] % 4 == 0
+                    z = affine_ctx_inverse(z, conv=mods[i - 1], act=m, context=context, unsqueeze=sq)
+                    i -= 3 if sq else 2
+                elif (not spec and self.fused and i >= 2 and z.dim() == 4 and isinstance(mods[i - 1], ActNorm)
                         and mods[i - 1].is_initialized()
                         and self._step_supported(mods[i - 2], mods[i - 1], m, tuple(z.shape[1:]))):
                     sq = i >= 3 and isinstance(mods[i - 3], Squeeze) and tuple(mods[i - 3].p) == (2, 2)
@@ -895,6 +977,8 @@ class FlowSequential(nn.Module):
                         if not latents:
                             raise ValueError("decode: no latent left for the SplitPrior at layer %d" % i)
                         z = m.reverse(z, context, latent=latents.pop())
+                    elif isinstance(m, SplitPrior) and ctx_draw:
+                        z = m.reverse(z, context, labels=labels, temperature=temperature, ctx_draw=True)
                     elif isinstance(m, SplitPrior) and (labels is not None or temperature != 1.0):
                         z = m.reverse(z, context, labels=labels, temperature=temperature)
                     else:
@@ -927,7 +1011,7 @@ class FlowSequential(nn.Module):
                       clamp[0], clamp[1], _hip.stream())
         return x
 
-    def sample(self, n_samples, context=None, labels=None, temperature=1.0):
+    def sample(self, n_samples, context=None, labels=None, temperature=1.0, noise=None):
         """flowsequential.py:32-39: a prior draw through the reverse chain.  By specification, for the image flows: the pixels
         are projected into [0, bins - 1].  The reverse chain ends in floor(bins (sigmoid(y) - a) / (1 - 2 a)) (dequantize.py:19-20,
         normalize.py:36-40), which is -1 / bins wherever sigmoid(y) leaves [a, 1 - a) - logits no forward pass can produce, but
@@ -937,7 +1021,21 @@ class FlowSequential(nn.Module):
         labels (an int, or one class index per sample) / temperature: the prior and every SplitPrior on the way back draw
         from the class-mixture of each sample's label, with the components' scales multiplied by `temperature` - one
         cf_gmm_draw launch per level (GaussianMixtureDistribution.draw).  labels=None is class-mixture 1, as the default
-        call.  Mixture priors only: ValueError otherwise."""
+        call.  Mixture priors only: ValueError otherwise.
+        A specialist flow takes its `context` ((n, nctx) integers; ValueError without one or with another number of rows) and
+        draws, by specification, from the density `log_prob(., context)` scores: the prior and every SplitPrior draw from the
+        mixtures with the per-sample shifts of their context nets (one cf_gmm_ctx_draw launch per level), where the
+        reference's own `sample` ignores the shifts.  noise (`context_noise`): the codes of the stochastic context encoders."""
+        self._need_context("sample", context)
+        if context is not None and self._has_context_nets():
+            if not isinstance(self.dist, GaussianMixtureDistribution):
+                raise ValueError("sample under a context needs a mixture prior, not %s" % type(self.dist).__name__)
+            if context.shape[0] != n_samples:
+                raise ValueError("sample: a context of %d rows for %d samples" % (context.shape[0], n_samples))
+            with self._pinned(noise, context):
+                labels = self.dist._class_labels(labels, n_samples)
+                z = self.dist.draw(n_samples, labels, temperature, context=context)
+                return self._inverse(z, context, self._pixel_range(), labels=labels, temperature=temperature, ctx_draw=True)
         if labels is not None or temperature != 1.0:
             if not isinstance(self.dist, GaussianMixtureDistribution):
                 raise ValueError("sample: labels / temperature need a mixture prior, not %s" % type(self.dist).__name__)
@@ -951,18 +1049,20 @@ class FlowSequential(nn.Module):
     def _split_priors(self):
         return [m for m in self.sequence_modules if isinstance(m, SplitPrior)]
 
-    def encode(self, x, context=None):
+    def encode(self, x, context=None, noise=None):
         """(latents, logp): the complete latent of x - latents = [half_1, ..., half_n, z], the channel half every SplitPrior
         split off, in forward order, and the final z, each a fresh contiguous tensor - and the (B, M) log-densities.  The
         same kernels as `forward` (the fused plan when it applies; never a replayed graph): the halves are the slices the
         mixture kernels score, copied out, and under the same seed / injected noise z and logp are `forward`'s bit for bit.
-        `decode` is the way back."""
+        `decode` is the way back.
+        A specialist flow takes its `context` (ValueError without) and runs layer by layer; noise (`context_noise`): the codes
+        of its stochastic context encoders - the same object given to `decode` makes the pair a round trip, and logp is what
+        `forward` returns under that noise."""
         _hip.require_device(x)
-        if self._has_context_nets():
-            raise NotImplementedError("encode of a context-conditioned (specialist) flow")
+        self._need_context("encode", context)
         self._refresh_generation()
         halves = []
-        with torch.no_grad():
+        with torch.no_grad(), self._pinned(noise, context):
             if self._fusable():
                 z, logp = self._forward_fused(x, context, halves=halves)
             else:
@@ -971,10 +1071,12 @@ class FlowSequential(nn.Module):
             latents = [h.clone(memory_format=torch.contiguous_format) for h in halves + [z]]
         return latents, logp
 
-    def decode(self, latents, context=None, clamp=False):
+    def decode(self, latents, context=None, clamp=False, noise=None):
         """The reverse chain on a complete latent (`encode`'s list: one half per SplitPrior in forward order, then z): every
         SplitPrior puts its half back instead of drawing one.  clamp=True: the projection into the pixel range that `sample`
-        applies.  ValueError for a wrong number of latents or a latent whose shape is not its level's."""
+        applies.  ValueError for a wrong number of latents or a latent whose shape is not its level's.  A specialist flow takes
+        its `context` (ValueError without) and `noise` as `encode`."""
+        self._need_context("decode", context)
         latents = list(latents)
         n = len(self._split_priors())
         if len(latents) != n + 1:
@@ -984,7 +1086,8 @@ class FlowSequential(nn.Module):
             raise ValueError("decode: latents of different batch sizes %s" % [h.shape[0] for h in latents])
         if isinstance(self.dist, GaussianMixtureDistribution) and tuple(z.shape[1:]) != tuple(self.dist.mG.shape[2:]):
             raise ValueError("decode: z of shape %s, the prior is over %s" % (tuple(z.shape), tuple(self.dist.mG.shape[2:])))
-        return self._inverse(z, context, self._pixel_range() if clamp else None, latents=latents[:-1])
+        with self._pinned(noise, context):
+            return self._inverse(z, context, self._pixel_range() if clamp else None, latents=latents[:-1])
 
 
 class GraphedFlow:

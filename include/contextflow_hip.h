@@ -223,6 +223,16 @@ int cf_gmm_sample(const float* mG, const float* sG, const int64_t* rows, const f
 int cf_gmm_draw(const float* mG, const float* sG, const float* cdf, const int32_t* labels, int label0, const float* u,
                 const float* eps, const unsigned long long* state, unsigned long long seed, const float* z1,
                 int64_t z1_bstride, int D1, float* out, int B, int M, int K, int D, float temperature, cf_stream_t stream);
+/* cf_gmm_draw for a prior with a context net (gaussian.py:146-158): c (B, 2 M K Dch), layout 'b (p m k d)', Dch = D / HW, holds
+ * per-sample shifts of the component means (p = 0) and pre-softplus scales (p = 1), constant over the HW pixels of a channel:
+ *   out[b, D1 + d HW + p] = fmaf(ts, eps, fl(mG + cm_b)),  ts = temperature * softplus(fl(sG + cs_b)),
+ *   cm_b = c[b, (m K + k) Dch + d], cs_b = c[b, (M K + m K + k) Dch + d].
+ * Labels, component pick, cdf, explicit u / eps, the Philox positions and the z1 copy are cf_gmm_draw's; with c == 0 the output
+ * is cf_gmm_draw's bit for bit, and temperature == 0 returns the rows fl(mG + cm_b).  D % HW == 0.  B == 0: no-op.  */
+int cf_gmm_ctx_draw(const float* mG, const float* sG, const float* cdf, const float* c, const int32_t* labels, int label0,
+                    const float* u, const float* eps, const unsigned long long* state, unsigned long long seed, const float* z1,
+                    int64_t z1_bstride, int D1, float* out, int B, int M, int K, int D, int HW, float temperature,
+                    cf_stream_t stream);
 
 /* ---- fused flow step: Conv1x1 -> ActNorm -> Coupling(conv net) in ONE kernel, fp32 MFMA ---------
  * (model.py:129-147 per-step triple; coupling.py:26-29 net; conv1x1.py:52-57; actnorm.py:53-60)
@@ -663,6 +673,16 @@ int cf_gmm_ctx_pgrad_tab(const float* x, const float* mG, const float* inv_sig, 
  * aligned operands, one workgroup per sample (LDS) elsewhere.                                                     */
 int cf_affine_ctx_bwd_data(const float* gz, const float* m1, const float* Wm, const float* m2, const float* logs, float* gx,
                            int B, int C, int H, int W, int64_t gz_bstride, int out_unsqueeze, cf_stream_t stream);
+/* ---- the same pair backwards (FlowSequential.inverse / decode / sample with a context): the inverse of cf_affine_ctx_fwd,
+ *   x[b] = W_b^-1 (z[b] * exp(l_b) + t_b) per pixel,  W_b from m1 (B, C*C) [+ Wm - I] as cf_conv1x1_ctx, [t_b | l_b] = m2[b] (B, 2C)
+ *   [+ t | logs] (both or neither).  m1 NULL: a lone ActNorm inverse (a streaming pass, no matrix); m2 NULL: a lone Conv1x1
+ * inverse.  It inverts the map z = W_b x that the forward applies (a full matrix under contextflow).  out_unsqueeze: x_out in the
+ * (B, C/4, 2H, 2W) layout in front of a Squeeze((2,2)).  One workgroup per sample: W_b inverted in LDS by fp32 Gauss-Jordan with
+ * partial pivoting (a singular W_b gives non-finite output), the product, and one refinement step x0 + W_b^-1 (y - W_b x0) with
+ * the residual in fp64 (the result is within eps + (cond(W_b) eps)^2 of the exact x).  C <= 256; CF_ERR_UNSUPPORTED above 160 KiB
+ * of LDS (4 (C (2C + 9) + 2 C H W) bytes, about).  Any alignment; z may be batch-strided.  B == 0: no-op.          */
+int cf_affine_ctx_inv(const float* z, const float* m1, const float* Wm, const float* m2, const float* t, const float* logs,
+                      float* x_out, int B, int C, int H, int W, int64_t z_bstride, int out_unsqueeze, cf_stream_t stream);
 /* cf_flow_step_bwd_ctx without its operand planes: s_gh is not written either, gx is bitwise the same.           */
 int cf_flow_step_bwd_ctx_data(const float* x, const float* gz, const float* gld, const void* ws, const void* wsb,
                               const float* sbias, float* gx, int B, int C, int H, int W, int64_t x_bstride, cf_stream_t stream);
