@@ -51,8 +51,7 @@ struct StepPackBatch {
     const float *Wm[kPrepBatch], *t[kPrepBatch], *logs[kPrepBatch], *w1[kPrepBatch], *b1[kPrepBatch], *w2[kPrepBatch], *b2[kPrepBatch],
         *w3[kPrepBatch], *b3[kPrepBatch];
     float* ws[kPrepBatch];
-    int pieces;                          // also the bf16 pieces of the Winograd-domain weights (CONTEXTFLOW_BF16_SPLIT=1)
-    int w24;                             // also the F(2x4, 3x3) Winograd-domain weights of the 4x4 / 8x8 levels (unless CONTEXTFLOW_WINO24=0)
+    int w24;                             // also the F(2x4, 3x3) Winograd-domain weights of the 4x4 / 8x8 levels (not under CONTEXTFLOW_DIRECT_CONV=1)
 };
 template <class G>
 __global__ __launch_bounds__(256) void k_step_pack(const StepPackBatch pb) {
@@ -113,48 +112,6 @@ __global__ __launch_bounds__(256) void k_step_pack(const StepPackBatch pb) {
             for (int a = 0; a < 3; ++a)
                 for (int b = 0; b < 3; ++b) u += Gm[xi][a] * Gm[nu][b] * (double)wk[a * 3 + b];
             ws[G::OFF_AW + e] = (float)u;
-        }
-        if (G::KB32 > 0 && G::HID == 32 && pb.pieces) {     // (the 16x16 level is the only consumer so far)
-            // the same values as three bf16 pieces each (truncation split: exact, u = p0 + p1 + p2), in the operand layout of
-            // v_mfma_f32_16x16x32_bf16 with k index (lane >> 4, j) = channel 4 j + (lane >> 4) of a 32-channel block
-            unsigned short* wb = reinterpret_cast<unsigned short*>(ws + G::OFF_AWB);
-            for (int e = gtid; e < 16 * G::RT16 * G::KB32 * 64 * 8; e += gsz) {
-                const int j = e & 7, ln = (e >> 3) & 63, q = e >> 9;
-                const int kb = q % G::KB32, rt16 = (q / G::KB32) % G::RT16, pos = q / (G::KB32 * G::RT16);
-                const int co = rt16 * 16 + (ln & 15), ci = 32 * kb + 4 * j + (ln >> 4), xi = pos >> 2, nu = pos & 3;
-                const float* wk = w2 + ((int64_t)co * HID + ci) * 9;
-                double u = 0.0;
-                for (int a = 0; a < 3; ++a)
-                    for (int b = 0; b < 3; ++b) u += Gm[xi][a] * Gm[nu][b] * (double)wk[a * 3 + b];
-                const float uf = (float)u;
-                const unsigned u0 = __float_as_uint(uf) & 0xffff0000u;
-                const float r1 = uf - __uint_as_float(u0);
-                const unsigned u1 = __float_as_uint(r1) & 0xffff0000u;
-                const float r2 = r1 - __uint_as_float(u1);
-                const unsigned pc[3] = {u0, u1, __float_as_uint(r2)};
-#pragma unroll
-                for (int pz = 0; pz < 3; ++pz)
-                    wb[((((int64_t)(pos * G::RT16 + rt16) * G::KB32 + kb) * 3 + pz) * 64 + ln) * 8 + j] = (unsigned short)(pc[pz] >> 16);
-            }
-        }
-        if (G::KB32 > 0 && G::HID == 32 && pb.pieces) {
-            // the taps of NN.2 themselves as three bf16 pieces each, operand layout of v_mfma_f32_16x16x32_bf16 in the hardware's own k
-            // order (direct_bf16_phases): element j of lane l = NN.2[16 rt + (l & 15)][32 kb + 8 (l >> 4) + j][tap]
-            unsigned short* wb = reinterpret_cast<unsigned short*>(ws + G::OFF_ADB);
-            for (int e = gtid; e < 9 * G::RT16 * G::KB32 * 64 * 8; e += gsz) {
-                const int j = e & 7, ln = (e >> 3) & 63, q = e >> 9;
-                const int kb = q % G::KB32, rt16 = (q / G::KB32) % G::RT16, tap = q / (G::KB32 * G::RT16);
-                const int co = rt16 * 16 + (ln & 15), ci = 32 * kb + 8 * (ln >> 4) + j;
-                const float uf = w2[((int64_t)co * HID + ci) * 9 + tap];
-                const unsigned u0 = __float_as_uint(uf) & 0xffff0000u;
-                const float r1 = uf - __uint_as_float(u0);
-                const unsigned u1 = __float_as_uint(r1) & 0xffff0000u;
-                const float r2 = r1 - __uint_as_float(u1);
-                const unsigned pc[3] = {u0, u1, __float_as_uint(r2)};
-#pragma unroll
-                for (int pz = 0; pz < 3; ++pz)
-                    wb[((((int64_t)(tap * G::RT16 + rt16) * G::KB32 + kb) * 3 + pz) * 64 + ln) * 8 + j] = (unsigned short)(pc[pz] >> 16);
-            }
         }
     }
     if (G::HAS_W24 && pb.w24) {
@@ -510,10 +467,7 @@ __device__ __forceinline__ void flow_step_small_body(const float* x, float* z, f
     (void)plane_mask_store;
 
     // ================= phases 1, 2: h2 = relu(NN.2 (*) relu(NN.0 y0 + b) + b)   (coupling.py:26-27)
-    if constexpr (G::DBF) {
-        static_assert(!DUMP && !DBG && CTX != 2, "evaluation form only");
-        direct_bf16_phases<G>(lds, ws, rs, lane, wave);
-    } else if constexpr (!G::HID16) {
+    if constexpr (!G::HID16) {
         const int li = lane & 31;
         int pix[PTW], pin[PTW];
 #pragma unroll
@@ -656,14 +610,8 @@ __device__ __forceinline__ void flow_step_small_body(const float* x, float* z, f
     __syncthreads();
     if (tid == 0 && tile < B) ldj_acc[tile] += ws[0] + ((Y0[0] + Y0[64]) + (Y0[128] + Y0[192]));
 }
-#ifndef CF_G16WB_MINW
-#define CF_G16WB_MINW 3
-#endif
-#ifndef CF_G16DB_MINW
-#define CF_G16DB_MINW 3
-#endif
 template <class G, bool SQ, bool DBG = false, bool DUMP = false, int CTX = 0>
-__global__ __launch_bounds__(256, G::DBF ? CF_G16DB_MINW : G::BF16S ? CF_G16WB_MINW : (G::WINO && DUMP) ? 3 : (G::WINO && G::C == 16) ? CF_G16W_MINW : G::MINW) void k_flow_step_small(const float* __restrict__ x, float* __restrict__ z,
+__global__ __launch_bounds__(256, (G::WINO && DUMP) ? 3 : (G::WINO && G::C == 16) ? CF_G16W_MINW : G::MINW) void k_flow_step_small(const float* __restrict__ x, float* __restrict__ z,
                                                                   float* __restrict__ ldj_acc, const float* __restrict__ ws,
                                                                   int B, int64_t xbs, float* __restrict__ dbg, StepTape tp,
                                                                   const float* __restrict__ sb = nullptr) {
@@ -1379,13 +1327,6 @@ int launch_prepare_inv(const float* Wm, const float* t, const float* logs, float
     return 0;
 }
 
-static int g_bf16_split = -1;             // -1: the environment decides (CONTEXTFLOW_BF16_SPLIT=1|2); 0 / 1 / 2: set by cf_bf16_split
-static int bf16_split_mode() {            // 0 off, 1 Winograd-domain products as bf16 pieces (G16wb), 2 direct 3x3 on bf16 pieces (G16db)
-    static const int v = [] { const char* e = getenv("CONTEXTFLOW_BF16_SPLIT"); return (e && (e[0] == '1' || e[0] == '2')) ? e[0] - '0' : 0; }();
-    return g_bf16_split < 0 ? v : g_bf16_split;
-}
-static bool bf16_split_enabled() { return bf16_split_mode() != 0; }
-
 template <class G>
 int launch_step_inv(const float* z, float* x, const float* ws, const float* wsi, int B, int64_t zbs, int x_unsq, hipStream_t s) {
     constexpr size_t lds_bytes = (size_t)G::LDS_FLOATS * sizeof(float);
@@ -1404,22 +1345,11 @@ static bool direct_conv_only() {
     static const bool v = [] { const char* e = getenv("CONTEXTFLOW_DIRECT_CONV"); return e && e[0] == '1'; }();
     return v;
 }
-// the 4x4 / 8x8 levels' evaluation forward in the Winograd F(2x4, 3x3) form (G64w24 / G32w24) unless CONTEXTFLOW_WINO24=0
-// (A/B: F(2x2, 3x3) everywhere, G64w2 / G32w); CONTEXTFLOW_WINO24_8X8=0 switches only the 8x8 level back (A/B of that level)
-static bool wino24_enabled() {
-    static const bool v = [] { const char* e = getenv("CONTEXTFLOW_WINO24"); return !(e && e[0] == '0'); }();
-    return v;
-}
-static bool wino24_8x8_enabled() {
-    static const bool v = [] { const char* e = getenv("CONTEXTFLOW_WINO24_8X8"); return !(e && e[0] == '0'); }();
-    return v && wino24_enabled();
-}
-
 // ---- dispatch: the ONE place that says which kernel runs a step ---------------------------------------------------------
 // A kernel family with its geometry, one value per pair the library launches outside the test hook's alternates.
 enum class Kernel {
     None,
-    Small_G8s, Small_G16s, Small_G8w, Small_G16w, Small_G16wb, Small_G16db,                                        // k_flow_step_small
+    Small_G8s, Small_G16s, Small_G8w, Small_G16w,                                                                  // k_flow_step_small
     Step_G8, Step_G16, Step_G32, Step_G32v2, Step_G32w, Step_G32w24, Step_G64, Step_G64v2, Step_G64w2, Step_G64w24,   // k_flow_step
     Rs_G32,                                                                                                        // k_flow_step_rs<.., 2>
     Rs16_G64,                                                                                                      // k_flow_step_rs16
@@ -1440,8 +1370,7 @@ constexpr int kW24MinB8x8 = 512 * G32w24::SPW;
 constexpr int kRsMaxB8x8 = 512;
 // 4x4: one sample per workgroup on 16-column tiles (twice the workgroups of the row-split kernel) up to here, Winograd above
 constexpr int kRs16MaxB4x4 = 1024;
-// 16x16 images: chained launches (cf_flow_step_fwd_chain) up to here; CONTEXTFLOW_BF16_SPLIT=2, the direct bf16-piece form, from
-// here - below, the chained launches of the fp32 form run
+// 16x16 images: chained launches (cf_flow_step_fwd_chain) up to here
 constexpr int kChainMaxB16x16 = 1024;
 
 // largest batch cf_flow_step_fwd_chain takes: the range in which a step is one of the small-batch kernels anyway
@@ -1484,29 +1413,24 @@ static Kernel select(Pass pass, int sid, int B) {
         case 1:                          // 16x16 images: k_flow_step_small, one sample per workgroup, Winograd at every batch size (taped: h1
                                          // reaches the tape from the accumulators there, its LDS plane is in the parity-split order)
             if (direct) return ctx ? Kernel::Step_G16 : Kernel::Small_G16s;
-            // CONTEXTFLOW_BF16_SPLIT=1 (off by default): the Winograd-domain products as bf16-piece MFMAs; 2: the direct bf16-piece form
-            if (eval && bf16_split_mode() == 1) return Kernel::Small_G16wb;
-            if (eval && bf16_split_mode() == 2 && B >= kChainMaxB16x16) return Kernel::Small_G16db;
             return Kernel::Small_G16w;
         case 2:
             if (!ctx && B <= kRsMaxB8x8) return Kernel::Rs_G32;
             if (B < kFullMinB8x8) return ctx ? Kernel::Step_G32 : Kernel::Step_G32v2;
             if (direct) return Kernel::Step_G32;
-            if (eval && wino24_8x8_enabled() && B >= kW24MinB8x8) return Kernel::Step_G32w24;
+            if (eval && B >= kW24MinB8x8) return Kernel::Step_G32w24;
             return Kernel::Step_G32w;
         case 3:
             if (!ctx && B <= kRs16MaxB4x4) return Kernel::Rs16_G64;      // (taped: one sample per workgroup, as the evaluation forward)
-            if (!direct && B >= kWinoMinB4x4) return (eval && wino24_enabled()) ? Kernel::Step_G64w24 : Kernel::Step_G64w2;
+            if (!direct && B >= kWinoMinB4x4) return eval ? Kernel::Step_G64w24 : Kernel::Step_G64w2;
             return (!ctx && B < kFullMinB4x4) ? Kernel::Step_G64v2 : Kernel::Step_G64;
     }
     return Kernel::None;
 }
 
 // Multiply-adds per pixel and C^2 of a kernel's step, from its geometry's own traits: the direct form runs C^2 (Conv1x1) + C^2 +
-// 36 C^2 + 2 C^2 = 40 C^2, the Winograd form of the 3x3 runs 16 instead of 36 C^2 (F(2x2, 3x3)) or 12 C^2 (F(2x4, 3x3)).  The
-// bf16-piece forms of the 16x16 level (BF16S, DBF: off by default) count as the fp32 Winograd form they stand in for, as they
-// always have - their products run on another pipe, and the roofline these counts feed is the fp32 one.
-template <class G> constexpr int step_macs_c2hw() { return G::W24 ? 16 : (G::WINO || G::BF16S || G::DBF) ? 20 : 40; }
+// 36 C^2 + 2 C^2 = 40 C^2, the Winograd form of the 3x3 runs 16 instead of 36 C^2 (F(2x2, 3x3)) or 12 C^2 (F(2x4, 3x3)).
+template <class G> constexpr int step_macs_c2hw() { return G::W24 ? 16 : G::WINO ? 20 : 40; }
 static int step_macs_c2hw(Kernel k) {
     switch (k) {
         case Kernel::None: return 0;
@@ -1514,8 +1438,6 @@ static int step_macs_c2hw(Kernel k) {
         case Kernel::Small_G16s: return step_macs_c2hw<G16s>();
         case Kernel::Small_G8w: case Kernel::Inv_G8w: return step_macs_c2hw<G8w>();
         case Kernel::Small_G16w: case Kernel::Inv_G16w: return step_macs_c2hw<G16w>();
-        case Kernel::Small_G16wb: return step_macs_c2hw<G16wb>();
-        case Kernel::Small_G16db: return step_macs_c2hw<G16db>();
         case Kernel::Step_G8: case Kernel::Inv_G8: return step_macs_c2hw<G8>();
         case Kernel::Step_G16: case Kernel::Inv_G16: return step_macs_c2hw<G16>();
         case Kernel::Step_G32: case Kernel::Rs_G32: case Kernel::Inv_G32: return step_macs_c2hw<G32>();
@@ -1542,8 +1464,6 @@ static int launch_fwd(Kernel k, const StepArgs& a) {         // evaluation forwa
         case Kernel::Small_G16s: return launch_step_small<G16s>(a);
         case Kernel::Small_G8w: return launch_step_small<G8w>(a);
         case Kernel::Small_G16w: return launch_step_small<G16w>(a);
-        case Kernel::Small_G16wb: return launch_step_small<G16wb>(a);
-        case Kernel::Small_G16db: return launch_step_small<G16db>(a);
         case Kernel::Step_G8: return launch_step<G8>(a);
         case Kernel::Step_G16: return launch_step<G16>(a);
         case Kernel::Step_G32: return launch_step<G32>(a);
@@ -1637,12 +1557,12 @@ static int unsupported_shape(const char* fn, int C, int H, int W) {
 
 // test hook: (shape, variant = flags bits 16..19) -> kernel.  0: the default geometry of the shape in k_flow_step (the only one
 // with per-phase dumps besides 3), 2: half the samples per workgroup, 3: k_flow_step_small in the direct form, 4: Winograd
-// F(2x2, 3x3), 5: ... row-split at 128 pixels per workgroup, 6: the bf16-piece form of 4 at 16x16 / Winograd F(2x4, 3x3) at 8x8
-// and 4x4, 7: direct 3x3 on bf16 pieces.  (1 was an operand-pipeline alternate of each shape: gone with its geometries.)
+// F(2x2, 3x3), 5: ... row-split at 128 pixels per workgroup, 6: Winograd F(2x4, 3x3) at 8x8 and 4x4.  (1 was an operand-pipeline
+// alternate of each shape, 6 at 16x16 and 7 two forms on the 16-bit matrix cores: gone with their geometries.)
 constexpr int kDebugVariants = 8;
 constexpr Kernel kDebugKernel[4][kDebugVariants] = {
     {Kernel::Step_G8, Kernel::None, Kernel::None, Kernel::Small_G8s, Kernel::Small_G8w, Kernel::None, Kernel::None, Kernel::None},
-    {Kernel::Step_G16, Kernel::None, Kernel::None, Kernel::Small_G16s, Kernel::Small_G16w, Kernel::None, Kernel::Small_G16wb, Kernel::Small_G16db},
+    {Kernel::Step_G16, Kernel::None, Kernel::None, Kernel::Small_G16s, Kernel::Small_G16w, Kernel::None, Kernel::None, Kernel::None},
     {Kernel::Step_G32, Kernel::None, Kernel::Step_G32v2, Kernel::None, Kernel::Step_G32w, Kernel::None, Kernel::Step_G32w24, Kernel::None},
     {Kernel::Step_G64, Kernel::None, Kernel::Step_G64v2, Kernel::None, Kernel::None, Kernel::Step_G64w2, Kernel::Step_G64w24, Kernel::None},
 };
@@ -1672,9 +1592,8 @@ int cf_flow_step_prepare_batch(int n, const float* const* Wm, const float* const
     for (int i0 = 0; i0 < n; i0 += kPrepBatch) {
         const int m = n - i0 < kPrepBatch ? n - i0 : kPrepBatch;
         StepPackBatch pb{};
-        pb.pieces = bf16_split_enabled() ? 1 : 0;
         // (the training tables too: they are bitwise those of the evaluation forward - test_prepare_train_equals_prepare_plus_inverse)
-        pb.w24 = (wino24_enabled() && !direct_conv_only()) ? 1 : 0;
+        pb.w24 = !direct_conv_only();
         for (int i = 0; i < m; ++i) {
             const int j = i0 + i;
             CF_REQUIRE(Wm[j] && t[j] && logs[j] && w1[j] && b1[j] && w2[j] && b2[j] && w3[j] && b3[j] && ws[j] &&
@@ -1787,13 +1706,6 @@ int cf_flow_step_fwd_chain(const float* x, float* z, float* ldj_acc, const void*
     if (int rc = launch_fwd_chain(k, StepArgs{x, z, ldj_acc, nullptr, B, x_bstride, in_squeeze != 0, cf_s(stream)}, wc, n)) return rc;
     CF_LAUNCH_CHECK();
     return 0;
-}
-
-// on = 0 / 1: switch the bf16-piece form of the 16x16 level off / on for the tables packed and the steps launched from now on
-// (overrides CONTEXTFLOW_BF16_SPLIT); on < 0: query.  Returns the setting in force.
-int cf_bf16_split(int on) {
-    if (on >= 0) g_bf16_split = on > 2 ? 1 : on;
-    return bf16_split_mode();
 }
 
 int cf_flow_step_fwd(const float* x, float* z, float* ldj_acc, const void* ws, int B, int C, int H, int W,

@@ -117,8 +117,8 @@ def _gmm_param_part(xv, xbs, r, dist, a, nm, g, gcol, B, M, K, D, dev, sink=None
 
 # ------------------------------------------------------------------------------------------------ flow step
 WGRAD_SIDE_MAX_BATCH = 1024      # below: the weight gradients of a step run on a side stream, next to the data-gradient chain
-WGRAD_SIDE_STREAMS = int(__import__("os").environ.get("CONTEXTFLOW_WGRAD_STREAMS", "4"))
-WGRAD_BATCH = __import__("os").environ.get("CONTEXTFLOW_WGRAD_BATCH", "1") == "1"    # see _step_param_part_batch
+WGRAD_SIDE_STREAMS = 4
+WGRAD_BATCH = True               # see _step_param_part_batch (False: one step at a time, the reference path of the tests)
 
 
 # Conv1x1 -> ActNorm in front of a coupling with what their parameter chain reads (_affine_param_grads): Wm = conv.NN, t = act.NN_t,

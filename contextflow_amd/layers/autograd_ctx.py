@@ -13,7 +13,6 @@ The same tape gives the input gradient of log p(x | c): the training walk goes o
 gradient, and with no trainable parameter (a frozen specialist, FlowSequential.score) input_gradient_ctx walks the data halves
 alone - cf_affine_ctx_bwd_data, cf_flow_step_bwd_ctx_data, cf_gmm_ctx_bwd_data - and forms no parameter gradient."""
 import math
-import os
 from typing import Any, NamedTuple
 
 import torch
@@ -179,9 +178,6 @@ def _embedding_grads(emb, context, gc, grads):
         o += d
 
 
-DEFER_LINEAR_WGRADS = os.environ.get("CONTEXTFLOW_SPEC_DEFER_WGRADS", "1") != "0"      # A/B switch (tools/specialist_train_bench.py)
-
-
 class _Pass(NamedTuple):
     """One specialist backward: what every record's backward reads, and where the gradients go.  The encoder, embedding, ViT and
     autograd_layers functions receive by_param alone."""
@@ -189,18 +185,14 @@ class _Pass(NamedTuple):
     glogp: Any               # d/d logp (B, M)
     gld: Any                 # d/d of a per-sample log-det (B,): its row sums
     by_param: dict           # Parameter -> gradient
-    deferred: Any            # [(x_in, gy, lin)]: CN Linears whose weight gradients are formed at the end of the backward; None = one by one
+    deferred: Any            # [(x_in, gy, lin)]: CN Linears whose weight gradients are formed at the end of the backward; None in the
+                             # data-only walk, which meets no CN Linear
 
 
 def _linear_bwd(x_in, lin, gy, bw, need_gx=True):
-    """nn.Linear of a CN net: weight / bias gradients and the data gradient through cf_linear_wgrad / cf_linear.  With a deferral
-    list (`bw.deferred`) only the data gradient is formed here; the weight gradients of all CN Linears of the
-    flow - 60 operand pairs in the cifar10 flow, 420 launches of 7 - 10 us one by one - leave in grouped launches at the end
-    (_flush_linear_wgrads: cf_linear_wgrad_group, the transformer step's LDS-free kernel)."""
-    if bw.deferred is None:
-        gx, gW, gb = _dense_bwd(_hip.f32(x_in), _hip.f32(lin.weight.detach()), _hip.f32(gy), need_gx)
-        bw.by_param[lin.weight], bw.by_param[lin.bias] = gW, gb
-        return gx
+    """nn.Linear of a CN net: only the data gradient (cf_linear) is formed here; the weight / bias gradients of all CN Linears of
+    the flow (`bw.deferred`) - 60 operand pairs in the cifar10 flow, 420 launches of 7 - 10 us one by one - leave in grouped
+    launches at the end (_flush_linear_wgrads: cf_linear_wgrad_group, the transformer step's LDS-free kernel)."""
     x_in, gy = _hip.f32(x_in).contiguous(), _hip.f32(gy).contiguous()
     bw.deferred.append((x_in, gy, lin))
     if not need_gx:
@@ -214,7 +206,7 @@ def _linear_bwd(x_in, lin, gy, bw, need_gx=True):
 
 def _flush_linear_wgrads(bw, dev):
     from .autograd import wgrad_group
-    todo = bw.deferred or []
+    todo = bw.deferred
     for i0 in range(0, len(todo), 32):                  # cf_linear_wgrad_group takes up to 32 members per launch pair
         part = todo[i0:i0 + 32]
         res = wgrad_group([(x_in, gy, True) for x_in, gy, _ in part], dev)
@@ -616,7 +608,7 @@ class SpecialistLogProb(torch.autograd.Function):
             return (None, input_gradient_ctx(ctx.tape + [ctx.prior], glogp).reshape(shape).to(dtype), None)
         glogp = _hip.f32(glogp)
         gld = glogp.sum(1).contiguous()
-        bw = _Pass(ctx.context, glogp, gld, {}, [] if DEFER_LINEAR_WGRADS else None)
+        bw = _Pass(ctx.context, glogp, gld, {}, [])
         gz = gmm_ctx_backward(ctx.prior, glogp, bw.by_param)
         gx = None
         for rec in reversed(ctx.tape):

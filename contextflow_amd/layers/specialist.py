@@ -14,7 +14,6 @@ and the per-sample log-dets accumulate in ONE (B,) buffer inside the kernels ins
 Evaluation only (no tape); `FlowSequential.forward` uses it under no_grad and falls back to the layer loop when a
 model does not have this shape."""
 import math
-import os
 
 import torch
 
@@ -133,7 +132,7 @@ def _draw_encoder_noise(flow, B, dev):
         e.__dict__["_noise_once"] = u[i] if e.D == width else u[i, :, :e.D].contiguous()
 
 
-FRONT_END = os.environ.get("CONTEXTFLOW_SPEC_FRONT", "1") != "0"      # A/B switch of _front_end (tools/specialist_bench.py)
+FRONT_END = True      # _front_end (False: the module-by-module walk, the reference path of the tests)
 
 
 def _uniform_encoder(net):

@@ -28,8 +28,10 @@ extern "C" {
 
 /* Version 13 also covers the entry points added after it that only ADD symbols (cf_adamw_step_batch_dev, cf_grad_norm_partials,
  * cf_grad_norm_batch, cf_grad_scale_batch): no existing signature or behaviour moved, so no caller of version 13 breaks.
- * Version 14: cf_gmm_quad (no caller; cf_gmm_resp feeds the backward) left the ABI. */
-#define CF_ABI_VERSION 14
+ * Version 14: cf_gmm_quad (no caller; cf_gmm_resp feeds the backward) left the ABI.
+ * Version 15: the switch entry of the 16x16 level's forms on the 16-bit matrix cores left the ABI with those kernels;
+ * cf_flow_step_ws_bytes shrank by their tables. */
+#define CF_ABI_VERSION 15
 #define CF_ERR_ARG (-1)          /* bad argument (shape, null pointer, unsupported size) */
 #define CF_ERR_UNSUPPORTED (-2)  /* shape not covered by this kernel; caller uses the generic path */
 
@@ -260,13 +262,6 @@ int cf_flow_step_prepare_batch(int n, const float* const* Wm, const float* const
 int cf_flow_step_bwd_prepare_batch(int n, const float* const* Wm, const float* const* logs, const float* const* w1,
                                    const float* const* w2, const float* const* w3, void* const* wsb, int C, int H, int W,
                                    cf_stream_t stream);
-
-/* The 16x16 level's 3x3 as exact bf16-piece MFMAs (default: the environment variable CONTEXTFLOW_BF16_SPLIT=1|2,
- * else off): 1 = the Winograd-domain products on bf16 pieces, 2 = the DIRECT 3x3 with h1 split once by its producer (from 1024
- * samples per launch).  on = 0 / 1 / 2 sets it for the tables packed and the steps launched from now on, on < 0 queries; returns the
- * setting in force.  Tables packed while it was off do not hold the weight pieces: prepare again after switching on.  Same fp32
- * results as the default (fp32 Winograd) kernels to their rounding; measured: no gain for a whole flow (power), see DESIGN.md. */
-int cf_bf16_split(int on);
 
 /* z = step(x); ldj_acc[b] += ldj_const + sum log_s   (ldj_acc is the running per-sample log-det).
  * in_squeeze != 0: x is the UN-squeezed (B, C/4, 2H, 2W) tensor and Squeeze((2,2)) (squeeze.py:10-11)

@@ -33,7 +33,7 @@ def test_library_exports_every_declared_symbol(built):
     for s in syms:
         assert hasattr(lib, s), "header declares %s but the library does not export it" % s
     assert sorted(_hip.SIGNATURES) == syms, set(_hip.SIGNATURES) ^ set(syms)
-    assert _hip.lib().cf_abi_version() == _hip.ABI_VERSION == 14
+    assert _hip.lib().cf_abi_version() == _hip.ABI_VERSION == 15
     # pure host-side queries work without a GPU
     assert _hip.lib().cf_flow_step_supported(64, 4, 4, 3, 3) == 1
     assert _hip.lib().cf_flow_step_supported(26, 8, 1, 3, 1) == 0
@@ -89,11 +89,6 @@ DISPATCH_SETTINGS = {
     "": {},
     "CONTEXTFLOW_DIRECT_CONV=1": {(8, 16, 16): ([D40] * 4, 0), (16, 16, 16): ([D40] * 4, 0),
                                   (32, 8, 8): ([D40] * 4, 512), (64, 4, 4): ([D40] * 4, 1024)},
-    "CONTEXTFLOW_WINO24=0": {(32, 8, 8): ([[(0, 40), (1024, 20)], [(0, 40), (1024, 20)], D40, W20], 512),
-                             (64, 4, 4): ([[(0, 40), (2048, 20)], [(0, 40), (2048, 20)], D40, W20], 1024)},
-    "CONTEXTFLOW_WINO24_8X8=0": {(32, 8, 8): ([[(0, 40), (1024, 20)], [(0, 40), (1024, 20)], D40, W20], 512)},
-    "CONTEXTFLOW_BF16_SPLIT=1": {},
-    "CONTEXTFLOW_BF16_SPLIT=2": {},
 }
 DISPATCH_SCRIPT = """
 import hashlib, sys
@@ -131,8 +126,36 @@ def test_step_dispatch_breakpoints(built, setting):
     for i, shape in enumerate(SHAPES):
         got = [ast.literal_eval(s) for s in lines[5 * i:5 * i + 4]]
         assert (got, int(lines[5 * i + 4])) == want[shape], (setting, shape, got, lines[5 * i + 4])
-    if setting in ("", "CONTEXTFLOW_BF16_SPLIT=1", "CONTEXTFLOW_BF16_SPLIT=2"):     # all 131 088 values, shape / pass / B ascending
+    if setting == "":     # all 131 088 values, shape / pass / B ascending
         assert lines[20] == "7c2a86c3ec00086a32d855de78c909fd1fc4e762fe67234ccf36ecf20a48c0cf"
+
+
+# Every environment variable the product reads.  A switch is part of the product's surface: one that selects nothing any more goes,
+# and a new one is a decision, made here.  (dist.py also WRITES MASTER_ADDR / MASTER_PORT defaults for torch.distributed.)
+ENVIRONMENT = {"CONTEXTFLOW_DIRECT_CONV", "CONTEXTFLOW_HIP_LIB", "CF_DIST_SINGLE_RANK", "RANK", "LOCAL_RANK", "WORLD_SIZE"}
+# cf_flow_step_ws_bytes per shape with the tables of the removed 16-bit-piece kernels (25 (HID / 16) (HID / 32) 768 floats, HID = 2 C)
+STEP_WS_BYTES_ABI14 = {(8, 16, 16): 51856, (16, 16, 16): 266896, (32, 8, 8): 1434384, (64, 4, 4): 6392848}
+
+
+def test_environment_switches_of_the_product(built):
+    import glob
+    from contextflow_amd.layers import _hip
+    pkg = os.path.join(ROOT, "contextflow_amd")
+    names = set()
+    for path in glob.glob(os.path.join(pkg, "**", "*.py"), recursive=True):
+        src = open(path).read()
+        reads = re.findall(r"""\benviron\s*(?:\.get\s*\(|\[)\s*(["']\w+["'])?|\bgetenv\s*\(\s*(["']\w+["'])?""", src)
+        assert all(a or b for a, b in reads), "%s reads an environment variable whose name is not a literal" % path
+        names |= {(a or b)[1:-1] for a, b in reads}
+    for path in glob.glob(os.path.join(pkg, "csrc", "*")):
+        if os.path.isfile(path):
+            names |= set(re.findall(r"""getenv\(\s*"(\w+)"\s*\)""", open(path).read()))
+    assert names == ENVIRONMENT, names ^ ENVIRONMENT
+    L = _hip.lib()
+    for (C, H, W), ws0 in STEP_WS_BYTES_ABI14.items():
+        hid = 2 * C
+        assert L.cf_flow_step_ws_bytes(C, H, W) == ws0 - 25 * (hid // 16) * (hid // 32) * 768 * 4, (C, H, W)
+    assert [25 * (2 * C // 16) * (2 * C // 32) * 768 * 4 for C in (8, 16, 32, 64)] == [0, 153600, 614400, 2457600]
 
 
 # ---- the weight-gradient launch plan as the size queries and the flop accounting see it ----------------------------------------

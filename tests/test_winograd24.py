@@ -2,7 +2,6 @@
 winograd24_phase2): F(2, 3) down the rows, F(4, 3) on the points {0, 1, -1, 1/2, -1/2, inf} along the columns.  CPU: the
 transforms, a restatement of the form in fp32 against the fp64 direct convolution, and the end-to-end fixtures through the
 oracle with the 4x4 level's 3x3 in this form.  GPU: the production step kernel against the oracle, and the tiled fixtures."""
-import os
 
 import pytest
 import torch
@@ -125,7 +124,7 @@ def test_production_step_kernel_at_a_saturating_batch(L, C, H, squeeze):
     from contextflow_amd.layers import _hip
     B, W = 4100, H
     if (C, H) == (64, 4):      # the dispatch takes the F(2x4) form here: 16 instead of 20 C^2 HW multiply-adds per step
-        per_px = 20 if os.environ.get("CONTEXTFLOW_WINO24", "1")[:1] == "0" else 16        # CONTEXTFLOW_WINO24=0: F(2x2) (A/B)
+        per_px = 16
         assert _hip.lib().cf_flow_step_macs(B, C, H, W, 0) == per_px * C * C * H * W
     torch.manual_seed(C * 1000 + 7)                      # the parameters of test_winograd_step_kernel_against_the_oracle
     conv, act, cpl = L.Conv1x1((C, H, W)), L.ActNorm((C, H, W)), L.Coupling(C, kernel_size=(3, 3), padding=(1, 1))
@@ -176,7 +175,7 @@ def test_cifar10_fixtures_tiled_to_4096_samples(L, tag):
         model.step_events = None
     # the 4x4 level's steps went through cf_flow_step_fwd at this batch, and its dispatch there is the F(2x4) kernel
     assert launches.count((B, 64, 16)) == 4, launches
-    per_px = 20 if os.environ.get("CONTEXTFLOW_WINO24", "1")[:1] == "0" else 16
+    per_px = 16
     assert _hip.lib().cf_flow_step_macs(B, 64, 4, 4, 0) == per_px * 64 * 64 * 16
     lp = logp.cpu()
     for key in ("logp", "logp_f64"):

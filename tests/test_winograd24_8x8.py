@@ -146,15 +146,13 @@ def macs_table(env):
 
 
 def test_executed_macs_of_the_8x8_level():
-    """20 C^2 HW below 2048 samples, 16 C^2 HW from there on in the evaluation forward (pass 0); either switch puts
-    F(2x2) back; the taped forward, the backward and the inverse (passes 1-3) are what they were."""
+    """20 C^2 HW below 2048 samples, 16 C^2 HW from there on in the evaluation forward (pass 0); the taped forward, the
+    backward and the inverse (passes 1-3) are what they were."""
     unit = 32 * 32 * 64
-    on, off_all, off_8 = macs_table({}), macs_table({"CONTEXTFLOW_WINO24": "0"}), macs_table({"CONTEXTFLOW_WINO24_8X8": "0"})
+    on = macs_table({})
     for b in (1024, 2047, 2048, 4101, 1 << 21):
         assert on[b, 0] == (16 if b >= MIN_B else 20) * unit, b
-        assert off_all[b, 0] == off_8[b, 0] == 20 * unit, b
-        for t in (on, off_all, off_8):
-            assert (t[b, 1], t[b, 2], t[b, 3]) == (20 * unit, 40 * unit, 20 * unit), b
+        assert (on[b, 1], on[b, 2], on[b, 3]) == (20 * unit, 40 * unit, 20 * unit), b
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------
