@@ -205,24 +205,45 @@ __global__ __launch_bounds__(256) void k_step_pack(const StepPackBatch pb) {
 // DUMP (training): y0 and the post-ReLU h1 / h2 planes are also written to the tape `tp`; the backward kernel then
 // loads them instead of recomputing phases 1 and 2 (cf_step_bwd.hip, TAPED).
 // DBG: the test-only instantiation that honours `dbg`; the production kernels carry no dump branches at all.
-template <class G, bool SQ, int CTX = 0, bool DUMP = false, bool DBG = false>
-__global__ __launch_bounds__(256, G::MINW) void k_flow_step(const float* __restrict__ x, float* __restrict__ z,
-                                                   float* __restrict__ ldj_acc, const float* __restrict__ ws, int B,
-                                                   int64_t xbs, float* __restrict__ dbg_arg, int flags,
-                                                   const float* __restrict__ sb, StepTape tp) {
+// Level kernels: this lane's index inside its wave, formed afresh where it is called (an asm statement with no inputs is neither
+// hoisted nor merged).  With the wave's index in a scalar register, a step of a level kernel rebuilds its thread index - and every
+// address table derived from it - per step, and the level loop carries no vector register at all: left to threadIdx.x, hipcc
+// hoists those tables in front of the loop and keeps them live across every phase (74 - 82 spilled registers).
+__device__ __forceinline__ int cf_lane_fresh() {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+// Chained / level launches: the packed tables of the n <= kChain consecutive steps of one resolution level, by value in the kernel
+// arguments
+constexpr int kChain = 4;
+struct WsChain { const float* ws[kChain]; };
+
+// Phases 0-3, the affine map and the log-det of ONE step on the x plane that sits in rows [0, C) of H1 (this wave's own columns):
+// the one body of the single-step kernel and of the level kernel below.
+// LEVEL: the step is one of a run that stays in LDS (k_flow_step_level).  Nothing of z goes to global memory here; at the end z =
+// [y0 | z1] is the NEXT step's x plane - y0 moves from the Y0 plane (every lane takes back the words it wrote itself), z1 goes
+// straight from the registers.  Cross-wave hazards of that hand-off: none that the step's own barriers do not cover.  The plane
+// rows are this wave's own columns, which no other wave reads (phase 0) and which the NEXT step overwrites with h1 only behind
+// the workgroup barrier in front of those writes (conditioner_net: the skewed / parity-split h1 order) - a barrier that every
+// wave reaches only after its own phase 3 of THIS step; the log-det finishes inside the wave (HW <= 32 PTW).
+template <class G, int CTX, bool DUMP, bool DBG, bool LEVEL>
+__device__ __forceinline__ void flow_step_phases(float* __restrict__ z, float* __restrict__ ldj_acc, const float* __restrict__ wsl, int B,
+                                                 float* __restrict__ dbg_arg, const float* __restrict__ sb, StepTape tp, int tile, int wave_u = 0) {
     float* const dbg = DBG ? dbg_arg : nullptr;
-    constexpr int C = G::C, HW = G::HW, W = G::W, H = G::H, PIX = G::PIX, HALF = G::HALF, HID = G::HID;
-    constexpr int PTW = G::PTW, RT03 = G::RT03, RT1 = G::RT1;
+    constexpr int C = G::C, HW = G::HW, PIX = G::PIX, HALF = G::HALF, HID = G::HID;
+    constexpr int PTW = G::PTW, RT03 = G::RT03;
     constexpr int WPX = 32 * PTW;                     // pixel columns owned by one wave
-    constexpr int XI = C * PTW / 8;                   // 16-byte x items per lane and tile
+    static_assert(!LEVEL || (CTX == 0 && !DUMP && !DBG && HW <= 32 * PTW), "level form: the evaluation step, log-det inside the wave");
     extern __shared__ __align__(16) float lds[];      // G::LDS_FLOATS floats (up to 160 KiB: dynamic)
     float* Y0 = lds;                    // [HALF][PIX]   y0 (phase 0 -> 1), later the z1 staging plane
     float* H1 = lds + HALF * PIX;       // [HID][PIX]    x plane (rows < C), then h1, then h2 in place
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lk = lane >> 5;
+    const int tid_ = LEVEL ? wave_u * 64 + cf_lane_fresh() : (int)threadIdx.x;      // (LEVEL: per step, see cf_lane_fresh)
+    const int tid = tid_, wave = tid >> 6;
+    int lane = tid & 63, li = lane & 31, lk = lane >> 5;
     const int ntiles = (B + G::SPW - 1) / G::SPW;
     const int64_t dbg_cols = (int64_t)ntiles * PIX;
-    (void)flags;
 
     int pix[PTW], pin[PTW];             // this lane's pixel column inside the workgroup / inside its sample
 #pragma unroll
@@ -230,22 +251,13 @@ __global__ __launch_bounds__(256, G::MINW) void k_flow_step(const float* __restr
         pix[q] = (wave * PTW + q) * 32 + li;
         pin[q] = pix[q] % HW;
     }
-
-    // One tile per workgroup (grid = ntiles).  A persistent tile loop with the next tile's x prefetched into
-    // registers was tried: hipcc then keeps 50-110 more VGPRs live across the loop (occupancy 4 -> 2 at C=16) and
-    // it measured slower; co-resident workgroups hide the x-load latency instead.
-    float4 xr[XI];
-    const int tile = blockIdx.x;
-    x_load<G, SQ>(xr, x, xbs, tile, B, wave, lane);
     {
-        const float* __restrict__ wsl = ws;
         const int b0 = tile * G::SPW;
         int smp[PTW];
         bool live[PTW];
 #pragma unroll
         for (int q = 0; q < PTW; ++q) { smp[q] = b0 + pix[q] / HW; live[q] = smp[q] < B; }
 
-        x_to_lds<G, SQ>(xr, H1, wave, lane);
         cf_wave_sync();                 // x plane: written 16 bytes per lane, read as MFMA operands by other lanes
 
         // ================= phase 0: y = (e^{-logs} Wm) x - t e^{-logs}        (conv1x1.py:54 + actnorm.py:59)
@@ -266,8 +278,16 @@ __global__ __launch_bounds__(256, G::MINW) void k_flow_step(const float* __restr
                 if (idx < HALF) Y0[idx * PIX + pix[q]] = acc0[0][q][r];
                 y1[q][r] = (HALF <= 16) ? acc0[0][q][r + 8] : acc0[RT03 - 1][q][r];
             }
+        if constexpr (LEVEL) {
+            // y1 is pinned HERE: inside the level loop hipcc otherwise sinks the MFMAs of the y1 row tile behind phase 2, next to
+            // their first use, and carries their operands - fragments and x values - there through scratch (50 registers at C = 64)
+#pragma unroll
+            for (int q = 0; q < PTW; ++q)
+#pragma unroll
+                for (int r = 0; r < (HALF <= 16 ? 8 : 16); ++r) asm volatile("" : "+v"(y1[q][r]));
+        }
         cf_wave_sync();                 // y0 plane complete for this wave's columns
-        z_store<G>(z, Y0, b0, 0, B, wave, lane);
+        if constexpr (!LEVEL) z_store<G>(z, Y0, b0, 0, B, wave, lane);
         if constexpr (DUMP) rows_store_t<G, HALF, HALF>(tp.y0, Y0, b0, B, wave, lane);
         if (dbg) {
             __syncthreads();
@@ -276,7 +296,24 @@ __global__ __launch_bounds__(256, G::MINW) void k_flow_step(const float* __restr
         }
 
         f32x16 acc3[RT03][PTW];
-        if constexpr (CTX == 0) {
+        if constexpr (LEVEL) {
+            // phases 1 and 2, then the lane's indices AGAIN and phase 3 with those: nothing but y1 is live across the 3x3, which fills
+            // the register file (the 8x8 kernel sits at 256 registers; carried, the indices cost the level form 4 spilled ones)
+            conditioner_net<G, 0, false, 2>(acc3, lds, wsl, pix, pin, lane, tid, nullptr, 0, tile, nullptr, nullptr, tp, B);
+            lane = cf_lane_fresh(); li = lane & 31; lk = lane >> 5;
+#pragma unroll
+            for (int q = 0; q < PTW; ++q) {
+                pix[q] = (wave_u * PTW + q) * 32 + li;
+                pin[q] = pix[q] % HW;
+                smp[q] = b0 + pix[q] / HW;
+                live[q] = smp[q] < B;
+            }
+#pragma unroll
+            for (int rt = 0; rt < RT03; ++rt)
+#pragma unroll
+                for (int q = 0; q < PTW; ++q) acc3[rt][q] = bias_tile(wsl + G::OFF_B3 + rt * 32, lk);
+            dense_phase<G, G::KS3, G::NG3, RT03>(acc3, ws_rsrc(wsl, G::WS_FLOATS), G::OFF_A3, H1, pix, lane);
+        } else if constexpr (CTX == 0) {
             conditioner_net<G, 0, DUMP>(acc3, lds, wsl, pix, pin, lane, tid, dbg, dbg_cols, tile, nullptr, nullptr, tp, B);
         } else {
             int soff[PTW];
@@ -284,6 +321,7 @@ __global__ __launch_bounds__(256, G::MINW) void k_flow_step(const float* __restr
             for (int q = 0; q < PTW; ++q) soff[q] = min(smp[q], B - 1) * (CTX == 1 ? C : HID);
             conditioner_net<G, CTX, DUMP>(acc3, lds, wsl, pix, pin, lane, tid, dbg, dbg_cols, tile, sb, soff, tp, B);
         }
+        if constexpr (LEVEL) cf_wave_sync();      // phase 3 has read h2 (other lanes' rows of these columns): rows < C are free
 
         float lsum[PTW];
 #pragma unroll
@@ -296,7 +334,12 @@ __global__ __launch_bounds__(256, G::MINW) void k_flow_step(const float* __restr
                     const float tt = acc3[0][q][r];
                     const float raw = (HALF <= 16) ? acc3[0][q][r + 8] : acc3[RT03 - 1][q][r];
                     const float ls = cf_log_scale(raw);
-                    Y0[idx * PIX + pix[q]] = fmaf(y1[q][r], __expf(ls), tt);      // coupling.py:63 (z1, staged in LDS)
+                    if constexpr (LEVEL) {          // [y0 | z1] = the next step's x plane (or the plane the level's epilogue stores)
+                        H1[(HALF + idx) * PIX + pix[q]] = fmaf(y1[q][r], __expf(ls), tt);
+                        H1[idx * PIX + pix[q]] = Y0[idx * PIX + pix[q]];
+                    } else {
+                        Y0[idx * PIX + pix[q]] = fmaf(y1[q][r], __expf(ls), tt);      // coupling.py:63 (z1, staged in LDS)
+                    }
                     lsum[q] += ls;
                     if constexpr (DUMP) {           // tape: 128 contiguous bytes per row and half wave
                         if (live[q]) {
@@ -314,8 +357,10 @@ __global__ __launch_bounds__(256, G::MINW) void k_flow_step(const float* __restr
             }
         }
         cf_wave_sync();                 // z1 plane complete for this wave's columns
-        z_store<G>(z, Y0, b0, HALF, B, wave, lane);
-        cf_wave_sync();                 // ... and read back, before the log-det scratch below reuses those words
+        if constexpr (!LEVEL) {
+            z_store<G>(z, Y0, b0, HALF, B, wave, lane);
+            cf_wave_sync();             // ... and read back, before the log-det scratch below reuses those words
+        }
 
         // per-sample reduction of log_s: lanes of one sample inside a 32-pixel tile first (shuffles) ...
         constexpr int SEG = HW < 32 ? HW : 32;            // lanes (pixels) of one sample inside a tile
@@ -329,6 +374,7 @@ __global__ __launch_bounds__(256, G::MINW) void k_flow_step(const float* __restr
         }
         if constexpr (HW <= 32 * PTW) {
             // ... whole samples live inside this wave: finish in registers, the first lane of a sample owns ldj_acc[b]
+            // (LEVEL: the same lane adds the per-step terms of its sample one step after the other - the order of n launches)
             constexpr int TPS = HW >= 32 ? HW / 32 : 1;   // tiles per sample
 #pragma unroll
             for (int q = 0; q < PTW; q += TPS) {
@@ -357,6 +403,47 @@ __global__ __launch_bounds__(256, G::MINW) void k_flow_step(const float* __restr
             __syncthreads();
         }
     }
+}
+
+template <class G, bool SQ, int CTX = 0, bool DUMP = false, bool DBG = false>
+__global__ __launch_bounds__(256, G::MINW) void k_flow_step(const float* __restrict__ x, float* __restrict__ z,
+                                                   float* __restrict__ ldj_acc, const float* __restrict__ ws, int B,
+                                                   int64_t xbs, float* __restrict__ dbg_arg, int flags,
+                                                   const float* __restrict__ sb, StepTape tp) {
+    constexpr int XI = G::C * G::PTW / 8;             // 16-byte x items per lane and tile
+    extern __shared__ __align__(16) float lds[];
+    float* H1 = lds + G::HALF * G::PIX;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    (void)flags;
+
+    // One tile per workgroup (grid = ntiles).  A persistent tile loop with the next tile's x prefetched into
+    // registers was tried: hipcc then keeps 50-110 more VGPRs live across the loop (occupancy 4 -> 2 at C=16) and
+    // it measured slower; co-resident workgroups hide the x-load latency instead.
+    float4 xr[XI];
+    const int tile = blockIdx.x;
+    x_load<G, SQ>(xr, x, xbs, tile, B, wave, lane);
+    x_to_lds<G, SQ>(xr, H1, wave, lane);
+    flow_step_phases<G, CTX, DUMP, DBG, false>(z, ldj_acc, ws, B, dbg_arg, sb, tp, tile);
+}
+// Level form (cf_flow_step_fwd_level): the n <= kChain steps of one resolution level on this workgroup's samples in ONE launch, z in
+// LDS from step to step.  x is fetched once (squeeze-folded where the level begins behind a Squeeze), the loop has one body for
+// every step and carries the step index alone, and z goes out once behind it, from the plane, as whole channel rows.
+template <class G, bool SQ>
+__global__ __launch_bounds__(256, G::MINW) void k_flow_step_level(const float* __restrict__ x, float* __restrict__ z,
+                                                                  float* __restrict__ ldj_acc, const WsChain wc, int nsteps, int B, int64_t xbs) {
+    constexpr int XI = G::C * G::PTW / 8;
+    extern __shared__ __align__(16) float lds[];
+    float* H1 = lds + G::HALF * G::PIX;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tile = blockIdx.x, wave_u = __builtin_amdgcn_readfirstlane(wave);
+    {
+        float4 xr[XI];
+        x_load<G, SQ>(xr, x, xbs, tile, B, wave, lane);
+        x_to_lds<G, SQ>(xr, H1, wave, lane);
+    }
+#pragma unroll 1
+    for (int st = 0; st < nsteps; ++st) flow_step_phases<G, 0, false, false, true>(z, ldj_acc, wc.ws[st], B, nullptr, nullptr, kNoTape, tile, wave_u);
+    rows_store<G, G::C>(z, H1, tile * G::SPW, 0, B, wave_u, cf_lane_fresh());       // (its addresses are formed here, not beside x_load's)
 }
 
 // ---- small-channel forward step (C = 8 / 16 on 16x16 images: first resolution level of mnist / cifar10) ------------
@@ -388,25 +475,31 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #else
 #define CF_ROWIDX(r, lg) (((r) + (lg)) * PIX)
 #endif
-template <class G, bool SQ, bool DBG = false, bool DUMP = false, int CTX = 0>
-__device__ __forceinline__ void flow_step_small_body(const float* x, float* z, float* __restrict__ ldj_acc, const float* __restrict__ ws,
-                                                     int B, int64_t xbs, float* __restrict__ dbg, StepTape tp,
-                                                     const float* __restrict__ sb = nullptr) {
+// flow_step_small_phases: phases 0-3, the affine map and the log-det of ONE step on the x plane in rows [0, C) of H1 - the one body of
+// the single-step kernel, of the small-batch chain and of the level kernel (k_flow_step_small_level).
+// LEVEL: the step is one of a run that stays in LDS.  Nothing of z goes to global memory here; z = [y0 | z1] becomes the next step's
+// x plane - y0 from the Y0 plane (every lane takes back its own words), z1 straight from the registers.  Cross-wave hazards of a step
+// boundary: (1) the log-det scratch - four partial sums that thread 0 reads behind the step's last workgroup barrier - sits in row C
+// of H1 instead of Y0: the next step's phase 0 writes Y0 at once, row C of H1 not before the barrier in front of its h1 writes, which
+// thread 0 reaches with the sums read; (2) C = 8: the next step's Winograd-domain weights overwrite this step's in LDS - behind that
+// same last barrier, which every wave reaches after its phase 2.  Everything else a wave touches between that barrier and the next
+// step's first one is its own pixel columns.
+template <class G, bool DBG, bool DUMP, int CTX, bool LEVEL>
+__device__ __forceinline__ void flow_step_small_phases(float* z, float* __restrict__ ldj_acc, const float* __restrict__ ws, int B,
+                                                       float* __restrict__ dbg, StepTape tp, const float* __restrict__ sb, int wave_u = 0) {
     static_assert(G::SMALL, "16x16 images, one sample per workgroup, C <= 16");
     static_assert(CTX == 0 || !G::HID16, "the per-sample bias is wired into the 32-row conditioner phases (C = 16)");
+    static_assert(!LEVEL || (G::WINO && CTX == 0 && !DUMP && !DBG), "level form: the evaluation step in its Winograd geometry");
     constexpr int C = G::C, W = 16, H = 16, PIX = 256, HALF = G::HALF, HID = G::HID, PTW = G::PTW;
-    constexpr int XI = C * PTW / 8;
     extern __shared__ __align__(16) float lds[];
     float* Y0 = lds;                    // [HALF][PIX]
     float* H1 = lds + HALF * PIX;       // [HID][PIX]: x plane, then h1, then h2
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, lg = lane >> 4;
+    const int tid_ = LEVEL ? wave_u * 64 + cf_lane_fresh() : (int)threadIdx.x;      // (LEVEL: per step, see cf_lane_fresh)
+    const int tid = tid_, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, lg = lane >> 4;
     const int tile = blockIdx.x;        // = sample index
     const int colb = wave * 64 + l15;   // this lane's pixel column in column tile 0 (tile ct: + 16 ct)
 
-    float4 xr[XI];
-    x_load<G, SQ>(xr, x, xbs, tile, B, wave, lane);
     const ws_rsrc_t rs = ws_rsrc(ws, G::WS_FLOATS);
-    x_to_lds<G, SQ>(xr, H1, wave, lane);
     if constexpr (G::LDS_W > 0) {
         // the Winograd-domain weights of the 3x3 into LDS (16 KB, fragment order as packed): read by every wave of phase 2,
         // two workgroup barriers from here
@@ -442,10 +535,14 @@ __device__ __forceinline__ void flow_step_small_body(const float* x, float* z, f
 #pragma unroll
         for (int j = 0; j < 2; ++j)
             if (2 * lg + j < HALF) Y0[(2 * lg + j) * PIX + colb + 16 * ct] = acc0[ct][j];
+    if constexpr (LEVEL) {               // y1 is pinned here (see flow_step_phases)
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) { asm volatile("" : "+v"(acc0[ct][2])); asm volatile("" : "+v"(acc0[ct][3])); }
+    }
     cf_wave_sync();
-    z_store<G>(z, Y0, tile, 0, B, wave, lane);
+    if constexpr (!LEVEL) z_store<G>(z, Y0, tile, 0, B, wave, lane);
     if constexpr (DUMP) rows_store_t<G, HALF, HALF>(tp.y0, Y0, tile, B, wave, lane);
-    const int64_t dbg_cols = (int64_t)B * PIX;       // test-only dumps (DBG): planes as [rows][B * PIX], see k_flow_step
+    const int64_t dbg_cols = (int64_t)B * PIX;      // test-only dumps (DBG): planes as [rows][B * PIX], see k_flow_step
     auto dump = [&](const float* plane, int rows, int row0) {
         __syncthreads();
         for (int e = tid; e < rows * PIX; e += 256) dbg[(int64_t)(row0 + e / PIX) * dbg_cols + (int64_t)tile * PIX + (e % PIX)] = plane[e];
@@ -582,6 +679,7 @@ __device__ __forceinline__ void flow_step_small_body(const float* x, float* z, f
         }
     }
     // ================= affine map and log-det   (coupling.py:52-66)
+    if constexpr (LEVEL) cf_wave_sync();      // phase 3 has read h2 (other lanes' rows of these columns): rows <= C are free
     float lsum = 0.f;
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct)
@@ -589,7 +687,12 @@ __device__ __forceinline__ void flow_step_small_body(const float* x, float* z, f
         for (int j = 0; j < 2; ++j)
             if (2 * lg + j < HALF) {
                 const float ls = cf_log_scale(acc3[ct][j + 2]);
-                Y0[(2 * lg + j) * PIX + colb + 16 * ct] = fmaf(acc0[ct][j + 2], __expf(ls), acc3[ct][j]);     // z1, staged in LDS
+                if constexpr (LEVEL) {       // [y0 | z1] = the next step's x plane (or the plane the level's epilogue stores)
+                    H1[(HALF + 2 * lg + j) * PIX + colb + 16 * ct] = fmaf(acc0[ct][j + 2], __expf(ls), acc3[ct][j]);
+                    H1[(2 * lg + j) * PIX + colb + 16 * ct] = Y0[(2 * lg + j) * PIX + colb + 16 * ct];
+                } else {
+                    Y0[(2 * lg + j) * PIX + colb + 16 * ct] = fmaf(acc0[ct][j + 2], __expf(ls), acc3[ct][j]);     // z1, staged in LDS
+                }
                 lsum += ls;
                 if constexpr (DUMP) {
                     const int64_t o = ((int64_t)tile * HALF + 2 * lg + j) * PIX + colb + 16 * ct;
@@ -603,12 +706,28 @@ __device__ __forceinline__ void flow_step_small_body(const float* x, float* z, f
                 }
             }
     cf_wave_sync();
-    z_store<G>(z, Y0, tile, HALF, B, wave, lane);
-    cf_wave_sync();
+    if constexpr (!LEVEL) {
+        z_store<G>(z, Y0, tile, HALF, B, wave, lane);
+        cf_wave_sync();
+    }
     lsum = cf_wave_sum(lsum);
-    if (lane == 0) Y0[wave * 64] = lsum;          // own column (its z1 value has been read back by z_store already)
+    // the four partial sums: own column of Y0 (its z1 value has been read back by z_store already); LEVEL: of row C of H1 (see above)
+    float* const LS = LEVEL ? H1 + C * PIX : Y0;
+    if (lane == 0) LS[wave * 64] = lsum;
     __syncthreads();
-    if (tid == 0 && tile < B) ldj_acc[tile] += ws[0] + ((Y0[0] + Y0[64]) + (Y0[128] + Y0[192]));
+    if (tid == 0 && tile < B) ldj_acc[tile] += ws[0] + ((LS[0] + LS[64]) + (LS[128] + LS[192]));
+}
+template <class G, bool SQ, bool DBG = false, bool DUMP = false, int CTX = 0>
+__device__ __forceinline__ void flow_step_small_body(const float* x, float* z, float* __restrict__ ldj_acc, const float* __restrict__ ws,
+                                                     int B, int64_t xbs, float* __restrict__ dbg, StepTape tp,
+                                                     const float* __restrict__ sb = nullptr) {
+    constexpr int XI = G::C * G::PTW / 8;
+    extern __shared__ __align__(16) float lds[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float4 xr[XI];
+    x_load<G, SQ>(xr, x, xbs, blockIdx.x, B, wave, lane);
+    x_to_lds<G, SQ>(xr, lds + G::HALF * G::PIX, wave, lane);
+    flow_step_small_phases<G, DBG, DUMP, CTX, false>(z, ldj_acc, ws, B, dbg, tp, sb);
 }
 template <class G, bool SQ, bool DBG = false, bool DUMP = false, int CTX = 0>
 __global__ __launch_bounds__(256, (G::WINO && DUMP) ? 3 : (G::WINO && G::C == 16) ? CF_G16W_MINW : G::MINW) void k_flow_step_small(const float* __restrict__ x, float* __restrict__ z,
@@ -621,8 +740,6 @@ __global__ __launch_bounds__(256, (G::WINO && DUMP) ? 3 : (G::WINO && G::C == 16
 // launch.  A workgroup owns whole samples end to end, so step k + 1 can read what step k wrote as soon as the workgroup has passed
 // a barrier; steps 2.. run in place on z.  At a batch of 256 a forward is ~20 launches of 10-35 us that a replayed graph issues
 // at 7-12 us per node whatever they do: 12 step launches become 3.
-constexpr int kChain = 4;
-struct WsChain { const float* ws[kChain]; };
 template <class G, bool SQ>
 __global__ __launch_bounds__(256, (G::WINO && G::C == 16) ? CF_G16W_MINW : G::MINW) void k_flow_step_small_chain(const float* x, float* z, float* __restrict__ ldj_acc,
                                                                                    const WsChain wc, int nsteps, int B, int64_t xbs) {
@@ -631,6 +748,31 @@ __global__ __launch_bounds__(256, (G::WINO && G::C == 16) ? CF_G16W_MINW : G::MI
         __syncthreads();                 // this workgroup's z of the step before is complete and visible to all of its waves
         flow_step_small_body<G, false>(z, z, ldj_acc, wc.ws[st], B, (int64_t)G::C * G::HW, nullptr, kNoTape);
     }
+}
+// Level form for saturating batches (cf_flow_step_fwd_level; see k_flow_step_level): z stays in LDS from step to step - one x fetch
+// in front of a loop with ONE body, one z store behind it.
+template <class G, bool SQ>
+__global__ __launch_bounds__(256, (G::WINO && G::C == 16) ? CF_G16W_MINW : G::MINW) void k_flow_step_small_level(const float* __restrict__ x, float* __restrict__ z,
+                                                                                   float* __restrict__ ldj_acc, const WsChain wc, int nsteps, int B,
+                                                                                   int64_t xbs) {
+    constexpr int XI = G::C * G::PTW / 8;
+    extern __shared__ __align__(16) float lds[];
+    float* H1 = lds + G::HALF * G::PIX;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wave_u = __builtin_amdgcn_readfirstlane(wave);
+    {
+        float4 xr[XI];
+        x_load<G, SQ>(xr, x, xbs, blockIdx.x, B, wave, lane);
+        x_to_lds<G, SQ>(xr, H1, wave, lane);
+    }
+#pragma unroll 1
+    for (int st = 0; st < nsteps; ++st) flow_step_small_phases<G, false, false, 0, true>(z, ldj_acc, wc.ws[st], B, nullptr, kNoTape, nullptr, wave_u);
+    rows_store<G, G::C>(z, H1, blockIdx.x, 0, B, wave_u, cf_lane_fresh());
+}
+template <class G>
+int launch_step_small_level(const StepArgs& a, const WsChain& wc, int n) {
+    const auto k = a.sq ? k_flow_step_small_level<G, true> : k_flow_step_small_level<G, false>;
+    k<<<dim3(a.B), dim3(256), (size_t)G::LDS_FLOATS * sizeof(float), a.s>>>(a.x, a.z, a.ldj, wc, n, a.B, a.xbs);
+    return 0;
 }
 // (the launch helpers take the squeeze flag at run time: a.sq picks the SQ instantiation)
 template <class G>
@@ -1195,6 +1337,21 @@ int launch_step(const StepArgs& a) {
     return launch_step_sq<G, false, CTX, DUMP, DBG>(a);
 }
 
+template <class G, bool SQ>
+int launch_step_level_sq(const StepArgs& a, const WsChain& wc, int n) {
+    constexpr size_t lds_bytes = (size_t)G::LDS_FLOATS * sizeof(float);
+    if (lds_bytes > 64 * 1024) {
+        static std::atomic<uint64_t> raised{0};
+        if (int rc_ = cf_raise_dynamic_lds((const void*)k_flow_step_level<G, SQ>, 160 * 1024, raised, __func__)) return rc_;
+    }
+    k_flow_step_level<G, SQ><<<dim3((a.B + G::SPW - 1) / G::SPW), dim3(256), lds_bytes, a.s>>>(a.x, a.z, a.ldj, wc, n, a.B, a.xbs);
+    return 0;
+}
+template <class G>
+int launch_step_level(const StepArgs& a, const WsChain& wc, int n) {
+    return a.sq ? launch_step_level_sq<G, true>(a, wc, n) : launch_step_level_sq<G, false>(a, wc, n);
+}
+
 // ---- inverse step: x = Conv1x1^-1(ActNorm^-1(Coupling^-1(z)))   (coupling.py:68-73, actnorm.py:78, conv1x1.py:72)
 // z0 conditions the same three contractions as in the forward direction; y1 = (z1 - t) e^{-log_s}; then
 // x = (Wm^-1 diag(e^{logs})) [z0 | y1] + Wm^-1 t  as one more MFMA phase with natural channel rows.
@@ -1537,6 +1694,25 @@ static int launch_fwd_chain(Kernel k, const StepArgs& a, const WsChain& wc, int 
         default: return not_built(__func__, k);
     }
 }
+static int launch_fwd_level(Kernel k, const StepArgs& a, const WsChain& wc, int n) {      // the level forms of the saturating-batch kernels
+    switch (k) {
+        case Kernel::Small_G8w: return launch_step_small_level<G8w>(a, wc, n);
+        case Kernel::Small_G16w: return launch_step_small_level<G16w>(a, wc, n);
+        case Kernel::Step_G32w24: return launch_step_level<G32w24>(a, wc, n);
+        case Kernel::Step_G64w24: return launch_step_level<G64w24>(a, wc, n);
+        default: return not_built(__func__, k);
+    }
+}
+// smallest batch at which the evaluation forward of a shape is its saturating-batch kernel (0: the shape has no level form)
+static int level_min_batch(int sid) {
+    if (direct_conv_only()) return 0;
+    switch (sid) {
+        case 0: case 1: return kChainMaxB16x16 + 1;
+        case 2: return kW24MinB8x8;
+        case 3: return kWinoMinB4x4;
+    }
+    return 0;
+}
 static int launch_inv(Kernel k, const float* z, float* x, const float* ws, const float* wsi, int B, int64_t zbs, int x_unsq, hipStream_t s) {
     switch (k) {
         case Kernel::Inv_G8: return launch_step_inv<G8>(z, x, ws, wsi, B, zbs, x_unsq, s);
@@ -1704,6 +1880,31 @@ int cf_flow_step_fwd_chain(const float* x, float* z, float* ldj_acc, const void*
     WsChain wc{};
     for (int i = 0; i < n; ++i) { CF_REQUIRE(ws[i]); wc.ws[i] = (const float*)ws[i]; }
     if (int rc = launch_fwd_chain(k, StepArgs{x, z, ldj_acc, nullptr, B, x_bstride, in_squeeze != 0, cf_s(stream)}, wc, n)) return rc;
+    CF_LAUNCH_CHECK();
+    return 0;
+}
+
+// Level form for saturating batches: the n <= 4 consecutive steps of one shape in ONE launch with z in LDS from step to step (x is
+// read once, z written once).  form 0: the level form of the kernel cf_flow_step_fwd runs at this batch - from
+// cf_flow_step_level_min_batch samples on; below, CF_ERR_UNSUPPORTED and nothing is launched.  form 1 (tests): the saturating-batch
+// geometry at any B >= 1.  Same numbers as n calls of that kernel, bit for bit.
+int cf_flow_step_level_min_batch(int C, int H, int W) { return level_min_batch(shape_id(C, H, W)); }
+
+int cf_flow_step_fwd_level(const float* x, float* z, float* ldj_acc, const void* const* ws, int n, int B, int C, int H, int W,
+                           int64_t x_bstride, int in_squeeze, int form, cf_stream_t stream) {
+    if (B == 0 || n == 0) return 0;
+    CF_REQUIRE(x && z && x != z && ldj_acc && ws && n >= 1 && n <= kChain && B > 0 && x_bstride >= (int64_t)C * H * W && (form == 0 || form == 1));
+    CF_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0 && x_bstride % 4 == 0);
+    const int sid = shape_id(C, H, W), minb = level_min_batch(sid);
+    if (sid < 0) return unsupported_shape(__func__, C, H, W);
+    if (minb == 0 || (form == 0 && B < minb)) {
+        cf_set_error("cf_flow_step_fwd_level: shape (%d,%d,%d) at a batch of %d is not a level case", C, H, W, B);
+        return CF_ERR_UNSUPPORTED;
+    }
+    const Kernel k = select(Pass::Eval, sid, form == 1 && B < minb ? minb : B);
+    WsChain wc{};
+    for (int i = 0; i < n; ++i) { CF_REQUIRE(ws[i]); wc.ws[i] = (const float*)ws[i]; }
+    if (int rc = launch_fwd_level(k, StepArgs{x, z, ldj_acc, nullptr, B, x_bstride, in_squeeze != 0, cf_s(stream)}, wc, n)) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }

@@ -324,6 +324,23 @@ class FlowSequential(nn.Module):
 
     CHAIN_STEPS = True               # False: every flow step its own launch at every batch size (A/B, tests)
 
+    _level_cache = {}
+
+    def _level_min(self, C, H, W):
+        """smallest batch at which cf_flow_step_fwd_level runs this shape's level in one launch (0: never)"""
+        if (C, H, W) not in self.LEVEL_STEPS:
+            return 0
+        v = self._level_cache.get((C, H, W))
+        if v is None:
+            v = self._level_cache[(C, H, W)] = int(_hip.lib().cf_flow_step_level_min_batch(C, H, W))
+        return v
+
+    # shapes whose resolution level runs as ONE launch at saturating batches, z in LDS from step to step (empty: every step its
+    # own launch; A/B, tests).  A shape is listed where its level launch measured faster than its step launches by more than five
+    # times their run-to-run spread (profiles/level_chain.md).  (64, 4, 4) did not: 17.84 against 17.86 - 17.94 ms per level pass;
+    # neither did mnist's (8, 16, 16): 5.03 against 5.12 - 5.16 ms, a gain of twice the spread of its step launches.
+    LEVEL_STEPS = frozenset({(16, 16, 16), (32, 8, 8)})
+
     @staticmethod
     def _prepare_steps(steps, shape, dev, train=False):
         """Packed tables of SEVERAL flow steps of one shape - steps: [(conv, act, cpl)] - in one factorisation launch and one
@@ -565,6 +582,23 @@ class FlowSequential(nn.Module):
                     if len(run) > 1:
                         _hip.call("cf_flow_step_fwd_chain", _hip.p(x), _hip.p(z), _hip.p(ld1), _hip.ptr_array(tabs), len(run), B, C, H, W, xbs,
                                   int(sq), st)
+                        chained.update(run[1:])
+                        x = z
+                        continue
+                if 0 < self._level_min(C, H, W) <= B:
+                    # saturating batch: the level in ONE launch, z in LDS from step to step.  With step_events the launch still
+                    # leaves one record per step: the first carries the launch, the others are empty (its end event twice)
+                    run, tabs = chain_run(k, ws, 4, lambda nxt: nxt[0] == "step" and tuple(nxt[4]) == (C, H, W) and not nxt[5])
+                    if len(run) > 1:
+                        if events is not None:
+                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            e0.record(main)
+                        _hip.call("cf_flow_step_fwd_level", _hip.p(x), _hip.p(z), _hip.p(ld1), _hip.ptr_array(tabs), len(run), B, C, H, W, xbs,
+                                  int(sq), 0, st)
+                        if events is not None:
+                            e1.record(main)
+                            events.append((e0, e1, B, C, H * W))
+                            events.extend((e1, e1, B, C, H * W) for _ in run[1:])
                         chained.update(run[1:])
                         x = z
                         continue

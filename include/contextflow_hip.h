@@ -30,7 +30,8 @@ extern "C" {
  * cf_grad_norm_batch, cf_grad_scale_batch): no existing signature or behaviour moved, so no caller of version 13 breaks.
  * Version 14: cf_gmm_quad (no caller; cf_gmm_resp feeds the backward) left the ABI.
  * Version 15: the switch entry of the 16x16 level's forms on the 16-bit matrix cores left the ABI with those kernels;
- * cf_flow_step_ws_bytes shrank by their tables. */
+ * cf_flow_step_ws_bytes shrank by their tables.  It also covers cf_flow_step_fwd_level / cf_flow_step_level_min_batch, which only ADD
+ * symbols. */
 #define CF_ABI_VERSION 15
 #define CF_ERR_ARG (-1)          /* bad argument (shape, null pointer, unsupported size) */
 #define CF_ERR_UNSUPPORTED (-2)  /* shape not covered by this kernel; caller uses the generic path */
@@ -280,7 +281,13 @@ int cf_flow_step_fwd(const float* x, float* z, float* ldj_acc, const void* ws, i
 int cf_flow_step_chain_max_batch(int C, int H, int W);
 int cf_flow_step_fwd_chain(const float* x, float* z, float* ldj_acc, const void* const* ws, int n, int B, int C, int H, int W,
                            int64_t x_bstride, int in_squeeze, cf_stream_t stream);
-
+/* Level form for saturating batches: the same n <= 4 steps of ONE shape in ONE launch of the kernel cf_flow_step_fwd runs at large
+ * batches, with z kept in LDS from step to step - x is read once (squeeze-folded if in_squeeze), z is written once, x != z.  form 0: for
+ * B >= cf_flow_step_level_min_batch(C, H, W) (0 = never); below it CF_ERR_UNSUPPORTED is returned and nothing is launched.  form 1
+ * (tests): that kernel's geometry at any B >= 1.  The numbers are bit for bit those of n single calls of that kernel.         */
+int cf_flow_step_level_min_batch(int C, int H, int W);
+int cf_flow_step_fwd_level(const float* x, float* z, float* ldj_acc, const void* const* ws, int n, int B, int C, int H, int W,
+                           int64_t x_bstride, int in_squeeze, int form, cf_stream_t stream);
 
 /* the fused step with a per-sample bias from the specialist coupling's CN net (coupling.py:39-47):
  * mode 1: sbias (B,C) added to the conditioner output (contextflow); mode 2: sbias (B,2C) added before the
