@@ -285,7 +285,7 @@ __global__ __launch_bounds__(NT) void k_coupling_apply(const float* __restrict__
         zb[half_n + i] = INV ? (x1 - tt) / expf(ls) : x1 * expf(ls) + tt;
         acc += ls;
     }
-    if (!INV) {
+    if (!INV || ldj != nullptr) {        // (inverse: the forward log-det at the recovered input, when asked for)
         acc = cf_block_sum<NT / 64>(acc, red);
         if (threadIdx.x == 0) ldj[b] = acc;
     }
@@ -419,6 +419,55 @@ int launch_postprocess_inv(const float* z, float* x, int B, int n_keep, int64_t 
     return 0;
 }
 
+// cf_postprocess_inv_ld: the same tail with the log-det the forward pre-processing has at the continuous point this walk passed
+// through, in ONE pass over z - one workgroup per sample, so the sum has one owner (a plain read-add-write, no float atomics).
+// In y = z[b, i]: -log v - log(1 - v) with v = sigmoid(y) is softplus(y) + softplus(-y) = |y| + 2 log1p(e^-|y|); the aug_n elements
+// behind the n_keep kept ones (the channels Augment.reverse drops) add -log N(e) = e^2 / 2 + log(2 pi) / 2 each.  c0: the
+// constant of the two Normalizations + aug_n log(2 pi) / 2.  The x operations are k_postprocess_inv's, in its order: bitwise equal.
+template <int V, bool CLAMP>
+__global__ __launch_bounds__(256) void k_postprocess_inv_ld(const float* __restrict__ z, float* __restrict__ x, float* __restrict__ ld_acc,
+                                                            int n_items, int aug_items, int64_t zbs, float t2, float s2, float t1,
+                                                            float s1, float lo, float hi, float c0) {
+    __shared__ float red[4];
+    const int b = blockIdx.x;
+    const float* zb = z + (int64_t)b * zbs;
+    float* xb = x + (int64_t)b * n_items * V;
+    float acc = 0.f, sq = 0.f;
+    for (int i = threadIdx.x; i < n_items; i += 256) {
+        float r[V];
+        vload<V>(zb + (int64_t)i * V, r);
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            const float a = fabsf(r[e]);
+            acc += a + 2.0f * log1pf(expf(-a));
+            float v = 1.0f / (1.0f + expf(-r[e]));               // OP_SIGMOID
+            v = __fmul_rn(__fsub_rn(v, t2), s2);                 // OP_AFFINE_INV, Normalization 2
+            v = __fmul_rn(__fsub_rn(v, t1), s1);                 // OP_AFFINE_INV, Normalization 1
+            v = floorf(v);                                       // OP_FLOOR
+            if constexpr (CLAMP) v = fmaxf(fminf(v, hi), lo);    // OP_CLAMP
+            r[e] = v;
+        }
+        vstore<V>(xb + (int64_t)i * V, r);
+    }
+    for (int i = threadIdx.x; i < aug_items; i += 256) {
+        float r[V];
+        vload<V>(zb + (int64_t)(n_items + i) * V, r);
+#pragma unroll
+        for (int e = 0; e < V; ++e) sq = fmaf(r[e], r[e], sq);
+    }
+    acc = cf_block_sum<4>(acc + 0.5f * sq, red);
+    if (threadIdx.x == 0) ld_acc[b] += acc + c0;
+}
+
+template <bool CLAMP>
+int launch_postprocess_inv_ld(const float* z, float* x, float* ld_acc, int B, int n_keep, int aug_n, int64_t z_bstride, float t2, float s2,
+                              float t1, float s1, float lo, float hi, float c0, hipStream_t s) {
+    const bool vec = n_keep % 4 == 0 && aug_n % 4 == 0 && z_bstride % 4 == 0 && aligned16(z) && aligned16(x);
+    if (vec) k_postprocess_inv_ld<4, CLAMP><<<dim3(B), dim3(256), 0, s>>>(z, x, ld_acc, n_keep / 4, aug_n / 4, z_bstride, t2, s2, t1, s1, lo, hi, c0);
+    else k_postprocess_inv_ld<1, CLAMP><<<dim3(B), dim3(256), 0, s>>>(z, x, ld_acc, n_keep, aug_n, z_bstride, t2, s2, t1, s1, lo, hi, c0);
+    return 0;
+}
+
 // Backward of the fused pre-processing (k_sample<1> / k_preprocess_rng) from its OUTPUT alone: with v = sigmoid(y),
 // dy/dv = 1 / (v (1 - v)) = 2 + e^y + e^-y and d ldj/dv = -1/v + 1/(1 - v) = e^y - e^-y, dv/dx = 1 / (s1 s2), so
 //   gx[b, i] = (gy[b, i] (2 + e^y + e^-y) + gld[b] (e^y - e^-y)) / (s1 s2),   i < n (the image elements of the row);
@@ -502,6 +551,17 @@ int cf_postprocess_inv_clamped(const float* z, float* x, int B, int n_keep, int6
     if (B == 0 || n_keep == 0) return 0;
     CF_REQUIRE(z && x && B > 0 && n_keep > 0 && z_bstride >= n_keep && lo <= hi);
     launch_postprocess_inv<true>(z, x, B, n_keep, z_bstride, t2, s2, t1, s1, lo, hi, cf_s(stream));
+    CF_LAUNCH_CHECK();
+    return 0;
+}
+
+int cf_postprocess_inv_ld(const float* z, float* x, float* ld_acc, int B, int n_keep, int aug_n, int64_t z_bstride, float t2, float s2,
+                          float t1, float s1, float ldj_const, int clamp, float lo, float hi, cf_stream_t stream) {
+    if (B == 0 || n_keep == 0) return 0;
+    CF_REQUIRE(z && x && ld_acc && B > 0 && n_keep > 0 && aug_n >= 0 && z_bstride >= (int64_t)n_keep + aug_n && (!clamp || lo <= hi));
+    const float c0 = ldj_const + 0.5f * aug_n * kLog2Pi;
+    if (clamp) launch_postprocess_inv_ld<true>(z, x, ld_acc, B, n_keep, aug_n, z_bstride, t2, s2, t1, s1, lo, hi, c0, cf_s(stream));
+    else launch_postprocess_inv_ld<false>(z, x, ld_acc, B, n_keep, aug_n, z_bstride, t2, s2, t1, s1, 0.f, 0.f, c0, cf_s(stream));
     CF_LAUNCH_CHECK();
     return 0;
 }

@@ -1382,13 +1382,17 @@ __global__ __launch_bounds__(256) void k_step_pack_inv(const float* __restrict__
     }
 }
 
-template <class G>
+// LD (cf_flow_step_inv_ld): ld_acc[b] += ws[0] + sum log_s as well - what the forward step adds for its log-det at the recovered
+// input x - reduced as flow_step_phases reduces it: lane, shuffles over the lanes of a sample, one LDS hop where a sample spans
+// waves, then the one owner of sample b reads, adds and writes (no float atomics: the same bits in every run).  Without the
+// flag ld_acc is not read (NULL) and the kernel is the one it was.
+template <class G, bool LD = false>
 #ifndef CF_INV16_MINW
 #define CF_INV16_MINW 3          // (4 waves per SIMD: 12 spilled registers, 6.55 vs 6.49 ms per cifar10 sample(16384))
 #endif
 __global__ __launch_bounds__(256, (G::WINO && G::C == 16) ? CF_INV16_MINW : G::MINW) void k_flow_step_inv(const float* __restrict__ z, float* __restrict__ x,
                                                        const float* __restrict__ ws, const float* __restrict__ wsi, int B,
-                                                       int64_t zbs, int x_unsq) {
+                                                       int64_t zbs, int x_unsq, float* __restrict__ ld_acc) {
     using I = GeoInv<G>;
     constexpr int C = G::C, HW = G::HW, PIX = G::PIX, HALF = G::HALF;
     constexpr int PTW = G::PTW, RT03 = G::RT03, NR = (HALF <= 16 ? 8 : 16);
@@ -1438,6 +1442,11 @@ __global__ __launch_bounds__(256, (G::WINO && G::C == 16) ? CF_INV16_MINW : G::M
         x_to_lds<G, false>(zr, H1, wave, lane);
         cf_wave_sync();
     }
+    [[maybe_unused]] float lsum[PTW];
+    if constexpr (LD) {
+#pragma unroll
+        for (int q = 0; q < PTW; ++q) lsum[q] = 0.f;
+    }
 #pragma unroll
     for (int q = 0; q < PTW; ++q)
 #pragma unroll
@@ -1449,9 +1458,47 @@ __global__ __launch_bounds__(256, (G::WINO && G::C == 16) ? CF_INV16_MINW : G::M
                 const float ls = cf_log_scale(raw);
                 float* y1 = &H1[(HALF + idx) * PIX + pix[q]];
                 *y1 = (*y1 - tt) * __expf(-ls);
+                if constexpr (LD) lsum[q] += ls;
             }
         }
     cf_wave_sync();
+    if constexpr (LD) {
+        constexpr int SEG = HW < 32 ? HW : 32;            // lanes (pixels) of one sample inside a tile
+#pragma unroll
+        for (int q = 0; q < PTW; ++q) {
+#pragma unroll
+            for (int o = 1; o < SEG; o <<= 1) lsum[q] += __shfl_xor(lsum[q], o, 64);
+            lsum[q] += __shfl_xor(lsum[q], 32, 64);
+        }
+        if constexpr (HW <= 32 * PTW) {                   // whole samples inside this wave: the first lane of a sample owns ld_acc[b]
+            constexpr int TPS = HW >= 32 ? HW / 32 : 1;   // tiles per sample
+#pragma unroll
+            for (int q = 0; q < PTW; q += TPS) {
+                float sum = lsum[q];
+#pragma unroll
+                for (int i = 1; i < TPS; ++i) sum += lsum[q + i];
+                const int b = b0 + pix[q] / HW;
+                if (lk == 0 && (li % SEG) == 0 && b < B) ld_acc[b] += ws[0] + sum;
+            }
+        } else {
+            // a sample spans several waves: one LDS hop through this wave's own columns of Y0 (z0: phase 1 of the conditioner has
+            // read it, and nothing reads or writes the plane behind this point)
+            constexpr int TPS = HW / 32, WPX = 32 * PTW;
+#pragma unroll
+            for (int q = 0; q < PTW; ++q)
+                if (lane == 0) Y0[wave * WPX + q] = lsum[q];
+            __syncthreads();
+            if (tid < G::SPW && b0 + tid < B) {
+                float sum = 0.f;
+#pragma unroll
+                for (int i = 0; i < TPS; ++i) {
+                    const int t = tid * TPS + i;          // tile index inside the workgroup
+                    sum += Y0[(t / PTW) * WPX + (t % PTW)];
+                }
+                ld_acc[b0 + tid] += ws[0] + sum;
+            }
+        }
+    }
     f32x16 acc[I::RTI][PTW];
 #pragma unroll
     for (int rt = 0; rt < I::RTI; ++rt)
@@ -1491,7 +1538,18 @@ int launch_step_inv(const float* z, float* x, const float* ws, const float* wsi,
         static std::atomic<uint64_t> raised{0};
         if (int rc_ = cf_raise_dynamic_lds((const void*)k_flow_step_inv<G>, 160 * 1024, raised, __func__)) return rc_;
     }
-    k_flow_step_inv<G><<<dim3((B + G::SPW - 1) / G::SPW), dim3(256), lds_bytes, s>>>(z, x, ws, wsi, B, zbs, x_unsq);
+    k_flow_step_inv<G><<<dim3((B + G::SPW - 1) / G::SPW), dim3(256), lds_bytes, s>>>(z, x, ws, wsi, B, zbs, x_unsq, nullptr);
+    return 0;
+}
+template <class G>
+int launch_step_inv_ld(const float* z, float* x, float* ld_acc, const float* ws, const float* wsi, int B, int64_t zbs, int x_unsq,
+                       hipStream_t s) {
+    constexpr size_t lds_bytes = (size_t)G::LDS_FLOATS * sizeof(float);
+    if (lds_bytes > 64 * 1024) {
+        static std::atomic<uint64_t> raised{0};
+        if (int rc_ = cf_raise_dynamic_lds((const void*)k_flow_step_inv<G, true>, 160 * 1024, raised, __func__)) return rc_;
+    }
+    k_flow_step_inv<G, true><<<dim3((B + G::SPW - 1) / G::SPW), dim3(256), lds_bytes, s>>>(z, x, ws, wsi, B, zbs, x_unsq, ld_acc);
     return 0;
 }
 
@@ -1726,6 +1784,21 @@ static int launch_inv(Kernel k, const float* z, float* x, const float* ws, const
         default: return not_built(__func__, k);
     }
 }
+// the same kernel with the log-det of the step next to x (cf_flow_step_inv_ld): the dispatch's choice, its flagged twin
+static int launch_inv_ld(Kernel k, const float* z, float* x, float* ld, const float* ws, const float* wsi, int B, int64_t zbs, int x_unsq,
+                         hipStream_t s) {
+    switch (k) {
+        case Kernel::Inv_G8: return launch_step_inv_ld<G8>(z, x, ld, ws, wsi, B, zbs, x_unsq, s);
+        case Kernel::Inv_G8w: return launch_step_inv_ld<G8w>(z, x, ld, ws, wsi, B, zbs, x_unsq, s);
+        case Kernel::Inv_G16: return launch_step_inv_ld<G16>(z, x, ld, ws, wsi, B, zbs, x_unsq, s);
+        case Kernel::Inv_G16w: return launch_step_inv_ld<G16w>(z, x, ld, ws, wsi, B, zbs, x_unsq, s);
+        case Kernel::Inv_G32: return launch_step_inv_ld<G32>(z, x, ld, ws, wsi, B, zbs, x_unsq, s);
+        case Kernel::Inv_G32w: return launch_step_inv_ld<G32w>(z, x, ld, ws, wsi, B, zbs, x_unsq, s);
+        case Kernel::Inv_G64: return launch_step_inv_ld<G64>(z, x, ld, ws, wsi, B, zbs, x_unsq, s);
+        case Kernel::Inv_G64w2: return launch_step_inv_ld<G64w2>(z, x, ld, ws, wsi, B, zbs, x_unsq, s);
+        default: return not_built(__func__, k);
+    }
+}
 static int unsupported_shape(const char* fn, int C, int H, int W) {
     cf_set_error("%s: shape (%d,%d,%d) unsupported", fn, C, H, W);
     return CF_ERR_UNSUPPORTED;
@@ -1839,6 +1912,18 @@ int cf_flow_step_inv(const float* z, float* x, const void* ws, const void* wsi, 
     const Kernel k = select(Pass::Inverse, shape_id(C, H, W), B);
     if (k == Kernel::None) return unsupported_shape(__func__, C, H, W);
     if (int rc = launch_inv(k, z, x, (const float*)ws, (const float*)wsi, B, z_bstride, x_unsqueezed, cf_s(stream))) return rc;
+    CF_LAUNCH_CHECK();
+    return 0;
+}
+
+int cf_flow_step_inv_ld(const float* z, float* x, float* ld_acc, const void* ws, const void* wsi, int B, int C, int H, int W,
+                        int64_t z_bstride, int x_unsqueezed, cf_stream_t stream) {
+    if (B == 0) return 0;                       // empty batch: nothing to do (pointers may be null)
+    CF_REQUIRE(z && x && ld_acc && ws && wsi && B >= 0 && z_bstride >= (int64_t)C * H * W && z_bstride % 4 == 0);
+    CF_REQUIRE((reinterpret_cast<uintptr_t>(z) & 15) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0);
+    const Kernel k = select(Pass::Inverse, shape_id(C, H, W), B);
+    if (k == Kernel::None) return unsupported_shape(__func__, C, H, W);
+    if (int rc = launch_inv_ld(k, z, x, ld_acc, (const float*)ws, (const float*)wsi, B, z_bstride, x_unsqueezed, cf_s(stream))) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }

@@ -321,7 +321,7 @@ __global__ __launch_bounds__(256, 2) void k_vit_coupling(const float* __restrict
         }
     for (int o = 1; o < ntok; o <<= 1) lsum += __shfl_xor(lsum, o, 64);
     lsum += __shfl_xor(lsum, 32, 64);
-    if (!inverse && ldj != nullptr && live && lk == 0 && n == 0) ldj[b] = lsum;
+    if (ldj != nullptr && live && lk == 0 && n == 0) ldj[b] = lsum;       // (inverse: the forward log-det at the recovered input)
 }
 
 bool vit_ok(int C, int H, int W, int p1, int p2, int dim, int dim_head, int heads) {

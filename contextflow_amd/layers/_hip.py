@@ -27,6 +27,7 @@ SIGNATURES = {
     "cf_floor": (_c_int, [_c_p, _c_p, _c_i64, _c_p]),
     "cf_postprocess_inv": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_i64] + [_c_f] * 4 + [_c_p]),
     "cf_postprocess_inv_clamped": (_c_int, [_c_p, _c_p, _c_int, _c_int, _c_i64] + [_c_f] * 6 + [_c_p]),
+    "cf_postprocess_inv_ld": (_c_int, [_c_p, _c_p, _c_p, _c_int, _c_int, _c_int, _c_i64] + [_c_f] * 5 + [_c_int, _c_f, _c_f, _c_p]),
     "cf_clamp": (_c_int, [_c_p, _c_p, _c_i64, _c_f, _c_f, _c_p]),
     "cf_preprocess_fwd": (_c_int, [_c_p, _c_p, _c_p, _c_p, _c_int, _c_int, _c_i64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_p]),
     "cf_preprocess_rng_fwd": (_c_int, [_c_p] * 4 + [ctypes.c_uint64, _c_int, _c_int, _c_int, _c_i64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_int, _c_p]),
@@ -67,6 +68,7 @@ SIGNATURES = {
     "cf_flow_step_inv_ws_bytes": (_c_i64, [_c_int] * 3),
     "cf_flow_step_inv_prepare": (_c_int, [_c_p] * 4 + [_c_int] * 3 + [_c_p]),
     "cf_flow_step_inv": (_c_int, [_c_p] * 4 + [_c_int] * 4 + [_c_i64, _c_int, _c_p]),
+    "cf_flow_step_inv_ld": (_c_int, [_c_p] * 5 + [_c_int] * 4 + [_c_i64, _c_int, _c_p]),
     "cf_gmm_bwd_coeffs": (_c_int, [_c_p] * 4 + [_c_int, _c_int, _c_int, _c_p]),
     "cf_gmm_bwd_gx": (_c_int, [_c_p] * 4 + [_c_int, _c_int, _c_i64, _c_p]),
     "cf_gmm_bwd_params": (_c_int, [_c_p] * 8 + [_c_int, _c_int, _c_p]),

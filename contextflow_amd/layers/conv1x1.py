@@ -70,6 +70,12 @@ class Conv1x1(FlowLayer):
             if self.contextflow:
                 self.NN.requires_grad_(False)
 
+    def logdet_const(self, HW, dev):
+        """(1,) tensor: H W log|det NN| of the shared matrix, kept while NN is unchanged (one factorisation per layer and call
+        otherwise) - the frozen matrix under contextflow, and the layer's constant along a backward walk that returns log p."""
+        return _derived.get(self, "lad", _derived.key((self.NN,), HW, str(dev)),
+                            lambda: slogdet_inverse(_hip.f32(self.NN.detach()), False)[0] * float(HW), dev)
+
     def _forward_ctx(self, x, context, tape=None, pre=None):
         """conv1x1.py:34-50: per-sample triangular matrix from CN(c).  `tape` (training): receives what the backward
         needs - the encoder is stochastic, so its output must be kept, not recomputed.  pre: the code, its log-density and CN(c)
@@ -82,9 +88,7 @@ class Conv1x1(FlowLayer):
         ldj = torch.empty(B, device=x.device, dtype=torch.float32)
         _hip.call("cf_conv1x1_ctx", _hip.p(x), _hip.p(cn.m), _hip.p(Wm), _hip.p(z), _hip.p(ldj), B, C, H * W, xbs, _hip.stream())
         if self.contextflow:
-            # H W log|det NN| of the frozen shared matrix: kept while NN is unchanged (one factorisation per layer and call otherwise)
-            ldj = ldj + _derived.get(self, "lad", _derived.key((self.NN,), H * W, str(x.device)),
-                                     lambda: slogdet_inverse(Wm, False)[0] * float(H * W), x.device)
+            ldj = ldj + self.logdet_const(H * W, x.device)
         if tape is not None:
             tape.append(_tape.CtxAffine(self, x, cn.c, cn.m, encoder_noise(self.context_net)))
         return z, ldj + cn.logp * float(H * W)

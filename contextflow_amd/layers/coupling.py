@@ -31,12 +31,13 @@ def conv2d_reflect(x, conv, relu):
     return out
 
 
-def coupling_apply(x, h, inverse):
+def coupling_apply(x, h, inverse, inverse_ldj=False):
+    """inverse_ldj: the inverse map also returns sum log_s, the forward log-det at the point it recovers (None otherwise)."""
     x, h = _hip.f32(x), _hip.f32(h)
     B, C = x.shape[0], x.shape[1]
     HW = x.numel() // max(B * C, 1) if B else 1
     z = torch.empty_like(x)
-    ldj = None if inverse else torch.empty(B, device=x.device, dtype=torch.float32)
+    ldj = None if inverse and not inverse_ldj else torch.empty(B, device=x.device, dtype=torch.float32)
     _hip.call("cf_coupling_apply", _hip.p(x), _hip.p(h), _hip.p(z), _hip.p(ldj), B, C, HW, int(inverse), _hip.stream())
     return z, ldj
 
@@ -68,6 +69,14 @@ class _AffineCoupling(FlowLayer):
         _hip.require_device(z)
         h = self.net(z[:, : z.shape[1] // 2])
         return coupling_apply(z, h, True)[0]
+
+    def reverse_ldj(self, z):
+        """(x, ldj): `reverse` and the forward log-det at x, from the same conditioner pass (context-free layers)."""
+        if self.context_net:
+            raise NotImplementedError("reverse_ldj: %s with a context net" % type(self).__name__)
+        _hip.require_device(z)
+        h = self.net(z[:, : z.shape[1] // 2])
+        return coupling_apply(z, h, True, inverse_ldj=True)
 
     def logdet(self, input, context=None):
         return self.forward(input, context)[1]
@@ -204,6 +213,10 @@ class CouplingFC(Coupling):
 
     def reverse(self, z, context=None):
         return super().reverse(z.view(-1, self.D, 1, 1), context).view(-1, self.D)
+
+    def reverse_ldj(self, z):
+        x, ldj = super().reverse_ldj(z.view(-1, self.D, 1, 1))
+        return x.view(-1, self.D), ldj
 
     def logdet(self, x, context=None):
         return super().logdet(x.view(-1, self.D, 1, 1))
@@ -367,7 +380,7 @@ class TransCoupling(_AffineCoupling):
         parts += [vit.transformer.norm.weight, vit.transformer.norm.bias]
         return torch.cat([t.detach().reshape(-1).float() for t in parts])
 
-    def _fused(self, x, inverse):
+    def _fused(self, x, inverse, inverse_ldj=False):
         vit = self.NN[0]
         x, xbs = _hip.bview(x)
         B, C, H, W = x.shape
@@ -387,7 +400,7 @@ class TransCoupling(_AffineCoupling):
         if vit.pos_embedding.device != x.device:
             vit.pos_embedding = vit.pos_embedding.to(x.device).contiguous()
         z = torch.empty(B, C, H, W, device=x.device, dtype=torch.float32)
-        ldj = None if inverse else torch.empty(B, device=x.device, dtype=torch.float32)
+        ldj = None if inverse and not inverse_ldj else torch.empty(B, device=x.device, dtype=torch.float32)
         events = VIT_EVENTS
         if events is not None:               # bench.py: HIP events on the launch stream around exactly this kernel
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -422,3 +435,9 @@ class TransCoupling(_AffineCoupling):
         if self._fused_ok(z):
             return self._fused(z, True)[0]
         return super().reverse(z, context)
+
+    def reverse_ldj(self, z):
+        if not self.context_net and self._fused_ok(z):
+            _hip.require_device(z)
+            return self._fused(z, True, inverse_ldj=True)
+        return super().reverse_ldj(z)

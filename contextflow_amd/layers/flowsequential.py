@@ -73,6 +73,54 @@ class ContextNoise:
         return iter(self.tensors)
 
 
+class _WalkDensity:
+    """What a backward walk gathers for the log-density of the point it produces (FlowSequential._inverse, return_logp):
+    ld1 (B,) - the forward log-det of every inverted layer at its recovered input and -log q of the channels an Augment drops,
+    added by the inverse kernels themselves - and the tensors the priors score, in place: the final z and every split-off half.
+    finish(): log p (B, M) = the mixtures' log-densities + ld1, through the kernels the forward uses."""
+
+    def __init__(self, z):
+        self.B, self.dev = z.shape[0], z.device
+        self.ld1 = torch.zeros(self.B, device=z.device, dtype=torch.float32)
+        self.levels = []              # (tensor, prepared mixture tables) in walk order: the prior first
+        self.terms = []               # (B, M) log-densities of priors that are no mixtures
+
+    def score(self, dist, x):
+        if isinstance(dist, GaussianMixtureDistribution) and not dist.context_net:
+            srcs = (dist.mG, dist.sG, dist.wG)
+            self.levels.append((x, _derived.get(dist, "walk_prep", _derived.key(srcs, str(self.dev)), dist.prepared, self.dev)))
+        elif callable(getattr(dist, "log_prob", None)) and not getattr(dist, "context_net", None):
+            lp = dist.log_prob(x)
+            self.terms.append(lp.reshape(self.B, -1))
+        else:
+            raise NotImplementedError("return_logp: no log-density rule for the prior %s" % type(dist).__name__)
+
+    def finish(self, M):
+        B, dev = self.B, self.dev
+        levels = self.levels[::-1]    # forward order: the halves, then the prior
+        ldM = None
+        for t in self.terms:
+            if t.shape[1] == 1:
+                self.ld1 += t[:, 0]
+            else:
+                ldM = t.clone() if ldM is None else ldM + t
+        if not levels:
+            return self.ld1.unsqueeze(-1).expand(B, M).clone() if ldM is None else ldM + self.ld1.unsqueeze(-1)
+        if B <= GMM_LEVELS_MAX_BATCH and gmm_levels_ok(levels):
+            return gmm_logprob_levels(levels, ldM, self.ld1)
+        if ldM is None:
+            ldM = torch.empty(B, M, device=dev, dtype=torch.float32)
+            acc = False
+        else:
+            acc = True
+        for x, prep in levels:
+            gmm_logprob(x, prep, out=ldM, accumulate=acc)
+            acc = True
+        logp = torch.empty(B, M, device=dev, dtype=torch.float32)
+        _hip.call("cf_logdet_combine", _hip.p(ldM), _hip.p(self.ld1), _hip.p(logp), B, M, _hip.stream())
+        return logp
+
+
 class FlowSequential(nn.Module):
     def __init__(self, dist, *modules):
         super().__init__()
@@ -879,9 +927,10 @@ class FlowSequential(nn.Module):
         `g(x) -> (z, logp)` (static output buffers, overwritten by the next replay)."""
         return GraphedFlow(self, example_input)
 
-    def _inverse_step(self, z, conv, act, cpl, unsqueeze=False):
+    def _inverse_step(self, z, conv, act, cpl, unsqueeze=False, ld=None):
         """Conv1x1^-1 o ActNorm^-1 o Coupling^-1 in one MFMA kernel (cf_flow_step_inv); unsqueeze: the Squeeze((2,2)) in front of
-        the step is inverted by the kernel's stores."""
+        the step is inverted by the kernel's stores.  ld (B,): the step's forward log-det at the recovered input is added to it
+        (cf_flow_step_inv_ld: the same kernel, the same x)."""
         z, zbs = _hip.bview(z)
         B, C, H, W = z.shape
         dev = z.device
@@ -903,7 +952,10 @@ class FlowSequential(nn.Module):
         if events is not None:               # HIP events on the launch stream, bracketing exactly this kernel
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(torch.cuda.current_stream(dev))
-        _hip.call("cf_flow_step_inv", pp(z), pp(x), pp(ws), pp(wsi), B, C, H, W, zbs, int(unsqueeze), st)
+        if ld is None:
+            _hip.call("cf_flow_step_inv", pp(z), pp(x), pp(ws), pp(wsi), B, C, H, W, zbs, int(unsqueeze), st)
+        else:
+            _hip.call("cf_flow_step_inv_ld", pp(z), pp(x), pp(ld), pp(ws), pp(wsi), B, C, H, W, zbs, int(unsqueeze), st)
         if events is not None:
             e1.record(torch.cuda.current_stream(dev))
             events.append((e0, e1, B, C, H * W))
@@ -960,14 +1012,24 @@ class FlowSequential(nn.Module):
         if context is None and self._has_context_nets():
             raise ValueError("%s: a context-conditioned (specialist) flow needs its context" % what)
 
-    def inverse(self, z, context=None, noise=None):
+    def inverse(self, z, context=None, noise=None, return_logp=False):
         """Run every layer's `reverse` from the last to the first (the loop of flowsequential.py:35-37); groups
         Coupling <- ActNorm <- Conv1x1 of a supported shape run as one fused kernel.  A specialist flow takes its `context`
         (ValueError without): ActNorm(c) <- Conv1x1(c) pairs, with the Squeeze((2,2)) in front of them, run as one
-        cf_affine_ctx_inv launch, the couplings layer by layer; noise (`context_noise`): the codes the encoders form."""
+        cf_affine_ctx_inv launch, the couplings layer by layer; noise (`context_noise`): the codes the encoders form.
+        return_logp: (x, logp) with logp (B, M) fp32 - what `forward` returns at the continuous point the walk passes through,
+        the noise layers given the noise this walk implies (the dequantisation noise is the fractional part the floor drops, the
+        Augment noise the channels Augment.reverse drops): log p_prior(z | m) + the SplitPriors' log p(half | m) + the forward
+        log-det of every inverted layer at its recovered input - log N(dropped Augment channels).  x is the plain call's bit for
+        bit.  NotImplementedError for a specialist flow and for a layer without a rule (activation layers, MaskedCoupling)."""
+        self._refuse_logp(return_logp)
         self._need_context("inverse", context)
         with self._pinned(noise, context):
-            return self._inverse(z, context, None)
+            return self._inverse(z, context, None, return_logp=return_logp)
+
+    def _refuse_logp(self, return_logp):
+        if return_logp and self._has_context_nets():
+            raise NotImplementedError("return_logp: a context-conditioned (specialist) flow - its inverse kernels have no log-det output")
 
     def _pixel_range(self):
         """(0, bins - 1) of the image flows - Dequantization followed by Normalization(0, bins) (model.py:97-98) - else None."""
@@ -976,8 +1038,40 @@ class FlowSequential(nn.Module):
             return 0.0, mods[1]._s - 1.0
         return None
 
-    def _inverse(self, z, context, clamp, latents=None, labels=None, temperature=1.0, ctx_draw=False):
+    def _reverse_scored(self, m, z, wd):
+        """m.reverse(z) for a layer other than a SplitPrior, with the layer's forward log-det at the recovered input added to the
+        walk's running term wd.ld1.  NotImplementedError, naming the layer, where there is no rule."""
+        if isinstance(m, (Squeeze, PermuteAxes)):
+            return m.reverse(z)                                     # index maps: 0
+        if isinstance(m, Conv1x1) and not m.context_net:
+            wd.ld1 += m.logdet_const(z.shape[2] * z.shape[3] if z.dim() == 4 else 1, z.device)
+            return m.reverse(z)
+        if isinstance(m, ActNorm) and not m.context_net:
+            wd.ld1 += _hip.f32(m.NN_logs.detach()).sum()            # actnorm.py:58: + sum logs, without the H W factor (the quirk kept)
+            return m.reverse(z)
+        if type(m) in (Coupling, _cpl.CouplingFC, TransCoupling) and not m.context_net:
+            x, ldj = m.reverse_ldj(z)
+            wd.ld1 += ldj
+            return x
+        if isinstance(m, Augment) and m.split_dim == 1 and isinstance(m.distribution, StandardNormal):
+            keep = z.shape[1] - m.aug_size
+            wd.ld1 -= m.distribution.log_prob(z[:, keep:]).squeeze(-1)          # -log N(e) of the dropped channels, read by stride
+            return m.reverse(z)
+        if isinstance(m, Dequantization) and isinstance(m.dist, UniformDistribution):
+            return m.reverse(z)                                     # uniform noise on [0, 1): log q = 0
+        if isinstance(m, Normalization):
+            wd.ld1 += m.logdet(z)
+            return m.reverse(z)
+        if isinstance(m, LogitTransform):
+            x = m.reverse(z)
+            wd.ld1 += m.logdet(x)                                   # -log v - log(1 - v) at v = sigmoid(z)
+            return x
+        raise NotImplementedError("return_logp: no log-det rule for the reverse of %s" % type(m).__name__)
+
+    def _inverse(self, z, context, clamp, latents=None, labels=None, temperature=1.0, ctx_draw=False, return_logp=False):
         """`inverse`; clamp = (lo, hi): the output of the leading Dequantization's reverse is projected into that range.
+        return_logp: (x, logp) - the walk also gathers the (B, M) log-density `forward` returns at the continuous point it
+        passes through (_WalkDensity); x and the random numbers drawn are those of the plain walk.
         latents: the split-off halves in forward order, put back by the SplitPriors instead of fresh draws (`decode`);
         labels / temperature: passed to every SplitPrior's draw (`sample`).  All at their defaults: the plain chain.
         A specialist flow (context nets, a context given): every ActNorm(c) <- Conv1x1(c) pair - with the Squeeze((2,2)) in front of
@@ -989,6 +1083,13 @@ class FlowSequential(nn.Module):
         mods = self.sequence_modules
         i = len(mods) - 1
         spec = context is not None and self._has_context_nets()
+        wd = None
+        if return_logp:
+            self._refuse_logp(True)
+            with torch.no_grad():
+                wd = _WalkDensity(z)
+                wd.score(self.dist, z)
+        ld = None if wd is None else wd.ld1
         with torch.no_grad():
             while i >= 0:
                 m = mods[i]
@@ -1001,13 +1102,15 @@ class FlowSequential(nn.Module):
                         and mods[i - 1].is_initialized()
                         and self._step_supported(mods[i - 2], mods[i - 1], m, tuple(z.shape[1:]))):
                     sq = i >= 3 and isinstance(mods[i - 3], Squeeze) and tuple(mods[i - 3].p) == (2, 2)
-                    z = self._inverse_step(z, mods[i - 2], mods[i - 1], m, unsqueeze=sq)
+                    z = self._inverse_step(z, mods[i - 2], mods[i - 1], m, unsqueeze=sq, ld=ld)
                     i -= 4 if sq else 3
                 elif self.fused and self._tail_fusable(i, z):
-                    z = self._inverse_tail(z, i, clamp)
+                    z = self._inverse_tail(z, i, clamp, ld=ld)
                     i = -1
                 else:
-                    if isinstance(m, SplitPrior) and latents is not None:
+                    if wd is not None and not isinstance(m, SplitPrior):
+                        z = self._reverse_scored(m, z, wd)
+                    elif isinstance(m, SplitPrior) and latents is not None:
                         if not latents:
                             raise ValueError("decode: no latent left for the SplitPrior at layer %d" % i)
                         z = m.reverse(z, context, latent=latents.pop())
@@ -1017,9 +1120,13 @@ class FlowSequential(nn.Module):
                         z = m.reverse(z, context, labels=labels, temperature=temperature)
                     else:
                         z = m.reverse(z, context)
+                    if wd is not None and isinstance(m, SplitPrior):
+                        wd.score(m.dist, z[:, z.shape[1] // 2:])     # the half just put back - drawn, or `decode`'s - scored in place
                     if i == 0 and clamp is not None and isinstance(m, Dequantization):
                         _hip.call("cf_clamp", _hip.p(z), _hip.p(z), z.numel(), clamp[0], clamp[1], _hip.stream())
                     i -= 1
+            if wd is not None:
+                return z, wd.finish(self.mixtures)
         return z
 
     def _tail_fusable(self, i, z):
@@ -1031,21 +1138,29 @@ class FlowSequential(nn.Module):
             return False
         return i == 3 or (isinstance(mods[4], Augment) and mods[4].split_dim == 1 and 0 < mods[4].aug_size < z.shape[1])
 
-    def _inverse_tail(self, z, i, clamp=None):
+    def _inverse_tail(self, z, i, clamp=None, ld=None):
+        """ld (B,): the pre-processing's forward log-det at the continuous point behind z - and -log q of the Augment channels that
+        are dropped - is added to it (cf_postprocess_inv_ld: one pass, the same x)."""
         mods = self.sequence_modules
         z, zbs = _hip.bview(z)
         B, C, H, W = z.shape
         keep = C - (mods[4].aug_size if i == 4 else 0)
         x = torch.empty(B, keep, H, W, device=z.device, dtype=torch.float32)
         n1, n2 = mods[1], mods[2]
-        if clamp is None:
+        if ld is not None:
+            N = keep * H * W
+            cst = -N * math.log(n1._s) - N * math.log(n2._s)          # normalize.py:42-49, twice (as the forward's `pre`)
+            lo, hi = clamp if clamp is not None else (0.0, 0.0)
+            _hip.call("cf_postprocess_inv_ld", _hip.p(z), _hip.p(x), _hip.p(ld), B, N, (C - keep) * H * W, zbs, n2._t, n2._s, n1._t, n1._s,
+                      cst, int(clamp is not None), lo, hi, _hip.stream())
+        elif clamp is None:
             _hip.call("cf_postprocess_inv", _hip.p(z), _hip.p(x), B, keep * H * W, zbs, n2._t, n2._s, n1._t, n1._s, _hip.stream())
         else:
             _hip.call("cf_postprocess_inv_clamped", _hip.p(z), _hip.p(x), B, keep * H * W, zbs, n2._t, n2._s, n1._t, n1._s,
                       clamp[0], clamp[1], _hip.stream())
         return x
 
-    def sample(self, n_samples, context=None, labels=None, temperature=1.0, noise=None):
+    def sample(self, n_samples, context=None, labels=None, temperature=1.0, noise=None, return_logp=False):
         """flowsequential.py:32-39: a prior draw through the reverse chain.  By specification, for the image flows: the pixels
         are projected into [0, bins - 1].  The reverse chain ends in floor(bins (sigmoid(y) - a) / (1 - 2 a)) (dequantize.py:19-20,
         normalize.py:36-40), which is -1 / bins wherever sigmoid(y) leaves [a, 1 - a) - logits no forward pass can produce, but
@@ -1059,7 +1174,12 @@ class FlowSequential(nn.Module):
         A specialist flow takes its `context` ((n, nctx) integers; ValueError without one or with another number of rows) and
         draws, by specification, from the density `log_prob(., context)` scores: the prior and every SplitPrior draw from the
         mixtures with the per-sample shifts of their context nets (one cf_gmm_ctx_draw launch per level), where the
-        reference's own `sample` ignores the shifts.  noise (`context_noise`): the codes of the stochastic context encoders."""
+        reference's own `sample` ignores the shifts.  noise (`context_noise`): the codes of the stochastic context encoders.
+        return_logp: (x, logp) as `inverse` - logp (n, M) is the MODEL's density, the one `log_prob` scores, for every class column
+        m, whatever labels and temperature the draw used (no density of the tempered proposal); where a pixel is clamped into
+        the data range, logp is still the density of the unclamped continuous point the walk passed through.  x and the random
+        numbers consumed are those of the call without the flag."""
+        self._refuse_logp(return_logp)
         self._need_context("sample", context)
         if context is not None and self._has_context_nets():
             if not isinstance(self.dist, GaussianMixtureDistribution):
@@ -1075,10 +1195,10 @@ class FlowSequential(nn.Module):
                 raise ValueError("sample: labels / temperature need a mixture prior, not %s" % type(self.dist).__name__)
             labels = self.dist._class_labels(labels, n_samples)      # checked and moved to the device once, for every level
             z = self.dist.draw(n_samples, labels, temperature)
-            return self._inverse(z, context, self._pixel_range(), labels=labels, temperature=temperature)
+            return self._inverse(z, context, self._pixel_range(), labels=labels, temperature=temperature, return_logp=return_logp)
         z = self.dist.sample(n_samples, context, need_log_prob=False)[0] if isinstance(self.dist, GaussianMixtureDistribution) \
-            else self.dist.sample(n_samples, context)[0]           # (the reference's sample() also returns log p(z): not needed here)
-        return self._inverse(z, context, self._pixel_range())
+            else self.dist.sample(n_samples, context)[0]           # (the reference's sample() also returns log p(z): the walk scores z itself)
+        return self._inverse(z, context, self._pixel_range(), return_logp=return_logp)
 
     def _split_priors(self):
         return [m for m in self.sequence_modules if isinstance(m, SplitPrior)]
@@ -1105,11 +1225,13 @@ class FlowSequential(nn.Module):
             latents = [h.clone(memory_format=torch.contiguous_format) for h in halves + [z]]
         return latents, logp
 
-    def decode(self, latents, context=None, clamp=False, noise=None):
+    def decode(self, latents, context=None, clamp=False, noise=None, return_logp=False):
         """The reverse chain on a complete latent (`encode`'s list: one half per SplitPrior in forward order, then z): every
         SplitPrior puts its half back instead of drawing one.  clamp=True: the projection into the pixel range that `sample`
         applies.  ValueError for a wrong number of latents or a latent whose shape is not its level's.  A specialist flow takes
-        its `context` (ValueError without) and `noise` as `encode`."""
+        its `context` (ValueError without) and `noise` as `encode`.  return_logp: (x, logp) as `inverse` - the halves given
+        here are the ones scored; with clamp=True logp stays the density of the unclamped continuous point."""
+        self._refuse_logp(return_logp)
         self._need_context("decode", context)
         latents = list(latents)
         n = len(self._split_priors())
@@ -1121,7 +1243,7 @@ class FlowSequential(nn.Module):
         if isinstance(self.dist, GaussianMixtureDistribution) and tuple(z.shape[1:]) != tuple(self.dist.mG.shape[2:]):
             raise ValueError("decode: z of shape %s, the prior is over %s" % (tuple(z.shape), tuple(self.dist.mG.shape[2:])))
         with self._pinned(noise, context):
-            return self._inverse(z, context, self._pixel_range() if clamp else None, latents=latents[:-1])
+            return self._inverse(z, context, self._pixel_range() if clamp else None, latents=latents[:-1], return_logp=return_logp)
 
 
 class GraphedFlow:

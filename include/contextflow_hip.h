@@ -62,6 +62,14 @@ int cf_postprocess_inv(const float* z, float* x, int B, int n_keep, int64_t z_bs
  * chain alone gives lo - 1 and hi + 1 where sigmoid(z) leaves [t2', 1 - t2'], as the reference's does). */
 int cf_postprocess_inv_clamped(const float* z, float* x, int B, int n_keep, int64_t z_bstride, float t2, float s2, float t1, float s1,
                                float lo, float hi, cf_stream_t stream);
+/* the same tail (clamp != 0: the clamped one) with the log-det the forward pre-processing has at the continuous point the walk
+ * passed through, in one pass over z: ld_acc[b] += ldj_const + sum_{i < n_keep} (softplus(y_i) + softplus(-y_i))
+ * + 0.5 sum_{aug} e^2 + 0.5 aug_n log(2 pi), y = z[b, :n_keep], e = the aug_n elements behind them in the row of stride z_bstride
+ * (the channels Augment.reverse drops: their -log q).  The first sum is cf_preprocess_fwd's -log v - log(1 - v) at
+ * v = sigmoid(y); where the clamp moves a pixel the log-det is still that of the unclamped point.  x bitwise equal to
+ * cf_postprocess_inv[_clamped]'s.  (Adds a symbol only: ABI 15.)                                                         */
+int cf_postprocess_inv_ld(const float* z, float* x, float* ld_acc, int B, int n_keep, int aug_n, int64_t z_bstride, float t2, float s2,
+                          float t1, float s1, float ldj_const, int clamp, float lo, float hi, cf_stream_t stream);
 /* y = min(max(x, lo), hi)                                       the same projection behind the layer-by-layer chain */
 int cf_clamp(const float* x, float* y, int64_t n, float lo, float hi, cf_stream_t stream);
 /* Fused layers 0-3 of the image flows (model.py:97-100): v = ((x+u)/s1 + t1)/s2 + t2,
@@ -134,7 +142,8 @@ int cf_conv2d_zero(const float* x, const float* w, const float* bias, float* y, 
                    int kh, int kw, int ph, int pw, int relu, int64_t x_bstride, cf_stream_t stream);
 int cf_reflect_pad_adjoint(const float* gpad, float* gx, int BC, int H, int W, int ph, int pw, cf_stream_t stream);
 /* affine map from the net output h (B,C,HW): t = h[:, :C/2], log_s = 2 tanh(h[:, C/2:]/2).
- * inverse=0: z = [x0 | x1*exp(log_s)+t], ldj[b] = sum log_s ;  inverse=1: z = [x0 | (x1-t)/exp(log_s)] */
+ * inverse=0: z = [x0 | x1*exp(log_s)+t], ldj[b] = sum log_s ;  inverse=1: z = [x0 | (x1-t)/exp(log_s)] and, where ldj is
+ * not NULL, ldj[b] = sum log_s as well: the forward log-det at the recovered input z (NULL: nothing is stored)  */
 int cf_coupling_apply(const float* x, const float* h, float* z, float* ldj, int B, int C, int HW, int inverse,
                       cf_stream_t stream);
 
@@ -306,6 +315,11 @@ int cf_flow_step_inv_prepare(const float* Wm, const float* t, const float* logs,
  * tensor BEFORE that Squeeze (squeeze.py:13-14), i.e. Squeeze.reverse is folded into the kernel's stores.                 */
 int cf_flow_step_inv(const float* z, float* x, const void* ws, const void* wsi, int B, int C, int H, int W,
                      int64_t z_bstride, int x_unsqueezed, cf_stream_t stream);
+/* ... with the step's log-det next to x: ld_acc[b] += ws[0] + sum log_s, what cf_flow_step_fwd adds for the step at the recovered
+ * input x.  The kernel the dispatch picks for cf_flow_step_inv at this shape and batch, x bitwise equal; every sample's sum has
+ * one owner (no float atomics): the same bits in every run.  (Adds a symbol only: ABI 15.)                              */
+int cf_flow_step_inv_ld(const float* z, float* x, float* ld_acc, const void* ws, const void* wsi, int B, int C, int H, int W,
+                        int64_t z_bstride, int x_unsqueezed, cf_stream_t stream);
 
 /* ---- backward of the fused step (training: experiment_cl.py:130-136) ------------------------------
  * cf_flow_step_bwd_prepare packs the TRANSPOSED weight fragments of the data-gradient chain (workspace of
@@ -451,7 +465,8 @@ int64_t cf_vit_flat_params(int patch_dim, int dim, int depth);
 /* pack the flat parameters into MFMA-fragment order (device side, every call).                        */
 int cf_vit_prepare(const float* flat_params, void* ws, int patch_dim, int dim, int depth, cf_stream_t stream);
 /* x: (B,C,H,W) batch stride x_bstride; z: (B,C,H,W) dense; pos: (tokens, dim) sin/cos table.
- * inverse=0: z = [x0 | x1*exp(log_s)+t], ldj[b] = sum log_s (assigned); inverse=1: z = [x0 | (x1-t)/exp(log_s)] */
+ * inverse=0: z = [x0 | x1*exp(log_s)+t], ldj[b] = sum log_s (assigned); inverse=1: z = [x0 | (x1-t)/exp(log_s)] and, where
+ * ldj is not NULL, ldj[b] = sum log_s (assigned): the forward log-det at the recovered input z (NULL: nothing is stored) */
 int cf_vit_coupling(const float* x, float* z, float* ldj, const void* ws, const float* pos, int B, int C, int H, int W,
                     int p1, int p2, int dim, int depth, int64_t x_bstride, int inverse, cf_stream_t stream);
 

@@ -3,13 +3,16 @@
 
 usage: sample_bench.py [name] [B] [iters] [--labels L] [--temperature T]
        sample_bench.py --compare [--names cifar10,mnist] [B] [--iters 20] [--warmup 5]
+       sample_bench.py --logp [--iters 20] [--warmup 5]
 
 --labels L: an integer class for every sample, or `cycle` (sample i gets class i % M); --temperature T: scale factor of the prior
 draws.  Either one selects the one-launch-per-level draw (cf_gmm_draw) instead of the reference's multinomial / randn / gather /
 concatenate.
 --compare: in ONE process, for each model, `sample(B)` against `sample(B, labels=1)` - the same class-mixture - as medians
 of HIP-event times per call after the warm-up calls, interleaved call by call, and per prior level the time of the cf_gmm_draw
-launch alone with the bytes it moves (write 4 B (D1 + D), read 4 B D1).  One JSON line per model."""
+launch alone with the bytes it moves (write 4 B (D1 + D), read 4 B D1).  One JSON line per model.
+--logp: in ONE process, cifar10 and mnist at 16 384 samples and smap at 32 768: `sample(B)`, `sample(B, return_logp=True)` and
+`sample(B)` followed by `log_prob(x)`, interleaved, and the inverse-step launches of both walks per level.  One JSON line per model."""
 import argparse, json, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -25,6 +28,7 @@ ap.add_argument("--labels", default=None)
 ap.add_argument("--temperature", type=float, default=1.0)
 ap.add_argument("--compare", action="store_true")
 ap.add_argument("--names", default="cifar10,mnist")
+ap.add_argument("--logp", action="store_true")
 args = ap.parse_args()
 dev = "cuda:0"
 
@@ -82,6 +86,50 @@ def compare(name, B, iters, warmup):
         res["cf_gmm_draw levels (incl. the nonce draw and the output allocation)"] = levels
     print(json.dumps(res))
 
+
+def logp_bench(name, B, iters, warmup):
+    """`sample(B)`, `sample(B, return_logp=True)` and `sample(B)` followed by `log_prob(x)` - what the density of a draw cost before
+    the flag - interleaved call by call, medians of HIP-event times; then, per resolution level, the inverse-step launches of
+    the plain and of the flagged walk (cf_flow_step_inv / cf_flow_step_inv_ld), from the events around each launch."""
+    model, M = make(name)
+
+    def two_pass():
+        x = model.sample(B)
+        return model.log_prob(x)
+    calls = {"sample": lambda: model.sample(B), "sample+logp": lambda: model.sample(B, return_logp=True), "sample; log_prob": two_pass}
+    ev = {k: [] for k in calls}
+    with torch.no_grad():
+        for it in range(warmup + iters):
+            for k, fn in calls.items():
+                e0, e1, _ = timed(fn)
+                if it >= warmup:
+                    ev[k].append((e0, e1))
+        torch.cuda.synchronize()
+        res = {"model": name, "B": B, "iters": iters, "warmup": warmup}
+        for k, pairs in ev.items():
+            t = [a.elapsed_time(b) for a, b in pairs]
+            res[k + " ms"] = round(statistics.median(t), 4)
+            res[k + " ms min/max"] = [round(min(t), 4), round(max(t), 4)]
+        levels = {}
+        for it in range(2 + iters):
+            for k, flag in (("inv", False), ("inv_ld", True)):
+                model.inv_events = []
+                model.sample(B, return_logp=flag)
+                torch.cuda.synchronize()
+                if it >= 2:
+                    for e0, e1, _, C, HW in model.inv_events:
+                        levels.setdefault((C, HW), {"inv": [], "inv_ld": []})[k].append(e0.elapsed_time(e1))
+                model.inv_events = None
+        res["inverse-step launches, us (median per launch)"] = [
+            {"C": C, "HW": HW, "launches per call": len(v["inv"]) // iters, "cf_flow_step_inv": round(statistics.median(v["inv"]) * 1e3, 1),
+             "cf_flow_step_inv_ld": round(statistics.median(v["inv_ld"]) * 1e3, 1)} for (C, HW), v in sorted(levels.items())]
+    print(json.dumps(res))
+
+
+if args.logp:
+    for nm, B in (("cifar10", 16384), ("mnist", 16384), ("smap", 32768)):
+        logp_bench(nm, B, args.iters or 20, 5 if args.warmup is None else args.warmup)
+    sys.exit(0)
 
 if args.compare:
     for nm in args.names.split(","):
