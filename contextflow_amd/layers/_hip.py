@@ -90,6 +90,9 @@ SIGNATURES = {
     "cf_step_param_grads": (_c_int, [_c_p] * 7 + [_c_int] + [_c_p] * 3 + [_c_int, _c_p]),
     "cf_adamw_step_batch": (_c_int, [_c_int] + [_c_p] * 6 + [ctypes.c_double] * 5 + [_c_int, _c_p]),
     "cf_adamw_step_batch_dev": (_c_int, [_c_int] + [_c_p] * 8 + [ctypes.c_double] * 4 + [_c_int, _c_p]),
+    "cf_adamw_ema_step_batch": (_c_int, [_c_int] + [_c_p] * 7 + [ctypes.c_double] * 5 + [_c_int, ctypes.c_double, _c_int, _c_p]),
+    "cf_adamw_ema_step_batch_dev": (_c_int, [_c_int] + [_c_p] * 9 + [ctypes.c_double] * 4 + [_c_int, ctypes.c_double, _c_int, _c_p]),
+    "cf_swap_batch": (_c_int, [_c_int, _c_p, _c_p, _c_p, _c_p]),
     "cf_grad_norm_partials": (_c_i64, [_c_int, _c_p]),
     "cf_grad_norm_batch": (_c_int, [_c_int, _c_p, _c_p, ctypes.c_double, _c_p, _c_i64, _c_p, _c_p]),
     "cf_grad_scale_batch": (_c_int, [_c_int, _c_p, _c_p, _c_p, _c_p]),

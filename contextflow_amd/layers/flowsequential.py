@@ -1339,6 +1339,8 @@ class GraphedTrainStep:
         return loss
 
     def __call__(self, x, *loss_args):
+        if getattr(self.opt, "_in_ema_scope", False):
+            raise RuntimeError("GraphedTrainStep inside the optimizer's ema_scope(): the parameters hold the averages; leave the scope first")
         if self.graph is None:
             self.static_args = tuple(a.detach().clone() if torch.is_tensor(a) else a for a in loss_args)
             self.static_in.copy_(x)

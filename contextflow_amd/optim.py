@@ -1,4 +1,5 @@
-"""AdamW for the flows' many small parameter tensors: torch.optim.AdamW's update in ceil(n / 72) launches.
+"""AdamW for the flows' many small parameter tensors: torch.optim.AdamW's update in ceil(n / 72) launches, optionally with an
+exponential moving average of the parameters written by the same kernel (ceil(n / 64) launches then).
 
 The reference trains with `optim.AdamW(filter(requires_grad, model.parameters()), lr=...)` (model.py:289) and calls
 `optimizer.step()` after every backward (experiment_cl.py:136, experiment_ad.py:213).  A flow has 135 (cifar10) ... 571 (smap)
@@ -6,8 +7,8 @@ parameter tensors of 9 ... 147 K elements; torch's fused multi-tensor kernel spe
 the captured training step at the reference's batch of 256.  `FusedAdamW` is a drop-in `torch.optim.Optimizer` whose `step()`
 is one `cf_adamw_step_batch` call per parameter group (the tensor table travels in the kernel arguments): same arithmetic term by
 term (decoupled weight decay, lerp form of the first moment, bias corrections; amsgrad off), same `state_dict` layout
-(`step`, `exp_avg`, `exp_avg_sq` per parameter - the moments are views of ONE flat buffer per group), capturable (the update
-count lives on the device).  fp32 parameters on one GPU per group; anything else raises.
+(`step`, `exp_avg`, `exp_avg_sq` per parameter - the moments are views of ONE flat buffer per group; with `ema_decay` one more
+entry, `ema`), capturable (the update count lives on the device).  fp32 parameters on one GPU per group; anything else raises.
 
 Schedules and clipping (the reference's `warmup_lr`, experiment_cl.py:98-105 / experiment_ad.py:175-181, `StepLR`, model.py:290,
 and `clip_grad_norm_`, experiment_cl.py:135 / experiment_ad.py:212).  Each group's learning rate also lives in a one-element fp64
@@ -36,7 +37,22 @@ parameter and moments but its bias corrections use the group's count from then o
 flows here give every trainable parameter a gradient in every step, where the two agree.  `load_state_dict` takes the count of the
 group's last parameter that carries one.  The moments are allocated at construction for the parameters that require a gradient
 then: a parameter unfrozen later has none, and `step()` raises instead of skipping or guessing - build a new optimizer.
+
+The average (`ema_decay=d`, Polyak / EMA weights; off by default, and then every call runs the code it ran without it).  Each group
+gets one more flat buffer laid out like the moments, `state[p]["ema"]` a view shaped like `p`, FILLED WITH THE PARAMETERS' VALUES AT
+CONSTRUCTION.  The update kernel (`cf_adamw_ema_step_batch` / `..._dev`, in whichever of the three forms `step()` would have chosen)
+writes, in the thread that just updated the parameter element, `ema = p` at the group's update count t = 1 and
+`ema += w (p - ema)`, `w = (float)(1 - d_t)`, afterwards; `d_t = min(d, (1 + t) / (10 + t))` with `ema_warmup=True`, else `d`, formed
+in double on the device from the count the kernel reads for the bias corrections.  So the average needs no kernel of its own and no host work (ceil(n / 64) update launches per group instead of ceil(n / 72)),
+and a REPLAYED captured step advances it and follows the warm-up of the decay.  Parameters, moments and count are bit for bit
+those of the same run without the average.  Like the bias corrections, the average goes by the group's SHARED count: a parameter
+that sits update 1 out keeps its construction copy (no element is ever uninitialised) and lerps from it at its first own update;
+the count's t = 1 copy happens only for the parameters that had a gradient in that step.  `ema_parameters()` returns the averages,
+`ema_scope(flow)` evaluates under them.  Data-parallel training needs nothing more: every rank applies the same averaged gradient to
+the same parameters, so the ranks' averages agree bit for bit as their parameters do.  Buffers (the ActNorm `initialized` flags) are
+not averaged; a non-finite gradient poisons parameters and average alike.
 """
+import contextlib
 import ctypes
 
 import torch
@@ -49,6 +65,16 @@ def _check_lr(lr):
         raise TypeError("FusedAdamW: lr must be a Python float (got a tensor): assign floats to param_group['lr'] - "
                         "push_hyperparameters() carries them to the device, also for a captured step")
     return float(lr)
+
+
+def _check_ema(ema_decay, ema_warmup):
+    if ema_decay is None:
+        if ema_warmup:
+            raise ValueError("FusedAdamW: ema_warmup needs ema_decay")
+        return None
+    if torch.is_tensor(ema_decay) or isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 <= ema_decay < 1.0:
+        raise ValueError("FusedAdamW: ema_decay must be a Python float in [0, 1) or None (got %r)" % (ema_decay,))
+    return float(ema_decay)
 
 
 def _grad_table(grads):
@@ -136,8 +162,13 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0):
 
 
 class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, maximize=False, max_grad_norm=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, maximize=False, max_grad_norm=None,
+                 ema_decay=None, ema_warmup=False):
         lr = _check_lr(lr)
+        self.ema_decay = _check_ema(ema_decay, ema_warmup)
+        self.ema_warmup = bool(ema_warmup)
+        self._ema_flats = []         # per parameter group: the flat buffer of the averages | None (ema_decay)
+        self._in_ema_scope = False   # ema_scope(): the parameters hold the averages - no update, no replay, no second entry
         if max_grad_norm is not None:
             if torch.is_tensor(max_grad_norm) or not float(max_grad_norm) > 0.0:
                 raise ValueError("FusedAdamW: max_grad_norm must be a float > 0 or None (got %r)" % (max_grad_norm,))
@@ -163,6 +194,7 @@ class FusedAdamW(torch.optim.Optimizer):
     def _init_group(self, group):
         ps = [p for p in group["params"] if p.requires_grad]
         if not ps:
+            self._ema_flats.append(None)
             return None
         dev = ps[0].device
         for p in ps:
@@ -179,10 +211,25 @@ class FusedAdamW(torch.optim.Optimizer):
         step = torch.zeros(1, device=dev, dtype=torch.float32)
         for p, lo in zip(ps, offs):
             self.state[p] = {"step": step[0], "exp_avg": m[lo:lo + p.numel()].view_as(p), "exp_avg_sq": v[lo:lo + p.numel()].view_as(p)}
+        ema = None
+        if self.ema_decay is not None:
+            # the average starts as a copy of the parameters: a parameter that sits the first update out lerps from this copy later
+            ema = torch.zeros_like(m)
+            for p, lo in zip(ps, offs):
+                self.state[p]["ema"] = ema[lo:lo + p.numel()].view_as(p)
+            self._fill_ema(ps)
+        self._ema_flats.append(ema)
         return (m, v, step)
 
+    def _fill_ema(self, ps):
+        with torch.no_grad():
+            torch._foreach_copy_([self.state[p]["ema"] for p in ps], [p.detach() for p in ps])
+
     def load_state_dict(self, state_dict):
-        """torch puts the loaded moments into fresh tensors: copy them back into the flat buffers the kernel updates."""
+        """torch puts the loaded moments into fresh tensors: copy them back into the flat buffers the kernel updates.  The `ema`
+        entry travels the same way.  A dict WITHOUT `ema` (saved by an optimizer without `ema_decay`) is no error: the average of
+        such a parameter is re-filled from the CURRENT parameter values, as at construction.  A dict with `ema` loaded into an
+        optimizer without `ema_decay` drops the entry."""
         views = {p: dict(self.state[p]) for g in self.param_groups for p in g["params"] if p in self.state}
         super().load_state_dict(state_dict)
         for g, flat in zip(self.param_groups, self._flats):
@@ -194,9 +241,11 @@ class FusedAdamW(torch.optim.Optimizer):
                     continue
                 new = self.state.get(p, {})
                 with torch.no_grad():
-                    for k in ("exp_avg", "exp_avg_sq"):
-                        if k in new and new[k] is not views[p][k]:
+                    for k in ("exp_avg", "exp_avg_sq", "ema"):
+                        if k in views[p] and k in new and new[k] is not views[p][k]:
                             views[p][k].copy_(new[k])
+                    if "ema" in views[p] and "ema" not in new:
+                        views[p]["ema"].copy_(p.detach())
                     if "step" in new:
                         loaded_step = float(new["step"])
                 self.state[p] = views[p]
@@ -233,12 +282,14 @@ class FusedAdamW(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
+        if self._in_ema_scope:
+            raise RuntimeError("FusedAdamW.step() inside ema_scope(): the parameters hold the averages; leave the scope first")
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         work = []
-        for group, flat, slot in zip(self.param_groups, self._flats, self._lr_dev):
+        for group, flat, slot, ema in zip(self.param_groups, self._flats, self._lr_dev, self._ema_flats):
             ps = [p for p in group["params"] if p.requires_grad and p.grad is not None]
             if not ps:
                 continue
@@ -252,7 +303,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 if g.is_sparse or g.dtype != torch.float32 or g.device != p.device:
                     raise RuntimeError("FusedAdamW: dense fp32 gradients on the parameter's device")
                 gs.append(g if g.is_contiguous() else g.contiguous())
-            work.append((group, flat, slot, ps, gs))
+            work.append((group, flat, slot, ps, gs, ema))
         if not work:
             return loss
         capturing = torch.cuda.is_current_stream_capturing()
@@ -265,7 +316,7 @@ class FusedAdamW(torch.optim.Optimizer):
             ws = self._workspace(work[0][3][0].device)
             ws.run([g for w in work for g in w[4]], self.max_grad_norm)
             rec = ws.rec
-        for group, flat, slot, ps, gs in work:
+        for group, flat, slot, ps, gs, ema in work:
             flat[2].add_(1.0)                                    # the update count of THIS step, on the device (capturable)
             n = len(ps)
             numel = (ctypes.c_int64 * n)(*[p.numel() for p in ps])
@@ -273,21 +324,102 @@ class FusedAdamW(torch.optim.Optimizer):
             beta1, beta2 = group["betas"]
             lr = _check_lr(group["lr"])
             ms, vs = [self.state[p]["exp_avg"] for p in ps], [self.state[p]["exp_avg_sq"] for p in ps]
+            tail = ()
+            if ema is not None:
+                es = [self.state[p]["ema"] for p in ps]
+                tail = (self.ema_decay, int(self.ema_warmup))
             if capturing or rec is not None:
                 # rate from the device scalar.  Under capture a fill would be baked into the graph: the scalar must be current
                 if capturing and lr != slot[1]:
                     raise RuntimeError("FusedAdamW: param_group['lr'] changed since the last push_hyperparameters(); call it "
                                        "before capturing a step (capture_train_step does)")
-                _hip.call("cf_adamw_step_batch_dev", n, A(ps), A(gs), A(ms), A(vs), ctypes.cast(numel, ctypes.c_void_p), _hip.p(flat[2]),
+                name, head = (("cf_adamw_step_batch_dev", (A(ps), A(gs), A(ms), A(vs))) if ema is None else
+                              ("cf_adamw_ema_step_batch_dev", (A(ps), A(gs), A(ms), A(vs), A(es))))
+                _hip.call(name, n, *head, ctypes.cast(numel, ctypes.c_void_p), _hip.p(flat[2]),
                           _hip.p(slot[0]), _hip.p(rec), float(beta1), float(beta2), float(group["eps"]),
-                          float(group["weight_decay"]), int(group["maximize"]), _hip.stream())
+                          float(group["weight_decay"]), int(group["maximize"]), *tail, _hip.stream())
             else:
-                _hip.call("cf_adamw_step_batch", n, A(ps), A(gs), A(ms), A(vs), ctypes.cast(numel, ctypes.c_void_p), _hip.p(flat[2]),
+                name, head = (("cf_adamw_step_batch", (A(ps), A(gs), A(ms), A(vs))) if ema is None else
+                              ("cf_adamw_ema_step_batch", (A(ps), A(gs), A(ms), A(vs), A(es))))
+                _hip.call(name, n, *head, ctypes.cast(numel, ctypes.c_void_p), _hip.p(flat[2]),
                           lr, float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]),
-                          int(group["maximize"]), _hip.stream())
+                          int(group["maximize"]), *tail, _hip.stream())
             # the kernel wrote through raw pointers: tell torch, so that everything keyed on `_version` (layers/_derived.py, the
             # auto-captured evaluation graphs) sees the update.  Host-only, also under capture; ONE call for the list (571 single
             # calls cost 0.5 ms of host time for the smap flow, the list 45 us).  The moment views share the counter of their flat buffer
             torch.autograd.graph.increment_version(ps)
-            torch.autograd.graph.increment_version((flat[0], flat[1]))
+            torch.autograd.graph.increment_version((flat[0], flat[1]) if ema is None else (flat[0], flat[1], ema))
         return loss
+
+    def ema_parameters(self):
+        """The averages (`state[p]["ema"]`, views of the groups' flat buffers) in `param_groups` order, for the parameters that
+        have one (those that required a gradient at construction).  Empty without `ema_decay`."""
+        return [self.state[p]["ema"] for g in self.param_groups for p in g["params"] if "ema" in self.state.get(p, ())]
+
+    def _swap_ema(self):
+        """Exchange parameters and averages, group by group.  Every group is checked before the first launch, and a launch that
+        fails after others went through exchanges those back before the error leaves: all groups swapped, or none."""
+        work = []
+        for g, ema in zip(self.param_groups, self._ema_flats):
+            ps = [p for p in g["params"] if "ema" in self.state.get(p, ())]
+            if ema is None or not ps:
+                continue
+            for p in ps:
+                if not p.is_contiguous() or p.dtype != torch.float32 or p.device != ema.device:
+                    raise RuntimeError("FusedAdamW.ema_scope: a parameter left the form it had at construction (contiguous fp32 on %s)" % (ema.device,))
+            work.append((ps, ema))
+        done = []
+        try:
+            for ps, ema in work:
+                self._swap_group(ps, ema)
+                done.append((ps, ema))
+        except BaseException:
+            for ps, ema in done:
+                self._swap_group(ps, ema)
+            raise
+
+    def _swap_group(self, ps, ema):
+        with torch.no_grad():
+            numel = (ctypes.c_int64 * len(ps))(*[p.numel() for p in ps])
+            _hip.call("cf_swap_batch", len(ps), _hip.ptr_array(ps), _hip.ptr_array([self.state[p]["ema"] for p in ps]),
+                      ctypes.cast(numel, ctypes.c_void_p), _hip.stream())
+            torch.autograd.graph.increment_version(ps)
+            torch.autograd.graph.increment_version((ema,))
+
+    @contextlib.contextmanager
+    def ema_scope(self, flow=None):
+        """Evaluate under the averaged weights: `with opt.ema_scope(flow): flow.log_prob(x)`.  On entry and on exit ONE
+        `cf_swap_batch` per group exchanges the CONTENTS of every parameter with its average - the addresses stay, so a captured
+        training graph stays valid - and the version counters of everything written advance.  Inside, `state[p]["ema"]` holds the
+        raw iterate.  Give the flow when a captured step (`capture_train_step`) trains it: a replay moves no counter, so the flow's
+        evaluation caches may hold tables of either weight set, and `flow.invalidate_caches()` is called on both sides.  The
+        parameters are restored on exceptions too.  Not re-entrant; `step()` and a replay of `GraphedTrainStep` raise inside
+        the scope, as does `state_dict()`; not under stream capture.  Every rank of a data-parallel run may enter on its own: the averages agree."""
+        if self.ema_decay is None:
+            raise RuntimeError("FusedAdamW.ema_scope: built without ema_decay")
+        if self._in_ema_scope:
+            raise RuntimeError("FusedAdamW.ema_scope is not re-entrant")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FusedAdamW.ema_scope under stream capture: a replay would exchange the weights again")
+        self._swap_ema()                                         # all groups or none: nothing to undo when it raises
+        self._in_ema_scope = True
+        try:
+            if flow is not None:
+                flow.invalidate_caches()
+            yield self
+        finally:
+            try:
+                self._swap_ema()
+            finally:
+                # all or none again; if the way back failed the parameters still hold the averages, and the error says so by
+                # leaving - the flag must not lock the optimizer for good on top of it
+                self._in_ema_scope = False
+                if flow is not None:
+                    flow.invalidate_caches()
+
+    def state_dict(self):
+        """torch's layout (+ `ema` per parameter with `ema_decay`).  Inside `ema_scope()` parameters and averages are exchanged, so
+        a dict taken there would carry the raw iterate under `ema`: it raises instead."""
+        if self._in_ema_scope:
+            raise RuntimeError("FusedAdamW.state_dict() inside ema_scope(): parameters and averages are exchanged; leave the scope first")
+        return super().state_dict()

@@ -736,6 +736,24 @@ int cf_adamw_step_batch_dev(int n, float* const* p, const float* const* g, float
                             const float* step, const double* lr, const float* norm_rec, double beta1, double beta2, double eps,
                             double weight_decay, int maximize, cf_stream_t stream);
 
+/* The two updates above with an exponential moving average of the parameters written by the same thread, right after the parameter
+ * element (additive entry points: no existing signature or behaviour moved, so CF_ABI_VERSION stays).  ema: host array of n device
+ * pointers, one fp32 tensor per parameter, non-null where numel > 0.  With t = step[0]:
+ *     t == 1    : ema = p_new                                     (a copy, not a lerp with weight 1)
+ *     otherwise : ema = ema + w (p_new - ema),  w = (float)(1 - d_t),  d_t = ema_warmup ? min(ema_decay, (1 + t) / (10 + t)) : ema_decay
+ * d_t in double ON THE DEVICE, so a captured launch follows the warm-up of the decay; difference, product and sum rounded
+ * separately, so the host-rate and the device-rate form give the same average bits.  ema_decay in [0, 1).  p, m, v come out bit for
+ * bit as from the twin without the average.  ceil(n / 64) launches (the table has one more pointer per tensor).                  */
+int cf_adamw_ema_step_batch(int n, float* const* p, const float* const* g, float* const* m, float* const* v, float* const* ema,
+                            const int64_t* numel, const float* step, double lr, double beta1, double beta2, double eps, double weight_decay,
+                            int maximize, double ema_decay, int ema_warmup, cf_stream_t stream);
+int cf_adamw_ema_step_batch_dev(int n, float* const* p, const float* const* g, float* const* m, float* const* v, float* const* ema,
+                                const int64_t* numel, const float* step, const double* lr, const float* norm_rec, double beta1, double beta2,
+                                double eps, double weight_decay, int maximize, double ema_decay, int ema_warmup, cf_stream_t stream);
+/* Exchange the contents of n pairs of fp32 tensors (host arrays of device pointers and element counts) in ceil(n / 128) launches:
+ * float4 where both pointers of a pair are 16-byte aligned, scalar otherwise; exact.  a[i] != b[i]; pairs must not overlap.        */
+int cf_swap_batch(int n, float* const* a, float* const* b, const int64_t* numel, cf_stream_t stream);
+
 /* ---- global gradient norm and clipping (experiment_cl.py:135, experiment_ad.py:212: nn.utils.clip_grad_norm_) -------------------- */
 /* Host only: the number of fp64 partials (= workgroups: one per 1024 elements of a tensor) cf_grad_norm_batch writes for these
  * element counts; negative on a bad argument.                                                                                  */
