@@ -1808,6 +1808,15 @@ static int unsupported_shape(const char* fn, int C, int H, int W) {
 // with per-phase dumps besides 3), 2: half the samples per workgroup, 3: k_flow_step_small in the direct form, 4: Winograd
 // F(2x2, 3x3), 5: ... row-split at 128 pixels per workgroup, 6: Winograd F(2x4, 3x3) at 8x8 and 4x4.  (1 was an operand-pipeline
 // alternate of each shape, 6 at 16x16 and 7 two forms on the 16-bit matrix cores: gone with their geometries.)
+template <class G>
+static int lane_table_copy(int* out, int cap) {      // host copy of kLaneTab<G> (cf_lane_table_debug): same constexpr initialiser
+    static const LaneTab<G> tab = make_lane_tab<G>();
+    constexpr int n = (int)(sizeof(LaneEntry<G>) / sizeof(int));
+    static_assert(sizeof(tab) == 256 * n * sizeof(int), "an entry is n ints, no padding");
+    const int* src = reinterpret_cast<const int*>(&tab);
+    for (int i = 0; out && i < cap && i < 256 * n; ++i) out[i] = src[i];
+    return n;
+}
 constexpr int kDebugVariants = 8;
 constexpr Kernel kDebugKernel[4][kDebugVariants] = {
     {Kernel::Step_G8, Kernel::None, Kernel::None, Kernel::Small_G8s, Kernel::Small_G8w, Kernel::None, Kernel::None, Kernel::None},
@@ -1944,6 +1953,15 @@ int cf_flow_step_fwd_debug(const float* x, float* z, float* ldj_acc, const void*
     a.dbg = dbg;
     if (int rc = dbg ? launch_fwd_dumps(k, a) : launch_fwd(k, a)) return rc;
     CF_LAUNCH_CHECK();
+    return 0;
+}
+// test hook (not part of the public header; host only): the per-lane address table the saturating-batch kernels of a shape read
+// (kLaneTab, cf_step_common.h) as 256 x n ints, thread-major.  Returns n, the ints per thread - 0 for a shape whose kernels derive
+// their addresses - and copies min(cap, 256 n) ints to `out`.
+int cf_lane_table_debug(int C, int H, int W, int* out, int cap) {
+    switch (shape_id(C, H, W)) {
+        case 1: static_assert(kLaneTabW22<G16w>, "16x16, C = 16: F(2x2) table"); return lane_table_copy<G16w>(out, cap);
+        case 2: static_assert(kLaneTabW24<G32w24>, "8x8: F(2x4) table"); return lane_table_copy<G32w24>(out, cap);    }
     return 0;
 }
 // n <= 4 consecutive flow steps of one shape in ONE launch, for the batch sizes at which a step is one of the small-batch

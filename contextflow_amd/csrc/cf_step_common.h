@@ -98,6 +98,11 @@ struct Geo {
     static_assert((HW & (HW - 1)) == 0 && (W & (W - 1)) == 0, "power-of-two images");
 };
 
+// geometries whose kernels read their per-lane address words from a compile-time table (kLaneTab below; each passed the per-level
+// gate of profiles/lane_tables.md); all others derive them
+template <class G> constexpr bool kLaneTabW24 = G::W24 && G::H == 8;
+template <class G> constexpr bool kLaneTabW22 = G::PIPE == 3 && G::SMALL && G::C == 16;
+
 // packed row p of a C-channel result -> channel, or -1 for a padding row.  First-half channels sit
 // in rows [0, HALF), second-half channels in rows [HP, HP + HALF): t / log_s / x1 of one channel
 // then share a lane and differ by a fixed register offset.
@@ -458,7 +463,7 @@ __device__ __forceinline__ void mask_store(unsigned* __restrict__ m, const f32x1
 //     k PIX + [ s HW + (y&1) HW/2 + (y>>1) W + (x&1) W/2 + (x>>1) ]  ^  (k&1) W/2
 // - rows and columns split by parity, so the stride-2 patch reads of neighbouring tiles are consecutive words, and the
 // XOR moves odd rows k to the other column-parity block: the 32 lanes of a half wave (16 tiles x 2 channels) hit 32 banks.
-template <class G> __device__ __forceinline__ int wino_pix(int sHW, int y, int x) {
+template <class G> __host__ __device__ constexpr int wino_pix(int sHW, int y, int x) {
     int p = sHW + (y & 1) * (G::HW / 2) + (y >> 1) * G::W + (x & 1) * (G::W / 2) + (x >> 1);
     if constexpr (G::HW == 16) p ^= ((p >> 5) & 1) << 3;       // 4x4: four samples per wave - fold the sample bit that would alias
     return p;
@@ -479,9 +484,11 @@ typedef float f32x4w __attribute__((ext_vector_type(4)));
 // during the last one of this xi - and sched_barrier keeps hipcc from sinking them to their first use.  k runs in chunks
 // of <= 64 channels (outer loop): inside a chunk every operand address is `patch offset + immediate`; the output
 // transform is linear, so each chunk's partial M is folded into Y.
+// tw (kLaneTabW22 geometries): the words of this thread's table entry (W22Lane), requested by the caller in front of the barrier
+// that ends phase 1; the others pass nothing and derive
 template <class G>
 __device__ __forceinline__ void winograd_phase2(float* __restrict__ lds, const float* __restrict__ wsl, ws_rsrc_t rs, int lane,
-                                                     int wave) {
+                                                     int wave, const int4* tw = nullptr) {
     constexpr int W = G::W, H = G::H, HW = G::HW, PIX = G::PIX, HALF = G::HALF, HID = G::HID, RT16 = G::RT16, KG4 = G::KG4;
     // Ownership.  PTW even: a wave takes the NT = PTW / 2 column tiles (16 output tiles = 64 pixels each) of its own pixel
     // columns and ALL output rows.  PTW = 1 (128 pixels per workgroup: half the LDS, two workgroups per CU): two waves share a
@@ -495,7 +502,14 @@ __device__ __forceinline__ void winograd_phase2(float* __restrict__ lds, const f
     float* H1 = lds + HALF * PIX;
     const int l15 = lane & 15, lg = lane >> 4;
     constexpr int TPS = HW / 4;
-    int smp[NT], ty[NT], tx[NT], rpart[NT][4], cpart[NT][4];
+    int smp[NT], ty[NT], tx[NT], rpart[NT][4], cpart[NT][4], dsto = 0;
+    if constexpr (kLaneTabW22<G>) {
+        static_assert(NT == 1 && RSPLIT == 1, "W22Lane holds one column tile");
+        const int4 t0 = tw[0], t1 = tw[1];
+        rpart[0][0] = t0.x; rpart[0][1] = t0.y; rpart[0][2] = t0.z; rpart[0][3] = t0.w;
+        cpart[0][0] = t1.x; cpart[0][1] = t1.y; cpart[0][2] = t1.z; cpart[0][3] = t1.w;
+        dsto = tw[2].z;
+    } else
 #pragma unroll
     for (int ct = 0; ct < NT; ++ct) {
         const int tg = (cw * NT + ct) * 16 + l15, ti = tg % TPS;
@@ -792,7 +806,8 @@ __device__ __forceinline__ void winograd_phase2(float* __restrict__ lds, const f
         for (int ct = 0; ct < NT; ++ct)
 #pragma unroll
             for (int i = 0; i < 2; ++i) {            // the two pixels (j = 0, 1) of an output row of the tile: one 8-byte store
-                float* dst = H1 + ((rt0 + rt) * 16 + 4 * lg) * PIX + smp[ct] * HW + (2 * ty[ct] + i) * W + 2 * tx[ct];
+                float* dst = kLaneTabW22<G> ? H1 + (rt0 + rt) * 16 * PIX + i * W + dsto
+                                            : H1 + ((rt0 + rt) * 16 + 4 * lg) * PIX + smp[ct] * HW + (2 * ty[ct] + i) * W + 2 * tx[ct];
                 const float bb[4] = {b.x, b.y, b.z, b.w};
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
@@ -830,15 +845,86 @@ __device__ __forceinline__ void winograd_phase2(float* __restrict__ lds, const f
 // - the low five bits (the bank) are distinct for the 32 lanes of a group for every patch element (lanes whose reflected row
 // coincides read the same word), and the low six for all 64 lanes.  The word is a row part + a column part (w24_row / w24_col), so an operand address is one
 // addition.  (tests/test_winograd24_8x8.py checks the order exhaustively.)
-template <class G> __device__ __forceinline__ int w24_row(int s, int y, int kq) {
+template <class G> __host__ __device__ constexpr int w24_row(int s, int y, int kq) {
     return 128 * (s >> 1) + 32 * ((y ^ (kq >> 1)) & 1) + 8 * (y >> 1) + 4 * (s & 1);
 }
-template <class G> __device__ __forceinline__ int w24_col(int x, int kq) {
+template <class G> __host__ __device__ constexpr int w24_col(int x, int kq) {
     return 64 * ((x >> 1) & 1) + 2 * (((x >> 2) ^ (x >> 1)) & 1) + ((x ^ kq) & 1);
 }
-template <class G> __device__ __forceinline__ int w24_pix(int s, int y, int x, int kq) {      // kq = row & 3
+template <class G> __host__ __device__ constexpr int w24_pix(int s, int y, int x, int kq) {      // kq = row & 3
     if constexpr (G::H == 4) return 8 * (4 * y + ((x + y + kq) & 3)) + s;
     else return w24_row<G>(s, y, kq) + w24_col<G>(x, kq);
+}
+
+// ---- per-lane address words of the F(2x4) form at 8x8, tabulated at compile time -------------------------------------------------
+// Everything a lane needs to address the skewed h1 plane depends on (wave, lane) and the geometry alone; a step of the level kernel
+// formed it afresh (twice: nothing may stay live across the 3x3).  w24_lane is the one definition of those words; kLaneTab holds
+// them for the 256 threads of a workgroup, and a lane fetches its entry with 16-byte loads (five per step, L2 / L1 hits).
+constexpr int cf_reflect(int v, int n) { return v < 0 ? -v : (v >= n ? 2 * (n - 1) - v : v); }      // padding_mode='reflect'
+template <class G> struct alignas(16) W24Lane {
+    int row[4];             // phase 2: BYTE offset of patch row a of this lane's output tile: 4 w24_row(smp, yrow[a], lg)
+    int col[6];             // ... of patch column c, with the lane's k row of H1: 4 (HALF PIX + lg PIX + w24_col(xcol[c], lg))
+    int dst;                // h2 epilogue: FLOAT offset of the tile's first pixel in row 4 lg of H1
+    int pad;
+    int pw[G::PTW][4];      // phase 1: skewed word of pixel pix[q] in a row with row & 3 = kq (float offset inside the row)
+};
+template <class G> __host__ __device__ constexpr W24Lane<G> w24_lane(int wave, int lane) {
+    static_assert(kLaneTabW24<G>, "tabulated for the 8x8 level");
+    constexpr int W = G::W, H = G::H, HW = G::HW, PIX = G::PIX, HALF = G::HALF, NCT = PIX / 128, TPS = HW / 8, TXN = W / 4;
+    W24Lane<G> e{};
+    const int l15 = lane & 15, lg = lane >> 4, li = lane & 31;
+    const int tg = (wave % NCT) * 16 + l15;              // this lane's output tile (winograd24_phase2)
+    const int smp = tg / TPS, ty = (tg % TPS) / TXN, tx = tg % TXN;
+    for (int a = 0; a < 4; ++a) e.row[a] = 4 * w24_row<G>(smp, cf_reflect(2 * ty - 1 + a, H), lg);
+    for (int c = 0; c < 6; ++c) e.col[c] = 4 * (HALF * PIX + lg * PIX + w24_col<G>(cf_reflect(4 * tx - 1 + c, W), lg));
+    e.dst = 4 * lg * PIX + smp * HW + 2 * ty * W + 4 * tx;
+    for (int q = 0; q < G::PTW; ++q) {
+        const int pix = (wave * G::PTW + q) * 32 + li, pin = pix % HW;
+        for (int kq = 0; kq < 4; ++kq) e.pw[q][kq] = w24_pix<G>(pix / HW, pin / W, pin % W, kq);
+    }
+    return e;
+}
+// the same for the F(2x2) form at 16x16, C = 16 (winograd_phase2 with one column tile per wave, phase 1 on 32-pixel tiles)
+template <class G> struct alignas(16) W22Lane {
+    int row[4];             // phase 2: rpart[a], BYTE offset of patch row a with the lane's k row of H1
+    int col[4];             // ... cpart[a], byte offset of patch column a
+    int pw[2];              // phase 1: parity-split word of pixel pix[q] in an even row (odd rows: ^ W / 2)
+    int dst;                // h2 epilogue: FLOAT offset of the tile's first pixel in row 4 lg of H1
+    int pad;
+};
+template <class G> __host__ __device__ constexpr W22Lane<G> w22_lane(int wave, int lane) {
+    static_assert(G::PIPE == 3 && G::PTW == 2, "one column tile of 16 output tiles per wave");
+    constexpr int W = G::W, H = G::H, HW = G::HW, PIX = G::PIX, HALF = G::HALF, TPS = HW / 4;
+    W22Lane<G> e{};
+    const int l15 = lane & 15, lg = lane >> 4, li = lane & 31;
+    const int tg = wave * 16 + l15, ti = tg % TPS;       // this lane's output tile (winograd_phase2)
+    const int smp = tg / TPS, ty = ti / (W / 2), tx = ti % (W / 2);
+    for (int a = 0; a < 4; ++a) {
+        const int yy = cf_reflect(2 * ty - 1 + a, H), xx = cf_reflect(2 * tx - 1 + a, W);
+        e.row[a] = 4 * (HALF * PIX + lg * PIX + wino_pix<G>(smp * HW, yy, 0));
+        e.col[a] = 4 * ((((xx ^ lg) & 1) * (W / 2)) + (xx >> 1));
+    }
+    for (int q = 0; q < 2; ++q) {
+        const int pix = (wave * G::PTW + q) * 32 + li, pin = pix % HW;
+        e.pw[q] = wino_pix<G>(pix - pin, pin / W, pin % W);
+    }
+    e.dst = 4 * lg * PIX + smp * HW + 2 * ty * W + 2 * tx;
+    return e;
+}
+template <class G> using LaneEntry = std::conditional_t<G::W24, W24Lane<G>, W22Lane<G>>;
+template <class G> struct LaneTab { LaneEntry<G> e[kWaves * 64]; };
+template <class G> constexpr LaneTab<G> make_lane_tab() {
+    LaneTab<G> t{};
+    for (int i = 0; i < kWaves * 64; ++i) {
+        if constexpr (G::W24) t.e[i] = w24_lane<G>(i >> 6, i & 63);
+        else t.e[i] = w22_lane<G>(i >> 6, i & 63);
+    }
+    return t;
+}
+template <class G> __device__ const LaneTab<G> kLaneTab = make_lane_tab<G>();
+// the 16-byte word `i` of thread tid's entry
+template <class G> __device__ __forceinline__ int4 lane_tab_word(int tid, int i) {
+    return reinterpret_cast<const int4*>(&kLaneTab<G>.e[tid])[i];
 }
 
 // CF_W24_SPREAD (A/B builds of tools/dev/make_abl.py): 1 = the 8x8 level issues the patch reads of the next k-group one patch column
@@ -846,16 +932,16 @@ template <class G> __device__ __forceinline__ int w24_pix(int s, int y, int x, i
 #ifndef CF_W24_SPREAD
 #define CF_W24_SPREAD 1
 #endif
+// tw (8x8): words 0 .. 2 of this thread's table entry (W24Lane), requested by the caller in front of the barrier that ends phase 1
 template <class G>
 __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const float* __restrict__ wsl, ws_rsrc_t rs, int lane,
-                                                  int wave) {
+                                                  int wave, const int4 (&tw)[3]) {
     constexpr int W = G::W, H = G::H, HW = G::HW, PIX = G::PIX, HALF = G::HALF, RT16 = G::RT16, KG4 = G::KG4;
     constexpr int NCT = PIX / 128;                       // column tiles (16 output tiles of 2x4 pixels) of the workgroup
     constexpr int RSP = kWaves / NCT;                    // waves that share a column tile and split the output rows
     static_assert(G::W24 && (NCT == 1 || NCT == 2) && RT16 % RSP == 0 && W % 4 == 0, "F(2x4, 3x3) geometry");
     constexpr int RTW = RT16 / RSP;                      // 16-row tiles of this wave
-    constexpr int TPS = HW / 8, TXN = W / 4;             // output tiles per sample / per image row
-    constexpr int NS = 6 * KG4;                          // (group, nu) steps per xi
+    constexpr int NS = 6 * KG4;                         // (group, nu) steps per xi
     // nu order inside a group: 0 and 5 first, so that A0 / A5 die early and A1 .. A4 live on as P, Q, R, D
     constexpr int NU[6] = {0, 5, 1, 2, 3, 4};
     typedef float f32x2w __attribute__((ext_vector_type(2)));
@@ -865,24 +951,24 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
     const int rt0 = __builtin_amdgcn_readfirstlane((NCT == 1 ? wave : wave / NCT) * RTW);
     float* H1 = lds + HALF * PIX;
     const int l15 = lane & 15, lg = lane >> 4;
-    const int tg = (wave % NCT) * 16 + l15;              // this lane's output tile
-    // (the 4x4 expressions are kept literally: hipcc's code for that instantiation is then instruction for instruction what it was)
-    const int smp = H == 4 ? l15 >> 1 : tg / TPS, ty = H == 4 ? l15 & 1 : (tg % TPS) / TXN, tx = H == 4 ? 0 : tg % TXN;
-    int yrow[4], xcol[6];                                 // reflect-padded patch rows / columns of this lane's tile
+    // 4x4 (derived: the table form measured slower there, profiles/lane_tables.md): this lane's output tile and its reflect-padded
+    // patch rows; the patch columns are constants (one tile per image row).  The expressions are kept literally: hipcc's code for
+    // that instantiation is then instruction for instruction what it was.
+    const int smp = l15 >> 1, ty = l15 & 1;
+    int yrow[4];
+    // 8x8: byte offsets of the patch rows and columns (the order is row part + column part) and the h2 offset, from the table
+    int rpart[4], cpart[6], dsto = 0;
+    if constexpr (H == 4) {
 #pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        const int yy = 2 * ty - 1 + a;
-        yrow[a] = yy < 0 ? -yy : (yy >= H ? 2 * (H - 1) - yy : yy);
-    }
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        const int xx = 4 * tx - 1 + c;
-        xcol[c] = xx < 0 ? -xx : (xx >= W ? 2 * (W - 1) - xx : xx);
-    }
-    int cpart[6];                                         // 8x8: byte offset of a patch column (the order is row part + column part)
-    if constexpr (H != 4) {
-#pragma unroll
-        for (int c = 0; c < 6; ++c) cpart[c] = 4 * (HALF * PIX + lg * PIX + w24_col<G>(xcol[c], lg));
+        for (int a = 0; a < 4; ++a) {
+            const int yy = 2 * ty - 1 + a;
+            yrow[a] = yy < 0 ? -yy : (yy >= H ? 2 * (H - 1) - yy : yy);
+        }
+    } else {
+        const int4 t0 = tw[0], t1 = tw[1], t2 = tw[2];
+        rpart[0] = t0.x; rpart[1] = t0.y; rpart[2] = t0.z; rpart[3] = t0.w;
+        cpart[0] = t1.x; cpart[1] = t1.y; cpart[2] = t1.z; cpart[3] = t1.w; cpart[4] = t2.x; cpart[5] = t2.y;
+        dsto = t2.z;
     }
     f32x4w Y[2][4][RTW];
 #pragma unroll
@@ -896,16 +982,19 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
     auto addrs = [&](int xi, int (&o)[2][6]) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const int yy = h == 0 ? (xi == 0 ? yrow[0] : (xi == 2 ? yrow[2] : yrow[1]))
-                                  : (xi == 2 ? yrow[1] : (xi == 3 ? yrow[3] : yrow[2]));
+            if constexpr (H == 4) {
+                const int yy = h == 0 ? (xi == 0 ? yrow[0] : (xi == 2 ? yrow[2] : yrow[1]))
+                                      : (xi == 2 ? yrow[1] : (xi == 3 ? yrow[3] : yrow[2]));
 #pragma unroll
-            for (int c = 0; c < 6; ++c) {
-                if constexpr (H == 4) {
+                for (int c = 0; c < 6; ++c) {
                     const int xx = c == 0 ? 1 : (c == 5 ? 2 : c - 1);
                     o[h][c] = 4 * (HALF * PIX + lg * PIX + w24_pix<G>(smp, yy, xx, lg & 1));
-                } else {
-                    o[h][c] = 4 * w24_row<G>(smp, yy, lg) + cpart[c];
                 }
+            } else {
+                const int rr = h == 0 ? (xi == 0 ? rpart[0] : (xi == 2 ? rpart[2] : rpart[1]))
+                                      : (xi == 2 ? rpart[1] : (xi == 3 ? rpart[3] : rpart[2]));
+#pragma unroll
+                for (int c = 0; c < 6; ++c) o[h][c] = rr + cpart[c];
             }
         }
     };
@@ -1022,7 +1111,8 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {        // the four pixels of an output row of the tile: one 16-byte store
-                float* dst = H1 + ((rt0 + rt) * 16 + 4 * lg + r) * PIX + smp * HW + (2 * ty + i) * W + (H == 4 ? 0 : 4 * tx);
+                float* dst = H == 4 ? H1 + ((rt0 + rt) * 16 + 4 * lg + r) * PIX + smp * HW + (2 * ty + i) * W
+                                    : H1 + ((rt0 + rt) * 16 + r) * PIX + i * W + dsto;
                 *reinterpret_cast<float4*>(dst) = make_float4(cf_relu(Y[i][0][rt][r] + bb[r]), cf_relu(Y[i][1][rt][r] + bb[r]),
                                                               cf_relu(Y[i][2][rt][r] + bb[r]), cf_relu(Y[i][3][rt][r] + bb[r]));
             }
@@ -1050,6 +1140,7 @@ __device__ __forceinline__ void conditioner_net(f32x16 (&acc3)[G::RT03][G::PTW],
     float* H1 = lds + HALF * PIX;
     const int lk = lane >> 5;
     const ws_rsrc_t rs = ws_rsrc(wsl, G::WS_FLOATS);
+    int4 tw2[3] = {};                // phase 2's words of this thread's kLaneTab entry, requested inside phase 1
     // ================= phase 1: h1 = relu(NN.0 y0 + b)                      (coupling.py:26)
     {
         f32x16 acc[RT1][PTW];
@@ -1068,11 +1159,25 @@ __device__ __forceinline__ void conditioner_net(f32x16 (&acc3)[G::RT03][G::PTW],
                         if (row < HID) acc[rt][q][r] += sb[soff[q] + row];
                     }
         }
+        // h1 goes to LDS in the pixel order phase 2 reads (F(2x4): skewed, w24_pix; F(2x2): parity-split, wino_pix).  Where the
+        // geometry has a table (kLaneTab) the words of this lane's pixels come from there: phase 1's travel behind the MFMAs of
+        // the dense phase, phase 2's behind the h1 stores and the barrier
+        constexpr bool T24 = kLaneTabW24<G>, T22 = kLaneTabW22<G>;
+        int4 w0{}, w1{};
+        if constexpr (T24) { w0 = lane_tab_word<G>(tid, 3); w1 = lane_tab_word<G>(tid, 4); }
+        else if constexpr (T22) w0 = lane_tab_word<G>(tid, 2);
         dense_phase<G, G::KS1, G::NG1, RT1>(acc, rs, G::OFF_A1, Y0, pix, lane);
+        if constexpr (T24) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) tw2[i] = lane_tab_word<G>(tid, i);
+        } else if constexpr (T22) {
+            tw2[0] = lane_tab_word<G>(tid, 0); tw2[1] = lane_tab_word<G>(tid, 1); tw2[2] = w0;
+        }
         // the parity-split h1 order of the Winograd form scatters a wave's pixels over its whole SAMPLE: where a sample spans
         // several waves (16x16), every wave must be done with its columns of what the H region held before (x / z plane)
         // (the F(2x4) order spreads every sample over the whole row)
         if constexpr (G::WINO && (G::HW > 32 * PTW || G::W24)) __syncthreads();
+        const int tw1[2][4] = {{w0.x, w0.y, w0.z, w0.w}, {w1.x, w1.y, w1.z, w1.w}};
 #pragma unroll
         for (int rt = 0; rt < RT1; ++rt)
 #pragma unroll
@@ -1080,7 +1185,11 @@ __device__ __forceinline__ void conditioner_net(f32x16 (&acc3)[G::RT03][G::PTW],
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int row = rt * 32 + tile_row(r, lk);
-                    if constexpr (G::W24) {      // skewed pixel order of winograd24_phase2 (row & 3 = r & 3)
+                    if constexpr (T24) {                // W24Lane::pw[q][row & 3]  (row & 3 = r & 3)
+                        if (row < HID) H1[row * PIX + tw1[q][r & 3]] = cf_relu(acc[rt][q][r]);
+                    } else if constexpr (T22) {         // W22Lane::pw[q], odd rows in the other column-parity block
+                        if (row < HID) H1[row * PIX + (tw1[0][q] ^ ((r & 1) * (W / 2)))] = cf_relu(acc[rt][q][r]);
+                    } else if constexpr (G::W24) {      // skewed pixel order of winograd24_phase2 (row & 3 = r & 3)
                         const int pw = w24_pix<G>((pix[q] - pin[q]) / G::HW, pin[q] / W, pin[q] % W, G::H == 4 ? r & 1 : r & 3);
                         if (row < HID) H1[row * PIX + pw] = cf_relu(acc[rt][q][r]);
                     } else if constexpr (G::WINO) {     // parity-split pixel order of winograd_phase2 (row & 1 = r & 1)
@@ -1124,9 +1233,9 @@ __device__ __forceinline__ void conditioner_net(f32x16 (&acc3)[G::RT03][G::PTW],
     if constexpr (G::WINO) {
         if constexpr (G::W24) {
             static_assert(!DUMP, "the F(2x4) form runs in the evaluation forward only");
-            winograd24_phase2<G>(lds, wsl, rs, lane, tid >> 6);
+            winograd24_phase2<G>(lds, wsl, rs, lane, tid >> 6, tw2);
         } else {
-            winograd_phase2<G>(lds, wsl, rs, lane, tid >> 6);
+            winograd_phase2<G>(lds, wsl, rs, lane, tid >> 6, tw2);
         }
         if constexpr (DUMP) {            // h2 sits in LDS in natural order (own columns): plane store + mask words from the plane
             rows_store_t<G, HID, HID>(tp.h2, H1, tile * G::SPW, B, tid >> 6, lane);
