@@ -15,7 +15,7 @@
 //    each, 64 KiB total, 2 workgroups/CU); weights arrive as pre-packed 16-byte MFMA fragments
 //    (cf_vit_prepare, L2 resident) through the same two-stage operand pipeline as cf_step.hip.
 // Limits: dim <= 64, patch_dim <= 64, dim_head == 64, heads == 1, tokens per sample in {1,2,4,8,16,32}.
-#include "cf_common.h"
+#include "cf_vit_common.h"
 #include <math.h>
 
 namespace {
@@ -56,12 +56,7 @@ __host__ __device__ inline VitLayout vit_layout(int pd, int dim, int depth) {
     return L;
 }
 
-// flat parameter order expected by cf_vit_prepare (host concatenates the reference's tensors in this order):
-//   ln0.w(pd) ln0.b(pd) We(dim x pd) be(dim) ln1.w(dim) ln1.b(dim)
-//   depth x [ lnA.w lnA.b Wqkv(192 x dim) Wout(dim x 64) lnF.w lnF.b W1(dim x dim) b1 W2(dim x dim) b2 ]
-//   lnO.w lnO.b
-__host__ __device__ inline int flat_layer_size(int dim) { return 2 * dim + 192 * dim + dim * 64 + 2 * dim + 2 * (dim * dim + dim); }
-
+// (flat parameter order expected by cf_vit_prepare: VitFlat, cf_vit_common.h)
 __device__ inline void pack_ln(float* dst, const float* w, const float* b, int n, int gtid, int gsz) {
     for (int i = gtid; i < 128; i += gsz) {
         const int f = i & 63;
@@ -86,23 +81,24 @@ __global__ __launch_bounds__(256) void k_vit_pack(const float* __restrict__ flat
                                                   int depth) {
     const VitLayout L = vit_layout(pd, dim, depth);
     const int gtid = blockIdx.x * 256 + threadIdx.x, gsz = gridDim.x * 256;
-    const float* p = flat;
-    pack_ln(ws + L.ln0, p, p + pd, pd, gtid, gsz); p += 2 * pd;
-    pack_frags(ws + L.we, p, dim, pd, 2, gtid, gsz); p += dim * pd;
-    pack_vec(ws + L.be, p, dim, gtid, gsz); p += dim;
-    pack_ln(ws + L.ln1, p, p + dim, dim, gtid, gsz); p += 2 * dim;
+    const VitFlat P(pd, dim);
+    pack_ln(ws + L.ln0, flat + P.ln0_w(), flat + P.ln0_b(), pd, gtid, gsz);
+    pack_frags(ws + L.we, flat + P.we(), dim, pd, 2, gtid, gsz);
+    pack_vec(ws + L.be, flat + P.be(), dim, gtid, gsz);
+    pack_ln(ws + L.ln1, flat + P.ln1_w(), flat + P.ln1_b(), dim, gtid, gsz);
     for (int l = 0; l < depth; ++l) {
         float* w = ws + L.layer0 + l * L.layer_stride;
-        pack_ln(w + L.lnA, p, p + dim, dim, gtid, gsz); p += 2 * dim;
-        pack_frags(w + L.wqkv, p, 192, dim, 6, gtid, gsz); p += 192 * dim;
-        pack_frags(w + L.wout, p, dim, 64, 2, gtid, gsz); p += dim * 64;
-        pack_ln(w + L.lnF, p, p + dim, dim, gtid, gsz); p += 2 * dim;
-        pack_frags(w + L.w1, p, dim, dim, 2, gtid, gsz); p += dim * dim;
-        pack_vec(w + L.b1, p, dim, gtid, gsz); p += dim;
-        pack_frags(w + L.w2, p, dim, dim, 2, gtid, gsz); p += dim * dim;
-        pack_vec(w + L.b2, p, dim, gtid, gsz); p += dim;
+        const float* p = flat + P.layer(l);
+        pack_ln(w + L.lnA, p + P.ga(), p + P.ba(), dim, gtid, gsz);
+        pack_frags(w + L.wqkv, p + P.wq(), 3 * P.head, dim, 6, gtid, gsz);
+        pack_frags(w + L.wout, p + P.wo(), dim, P.head, 2, gtid, gsz);
+        pack_ln(w + L.lnF, p + P.gf(), p + P.bf(), dim, gtid, gsz);
+        pack_frags(w + L.w1, p + P.w1(), dim, dim, 2, gtid, gsz);
+        pack_vec(w + L.b1, p + P.b1(), dim, gtid, gsz);
+        pack_frags(w + L.w2, p + P.w2(), dim, dim, 2, gtid, gsz);
+        pack_vec(w + L.b2, p + P.b2(), dim, gtid, gsz);
     }
-    pack_ln(ws + L.lnO, p, p + dim, dim, gtid, gsz);
+    pack_ln(ws + L.lnO, flat + P.lno_w(depth), flat + P.lno_b(depth), dim, gtid, gsz);
 }
 
 // ---- device helpers ------------------------------------------------------------------------------
@@ -342,7 +338,7 @@ int cf_vit_supported(int C, int H, int W, int p1, int p2, int dim, int dim_head,
 int64_t cf_vit_ws_bytes(int patch_dim, int dim, int depth) { return (int64_t)vit_layout(patch_dim, dim, depth).total * 4; }
 
 int64_t cf_vit_flat_params(int patch_dim, int dim, int depth) {
-    return 2 * patch_dim + (int64_t)dim * patch_dim + dim + 2 * dim + (int64_t)depth * flat_layer_size(dim) + 2 * dim;
+    return VitFlat(patch_dim, dim).total(depth);
 }
 
 int cf_vit_prepare(const float* flat_params, void* ws, int patch_dim, int dim, int depth, cf_stream_t stream) {

@@ -22,7 +22,6 @@
 //    a whole layer of lead time, no copies.
 #include "cf_vit_rs_common.h"
 
-extern "C" int cf_slogdet_inverse(const float* W, int C, float* logabsdet, float* Winv, cf_stream_t stream);
 extern "C" int cf_slogdet_inverse_batch(int n, const float* const* Wm, int C, float* const* logabsdet, float* const* inv, cf_stream_t stream);
 extern "C" int cf_vit_step_bwd_prepare_batch(int n, const float* const* Wm, const float* const* logs, const float* const* flat, void* const* wsb,
                                              int C, int depth, cf_stream_t stream);
@@ -36,7 +35,7 @@ namespace {
 #define CF_VIT_RS_MINW 1
 #endif
 // DUMP (training forward): the residual stream at the depth + 1 layer boundaries also goes to xtape ([boundary][DIM][T],
-// as cf_vit_step_fwd_taped writes it) - the owner's tile, 64 contiguous bytes per feature row.
+// as the wave form of cf_vit_step_fwd writes it) - the owner's tile, 64 contiguous bytes per feature row.
 // (x and z may be the same buffer: a workgroup reads its four samples before it writes them - the chained form below)
 template <class V, bool DUMP = false>
 __device__ __forceinline__ void vit_step_rs_body(const float* x, float* z, float* __restrict__ ldj_acc, const float* __restrict__ ws,
@@ -267,7 +266,6 @@ __global__ __launch_bounds__(256, CF_VIT_RS_MINW) void k_vit_step_rs(const float
 // Consecutive transformer flow steps in ONE launch (evaluation at small batches: a step is latency - 28 us on 64 workgroups at a
 // batch of 256 - and so is the gap between two launches): a workgroup owns its four samples end to end, steps 2.. run in place
 // on z behind a workgroup barrier.  Same code per step: bit for bit the per-step launches.
-constexpr int kVitChain = 8;
 struct VitWsChain { const float* ws[kVitChain]; };
 template <class V>
 __global__ __launch_bounds__(256, CF_VIT_RS_MINW) void k_vit_step_rs_chain(const float* x, float* z, float* __restrict__ ldj_acc,
@@ -281,29 +279,18 @@ __global__ __launch_bounds__(256, CF_VIT_RS_MINW) void k_vit_step_rs_chain(const
 
 using RS26 = RS<26>;
 
-bool rs_ok(int C, int H, int W, int p1, int p2, int dim, int dim_head, int heads) {
-    return C == 26 && H == 8 && W == 1 && p1 == 2 && p2 == 1 && dim == 2 * C && dim_head == 64 && heads == 1;
-}
-
 }  // namespace
 
-extern "C" {
+// ---- the row-split form behind the cf_vit_step_* entry points (cf_vit_step.hip validates; declared in cf_vit_common.h) --------
+int64_t vit_rs_ws_floats(int depth) { return ws_floats<RS26>(depth); }
 
-int cf_vit_step_rs_supported(int C, int H, int W, int p1, int p2, int dim, int dim_head, int heads) {
-    return rs_ok(C, H, W, p1, p2, dim, dim_head, heads) ? 1 : 0;
-}
-
-int64_t cf_vit_step_rs_ws_bytes(int C, int depth) { return C == 26 ? (int64_t)ws_floats<RS26>(depth) * 4 : 0; }
-
-// The row-split tables of n flow steps in ONE factorisation launch, ONE k_vit_fuse launch and ONE packing launch (a training
-// step at a batch of 256 packs all 8 steps of the SMAP flow per update: 24 serial launches of 14-27 us before).  HOST arrays
-// of device pointers.  winv (NULL or n): also Wm^-1 (the Conv1x1 log-det gradient); wsb (NULL or n): also the backward
-// kernel's transposed fragments (cf_vit_step_bwd_prepare).
-int cf_vit_step_rs_prepare_batch(int n, const float* const* Wm, const float* const* t, const float* const* logs,
-                                 const float* const* flat_vit_params, const float* pos, void* const* ws, float* const* winv,
-                                 void* const* wsb, int C, int depth, cf_stream_t stream) {
-    CF_REQUIRE(n >= 0 && Wm && t && logs && flat_vit_params && pos && ws && depth >= 1);
-    if (C != 26) { cf_set_error("cf_vit_step_rs_prepare: C=%d unsupported", C); return CF_ERR_UNSUPPORTED; }
+// The tables of n flow steps in ONE factorisation launch, ONE k_vit_fuse launch and ONE packing launch per kVitPrepBatch steps (a
+// training step at a batch of 256 packs all 8 steps of the SMAP flow per update: 24 serial launches of 14-27 us before).
+// winv (NULL or n): also Wm^-1 (the Conv1x1 log-det gradient); wsb (NULL or n): also the backward kernel's transposed fragments.
+int vit_rs_prepare_batch(int n, const float* const* Wm, const float* const* t, const float* const* logs, const float* const* flat,
+                         const float* pos, void* const* ws, float* const* winv, void* const* wsb, int depth, cf_stream_t stream) {
+    constexpr int C = RS26::C;
+    constexpr VitFlat P(RS26::PD, RS26::DIM, RS26::HEAD);
     for (int i0 = 0; i0 < n; i0 += kVitPrepBatch) {
         const int m = n - i0 < kVitPrepBatch ? n - i0 : kVitPrepBatch;
         VitRsPackBatch pb{};
@@ -311,10 +298,10 @@ int cf_vit_step_rs_prepare_batch(int n, const float* const* Wm, const float* con
         float* lad[kVitPrepBatch];
         for (int i = 0; i < m; ++i) {
             const int j = i0 + i;
-            CF_REQUIRE(Wm[j] && t[j] && logs[j] && flat_vit_params[j] && ws[j] && (reinterpret_cast<uintptr_t>(ws[j]) & 15) == 0);
+            CF_REQUIRE(Wm[j] && t[j] && logs[j] && flat[j] && ws[j] && (reinterpret_cast<uintptr_t>(ws[j]) & 15) == 0);
             float* w = (float*)ws[j];
-            pb.Wm[i] = Wm[j]; pb.t[i] = t[j]; pb.logs[i] = logs[j]; pb.flat[i] = flat_vit_params[j]; pb.ws[i] = w;
-            fb.layers[i] = flat_vit_params[j] + 2 * RS26::PD + RS26::DIM * RS26::PD + RS26::DIM + 2 * RS26::DIM;
+            pb.Wm[i] = Wm[j]; pb.t[i] = t[j]; pb.logs[i] = logs[j]; pb.flat[i] = flat[j]; pb.ws[i] = w;
+            fb.layers[i] = flat[j] + P.layer0();
             fb.scratch[i] = w + off_fuse_scratch<RS26>(depth);
             lad[i] = w + 1;
         }
@@ -324,53 +311,25 @@ int cf_vit_step_rs_prepare_batch(int n, const float* const* Wm, const float* con
         k_vit_rs_pack<RS26><<<dim3(64, m), dim3(256), 0, cf_s(stream)>>>(pb, pos, depth);
         CF_LAUNCH_CHECK();
     }
-    if (wsb) return cf_vit_step_bwd_prepare_batch(n, Wm, logs, flat_vit_params, wsb, C, depth, stream);
+    if (wsb) return cf_vit_step_bwd_prepare_batch(n, Wm, logs, flat, wsb, C, depth, stream);
     return 0;
 }
 
-int cf_vit_step_rs_prepare(const float* Wm, const float* t, const float* logs, const float* flat_vit_params, const float* pos,
-                           void* ws, int C, int depth, cf_stream_t stream) {
-    CF_REQUIRE(Wm && t && logs && flat_vit_params && pos && ws && depth >= 1 && (reinterpret_cast<uintptr_t>(ws) & 15) == 0);
-    return cf_vit_step_rs_prepare_batch(1, &Wm, &t, &logs, &flat_vit_params, pos, &ws, nullptr, nullptr, C, depth, stream);
-}
-
-int cf_vit_step_rs_fwd(const float* x, float* z, float* ldj_acc, const void* ws, float* h_out, int B, int C, int depth,
-                       int64_t x_bstride, cf_stream_t stream) {
-    if (B == 0) return 0;
-    CF_REQUIRE(x && z && ldj_acc && ws && B > 0 && depth >= 1 && x_bstride >= (int64_t)C * 8);
-    if (C != 26) { cf_set_error("cf_vit_step_rs_fwd: C=%d unsupported", C); return CF_ERR_UNSUPPORTED; }
-    k_vit_step_rs<RS26><<<dim3((unsigned)((B + 3) / 4)), dim3(256), 0, cf_s(stream)>>>(x, z, ldj_acc, (const float*)ws, B,
-                                                                                   x_bstride, depth, h_out);
+int vit_rs_fwd(const float* x, float* z, float* ldj_acc, const float* ws, float* h_out, float* xtape, int B, int depth, int64_t xbs,
+               cf_stream_t stream) {
+    const dim3 grid((unsigned)((B + 3) / 4)), block(256);
+    if (xtape) k_vit_step_rs<RS26, true><<<grid, block, 0, cf_s(stream)>>>(x, z, ldj_acc, ws, B, xbs, depth, nullptr, xtape, vit_tape_tokens(B));
+    else k_vit_step_rs<RS26><<<grid, block, 0, cf_s(stream)>>>(x, z, ldj_acc, ws, B, xbs, depth, h_out);
     CF_LAUNCH_CHECK();
     return 0;
 }
 
-int cf_vit_step_rs_chain_max_steps(void) { return kVitChain; }
-
-// n <= cf_vit_step_rs_chain_max_steps() consecutive steps (ws: host array of their packed tables); z may not alias x
-int cf_vit_step_rs_fwd_chain(const float* x, float* z, float* ldj_acc, const void* const* ws, int n, int B, int C, int depth,
-                             int64_t x_bstride, cf_stream_t stream) {
-    if (B == 0 || n == 0) return 0;
-    CF_REQUIRE(x && z && ldj_acc && ws && n >= 1 && n <= kVitChain && B > 0 && depth >= 1 && x_bstride >= (int64_t)C * 8 && (const float*)z != x);
-    if (C != 26) { cf_set_error("cf_vit_step_rs_fwd_chain: C=%d unsupported", C); return CF_ERR_UNSUPPORTED; }
+int vit_rs_fwd_chain(const float* x, float* z, float* ldj_acc, const void* const* ws, int n, int B, int depth, int64_t xbs,
+                     cf_stream_t stream) {
     VitWsChain wc{};
     for (int i = 0; i < n; ++i) { CF_REQUIRE(ws[i]); wc.ws[i] = (const float*)ws[i]; }
-    k_vit_step_rs_chain<RS26><<<dim3((unsigned)((B + 3) / 4)), dim3(256), 0, cf_s(stream)>>>(x, z, ldj_acc, wc, n, B, x_bstride, depth);
+    k_vit_step_rs_chain<RS26><<<dim3((unsigned)((B + 3) / 4)), dim3(256), 0, cf_s(stream)>>>(x, z, ldj_acc, wc, n, B, xbs, depth);
     CF_LAUNCH_CHECK();
     return 0;
 }
 
-// training forward: cf_vit_step_rs_fwd that also writes the residual-stream tape of cf_vit_step_fwd_taped (same layout and size)
-int cf_vit_step_rs_fwd_taped(const float* x, float* z, float* ldj_acc, const void* ws, float* xtape, int B, int C, int depth,
-                             int64_t x_bstride, cf_stream_t stream) {
-    if (B == 0) return 0;
-    CF_REQUIRE(x && z && ldj_acc && ws && xtape && B > 0 && depth >= 1 && x_bstride >= (int64_t)C * 8);
-    if (C != 26) { cf_set_error("cf_vit_step_rs_fwd_taped: C=%d unsupported", C); return CF_ERR_UNSUPPORTED; }
-    k_vit_step_rs<RS26, true><<<dim3((unsigned)((B + 3) / 4)), dim3(256), 0, cf_s(stream)>>>(x, z, ldj_acc, (const float*)ws, B,
-                                                                                         x_bstride, depth, nullptr, xtape,
-                                                                                         4ll * ((B + 31) / 32 * 32));
-    CF_LAUNCH_CHECK();
-    return 0;
-}
-
-}  // extern "C"

@@ -24,7 +24,6 @@
 namespace {
 
 template <class V> struct RSB {
-    static constexpr int MAXD = 6;                                   // transformer depth the LDS budget is sized for
     static constexpr int NG_Q = ngrp(48);                            // qkv^T: contraction over 192 rows
     // backward workspace (floats): transposed fragments + the LayerNorm vectors the forward workspace folds away
     static constexpr int OFF_CT = 0, OFF_G0 = OFF_CT + 2 * V::NG_C * 256, OFF_BT0 = OFF_G0 + 32;
@@ -42,7 +41,7 @@ template <class V> struct RSB {
     static constexpr int P_A = P_GY + 32 * PS, P_B = P_A + PL, P_H = P_B + PL, P_O = P_H + PL, P_G = P_O + PL;
     static constexpr int P_Q = P_A, P_XIN = P_O;
     static constexpr int P_SC = P_G + PL, P_XS = (P_SC + 2 * 256 + 3) & ~3;            // SC: two halves of [4 waves][4][16]
-    static constexpr int LDS_FLOATS = P_XS + (MAXD - 1) * 1024;
+    static constexpr int LDS_FLOATS = P_XS + (kVitMaxDepth - 1) * 1024;
     static_assert(4 * V::KS_C * PS <= PL && 192 * TS <= 3 * PL, "aliased planes fit");
     // LayerNorm partial sums of one workgroup (floats): [gamma | beta] per LayerNorm
     static constexpr int LN_0 = 0, LN_1 = 64, LN_L = 192, LN_LSTRIDE = 256;       // per layer: [ga | ba | gf | bf]
@@ -82,18 +81,18 @@ __global__ __launch_bounds__(256) void k_vit_rs_pack_bwd(const VitRsPackBwdBatch
         const int k = 16 * rt + (lane & 15), ch = 4 * (4 * gi + e) + (lane >> 4);
         wsb[R::OFF_CT + i] = (k < C && ch < C) ? expf(-logs[ch]) * Wm[ch * C + k] : 0.f;
     }
-    const float* p = flat;
-    vec(wsb + R::OFF_G0, p, PD, 32); vec(wsb + R::OFF_BT0, p + PD, PD, 32); p += 2 * PD;
-    fragsT(wsb + R::OFF_WET, p, DIM, PD, 2, V::NG_D); p += DIM * PD + DIM;
-    p += 2 * DIM;                                                     // to_patch_embedding.3: in the forward workspace
+    constexpr VitFlat P(PD, DIM, V::HEAD);
+    vec(wsb + R::OFF_G0, flat + P.ln0_w(), PD, 32); vec(wsb + R::OFF_BT0, flat + P.ln0_b(), PD, 32);
+    fragsT(wsb + R::OFF_WET, flat + P.we(), DIM, PD, 2, V::NG_D);       // (to_patch_embedding.3 is in the forward workspace)
     for (int l = 0; l < depth; ++l) {
         float* w = wsb + R::OFF_LAYER + l * R::LB_STRIDE;
-        vec(w + R::LB_GA, p, DIM, 64); vec(w + R::LB_BA, p + DIM, DIM, 64); p += 2 * DIM;
-        fragsT(w + R::LB_WQKVT, p, 192, DIM, 4, R::NG_Q); p += 192 * DIM;
-        fragsT(w + R::LB_WOUTT, p, DIM, 64, 4, V::NG_D); p += DIM * 64;
-        vec(w + R::LB_GF, p, DIM, 64); vec(w + R::LB_BF, p + DIM, DIM, 64); p += 2 * DIM;
-        fragsT(w + R::LB_W1T, p, DIM, DIM, 4, V::NG_D); p += DIM * DIM + DIM;
-        fragsT(w + R::LB_W2T, p, DIM, DIM, 4, V::NG_D); p += DIM * DIM + DIM;
+        const float* p = flat + P.layer(l);
+        vec(w + R::LB_GA, p + P.ga(), DIM, 64); vec(w + R::LB_BA, p + P.ba(), DIM, 64);
+        fragsT(w + R::LB_WQKVT, p + P.wq(), 3 * V::HEAD, DIM, 4, R::NG_Q);
+        fragsT(w + R::LB_WOUTT, p + P.wo(), DIM, V::HEAD, 4, V::NG_D);
+        vec(w + R::LB_GF, p + P.gf(), DIM, 64); vec(w + R::LB_BF, p + P.bf(), DIM, 64);
+        fragsT(w + R::LB_W1T, p + P.w1(), DIM, DIM, 4, V::NG_D);
+        fragsT(w + R::LB_W2T, p + P.w2(), DIM, DIM, 4, V::NG_D);
     }
 }
 
@@ -108,9 +107,9 @@ __device__ __forceinline__ float gelu_d(float x) {                    // d/dx of
 
 // ---- the backward kernel --------------------------------------------------------------------------------------------
 // x: step input (B, C, 8, 1), batch stride xbs; gz: dL/dz (B, C, 8, 1) dense; gld: dL/d(log-det) (B,); gx: dL/dx dense.
-// ws: forward workspace of cf_vit_step_rs_prepare; wsb: k_vit_rs_pack_bwd.  tp: token-major planes (layout: RSB::TL_*,
+// ws: row-split forward workspace (cf_vit_step_prepare_batch); wsb: k_vit_rs_pack_bwd.  tp: token-major planes (layout: RSB::TL_*,
 // see cf_vit_step_bwd_plane_floats); lnp: one row of LayerNorm partial sums per workgroup.
-// TAPED: the residual stream at the layer boundaries comes from the training forward (cf_vit_step_fwd_taped: xtape
+// TAPED: the residual stream at the layer boundaries comes from the training forward (cf_vit_step_fwd with xtape:
 // [depth + 1][DIM][T], feature-major) - phase A then runs the Conv1x1 / ActNorm / patch embedding only (their statistics and
 // planes are needed on the way back) and skips the six layers, a quarter of this kernel's work.
 template <class V, bool TAPED = false>
@@ -657,8 +656,8 @@ int64_t cf_vit_step_bwd_ln_floats(int B, int C, int depth) { return C == 26 ? (i
 
 int cf_vit_step_bwd_prepare_batch(int n, const float* const* Wm, const float* const* logs, const float* const* flat_vit_params,
                                   void* const* wsb, int C, int depth, cf_stream_t stream) {
-    CF_REQUIRE(n >= 0 && Wm && logs && flat_vit_params && wsb && depth >= 1 && depth <= RB26::MAXD);
-    if (C != 26) { cf_set_error("cf_vit_step_bwd_prepare: C=%d unsupported", C); return CF_ERR_UNSUPPORTED; }
+    CF_REQUIRE(n >= 0 && Wm && logs && flat_vit_params && wsb && depth >= 1 && depth <= kVitMaxDepth);
+    if (C != 26) { cf_set_error("cf_vit_step_bwd_prepare_batch: C=%d unsupported", C); return CF_ERR_UNSUPPORTED; }
     for (int i0 = 0; i0 < n; i0 += kVitPrepBatch) {
         const int m = n - i0 < kVitPrepBatch ? n - i0 : kVitPrepBatch;
         VitRsPackBwdBatch pb{};
@@ -673,45 +672,26 @@ int cf_vit_step_bwd_prepare_batch(int n, const float* const* Wm, const float* co
     return 0;
 }
 
-int cf_vit_step_bwd_prepare(const float* Wm, const float* logs, const float* flat_vit_params, void* wsb, int C, int depth,
-                            cf_stream_t stream) {
-    CF_REQUIRE(Wm && logs && flat_vit_params && wsb && (reinterpret_cast<uintptr_t>(wsb) & 15) == 0);
-    return cf_vit_step_bwd_prepare_batch(1, &Wm, &logs, &flat_vit_params, &wsb, C, depth, stream);
-}
 
+// xtape (NULL, or the cf_vit_step_tape_floats(B, C, depth) floats a forward with xtape wrote): the six layers are not run a second
+// time before the way back.  Same outputs to fp32 rounding (the tape holds the forward's own residual stream, the recompute
+// form rebuilds it in the row-split kernel's summation order).
 int cf_vit_step_bwd(const float* x, const float* gz, const float* gld, float* gx, const void* ws, const void* wsb, float* planes,
-                    float* ln_partials, int B, int C, int depth, int64_t x_bstride, cf_stream_t stream) {
+                    float* ln_partials, const float* xtape, int B, int C, int depth, int64_t x_bstride, cf_stream_t stream) {
     if (B == 0) return 0;
-    CF_REQUIRE(x && gz && gld && gx && ws && wsb && planes && ln_partials && B > 0 && depth >= 1 && depth <= RB26::MAXD &&
+    CF_REQUIRE(x && gz && gld && gx && ws && wsb && planes && ln_partials && B > 0 && depth >= 1 && depth <= kVitMaxDepth &&
                x_bstride >= (int64_t)C * 8);
     if (C != 26) { cf_set_error("cf_vit_step_bwd: C=%d unsupported", C); return CF_ERR_UNSUPPORTED; }
     constexpr size_t lds_bytes = (size_t)RB26::LDS_FLOATS * sizeof(float);
-    static std::atomic<uint64_t> raised{0};
-    if (int rc_ = cf_raise_dynamic_lds((const void*)k_vit_step_bwd_rs<RS26>, 160 * 1024, raised, __func__)) return rc_;
+    static std::atomic<uint64_t> raised[2];
+    const void* kernel = xtape ? (const void*)k_vit_step_bwd_rs<RS26, true> : (const void*)k_vit_step_bwd_rs<RS26>;
+    if (int rc_ = cf_raise_dynamic_lds(kernel, 160 * 1024, raised[xtape != nullptr], __func__)) return rc_;
     const int nwg = (B + 3) / 4;
-    k_vit_step_bwd_rs<RS26><<<dim3((unsigned)nwg), dim3(256), lds_bytes, cf_s(stream)>>>(
-        x, gz, gld, gx, (const float*)ws, (const float*)wsb, planes, ln_partials, B, nwg * 4, x_bstride, depth);
-    CF_LAUNCH_CHECK();
-    return 0;
-}
-
-// the same from the residual-stream tape of cf_vit_step_fwd_taped (xtape: cf_vit_step_tape_floats(B, C, depth) floats): the
-// six layers are not run a second time before the way back.  Same outputs to fp32 rounding (the tape holds the forward's own
-// residual stream, the recompute form rebuilds it in the row-split kernel's summation order).
-int cf_vit_step_bwd_taped(const float* x, const float* gz, const float* gld, float* gx, const void* ws, const void* wsb,
-                          float* planes, float* ln_partials, const float* xtape, int B, int C, int depth, int64_t x_bstride,
-                          cf_stream_t stream) {
-    if (B == 0) return 0;
-    CF_REQUIRE(x && gz && gld && gx && ws && wsb && planes && ln_partials && xtape && B > 0 && depth >= 1 && depth <= RB26::MAXD &&
-               x_bstride >= (int64_t)C * 8);
-    if (C != 26) { cf_set_error("cf_vit_step_bwd_taped: C=%d unsupported", C); return CF_ERR_UNSUPPORTED; }
-    constexpr size_t lds_bytes = (size_t)RB26::LDS_FLOATS * sizeof(float);
-    static std::atomic<uint64_t> raised{0};
-    if (int rc_ = cf_raise_dynamic_lds((const void*)k_vit_step_bwd_rs<RS26, true>, 160 * 1024, raised, __func__)) return rc_;
-    const int nwg = (B + 3) / 4;
-    k_vit_step_bwd_rs<RS26, true><<<dim3((unsigned)nwg), dim3(256), lds_bytes, cf_s(stream)>>>(
-        x, gz, gld, gx, (const float*)ws, (const float*)wsb, planes, ln_partials, B, nwg * 4, x_bstride, depth, xtape,
-        4ll * ((B + 31) / 32 * 32));
+    const dim3 grid((unsigned)nwg), block(256);
+    const float *w = (const float*)ws, *wb = (const float*)wsb;
+    if (xtape) k_vit_step_bwd_rs<RS26, true><<<grid, block, lds_bytes, cf_s(stream)>>>(x, gz, gld, gx, w, wb, planes, ln_partials, B, nwg * 4,
+                                                                                       x_bstride, depth, xtape, vit_tape_tokens(B));
+    else k_vit_step_bwd_rs<RS26><<<grid, block, lds_bytes, cf_s(stream)>>>(x, gz, gld, gx, w, wb, planes, ln_partials, B, nwg * 4, x_bstride, depth);
     CF_LAUNCH_CHECK();
     return 0;
 }

@@ -1,17 +1,14 @@
 // Shared device code of the row-split transformer-coupling step kernels (cf_vit_rs.hip: forward for small batches,
 // cf_vit_rs_bwd.hip: the training backward): geometry, workspace layout, packing helpers, 16x16x4 product helpers, token
-// statistics.  Everything lives in an anonymous namespace of the including translation unit.
+// statistics.  What they share with the wave form is in cf_vit_common.h.  Everything lives in an anonymous namespace of the
+// including translation unit.
 #pragma once
-#include "cf_common.h"
-#include "cf_vit_fuse.h"
+#include "cf_vit_common.h"
 #include <math.h>
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-
-__host__ __device__ constexpr int ngrp(int ks) { return (ks + 3) / 4; }
 
 template <int C_> struct RS {
     static constexpr int C = C_, CIN = C / 2, HW = 8, NTOK = 4, DIM = 2 * C, PD = 2 * CIN, HEAD = 64;
@@ -84,11 +81,7 @@ __global__ __launch_bounds__(256) void k_vit_rs_pack(const VitRsPackBatch pb, co
     auto vec = [&](float* dst, const float* src, int n, int rows) {
         for (int r = gtid; r < rows; r += gsz) dst[r] = r < n ? src[r] : 0.f;
     };
-    if (gtid == 0) {       // ldj_const = H*W*log|det Wm| + sum_c logs  (ws[1] holds log|det| from cf_slogdet_inverse)
-        float s = 0.f;
-        for (int c = 0; c < C; ++c) s += logs[c];
-        ws[0] = (float)V::HW * ws[1] + s;                                   // conv1x1.py:53 + actnorm.py:58
-    }
+    if (gtid == 0) pack_ldj_const<V>(ws, logs);
     // Conv1x1 + ActNorm: y = e^{-logs} (Wm x - t)                          (conv1x1.py:54, actnorm.py:59)
     for (int r = gtid; r < 32; r += gsz) ws[V::OFF_B0 + r] = r < C ? -t[r] * expf(-logs[r]) : 0.f;
     for (int i = gtid; i < 2 * V::NG_C * 256; i += gsz) {
@@ -96,16 +89,16 @@ __global__ __launch_bounds__(256) void k_vit_rs_pack(const VitRsPackBatch pb, co
         const int row = 16 * rt + (lane & 15), k = 4 * (4 * gi + e) + (lane >> 4);
         ws[V::OFF_A0 + i] = (row < C && k < C) ? expf(-logs[row]) * Wm[row * C + k] : 0.f;
     }
-    const float* p = flat;       // order of TransCoupling._flat_params(): see cf_vit_fused.hip
-    const float *g0 = p, *b0 = p + PD; p += 2 * PD;                                          // to_patch_embedding.1 (LayerNorm(pd))
-    frags(ws + V::OFF_WE, p, DIM, PD, 4, V::NG_PD, g0);
-    fold_bias(ws + V::OFF_BE, p, p + DIM * PD, b0, DIM, PD, 64); p += DIM * PD + DIM;
-    vec(ws + V::OFF_LN1, p, DIM, 64); vec(ws + V::OFF_LN1 + 64, p + DIM, DIM, 64); p += 2 * DIM;
+    constexpr VitFlat P(PD, DIM, HEAD);
+    // to_patch_embedding: the first LayerNorm's affine part folded into the Linear
+    frags(ws + V::OFF_WE, flat + P.we(), DIM, PD, 4, V::NG_PD, flat + P.ln0_w());
+    fold_bias(ws + V::OFF_BE, flat + P.we(), flat + P.be(), flat + P.ln0_b(), DIM, PD, 64);
+    vec(ws + V::OFF_LN1, flat + P.ln1_w(), DIM, 64); vec(ws + V::OFF_LN1 + 64, flat + P.ln1_b(), DIM, 64);
     for (int n = 0; n < V::NTOK; ++n) vec(ws + V::OFF_POS + 64 * n, pos + n * DIM, DIM, 64);
     for (int l = 0; l < depth; ++l) {
         float* w = ws + V::OFF_LAYER + l * V::L_STRIDE;
-        const float *ga = p, *ba = p + DIM; p += 2 * DIM;                                    // attention pre-norm
-        {   // fused attention tables of the forward kernel (cf_vit_fuse.h: k_vit_fuse has formed the matrices in fp64)
+        const float* p = flat + P.layer(l);
+        {   // fused attention tables of the forward kernel (cf_vit_common.h: k_vit_fuse has formed the matrices in fp64)
             float* wf = ws + off_fused<V>(depth) + l * V::F_STRIDE;
             const float* fz = ws + off_fuse_scratch<V>(depth) + l * F::LAYER_FLOATS;
             frags_fn(wf + V::F_A1, DIM, DIM, 4, V::NG_D, [&](int a, int b) { return fz[F::M1 + a * DIM + b]; });
@@ -115,28 +108,18 @@ __global__ __launch_bounds__(256) void k_vit_rs_pack(const VitRsPackBatch pb, co
                 wf[V::F_C2 + r] = r < DIM ? fz[F::C2 + r] : 0.f;
             }
         }
-        frags(w + V::L_WQKV, p, 192, DIM, 12, V::NG_D, ga);
-        fold_bias(w + V::L_CQKV, p, nullptr, ba, 192, DIM, 192); p += 192 * DIM;
-        frags(w + V::L_WOUT, p, DIM, 64, 4, V::NG_H, nullptr); p += DIM * 64;
-        const float *gf = p, *bf = p + DIM; p += 2 * DIM;                                    // feed-forward pre-norm
-        frags(w + V::L_W1, p, DIM, DIM, 4, V::NG_D, gf);
-        fold_bias(w + V::L_B1, p, p + DIM * DIM, bf, DIM, DIM, 64); p += DIM * DIM + DIM;
-        frags(w + V::L_W2, p, DIM, DIM, 4, V::NG_D, nullptr);
-        vec(w + V::L_B2, p + DIM * DIM, DIM, 64); p += DIM * DIM + DIM;
+        frags(w + V::L_WQKV, p + P.wq(), 3 * HEAD, DIM, 12, V::NG_D, p + P.ga());         // pre-norms folded in as above
+        fold_bias(w + V::L_CQKV, p + P.wq(), nullptr, p + P.ba(), 3 * HEAD, DIM, 192);
+        frags(w + V::L_WOUT, p + P.wo(), DIM, HEAD, 4, V::NG_H, nullptr);
+        frags(w + V::L_W1, p + P.w1(), DIM, DIM, 4, V::NG_D, p + P.gf());
+        fold_bias(w + V::L_B1, p + P.w1(), p + P.b1(), p + P.bf(), DIM, DIM, 64);
+        frags(w + V::L_W2, p + P.w2(), DIM, DIM, 4, V::NG_D, nullptr);
+        vec(w + V::L_B2, p + P.b2(), DIM, 64);
     }
-    vec(ws + off_lno<V>(depth), p, DIM, 64); vec(ws + off_lno<V>(depth) + 64, p + DIM, DIM, 64);
+    vec(ws + off_lno<V>(depth), flat + P.lno_w(depth), DIM, 64); vec(ws + off_lno<V>(depth) + 64, flat + P.lno_b(depth), DIM, 64);
 }
 
 // ---- device helpers -----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ rsrc_t make_rsrc(const float* ws, int floats) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ws), 0, floats * 4, 0x00020000);
-}
-__device__ __forceinline__ float4 frag(rsrc_t rs, int lane, int foff) {
-    typedef int i32x4_t __attribute__((ext_vector_type(4)));
-    const i32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, foff * 4, 0);
-    return make_float4(__int_as_float(v.x), __int_as_float(v.y), __int_as_float(v.z), __int_as_float(v.w));
-}
-__device__ __forceinline__ float f4e(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
 __device__ __forceinline__ f32x4 to4(const float4& v) { return f32x4{v.x, v.y, v.z, v.w}; }
 template <int NG> __device__ __forceinline__ void load_frags(float4 (&f)[NG], rsrc_t rs, int lane, int foff) {
 #pragma unroll
@@ -159,15 +142,6 @@ __device__ __forceinline__ f32x4 gemm1(f32x4 init, const float4 (&fr)[NG], BOP b
     return a0 + a1;
 }
 
-template <int CTRL> __device__ __forceinline__ float quad(float v) {          // DPP quad permutation of the 4 tokens of a sample
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-template <int M> __device__ __forceinline__ float tok_xor(float v) {
-    if constexpr (M == 0) return v;
-    else if constexpr (M == 1) return quad<0xB1>(v);      // [1,0,3,2]
-    else if constexpr (M == 2) return quad<0x4E>(v);      // [2,3,0,1]
-    else return quad<0x1B>(v);                            // [3,2,1,0]
-}
 __device__ __forceinline__ float group_sum(float v) {      // over the four lane groups g (same token column)
     v += __shfl_xor(v, 16, 64);
     return v + __shfl_xor(v, 32, 64);
@@ -185,6 +159,5 @@ __device__ __forceinline__ void token_stats(const float (&xv)[NR], int n, int g,
     for (int i = 0; i < NR; ++i) { const float d = (g + 4 * i < n) ? xv[i] - mean : 0.f; q = fmaf(d, d, q); }
     rstd = 1.0f / sqrtf(group_sum(q) * (1.0f / (float)n) + 1e-5f);
 }
-
 
 }  // namespace

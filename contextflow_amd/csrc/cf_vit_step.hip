@@ -36,8 +36,9 @@
 //    HBM traffic = read x + write z.
 // Geometry covered: C even, C <= 32 (SMAP: 26), H = 8, W = 1, patch (2, 1), dim = 2C, 1 head x 64, any depth.  Other
 // transformer couplings keep the LDS-plane kernel (cf_vit_fused.hip) or the layer-by-layer kernels (cf_vit.hip).
-#include "cf_common.h"
-#include "cf_vit_fuse.h"
+//
+// This file also holds the cf_vit_step_* entry points of BOTH forward forms (the row-split form for small batches: cf_vit_rs.hip).
+#include "cf_vit_common.h"
 #include <math.h>
 
 extern "C" int cf_slogdet_inverse(const float* W, int C, float* logabsdet, float* Winv, cf_stream_t stream);
@@ -46,12 +47,10 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
 
 // accumulator register r of lane half lk <-> row of a 32-row result tile (v_mfma_f32_32x32x2_f32)
 __host__ __device__ constexpr int trow(int r, int lk) { return (r & 3) + 8 * (r >> 2) + 4 * lk; }
 __host__ __device__ constexpr int reg_of_row(int q) { return (q & 3) + 4 * (q >> 3); }
-__host__ __device__ constexpr int ngrp(int ks) { return (ks + 3) / 4; }
 
 // ---- compile-time geometry ------------------------------------------------------------------------------------
 template <int C_> struct VS {
@@ -95,7 +94,7 @@ template <class V> __host__ __device__ constexpr int feat_of_phys(int p) {
 // k-step s of a product whose B operand is the residual tile pair -> physical row supplied by lane half lk
 template <class V> __host__ __device__ constexpr int phys_of_kstep(int s, int lk) { return trow(s % V::KPT, lk) + 32 * (s / V::KPT); }
 
-// ---- packing (cf_vit_step_prepare) ----------------------------------------------------------------------------------
+// ---- packing (cf_vit_step_prepare_batch) ----------------------------------------------------------------------------------
 // fragment element ((g * RT + rt) * 64 + lane) * 4 + e = A[row = rt * 32 + (lane & 31)][k-step 4 g + e, lane half]
 template <class V>
 __global__ __launch_bounds__(256) void k_vit_step_pack(const float* __restrict__ Wm, const float* __restrict__ t,
@@ -127,11 +126,7 @@ __global__ __launch_bounds__(256) void k_vit_step_pack(const float* __restrict__
     auto res_k = [](int s, int lk) { return feat_of_phys<V>(phys_of_kstep<V>(s, lk)); };
     auto in_k = [](int s, int lk) { return logical_of_row<V>(trow(s, lk)); };                   // patch feature = logical tile-0 row
 
-    if (gtid == 0) {       // ldj_const = H*W*log|det Wm| + sum_c logs  (ws[1] holds log|det| from cf_slogdet_inverse)
-        float s = 0.f;
-        for (int c = 0; c < C; ++c) s += logs[c];
-        ws[0] = (float)V::HW * ws[1] + s;                                   // conv1x1.py:53 + actnorm.py:58
-    }
+    if (gtid == 0) pack_ldj_const<V>(ws, logs);
     // Conv1x1 + ActNorm as a product over (position-in-patch, channel): rows = physical rows, k-step s = input channel s,
     // lane half = position ii'; block diagonal in the position
     for (int i = gtid; i < 64; i += gsz) {
@@ -144,20 +139,20 @@ __global__ __launch_bounds__(256) void k_vit_step_pack(const float* __restrict__
         const int j = logical_of_row<V>(lane & 31), ii = j >= 0 ? j / CIN : -1, ch = j >= 0 ? (j % CIN) + CIN * rt : -1;
         ws[V::OFF_A0 + i] = (ch >= 0 && s < C && ii == (lane >> 5)) ? (float)(exp(-(double)logs[ch]) * (double)Wm[ch * C + s]) : 0.f;
     }
-    const float* p = flat;       // order of TransCoupling._flat_params(): see cf_vit_fused.hip
+    constexpr VitFlat P(C, DIM, HEAD);
     {   // to_patch_embedding: LN(pd = C) -> Linear(C, DIM) -> LN(DIM); the first LayerNorm's affine part folded into the Linear
-        const float *g0 = p, *b0 = p + C, *We = p + 2 * C, *be = We + DIM * C, *g1 = be + DIM, *b1 = g1 + DIM;
+        const float *g0 = flat + P.ln0_w(), *b0 = flat + P.ln0_b(), *We = flat + P.we(), *be = flat + P.be();
+        const float *g1 = flat + P.ln1_w(), *b1 = flat + P.ln1_b();
         frags(ws + V::OFF_WE, V::KS_IN, res_row, in_k, [&](int f, int k) { return (double)We[f * C + k] * (double)g0[k]; });
         vec(ws + V::OFF_BE, [&](int f) { double a = be[f]; for (int k = 0; k < C; ++k) a += (double)We[f * C + k] * (double)b0[k]; return a; });
         vec(ws + V::OFF_LN1, [&](int f) { return g1[f]; });
         for (int n = 0; n < V::NTOK; ++n) vec(ws + V::OFF_LN1 + 64 * (1 + n), [&](int f) { return b1[f] + pos[n * DIM + f]; });
-        p = b1 + DIM;
     }
     for (int l = 0; l < depth; ++l) {
         float* w = ws + V::OFF_LAYER + l * V::L_STRIDE;
-        const float* Wo = p + 2 * DIM + 3 * HEAD * DIM;
-        const float *gf = Wo + DIM * HEAD, *bf = gf + DIM, *W1 = bf + DIM, *b1 = W1 + DIM * DIM, *W2 = b1 + DIM, *b2 = W2 + DIM * DIM;
-        // attention through the fused matrices (cf_vit_fuse.h: k_vit_fuse has formed them in fp64):  s_ij = (A1 n_i + c1) . n_j,
+        const float* p = flat + P.layer(l);
+        const float *gf = p + P.gf(), *bf = p + P.bf(), *W1 = p + P.w1(), *b1 = p + P.b1(), *W2 = p + P.w2(), *b2 = p + P.b2();
+        // attention through the fused matrices (cf_vit_common.h: k_vit_fuse has formed them in fp64):  s_ij = (A1 n_i + c1) . n_j,
         // x += A2 (sum_j p_ij n_j) + c2
         const float* fz = ws + off_fuse<V>(depth) + l * F::LAYER_FLOATS;
         frags(w + V::L_A1, V::KS_RES, res_row, res_k, [&](int a, int b) { return fz[F::M1 + a * DIM + b]; });
@@ -169,26 +164,12 @@ __global__ __launch_bounds__(256) void k_vit_step_pack(const float* __restrict__
         vec(w + V::L_B1, [&](int f) { double a = b1[f]; for (int k = 0; k < DIM; ++k) a += (double)W1[f * DIM + k] * (double)bf[k]; return a; });
         frags(w + V::L_W2, V::KS_RES, res_row, res_k, [&](int f, int b) { return (double)W2[f * DIM + b]; });
         vec(w + V::L_B2, [&](int f) { return b2[f]; });
-        p = b2 + DIM;
     }
-    vec(ws + off_lno<V>(depth), [&](int f) { return p[f]; });
-    vec(ws + off_lno<V>(depth) + 64, [&](int f) { return p[DIM + f]; });
+    vec(ws + off_lno<V>(depth), [&](int f) { return flat[P.lno_w(depth) + f]; });
+    vec(ws + off_lno<V>(depth) + 64, [&](int f) { return flat[P.lno_b(depth) + f]; });
 }
 
 // ---- device helpers ----------------------------------------------------------------------------------------------------
-__device__ __forceinline__ rsrc_t make_rsrc(const float* ws, int floats) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ws), 0, floats * 4, 0x00020000);
-}
-__device__ __forceinline__ float4 frag(rsrc_t rs, int lane, int foff) {
-#ifdef CF_ABL_VS_NOFRAG
-    return make_float4(1e-3f * lane, 2e-3f, 3e-3f * foff, 1e-3f);
-#endif
-    typedef int i32x4_t __attribute__((ext_vector_type(4)));
-    const i32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, foff * 4, 0);
-    return make_float4(__int_as_float(v.x), __int_as_float(v.y), __int_as_float(v.z), __int_as_float(v.w));
-}
-__device__ __forceinline__ float f4e(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
-
 // register-order vector (64 floats [lk][tile][r]) -> this lane's two tiles
 __device__ __forceinline__ void load_vec(f32x16 (&v)[2], const float* __restrict__ base, int lk) {
 #pragma unroll
@@ -366,22 +347,12 @@ template <int K> __device__ __forceinline__ void add_tiles(f32x16 (&X)[2], const
     }
 }
 
-template <int CTRL> __device__ __forceinline__ float quad(float v) {          // DPP quad permutation of the 4 tokens of a sample
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-template <int M> __device__ __forceinline__ float tok_xor(float v) {
-    if constexpr (M == 0) return v;
-    else if constexpr (M == 1) return quad<0xB1>(v);      // [1,0,3,2]
-    else if constexpr (M == 2) return quad<0x4E>(v);      // [2,3,0,1]
-    else return quad<0x1B>(v);                            // [3,2,1,0]
-}
-
 // ---- the kernel ---------------------------------------------------------------------------------------------------------
 // x, z: (B, C, 8, 1).  ldj_acc[b] += H*W*log|det W| + sum logs + sum log_s.  hout (optional, tests): the conditioner's
 // output un-patchified, (B, C, 8, 1) = [t | raw].
 // DUMP (training forward at saturating batches): the residual stream at the depth + 1 layer boundaries goes to `xtape`,
 // feature-major [boundary][feature < DIM][token < T] (token = 4 sample + n: 128 contiguous bytes per feature and half wave) -
-// cf_vit_step_bwd_taped then walks back from these instead of running the six layers again.
+// cf_vit_step_bwd then walks back from these instead of running the six layers again.
 #ifndef CF_VS_MINW
 #define CF_VS_MINW 2          // waves per SIMD the register budget allows for (measured: 3 - with the DPP copies formed twice, 145 VGPRs - 3 899 us
 #endif                        // per 524 288 samples against 3 385, 4 with spills 4 615: more resident waves only fight over the L1 / L2 weight traffic)
@@ -535,47 +506,77 @@ __global__ __launch_bounds__(256, CF_VS_MINW) void k_vit_step(const float* __res
 
 using VS26 = VS<26>;
 
-bool step_ok(int C, int H, int W, int p1, int p2, int dim, int dim_head, int heads) {
-    return C == 26 && H == 8 && W == 1 && p1 == 2 && p2 == 1 && dim == 2 * C && dim_head == 64 && heads == 1;
+// one step's tables, wave form: factorisation, fused attention matrices, fragments
+int wave_prepare(const float* Wm, const float* t, const float* logs, const float* flat, const float* pos, float* w, int depth,
+                 cf_stream_t stream) {
+    CF_REQUIRE(Wm && t && logs && flat && w && (reinterpret_cast<uintptr_t>(w) & 15) == 0);
+    int rc = cf_slogdet_inverse(Wm, VS26::C, w + 1, nullptr, stream);
+    if (rc) return rc;
+    if (depth > 0) {
+        VitFuseBatch fb{};
+        fb.layers[0] = flat + VitFlat(VS26::C, VS26::DIM, VS26::HEAD).layer0();
+        fb.scratch[0] = w + off_fuse<VS26>(depth);
+        k_vit_fuse<VS26::DIM, VS26::HEAD><<<dim3(depth, 2, FUSE_SPLIT), dim3(256), 0, cf_s(stream)>>>(fb, depth);
+    }
+    k_vit_step_pack<VS26><<<dim3(64), dim3(256), 0, cf_s(stream)>>>(Wm, t, logs, flat, pos, w, depth);
+    CF_LAUNCH_CHECK();
+    return 0;
 }
+
+int wave_fwd(const float* x, float* z, float* ldj_acc, const float* ws, float* h_out, float* xtape, int B, int depth, int64_t xbs,
+             cf_stream_t stream) {
+    const dim3 grid((unsigned)((B + 31) / 32)), block(256);
+    if (xtape) k_vit_step<VS26, true><<<grid, block, 0, cf_s(stream)>>>(x, z, ldj_acc, ws, B, xbs, depth, nullptr, xtape, vit_tape_tokens(B));
+    else k_vit_step<VS26><<<grid, block, 0, cf_s(stream)>>>(x, z, ldj_acc, ws, B, xbs, depth, h_out);
+    CF_LAUNCH_CHECK();
+    return 0;
+}
+
+bool form_ok(int form) { return form == CF_VIT_FORM_WAVE || form == CF_VIT_FORM_RS; }
+int min_depth(int form) { return form == CF_VIT_FORM_RS ? 1 : 0; }       // (the row-split kernel prefetches layer 0)
 
 }  // namespace
 
 extern "C" {
 
-int cf_vit_step_supported(int C, int H, int W, int p1, int p2, int dim, int dim_head, int heads) {
-    return step_ok(C, H, W, p1, p2, dim, dim_head, heads) ? 1 : 0;
+int cf_vit_step_supported(int C, int H, int W, int p1, int p2, int dim, int dim_head, int heads, int depth) {
+    return vit_step_geometry_ok(C, H, W, p1, p2, dim, dim_head, heads) && depth >= 1 && depth <= kVitMaxDepth ? 1 : 0;
 }
 
-int64_t cf_vit_step_ws_bytes(int C, int depth) { return C == 26 ? (int64_t)ws_floats<VS26>(depth) * 4 : 0; }
+int64_t cf_vit_step_ws_bytes(int C, int depth, int form) {
+    if (C != 26 || !form_ok(form)) return 0;
+    return 4 * (form == CF_VIT_FORM_RS ? vit_rs_ws_floats(depth) : (int64_t)ws_floats<VS26>(depth));
+}
 
-int cf_vit_step_prepare(const float* Wm, const float* t, const float* logs, const float* flat_vit_params, const float* pos,
-                        void* ws, int C, int depth, cf_stream_t stream) {
-    CF_REQUIRE(Wm && t && logs && flat_vit_params && pos && ws && depth >= 0 && (reinterpret_cast<uintptr_t>(ws) & 15) == 0);
-    if (C != 26) { cf_set_error("cf_vit_step_prepare: C=%d unsupported", C); return CF_ERR_UNSUPPORTED; }
-    float* w = (float*)ws;
-    int rc = cf_slogdet_inverse(Wm, C, w + 1, nullptr, stream);
-    if (rc) return rc;
-    if (depth > 0) {
-        VitFuseBatch fb{};
-        fb.layers[0] = flat_vit_params + 2 * C + VS26::DIM * C + VS26::DIM + 2 * VS26::DIM;
-        fb.scratch[0] = w + off_fuse<VS26>(depth);
-        k_vit_fuse<VS26::DIM, VS26::HEAD><<<dim3(depth, 2, FUSE_SPLIT), dim3(256), 0, cf_s(stream)>>>(fb, depth);
-    }
-    k_vit_step_pack<VS26><<<dim3(64), dim3(256), 0, cf_s(stream)>>>(Wm, t, logs, flat_vit_params, pos, w, depth);
-    CF_LAUNCH_CHECK();
+int cf_vit_step_prepare_batch(int n, const float* const* Wm, const float* const* t, const float* const* logs,
+                              const float* const* flat_vit_params, const float* pos, void* const* ws, float* const* winv,
+                              void* const* wsb, int C, int depth, int form, cf_stream_t stream) {
+    CF_REQUIRE(n >= 0 && Wm && t && logs && flat_vit_params && pos && ws && form_ok(form) && depth >= min_depth(form) &&
+               (form == CF_VIT_FORM_RS || (!winv && !wsb)));
+    if (C != 26) { cf_set_error("cf_vit_step_prepare_batch: C=%d unsupported", C); return CF_ERR_UNSUPPORTED; }
+    if (form == CF_VIT_FORM_RS) return vit_rs_prepare_batch(n, Wm, t, logs, flat_vit_params, pos, ws, winv, wsb, depth, stream);
+    for (int i = 0; i < n; ++i)
+        if (int rc = wave_prepare(Wm[i], t[i], logs[i], flat_vit_params[i], pos, (float*)ws[i], depth, stream)) return rc;
     return 0;
 }
 
-int cf_vit_step_fwd(const float* x, float* z, float* ldj_acc, const void* ws, float* h_out, int B, int C, int depth,
-                    int64_t x_bstride, cf_stream_t stream) {
+int cf_vit_step_fwd(const float* x, float* z, float* ldj_acc, const void* ws, float* h_out, float* xtape, int B, int C, int depth,
+                    int64_t x_bstride, int form, cf_stream_t stream) {
     if (B == 0) return 0;
-    CF_REQUIRE(x && z && ldj_acc && ws && B > 0 && x_bstride >= (int64_t)C * 8);
+    CF_REQUIRE(x && z && ldj_acc && ws && !(h_out && xtape) && B > 0 && form_ok(form) && depth >= min_depth(form) &&
+               x_bstride >= (int64_t)C * 8);
     if (C != 26) { cf_set_error("cf_vit_step_fwd: C=%d unsupported", C); return CF_ERR_UNSUPPORTED; }
-    k_vit_step<VS26><<<dim3((unsigned)((B + 31) / 32)), dim3(256), 0, cf_s(stream)>>>(x, z, ldj_acc, (const float*)ws, B,
-                                                                                    x_bstride, depth, h_out);
-    CF_LAUNCH_CHECK();
-    return 0;
+    return (form == CF_VIT_FORM_RS ? vit_rs_fwd : wave_fwd)(x, z, ldj_acc, (const float*)ws, h_out, xtape, B, depth, x_bstride, stream);
+}
+
+int cf_vit_step_chain_max_steps(void) { return kVitChain; }
+
+int cf_vit_step_fwd_chain(const float* x, float* z, float* ldj_acc, const void* const* ws, int n, int B, int C, int depth,
+                          int64_t x_bstride, cf_stream_t stream) {
+    if (B == 0 || n == 0) return 0;
+    CF_REQUIRE(x && z && ldj_acc && ws && n >= 1 && n <= kVitChain && B > 0 && depth >= 1 && x_bstride >= (int64_t)C * 8 && (const float*)z != x);
+    if (C != 26) { cf_set_error("cf_vit_step_fwd_chain: C=%d unsupported", C); return CF_ERR_UNSUPPORTED; }
+    return vit_rs_fwd_chain(x, z, ldj_acc, ws, n, B, depth, x_bstride, stream);
 }
 
 int64_t cf_vit_step_macs(int C, int depth, int what) {
@@ -589,21 +590,8 @@ int64_t cf_vit_step_macs(int C, int depth, int what) {
     return (int64_t)C * C * V::HW + tok * (D * C + depth * 4 * D * D);
 }
 
-// training forward at saturating batches: cf_vit_step_fwd that also writes the residual stream at the layer boundaries -
-// xtape: cf_vit_step_tape_floats(B, C, depth) floats, [depth + 1][2C][T] with T = 4 * (B rounded up to 32) tokens.
-int64_t cf_vit_step_tape_tokens(int B) { return 4ll * ((B + 31) / 32 * 32); }
-int64_t cf_vit_step_tape_floats(int B, int C, int depth) { return C == 26 ? (int64_t)(depth + 1) * 2 * C * cf_vit_step_tape_tokens(B) : 0; }
-
-int cf_vit_step_fwd_taped(const float* x, float* z, float* ldj_acc, const void* ws, float* xtape, int B, int C, int depth,
-                          int64_t x_bstride, cf_stream_t stream) {
-    if (B == 0) return 0;
-    CF_REQUIRE(x && z && ldj_acc && ws && xtape && B > 0 && x_bstride >= (int64_t)C * 8);
-    if (C != 26) { cf_set_error("cf_vit_step_fwd_taped: C=%d unsupported", C); return CF_ERR_UNSUPPORTED; }
-    k_vit_step<VS26, true><<<dim3((unsigned)((B + 31) / 32)), dim3(256), 0, cf_s(stream)>>>(x, z, ldj_acc, (const float*)ws, B,
-                                                                                          x_bstride, depth, nullptr, xtape,
-                                                                                          cf_vit_step_tape_tokens(B));
-    CF_LAUNCH_CHECK();
-    return 0;
-}
+// the residual-stream tape of a training forward (cf_vit_step_fwd with xtape, either form): [depth + 1][2C][T] floats
+int64_t cf_vit_step_tape_tokens(int B) { return vit_tape_tokens(B); }
+int64_t cf_vit_step_tape_floats(int B, int C, int depth) { return C == 26 ? (int64_t)(depth + 1) * 2 * C * vit_tape_tokens(B) : 0; }
 
 }  // extern "C"

@@ -45,6 +45,14 @@ class Step(NamedTuple):
     aux: Any = None          # data-only walk (input gradient with frozen weights): the tape's aux buffer, all that is kept of the step
 
 
+class VitTables(NamedTuple):
+    """Packed tables of one transformer flow step (TransCoupling.step_tables)"""
+    form: str                # "wave" | "rs": the forward kernel they are laid out for (TransCoupling.step_variant)
+    ws: Any                  # forward tables
+    winv: Any = None         # Wm^-1 (training, rs)
+    wsb: Any = None          # backward kernel's tables (training, rs)
+
+
 class VStep(NamedTuple):
     """Conv1x1 -> ActNorm -> TransCoupling in one kernel"""
     kind = "vstep"
@@ -52,10 +60,8 @@ class VStep(NamedTuple):
     act: Any
     cpl: Any
     x: Any = None
-    ws: Any = None           # packed row-split tables, or None = the forward ran the wave form
+    tables: Any = None       # the forward's VitTables (the backward kernel reads row-split ones: a wave forward's are packed anew)
     xtape: Any = None        # residual-stream tape, or None = recomputed
-    winv: Any = None
-    wsb: Any = None
 
 
 class Squeeze(NamedTuple):

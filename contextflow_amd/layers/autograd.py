@@ -334,7 +334,7 @@ def vstep_backward(rec, gz, gld, gsum=None, side=None, keep=None, sink=None, par
     weight-gradient operand pairs it leaves (cf_linear_wgrad_group), the LayerNorm gradients are column sums of its
     per-workgroup partials, and the Conv1x1 / ActNorm chain is _affine_param_grads - as for the conv flows.
     Returns (dL/dx, {param: grad}); params=False: the kernel alone, (dL/dx, None)."""
-    conv, act, cpl, ws, xtape, wsb = rec.conv, rec.act, rec.cpl, rec.ws, rec.xtape, rec.wsb
+    conv, act, cpl, tables, xtape = rec.conv, rec.act, rec.cpl, rec.tables, rec.xtape
     xv, xbs = _hip.bview(rec.x)
     B, C = xv.shape[0], xv.shape[1]
     dev = xv.device
@@ -343,28 +343,24 @@ def vstep_backward(rec, gz, gld, gsum=None, side=None, keep=None, sink=None, par
     L = _hip.lib()
     f, pp, st = _hip.f32, _hip.p, _hip.stream()
     Wm, t, logs = f(conv.NN.detach()), f(act.NN_t.detach()), f(act.NN_logs.detach())
-    if ws is None:                                        # the forward ran the wave form: pack the row-split table now
-        ws = cpl.step_prepare(conv.NN, act.NN_t, act.NN_logs, dev, "rs")
-    if wsb is None:              # (the training forward at small batches packs these with its own tables: cf_vit_step_rs_prepare_batch)
-        flat = cpl._flat_params()
-        wsb = torch.empty(L.cf_vit_step_bwd_ws_bytes(C, depth), device=dev, dtype=torch.uint8)
-        _hip.call("cf_vit_step_bwd_prepare", pp(Wm), pp(logs), pp(flat), pp(wsb), C, depth, st)
+    if tables is None or tables.form != "rs" or tables.wsb is None:
+        # the forward ran the wave form: pack the row-split and the backward tables now (the training forward at small
+        # batches packs both with its own call)
+        tables = cpl.step_tables([(cpl, conv.NN, act.NN_t, act.NN_logs)], dev, "rs", bwd=True)[0]
+    ws, wsb = tables.ws, tables.wsb
     nwg = (B + 3) // 4
     planes = torch.empty(L.cf_vit_step_bwd_plane_floats(B, C, depth), device=dev, dtype=torch.float32)
     lnp = torch.empty(nwg, L.cf_vit_step_bwd_ln_floats(B, C, depth) // nwg, device=dev, dtype=torch.float32)
     gx = torch.empty(B, C, xv.shape[2], xv.shape[3], device=dev, dtype=torch.float32)
-    if xtape is not None:        # the forward taped the residual stream at the layer boundaries: the layers are not run again
-        _hip.call("cf_vit_step_bwd_taped", pp(xv), pp(f(gz).contiguous()), pp(f(gld)), pp(gx), pp(ws), pp(wsb), pp(planes), pp(lnp),
-                  pp(xtape), B, C, depth, xbs, st)
-    else:
-        _hip.call("cf_vit_step_bwd", pp(xv), pp(f(gz).contiguous()), pp(f(gld)), pp(gx), pp(ws), pp(wsb), pp(planes), pp(lnp), B, C,
-                  depth, xbs, st)
+    # (xtape: the forward taped the residual stream at the layer boundaries - the layers are not run again)
+    _hip.call("cf_vit_step_bwd", pp(xv), pp(f(gz).contiguous()), pp(f(gld)), pp(gx), pp(ws), pp(wsb), pp(planes), pp(lnp), pp(xtape),
+              B, C, depth, xbs, st)
     # ---- weight gradients: the planes as (rows, width) matrices (layout: include/contextflow_hip.h, cf_vit_step_bwd)
     # (small batches: on the side stream, as in step_backward)
     if not params:
         return gx, None
     HWv = xv.shape[2] * xv.shape[3]
-    aff = Affine(conv, act, Wm, t, logs, rec.winv)
+    aff = Affine(conv, act, Wm, t, logs, tables.winv)
     return gx, _param_part_on(side, keep, (planes, lnp, xv, ws, wsb, gsum, aff),
                               lambda: _vstep_param_part(aff, vit, depth, planes, lnp, nwg, C, HWv, gsum, gld, dev, sink), dev)
 

@@ -280,11 +280,10 @@ class TransCoupling(_AffineCoupling):
         if att is None:
             return False
         C, H, W = shape
-        L = _hip.lib()
-        a = (C, H, W, self.p_sz[0], self.p_sz[1], vit.dim, att.dim_head, att.heads)
-        # both one-kernel forms must cover the geometry (the dispatch picks by batch size, the training step runs the
-        # row-split backward kernel, depth <= STEP_MAX_DEPTH); anything else keeps the layer path
-        return bool(L.cf_vit_step_supported(*a)) and bool(L.cf_vit_step_rs_supported(*a)) and len(vit.transformer.layers) <= self.STEP_MAX_DEPTH
+        # one predicate for both forms of the forward (the dispatch picks by batch size) and the backward kernel (its depth limit);
+        # anything else keeps the layer path
+        return bool(_hip.lib().cf_vit_step_supported(C, H, W, self.p_sz[0], self.p_sz[1], vit.dim, att.dim_head, att.heads,
+                                                     len(vit.transformer.layers)))
 
     def step_sources(self):
         """Parameters the packed step workspace derives from (cache key of FlowSequential).  The tuple is built once: walking
@@ -295,70 +294,51 @@ class TransCoupling(_AffineCoupling):
             src = self.__dict__.setdefault("_derived", {})["step_src"] = tuple(self.NN[0].parameters())
         return src
 
-    # batches up to this size take the row-split step kernel (cf_vit_step_rs_fwd: 4 samples per workgroup, an eighth of the
-    # serial chain); larger ones the one-wave-per-8-samples kernel (cf_vit_step_fwd)
+    # batches up to this size take the row-split form of the step kernel (4 samples per workgroup, an eighth of the serial
+    # chain); larger ones the one-wave-per-8-samples form
     STEP_RS_MAX_BATCH = 3584          # measured cross-over (tools/dev/vit_variants.py, round 4, both forms with the fused attention tables): 36 vs 61 us at 2048, 46 vs 61 at 3072, 64 vs 61 at 4096
-
-    STEP_MAX_DEPTH = 6                # cf_vit_step_bwd parks the residual stream of <= 6 layer boundaries in LDS
+    STEP_FORMS = {"wave": 0, "rs": 1}         # CF_VIT_FORM_* (include/contextflow_hip.h)
 
     def step_variant(self, B):
-        """'rs' | 'wave': which one-kernel form of the step a batch of B samples takes (FlowSequential keys its packed
+        """'rs' | 'wave': which form of the step kernel a batch of B samples takes (FlowSequential keys its packed
         workspaces on it: the two kernels have their own fragment layouts)."""
         return "rs" if B <= self.STEP_RS_MAX_BATCH else "wave"
 
-    def step_prepare(self, Wm, t, logs, dev, variant="wave"):
-        """Pack Conv1x1 / ActNorm / ViT parameters into the fragment order of the one-kernel step."""
-        vit = self.NN[0]
-        C, depth = self.in_sz[0], len(vit.transformer.layers)
-        rs = variant == "rs"
-        L = _hip.lib()
-        ws = torch.empty((L.cf_vit_step_rs_ws_bytes if rs else L.cf_vit_step_ws_bytes)(C, depth), device=dev, dtype=torch.uint8)
-        if vit.pos_embedding.device != dev:
-            vit.pos_embedding = vit.pos_embedding.to(dev).contiguous()
-        flat = self._flat_params()
-        _hip.call("cf_vit_step_rs_prepare" if rs else "cf_vit_step_prepare", _hip.p(_hip.f32(Wm.detach())), _hip.p(_hip.f32(t.detach())),
-                  _hip.p(_hip.f32(logs.detach())), _hip.p(flat), _hip.p(_hip.f32(vit.pos_embedding)), _hip.p(ws), C, depth, _hip.stream())
-        return ws
-
     @staticmethod
-    def step_prepare_rs_batch(items, dev, train=False):
-        """The row-split tables of SEVERAL steps - items: [(coupling, Wm, t, logs)] - in one factorisation, one fuse and one
-        packing launch (cf_vit_step_rs_prepare_batch).  train: also Wm^-1 and the backward kernel's tables per step.  Returns
-        [ws] or [(ws, winv, wsb)]."""
+    def step_tables(items, dev, form, winv=False, bwd=False):
+        """Pack Conv1x1 / ActNorm / ViT parameters of SEVERAL steps - items: [(coupling, Wm, t, logs)] - into the fragment order
+        of one form of the step kernel (cf_vit_step_prepare_batch; 'rs': one factorisation, one fuse and one packing launch for
+        all of them).  winv, bwd ('rs' only): also Wm^-1 / the backward kernel's tables per step.  Returns [_tape.VitTables]."""
         L = _hip.lib()
         cpl0 = items[0][0]
         vit = cpl0.NN[0]
-        C, depth, n = cpl0.in_sz[0], len(vit.transformer.layers), len(items)
+        C, depth, n, fid = cpl0.in_sz[0], len(vit.transformer.layers), len(items), TransCoupling.STEP_FORMS[form]
         if vit.pos_embedding.device != dev:
             vit.pos_embedding = vit.pos_embedding.to(dev).contiguous()
         f, A = _hip.f32, _hip.ptr_array
-        ws = [torch.empty(L.cf_vit_step_rs_ws_bytes(C, depth), device=dev, dtype=torch.uint8) for _ in range(n)]
+        byte_bufs = lambda nbytes: [torch.empty(nbytes, device=dev, dtype=torch.uint8) for _ in range(n)]
+        ws = byte_bufs(L.cf_vit_step_ws_bytes(C, depth, fid))
         Wm, t, logs = [f(i[1].detach()) for i in items], [f(i[2].detach()) for i in items], [f(i[3].detach()) for i in items]
         flat = [i[0]._flat_params() for i in items]
-        winv = [torch.empty(C, C, device=dev, dtype=torch.float32) for _ in range(n)] if train else None
-        wsb = [torch.empty(L.cf_vit_step_bwd_ws_bytes(C, depth), device=dev, dtype=torch.uint8) for _ in range(n)] if train else None
-        _hip.call("cf_vit_step_rs_prepare_batch", n, A(Wm), A(t), A(logs), A(flat), _hip.p(_hip.f32(vit.pos_embedding)), A(ws),
-                  A(winv) if train else None, A(wsb) if train else None, C, depth, _hip.stream())
-        return list(zip(ws, winv, wsb)) if train else ws
+        wi = [torch.empty(C, C, device=dev, dtype=torch.float32) for _ in range(n)] if winv else [None] * n
+        wb = byte_bufs(L.cf_vit_step_bwd_ws_bytes(C, depth)) if bwd else [None] * n
+        _hip.call("cf_vit_step_prepare_batch", n, A(Wm), A(t), A(logs), A(flat), _hip.p(_hip.f32(vit.pos_embedding)), A(ws),
+                  A(wi) if winv else None, A(wb) if bwd else None, C, depth, fid, _hip.stream())
+        return [_tape.VitTables(form, *bufs) for bufs in zip(ws, wi, wb)]
 
-    def step_forward(self, x, ws, ld1, h_out=None, variant="wave", xtape=None):
-        """z = TransCoupling(ActNorm(Conv1x1(x))) and ld1 += the step's log-det, one launch.  xtape (training, wave form):
-        receives the residual stream at the layer boundaries (cf_vit_step_fwd_taped) for cf_vit_step_bwd_taped."""
+    def step_forward(self, x, tables, ld1, h_out=None, xtape=None):
+        """z = TransCoupling(ActNorm(Conv1x1(x))) and ld1 += the step's log-det, one launch of the form `tables` are packed for.
+        xtape (training): receives the residual stream at the layer boundaries for cf_vit_step_bwd."""
         x, xbs = _hip.bview(x)
         B, C = x.shape[0], x.shape[1]
         depth = len(self.NN[0].transformer.layers)
         z = torch.empty(B, C, x.shape[2], x.shape[3], device=x.device, dtype=torch.float32)
-        if xtape is not None:
-            assert h_out is None
-            _hip.call("cf_vit_step_rs_fwd_taped" if variant == "rs" else "cf_vit_step_fwd_taped", _hip.p(x), _hip.p(z), _hip.p(ld1), _hip.p(ws), _hip.p(xtape), B, C, depth, xbs,
-                      _hip.stream())
-            return z
-        events = VIT_EVENTS
+        events = VIT_EVENTS if xtape is None else None
         if events is not None:               # bench.py: HIP events on the launch stream around exactly this kernel
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(torch.cuda.current_stream(x.device))
-        _hip.call("cf_vit_step_rs_fwd" if variant == "rs" else "cf_vit_step_fwd", _hip.p(x), _hip.p(z), _hip.p(ld1), _hip.p(ws),
-                  _hip.p(h_out), B, C, depth, xbs, _hip.stream())
+        _hip.call("cf_vit_step_fwd", _hip.p(x), _hip.p(z), _hip.p(ld1), _hip.p(tables.ws), _hip.p(h_out), _hip.p(xtape), B, C, depth,
+                  xbs, self.STEP_FORMS[tables.form], _hip.stream())
         if events is not None:
             e1.record(torch.cuda.current_stream(x.device))
             events.append((e0, e1, B))
@@ -378,7 +358,10 @@ class TransCoupling(_AffineCoupling):
             parts += [attn.norm.weight, attn.norm.bias, attn.to_qkv.weight, attn.to_out.weight,
                       ff.net[0].weight, ff.net[0].bias, ff.net[1].weight, ff.net[1].bias, ff.net[3].weight, ff.net[3].bias]
         parts += [vit.transformer.norm.weight, vit.transformer.norm.bias]
-        return torch.cat([t.detach().reshape(-1).float() for t in parts])
+        flat = torch.cat([t.detach().reshape(-1).float() for t in parts])
+        # the layout every pack kernel walks (VitFlat, csrc/cf_vit_common.h)
+        assert flat.numel() == _hip.lib().cf_vit_flat_params(tpe[1].weight.numel(), vit.dim, len(vit.transformer.layers))
+        return flat
 
     def _fused(self, x, inverse, inverse_ldj=False):
         vit = self.NN[0]
@@ -388,7 +371,6 @@ class TransCoupling(_AffineCoupling):
         pd, dim, depth = (C // 2) * p1 * p2, vit.dim, len(vit.transformer.layers)
         L = _hip.lib()
         flat = self._flat_params()
-        assert flat.numel() == L.cf_vit_flat_params(pd, dim, depth)
         st = _hip.stream()
         # the packed table follows the flat parameter tensor (rebuilt when a version counter moves): packed once per parameter version,
         # not once per call (`sample` walks eight such layers per call).  The entry holds `flat`, so its id stays taken.

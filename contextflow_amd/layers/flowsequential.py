@@ -476,12 +476,13 @@ class FlowSequential(nn.Module):
                 for (k, op, ver), buf in zip(items, bufs):
                     done[k] = buf
                     done_ev[k] = gev
-            # transformer steps at small batches: the row-split tables of all steps in one launch triple (training: with
-            # Wm^-1 and the backward kernel's tables) - cf_vit_step_rs_prepare_batch
+            # transformer steps (TransCoupling.step_tables) at small batches: the row-split tables of all steps in one launch
+            # triple (training: with Wm^-1 and the backward kernel's tables); at saturating batches: a step at a time, below
+            vitem = lambda op: (op[3], op[1].NN, op[2].NN_t, op[2].NN_logs)
             vitems = [(k, op, ver) for k, op, ver in todo if op[0] == "vstep" and vkey[k] == "rs"]
             if vitems:
-                bufs = TransCoupling.step_prepare_rs_batch([(it[1][3], it[1][1].NN, it[1][2].NN_t, it[1][2].NN_logs) for it in vitems], dev,
-                                                           train=tape is not None)
+                train = tape is not None
+                bufs = TransCoupling.step_tables([vitem(it[1]) for it in vitems], dev, "rs", winv=train, bwd=train)
                 gev = torch.cuda.Event()
                 gev.record(side)
                 for (k, op, ver), buf in zip(vitems, bufs):
@@ -492,7 +493,7 @@ class FlowSequential(nn.Module):
                     buf, ev = done[k], done_ev[k]
                 else:
                     if op[0] == "vstep":
-                        buf = op[3].step_prepare(op[1].NN, op[2].NN_t, op[2].NN_logs, dev, vkey[k])
+                        buf = TransCoupling.step_tables([vitem(op)], dev, vkey[k])[0]
                     else:
                         buf = op[1].dist.prepared()
                     ev = torch.cuda.Event()
@@ -659,41 +660,37 @@ class FlowSequential(nn.Module):
                     events.append((e0, e1, B, C, H * W))
                 x = z
             elif kind == "vstep":
-                ws, ev = prepared[k]
-                variant = op[3].step_variant(B)
-                winv_v = wsb_v = None
-                if isinstance(ws, tuple):    # training, row-split form: (tables, Wm^-1, backward tables) from the batched prepare
-                    ws, winv_v, wsb_v = ws
+                tables, ev = prepared[k]
                 if tape is not None:         # training: the same one-kernel forward; the backward re-runs the step from its input
-                    #                          (and reuses the packed forward table when it is the row-split one)
+                    #                          (and reuses the packed tables when they are the row-split ones)
                     # the residual stream at the layer boundaries goes to a tape (5.8 KB per sample and step) and the backward
                     # kernel does not run the six layers a second time
                     xt = None
                     if VSTEP_TAPE:
                         depth = len(op[3].NN[0].transformer.layers)
                         xt = torch.empty(_hip.lib().cf_vit_step_tape_floats(B, x.shape[1], depth), device=dev, dtype=torch.float32)
-                    tape.append(_tape.VStep(op[1], op[2], op[3], x, ws if variant == "rs" else None, xt, winv_v, wsb_v))
+                    tape.append(_tape.VStep(op[1], op[2], op[3], x, tables, xt))
                     if ev is not None:
                         main.wait_event(ev)
-                    x = op[3].step_forward(x, ws, ld1, variant=variant, xtape=xt)
+                    x = op[3].step_forward(x, tables, ld1, xtape=xt)
                     continue
                 if ev is not None:
                     main.wait_event(ev)
-                if self.CHAIN_STEPS and variant == "rs" and _cpl.VIT_EVENTS is None:
+                if self.CHAIN_STEPS and tables.form == "rs" and _cpl.VIT_EVENTS is None:
                     # small batch (row-split form): this step and the transformer steps that follow it in ONE launch
                     depth = len(op[3].NN[0].transformer.layers)
-                    run, tabs = chain_run(k, ws, int(_hip.lib().cf_vit_step_rs_chain_max_steps()),
+                    run, tabs = chain_run(k, tables, int(_hip.lib().cf_vit_step_chain_max_steps()),
                                           lambda nxt: (nxt[0] == "vstep" and nxt[3].step_variant(B) == "rs"
                                                        and len(nxt[3].NN[0].transformer.layers) == depth))
                     if len(run) > 1:
                         xv, xbs = _hip.bview(x)
                         z = torch.empty(B, xv.shape[1], xv.shape[2], xv.shape[3], device=dev, dtype=torch.float32)
-                        _hip.call("cf_vit_step_rs_fwd_chain", _hip.p(xv), _hip.p(z), _hip.p(ld1), _hip.ptr_array(tabs), len(run), B, xv.shape[1],
-                                  depth, xbs, st)
+                        _hip.call("cf_vit_step_fwd_chain", _hip.p(xv), _hip.p(z), _hip.p(ld1), _hip.ptr_array([tb.ws for tb in tabs]), len(run), B,
+                                  xv.shape[1], depth, xbs, st)
                         chained.update(run[1:])
                         x = z
                         continue
-                x = op[3].step_forward(x, ws, ld1, variant=variant)
+                x = op[3].step_forward(x, tables, ld1)
             elif kind == "squeeze":
                 if tape is not None:
                     tape.append(_tape.Squeeze(tuple(op[1].p)))

@@ -31,8 +31,11 @@ extern "C" {
  * Version 14: cf_gmm_quad (no caller; cf_gmm_resp feeds the backward) left the ABI.
  * Version 15: the switch entry of the 16x16 level's forms on the 16-bit matrix cores left the ABI with those kernels;
  * cf_flow_step_ws_bytes shrank by their tables.  It also covers cf_flow_step_fwd_level / cf_flow_step_level_min_batch, which only ADD
- * symbols. */
-#define CF_ABI_VERSION 15
+ * symbols.
+ * Version 16: the transformer flow step has ONE entry-point family with a `form` argument (cf_vit_step_supported / _ws_bytes /
+ * _prepare_batch / _fwd / _fwd_chain / _chain_max_steps, cf_vit_step_bwd with an optional tape); the per-form and `_taped` twins
+ * and the single-step prepares left the ABI. */
+#define CF_ABI_VERSION 16
 #define CF_ERR_ARG (-1)          /* bad argument (shape, null pointer, unsupported size) */
 #define CF_ERR_UNSUPPORTED (-2)  /* shape not covered by this kernel; caller uses the generic path */
 
@@ -470,44 +473,47 @@ int cf_vit_prepare(const float* flat_params, void* ws, int patch_dim, int dim, i
 int cf_vit_coupling(const float* x, float* z, float* ldj, const void* ws, const float* pos, int B, int C, int H, int W,
                     int p1, int p2, int dim, int depth, int64_t x_bstride, int inverse, cf_stream_t stream);
 
-/* One transformer-coupling flow step (model.py:129-147 with --coupling trans: Conv1x1 -> ActNorm -> TransCoupling) as ONE
- * kernel, activations register-resident between x and z (csrc/cf_vit_step.hip).  Geometry: C = 26 channels on 8 x 1
- * windows, patch (2,1), dim = 2C, one head of 64 (SMAP; cf_vit_step_supported).  prepare: Wm (C,C), ActNorm t / logs (C),
- * the ViT parameters flattened in the order of cf_vit_prepare, pos (4, dim); ws: cf_vit_step_ws_bytes(C, depth) bytes.
- * fwd: z (B,C,8,1); ldj_acc[b] += 8 log|det Wm| + sum logs + sum log_s (conv1x1.py:53, actnorm.py:58, coupling.py:151);
- * h_out (optional, may be NULL): the conditioner's output [t | raw], (B,C,8,1).                                         */
-int cf_vit_step_supported(int C, int H, int W, int p1, int p2, int dim, int dim_head, int heads);
-int64_t cf_vit_step_ws_bytes(int C, int depth);
-int cf_vit_step_prepare(const float* Wm, const float* t, const float* logs, const float* flat_vit_params, const float* pos,
-                        void* ws, int C, int depth, cf_stream_t stream);
-int cf_vit_step_fwd(const float* x, float* z, float* ldj_acc, const void* ws, float* h_out, int B, int C, int depth,
-                    int64_t x_bstride, cf_stream_t stream);
-/* Multiply-adds PER SAMPLE of one cf_vit_step_fwd launch: what = 0 the reference's count (Conv1x1 + every Linear of the
- * SimpleViT + q.k^T / p.v, SURVEY.md 8d: 472 384 for C = 26, depth 6); 1 = what the matrix pipe executes, padding rows of
- * its 32-row tiles included (1 326 v_mfma_f32_32x32x2_f32 per wave of 8 samples); 2 = the useful part of that (the fused
- * 52 x 52 products of the round-4 kernel: q.k through Wq^T Wk, value / output through Wout Wv).  Host-only, no stream. */
+/* ---- One transformer-coupling flow step (model.py:129-147 with --coupling trans: Conv1x1 -> ActNorm -> TransCoupling) as ONE
+ * kernel.  Geometry: C = 26 channels on 8 x 1 windows, patch (2,1), dim = 2C, one head of 64, 1 <= depth <= 6 (SMAP;
+ * cf_vit_step_supported).  Two forms of the forward kernel, each with its own table layout (cf_vit_step_ws_bytes(C, depth, form)):
+ *   CF_VIT_FORM_WAVE  a sample's whole step inside one wave, activations register-resident between x and z, 8 samples per wave
+ *                     (csrc/cf_vit_step.hip): saturating batches;
+ *   CF_VIT_FORM_RS    row-split: the four waves of a workgroup share 16 token columns (4 samples) and split the output rows of
+ *                     every Linear, planes through LDS (csrc/cf_vit_rs.hip) - an eighth of the serial chain per workgroup at 8x
+ *                     the workgroups: small batches (the reference's operating point is 256 samples, config.py:10).
+ * prepare_batch: the tables of n flow steps - HOST arrays of n device pointers: Wm (C,C), ActNorm t / logs (C), the ViT
+ *   parameters flattened in the order of cf_vit_prepare, ws; pos (4, dim) is shared.  Row-split form: one factorisation, one fuse
+ *   and one packing launch per 16 steps; winv: NULL or n (C,C) outputs for Wm^-1; wsb: NULL or n backward workspaces
+ *   (cf_vit_step_bwd_ws_bytes) that also receive the backward kernel's tables (cf_vit_step_bwd_prepare_batch).  Wave form: the
+ *   three launches per step; winv and wsb must be NULL.
+ * fwd: z (B,C,8,1); ldj_acc[b] += 8 log|det Wm| + sum logs + sum log_s (conv1x1.py:53, actnorm.py:58, coupling.py:151).
+ *   h_out (NULL or (B,C,8,1)): the conditioner's output [t | raw].  xtape (NULL or cf_vit_step_tape_floats(B, C, depth) floats;
+ *   h_out must then be NULL): the training forward - the residual stream of the conditioner at its depth + 1 layer boundaries,
+ *   feature-major [boundary][2C][T] (slot 0, the embedding output, is left unwritten: the backward rebuilds it),
+ *   T = cf_vit_step_tape_tokens(B) = 4 x (B rounded up to 32), token = 4 sample + n (5.8 KB per sample at C = 26, depth 6); the
+ *   same tape from either form.
+ * fwd_chain: n <= cf_vit_step_chain_max_steps() CONSECUTIVE steps in one launch of the row-split form (evaluation at small
+ *   batches; ws: host array of n row-split tables; a workgroup owns its samples end to end, steps 2.. run in place on z, which
+ *   may not alias x).  Bitwise equal to n cf_vit_step_fwd calls.
+ * macs: multiply-adds PER SAMPLE of one wave-form launch: what = 0 the reference's count (Conv1x1 + every Linear of the
+ *   SimpleViT + q.k^T / p.v, SURVEY.md 8d: 472 384 for C = 26, depth 6); 1 = what the matrix pipe executes, padding rows of
+ *   its 32-row tiles included (1 326 v_mfma_f32_32x32x2_f32 per wave of 8 samples); 2 = the useful part of that (the fused
+ *   52 x 52 products: q.k through Wq^T Wk, value / output through Wout Wv).  Host-only, no stream.                          */
+#define CF_VIT_FORM_WAVE 0
+#define CF_VIT_FORM_RS 1
+int cf_vit_step_supported(int C, int H, int W, int p1, int p2, int dim, int dim_head, int heads, int depth);
+int64_t cf_vit_step_ws_bytes(int C, int depth, int form);
+int cf_vit_step_prepare_batch(int n, const float* const* Wm, const float* const* t, const float* const* logs,
+                              const float* const* flat_vit_params, const float* pos, void* const* ws, float* const* winv,
+                              void* const* wsb, int C, int depth, int form, cf_stream_t stream);
+int cf_vit_step_fwd(const float* x, float* z, float* ldj_acc, const void* ws, float* h_out, float* xtape, int B, int C, int depth,
+                    int64_t x_bstride, int form, cf_stream_t stream);
+int cf_vit_step_chain_max_steps(void);
+int cf_vit_step_fwd_chain(const float* x, float* z, float* ldj_acc, const void* const* ws, int n, int B, int C, int depth,
+                          int64_t x_bstride, cf_stream_t stream);
+int64_t cf_vit_step_tape_tokens(int B);
+int64_t cf_vit_step_tape_floats(int B, int C, int depth);
 int64_t cf_vit_step_macs(int C, int depth, int what);
-
-
-/* The same step for SMALL batches (the reference's operating point is 256 samples, config.py:10), row-split: the four waves
- * of a workgroup share 16 token columns (4 samples) and split the output rows of every Linear (v_mfma_f32_16x16x4_f32,
- * planes through LDS; csrc/cf_vit_rs.hip) - an eighth of the serial chain of cf_vit_step_fwd per workgroup, at 8x the
- * workgroups.  Its own workspace layout (LayerNorm weights folded into the packed Linears); same arguments and results. */
-int cf_vit_step_rs_supported(int C, int H, int W, int p1, int p2, int dim, int dim_head, int heads);
-int64_t cf_vit_step_rs_ws_bytes(int C, int depth);
-int cf_vit_step_rs_prepare(const float* Wm, const float* t, const float* logs, const float* flat_vit_params, const float* pos,
-                           void* ws, int C, int depth, cf_stream_t stream);
-/* The row-split tables of n flow steps in one factorisation, one fuse and one packing launch (HOST arrays of n device
- * pointers; pos is shared).  winv: NULL or n (C, C) outputs for Wm^-1; wsb: NULL or n backward workspaces
- * (cf_vit_step_bwd_ws_bytes) that also receive the backward kernel's tables (cf_vit_step_bwd_prepare_batch).            */
-int cf_vit_step_rs_prepare_batch(int n, const float* const* Wm, const float* const* t, const float* const* logs,
-                                 const float* const* flat_vit_params, const float* pos, void* const* ws, float* const* winv,
-                                 void* const* wsb, int C, int depth, cf_stream_t stream);
-int cf_vit_step_bwd_prepare_batch(int n, const float* const* Wm, const float* const* logs, const float* const* flat_vit_params,
-                                  void* const* wsb, int C, int depth, cf_stream_t stream);
-
-int cf_vit_step_rs_fwd(const float* x, float* z, float* ldj_acc, const void* ws, float* h_out, int B, int C, int depth,
-                       int64_t x_bstride, cf_stream_t stream);
 
 /* Backward of that step as ONE kernel (training step of the anomaly-detection flows, experiment_ad.py:204-213;
  * csrc/cf_vit_rs_bwd.hip): from the step INPUT x, dL/dz (gz, dense (B,C,8,1)) and dL/d(log-det) (gld (B,)) it re-runs the
@@ -521,36 +527,17 @@ int cf_vit_step_rs_fwd(const float* x, float* z, float* ldj_acc, const void* ws,
  *   ln_partials: ceil(B/4) rows of cf_vit_step_bwd_ln_floats / ceil(B/4) floats: per-workgroup sums of the LayerNorm
  *           weight / bias gradients: [LN(pd): g 32 | b 32][LN(dim) of the embedding: g 64 | b 64][per layer: attention norm
  *           g 64 | b 64 | feed-forward norm g 64 | b 64][transformer.norm: g 64 | b 64]; the column sums are the gradients.
- * ws: cf_vit_step_rs_prepare; wsb: cf_vit_step_bwd_prepare (cf_vit_step_bwd_ws_bytes).  depth <= 6.                    */
+ * ws: the ROW-SPLIT tables of the step; wsb: cf_vit_step_bwd_ws_bytes bytes, packed by cf_vit_step_prepare_batch (wsb) or
+ * cf_vit_step_bwd_prepare_batch alone.  xtape (NULL or the tape a cf_vit_step_fwd with xtape wrote, either form): the kernel starts
+ * from it - the Conv1x1 / ActNorm / patch embedding are re-run (their statistics are needed on the way back), the transformer
+ * layers are not, a quarter of the kernel's work.  Same outputs to fp32 rounding.                                            */
 int64_t cf_vit_step_bwd_ws_bytes(int C, int depth);
 int64_t cf_vit_step_bwd_plane_floats(int B, int C, int depth);
 int64_t cf_vit_step_bwd_ln_floats(int B, int C, int depth);
-int cf_vit_step_bwd_prepare(const float* Wm, const float* logs, const float* flat_vit_params, void* wsb, int C, int depth,
-                            cf_stream_t stream);
+int cf_vit_step_bwd_prepare_batch(int n, const float* const* Wm, const float* const* logs, const float* const* flat_vit_params,
+                                  void* const* wsb, int C, int depth, cf_stream_t stream);
 int cf_vit_step_bwd(const float* x, const float* gz, const float* gld, float* gx, const void* ws, const void* wsb, float* planes,
-                    float* ln_partials, int B, int C, int depth, int64_t x_bstride, cf_stream_t stream);
-
-/* Taped pair for saturating batches (the register-resident forward): cf_vit_step_fwd_taped = cf_vit_step_fwd that also writes
- * the residual stream of the conditioner at its depth + 1 layer boundaries to xtape - cf_vit_step_tape_floats(B, C, depth)
- * floats, feature-major [boundary][2C][T] (slot 0, the embedding output, is left unwritten: the backward rebuilds it), T = cf_vit_step_tape_tokens(B) = 4 x (B rounded up to 32), token = 4 sample + n
- * (5.8 KB per sample at C = 26, depth 6).  cf_vit_step_bwd_taped = cf_vit_step_bwd that starts from that tape: the Conv1x1 /
- * ActNorm / patch embedding are re-run (their statistics are needed on the way back), the transformer layers are not - a
- * quarter of the kernel's work.  Same outputs to fp32 rounding.                                                          */
-int64_t cf_vit_step_tape_tokens(int B);
-int64_t cf_vit_step_tape_floats(int B, int C, int depth);
-int cf_vit_step_fwd_taped(const float* x, float* z, float* ldj_acc, const void* ws, float* xtape, int B, int C, int depth,
-                          int64_t x_bstride, cf_stream_t stream);
-int cf_vit_step_rs_fwd_taped(const float* x, float* z, float* ldj_acc, const void* ws, float* xtape, int B, int C, int depth,
-                             int64_t x_bstride, cf_stream_t stream);
-/* n <= cf_vit_step_rs_chain_max_steps() CONSECUTIVE transformer flow steps in one launch (evaluation at small batches; ws: host
- * array of n packed tables; a workgroup owns its samples end to end, steps 2.. run in place on z).  Bitwise equal to n
- * cf_vit_step_rs_fwd calls.                                                                                                  */
-int cf_vit_step_rs_chain_max_steps(void);
-int cf_vit_step_rs_fwd_chain(const float* x, float* z, float* ldj_acc, const void* const* ws, int n, int B, int C, int depth,
-                             int64_t x_bstride, cf_stream_t stream);       /* the row-split (small-batch) forward, same tape */
-int cf_vit_step_bwd_taped(const float* x, const float* gz, const float* gld, float* gx, const void* ws, const void* wsb,
-                          float* planes, float* ln_partials, const float* xtape, int B, int C, int depth, int64_t x_bstride,
-                          cf_stream_t stream);
+                    float* ln_partials, const float* xtape, int B, int C, int depth, int64_t x_bstride, cf_stream_t stream);
 
 /* ---- SplineActivation: monotone rational-quadratic spline, linear tails (layers/activations.py:120-211,
  * layers/splines/rational_quadratic.py:21-176) ----------------------------------------------------- */

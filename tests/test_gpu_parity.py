@@ -631,8 +631,8 @@ def test_transcoupling(L, tag, fused):
 @pytest.mark.parametrize("variant", ["wave", "rs"])
 @pytest.mark.parametrize("B", [3, 37])
 def test_vit_step_kernel(L, B, variant):
-    """Conv1x1 -> ActNorm -> TransCoupling as ONE kernel (SMAP geometry), in both forms - cf_vit_step_fwd (register-resident,
-    8 samples per wave) and cf_vit_step_rs_fwd (row-split over the four waves of a workgroup, 4 samples per workgroup): with an
+    """Conv1x1 -> ActNorm -> TransCoupling as ONE kernel (SMAP geometry), in both forms of cf_vit_step_fwd - 'wave' (register-resident,
+    8 samples per wave) and 'rs' (row-split over the four waves of a workgroup, 4 samples per workgroup): with an
     identity Conv1x1 / ActNorm it must reproduce the reference's TransCoupling vectors (conditioner output h, z, log-det);
     with random ones, the composition of the three oracle layers at a ragged batch (last wave partly filled)."""
     from contextflow_amd.layers import _hip
@@ -645,10 +645,10 @@ def test_vit_step_kernel(L, B, variant):
     assert m.step_supported(sz)
     # identity front: the layer alone against the reference's own output
     x = t["x"].to(DEV)
-    ws = m.step_prepare(torch.eye(C, device=DEV), torch.zeros(C, device=DEV), torch.zeros(C, device=DEV), torch.device(DEV), variant)
+    tables = m.step_tables([(m, torch.eye(C, device=DEV), torch.zeros(C, device=DEV), torch.zeros(C, device=DEV))], torch.device(DEV), variant)[0]
     ld = torch.zeros(x.shape[0], device=DEV)
     h = torch.full_like(x, float("nan"))
-    z = m.step_forward(x, ws, ld, h_out=h, variant=variant)
+    z = m.step_forward(x, tables, ld, h_out=h)
     close(h, t["h"], tol=2e-5); close(z, t["z"], tol=2e-5); close(ld, t["ldj"], tol=2e-5)
     # random Conv1x1 / ActNorm in front, ragged batch, accumulation into a non-zero running log-det
     g = torch.Generator().manual_seed(B)
@@ -659,11 +659,47 @@ def test_vit_step_kernel(L, B, variant):
     y, l0 = fo.conv1x1_fwd(xx, Wm)
     y, l1 = fo.actnorm_fwd(y, tt, logs)
     zref, l2 = fo.transcoupling_fwd(y, p, "0.", sz, patch)
-    ws = m.step_prepare(Wm.to(DEV), tt.to(DEV), logs.to(DEV), torch.device(DEV), variant)
+    tables = m.step_tables([(m, Wm.to(DEV), tt.to(DEV), logs.to(DEV))], torch.device(DEV), variant)[0]
     ld = torch.full((B,), 1.5, device=DEV)
-    z = m.step_forward(xx.to(DEV), ws, ld, variant=variant)
+    z = m.step_forward(xx.to(DEV), tables, ld)
     close(z, zref, tol=2e-5)
     close(ld, 1.5 + l0 + l1 + l2, tol=2e-5)
+
+
+@pytest.mark.parametrize("form", ["wave", "rs"])
+def test_vit_step_tables_batched_equal_single(L, form):
+    """TransCoupling.step_tables on 17 SMAP-geometry steps at once packs, bit for bit, what 17 calls with one step each pack:
+    17 is the smallest count that crosses the 16-step chunk of the batched pack kernels (the `+ i0` offsets of the Wm^-1 and
+    backward-table arrays can go wrong only there).  Row-split form: with Wm^-1 and the backward kernel's tables."""
+    t, sd = unit("trans_ts")
+    sz = tuple(int(v) for v in t["in_sz"]); patch = tuple(int(v) for v in t["p"])
+    C, dev = sz[0], torch.device(DEV)
+    items = []
+    for i in range(17):
+        g = torch.Generator().manual_seed(100 + i)
+        m = L.TransCoupling(sz, patch)
+        m.load_state_dict({k: v + 0.05 * torch.randn(v.shape, generator=g) if v.is_floating_point() else v for k, v in sd.items()})
+        Wm = torch.linalg.qr(torch.randn(C, C, generator=g))[0] + 0.1 * torch.randn(C, C, generator=g)
+        items.append((m.to(DEV), Wm.to(DEV), (0.3 * torch.randn(C, generator=g)).to(DEV), (0.4 * torch.randn(C, generator=g)).to(DEV)))
+    train = form == "rs"
+    batched = L.TransCoupling.step_tables(items, dev, form, winv=train, bwd=train)
+    single = [L.TransCoupling.step_tables([it], dev, form, winv=train, bwd=train)[0] for it in items]
+    torch.cuda.synchronize()
+
+    def bits(ws):            # floats 2 and 3 of a forward table's header are padding: no kernel writes or reads them
+        v = ws.view(torch.int32).clone()
+        v[2:4] = 0
+        return v
+    assert len(batched) == len(single) == 17
+    for i, (a, b) in enumerate(zip(batched, single)):
+        assert a.form == b.form == form
+        assert torch.equal(bits(a.ws), bits(b.ws)), i
+        if train:
+            assert torch.equal(a.winv.view(torch.int32), b.winv.view(torch.int32)), i
+            assert torch.equal(a.wsb.view(torch.int32), b.wsb.view(torch.int32)), i
+        else:
+            assert a.winv is None and a.wsb is None
+    assert not torch.equal(bits(batched[0].ws), bits(batched[16].ws))          # (different parameters per step)
 
 
 # ------------------------------------------------------------------------------------------ fused step kernel
@@ -727,7 +763,7 @@ def test_e2e_golden(L, name, fused):
 
 @pytest.fixture
 def smap_step_form(request):
-    """Forces one of the two one-kernel forms of the transformer step ('rs': cf_vit_step_rs_fwd, 'wave': cf_vit_step_fwd)
+    """Forces one of the two forms of the one-kernel transformer step (cf_vit_step_fwd: 'rs' | 'wave')
     whatever the batch size; None = the production dispatch (TransCoupling.step_variant)."""
     from contextflow_amd.layers.coupling import TransCoupling
     form = getattr(request, "param", None)
@@ -1258,8 +1294,8 @@ def test_smap_backward_is_additive_over_the_batch(L):
 
 @pytest.mark.parametrize("B", [3, 37, 70])
 def test_smap_taped_backward_equals_the_recompute_form(L, B):
-    """Transformer steps at saturating batches keep the residual stream of the forward (cf_vit_step_fwd_taped) and the backward
-    kernel starts from it (cf_vit_step_bwd_taped) instead of running the layers again: forced at small, ragged batches
+    """Transformer steps at saturating batches keep the residual stream of the forward (cf_vit_step_fwd with xtape) and the backward
+    kernel starts from it (cf_vit_step_bwd with xtape) instead of running the layers again: forced at small, ragged batches
     (the 8-samples-per-wave forward), its gradients equal those of the recompute form to fp32 rounding - the forward's
     residual stream and the row-split kernel's differ by summation order only - and the log-densities are the same bits."""
     import contextflow_amd.layers.flowsequential as fs
@@ -1938,7 +1974,7 @@ def test_captured_training_step_with_fused_adamw_equals_the_eager_loop(L):
 
 
 def test_chained_transformer_steps_equal_single_launches(L, monkeypatch):
-    """Evaluation of the SMAP flow at small batches: its eight transformer flow steps in ONE launch (cf_vit_step_rs_fwd_chain:
+    """Evaluation of the SMAP flow at small batches: its eight transformer flow steps in ONE launch (cf_vit_step_fwd_chain:
     a workgroup owns its four samples end to end, steps 2.. in place on z) - z and logp of the per-step launches bit for bit,
     at a ragged batch as well."""
     import contextflow_amd as cfa

@@ -33,7 +33,7 @@ def test_library_exports_every_declared_symbol(built):
     for s in syms:
         assert hasattr(lib, s), "header declares %s but the library does not export it" % s
     assert sorted(_hip.SIGNATURES) == syms, set(_hip.SIGNATURES) ^ set(syms)
-    assert _hip.lib().cf_abi_version() == _hip.ABI_VERSION == 15
+    assert _hip.lib().cf_abi_version() == _hip.ABI_VERSION == 16
     # pure host-side queries work without a GPU
     assert _hip.lib().cf_flow_step_supported(64, 4, 4, 3, 3) == 1
     assert _hip.lib().cf_flow_step_supported(26, 8, 1, 3, 1) == 0
@@ -63,7 +63,8 @@ def test_host_side_size_queries_of_round_3(built):
     assert L.cf_vit_step_bwd_plane_floats(B, C, depth) == 2 * 8 * Bp * 26 + 4 * Bp * (26 + 52) + depth * 4 * Bp * 568
     assert L.cf_vit_step_bwd_ln_floats(B, C, depth) == 3 * (64 + 128 + depth * 256 + 128)
     assert L.cf_vit_step_bwd_ws_bytes(C, depth) > 4 * depth * (192 * 52 + 52 * 64 + 2 * 52 * 52)
-    assert L.cf_vit_step_rs_supported(26, 8, 1, 2, 1, 52, 64, 1) == 1 and L.cf_vit_step_rs_supported(38, 144, 1, 2, 1, 76, 64, 1) == 0
+    assert L.cf_vit_step_supported(26, 8, 1, 2, 1, 52, 64, 1, 6) == 1 and L.cf_vit_step_supported(38, 144, 1, 2, 1, 76, 64, 1, 6) == 0
+    assert L.cf_vit_step_supported(26, 8, 1, 2, 1, 52, 64, 1, 1) == 1 and L.cf_vit_step_supported(26, 8, 1, 2, 1, 52, 64, 1, 7) == 0
     arr = lambda v: (ctypes.c_int * len(v))(*v)
     # grouped weight gradients: partials [N][K] | [N] per row range; about 4096 waves per group, >= 64 rows per range
     one = L.cf_linear_wgrad_group_ws_bytes(arr([4096]), arr([52]), arr([192]), 1)
@@ -71,6 +72,36 @@ def test_host_side_size_queries_of_round_3(built):
     many = L.cf_linear_wgrad_group_ws_bytes(arr([131072] * 26), arr([52] * 26), arr([192] * 26), 26)
     assert many == 26 * 79 * (192 * 52 + 192) * 4                          # 52 tile groups -> 79 ranges (of 1664 rows) per member
     assert L.cf_linear_wgrad_group_ws_bytes(arr([1]), arr([1]), arr([1]), 0) == -1
+
+
+def test_vit_step_family_sizes_and_symbols(built):
+    """The transformer flow step has one entry-point family with a `form` argument (ABI 16).  Its host-only queries give what
+    the per-form functions of ABI 15 gave (literals read from that library), the flat parameter count is the one
+    TransCoupling._flat_params_build produces, and the per-form / `_taped` / single-step names are gone from the header and
+    from the ctypes table."""
+    import contextflow_amd.layers as CL
+    from contextflow_amd.layers import _hip
+    from tests.helpers import unit
+    L = _hip.lib()
+    WAVE, RS = CL.TransCoupling.STEP_FORMS["wave"], CL.TransCoupling.STEP_FORMS["rs"]
+    assert (WAVE, RS) == (0, 1)
+    assert L.cf_vit_step_ws_bytes(26, 6, WAVE) == 507344           # cf_vit_step_ws_bytes(26, 6) of ABI 15
+    assert L.cf_vit_step_ws_bytes(26, 6, RS) == 944208             # cf_vit_step_rs_ws_bytes(26, 6)
+    assert L.cf_vit_step_ws_bytes(26, 6, 2) == 0 and L.cf_vit_step_ws_bytes(24, 6, RS) == 0
+    assert L.cf_vit_step_bwd_ws_bytes(26, 6) == 608512
+    assert L.cf_vit_step_tape_floats(37, 26, 6) == 93184 == 7 * 52 * L.cf_vit_step_tape_tokens(37)
+    assert L.cf_vit_step_chain_max_steps() == 8                    # cf_vit_step_rs_chain_max_steps()
+    t, sd = unit("trans_ts")
+    m = CL.TransCoupling(tuple(int(v) for v in t["in_sz"]), tuple(int(v) for v in t["p"]))
+    m.load_state_dict(sd)
+    assert m._flat_params_build().numel() == L.cf_vit_flat_params(26, 52, 6) == 115856
+    gone = ["cf_vit_step_prepare", "cf_vit_step_fwd_taped", "cf_vit_step_bwd_prepare", "cf_vit_step_bwd_taped", "cf_vit_step_rs_supported",
+            "cf_vit_step_rs_ws_bytes", "cf_vit_step_rs_prepare", "cf_vit_step_rs_prepare_batch", "cf_vit_step_rs_fwd",
+            "cf_vit_step_rs_fwd_taped", "cf_vit_step_rs_fwd_chain", "cf_vit_step_rs_chain_max_steps"]
+    syms = header_symbols()
+    for name in gone:
+        assert name not in syms and name not in _hip.SIGNATURES, name
+    assert sum(s.startswith("cf_vit_step") for s in syms) == 14
 
 
 # ---- the step dispatch as the flop accounting sees it -----------------------------------------------------------------

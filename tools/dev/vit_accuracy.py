@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Which of the transformer-step forms is closest to the fp64 oracle?  N random SMAP samples through the fixture's model
-(random init, and the "stress" parameter set): one-kernel step 'wave' (cf_vit_step_fwd), 'rs' (cf_vit_step_rs_fwd), layer
+(random init, and the "stress" parameter set): one-kernel step (cf_vit_step_fwd) in its forms 'wave' and 'rs', layer
 mode (cf_vit_coupling), and the fp32 oracle (= the reference's arithmetic) - each against the fp64 oracle on ALL samples:
 max and rms |d bits/dim|.  usage: vit_accuracy.py [N=4096]"""
 import math, os, sys

@@ -17,13 +17,13 @@ model(torch.rand(256, *ds, device=dev))
 conv, act, cpl = model.sequence_modules[1:4]
 x = torch.randn(B, 26, 8, 1, device=dev)
 ld = torch.zeros(B, device=dev)
-ws = cpl.step_prepare(conv.NN, act.NN_t, act.NN_logs, dev, "wave")
+tables = cpl.step_tables([(cpl, conv.NN, act.NN_t, act.NN_logs)], dev, "wave")[0]
 h = torch.zeros(B, 26, 8, 1, device=dev)
 for _ in range(5):
-    cpl.step_forward(x, ws, ld, variant="wave")
+    cpl.step_forward(x, tables, ld)
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record()
-cpl.step_forward(x, ws, ld, h_out=h, variant="wave")
+cpl.step_forward(x, tables, ld, h_out=h)
 e1.record()
 torch.cuda.synchronize()
 nw = B // 8

@@ -56,8 +56,8 @@ def rep(name, h, z, l):
 rep("fp32 oracle", h32, z32, l32)
 with torch.no_grad():
     for variant in ("wave", "rs"):
-        ws = cpl.step_prepare(conv.NN, act.NN_t, act.NN_logs, torch.device(DEV), variant)
+        tables = cpl.step_tables([(cpl, conv.NN, act.NN_t, act.NN_logs)], torch.device(DEV), variant)[0]
         ld = torch.zeros(B, device=DEV)
         h = torch.full((B, 26, 8, 1), float("nan"), device=DEV)
-        z = cpl.step_forward(xin.to(DEV), ws, ld, h_out=h, variant=variant)
+        z = cpl.step_forward(xin.to(DEV), tables, ld, h_out=h)
         rep(variant, h, z, ld)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel time of ONE transformer flow step (SMAP geometry) per batch size in its two one-kernel forms (rs: row-split
-workgroups of 4 samples, cf_vit_step_rs_fwd; wave: 8 samples per wave, cf_vit_step_fwd): where does the cross-over sit?
+workgroups of 4 samples; wave: 8 samples per wave - the two forms of cf_vit_step_fwd): where does the cross-over sit?
 20 back-to-back launches between HIP events.  usage: vit_variants.py [B ...]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -21,15 +21,15 @@ for B in Bs:
     ld = torch.zeros(B, device=dev)
     res = []
     for variant in ("rs", "wave"):
-        ws = cpl.step_prepare(conv.NN, act.NN_t, act.NN_logs, dev, variant)
+        tables = cpl.step_tables([(cpl, conv.NN, act.NN_t, act.NN_logs)], dev, variant)[0]
         for _ in range(3):
-            cpl.step_forward(x, ws, ld, variant=variant)
+            cpl.step_forward(x, tables, ld)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         n = 20
         e0.record()
         for _ in range(n):
-            cpl.step_forward(x, ws, ld, variant=variant)
+            cpl.step_forward(x, tables, ld)
         e1.record()
         torch.cuda.synchronize()
         us = e0.elapsed_time(e1) * 1e3 / n

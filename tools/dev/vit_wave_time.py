@@ -16,9 +16,9 @@ model(torch.rand(256, *ds, device=dev))
 conv, act, cpl = model.sequence_modules[1:4]
 x = torch.randn(B, 26, 8, 1, device=dev)
 ld = torch.zeros(B, device=dev)
-ws = cpl.step_prepare(conv.NN, act.NN_t, act.NN_logs, dev, "wave")
+tables = cpl.step_tables([(cpl, conv.NN, act.NN_t, act.NN_logs)], dev, "wave")[0]
 for _ in range(3):
-    cpl.step_forward(x, ws, ld, variant="wave")
+    cpl.step_forward(x, tables, ld)
 torch.cuda.synchronize()
 best = 1e9
 for rep in range(3):
@@ -26,7 +26,7 @@ for rep in range(3):
     n = 20
     e0.record()
     for _ in range(n):
-        cpl.step_forward(x, ws, ld, variant="wave")
+        cpl.step_forward(x, tables, ld)
     e1.record()
     torch.cuda.synchronize()
     best = min(best, e0.elapsed_time(e1) * 1e3 / n)
