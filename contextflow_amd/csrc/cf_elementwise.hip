@@ -505,6 +505,46 @@ int launch_preprocess_bwd(const float* y, const float* gy, const float* gld, flo
     return 0;
 }
 
+// Vector-Jacobian product of the CONTINUOUS tail of `inverse` (k_postprocess_inv in front of its floor): x = ((v - t2) s2 - t1) s1
+// with v = sigmoid(y), so  gy[b, i] = gx[b, i] s1 s2 v (1 - v)  for the n_keep kept elements of a row; the aug_n elements behind
+// them (the channels Augment.reverse drops) do not reach x: their gradient is an exact 0.  gx is dense (B, n_keep).
+template <int V>
+__global__ __launch_bounds__(256) void k_postprocess_inv_bwd(const float* __restrict__ y, const float* __restrict__ gx,
+                                                             float* __restrict__ gy, int64_t n_items, int keep_items, int row_items,
+                                                             int64_t ybs, int64_t gybs, float s12) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_items; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / row_items;
+        const int j = (int)(i - b * row_items);
+        float r[V];
+        if (j < keep_items) {
+            float g[V];
+            vload<V>(y + b * ybs + (int64_t)j * V, r);
+            vload<V>(gx + (b * keep_items + j) * V, g);
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                const float v = 1.0f / (1.0f + expf(-r[e]));
+                r[e] = g[e] * s12 * (v * (1.0f - v));
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < V; ++e) r[e] = 0.f;
+        }
+        vstore<V>(gy + b * gybs + (int64_t)j * V, r);
+    }
+}
+
+int launch_postprocess_inv_bwd(const float* y, const float* gx, float* gy, int B, int n_keep, int aug_n, int64_t ybs, int64_t gybs,
+                               float s12, hipStream_t s) {
+    const bool vec = n_keep % 4 == 0 && aug_n % 4 == 0 && ybs % 4 == 0 && gybs % 4 == 0 && aligned16(y) && aligned16(gx) && aligned16(gy);
+    const int d = vec ? 4 : 1;
+    const int64_t items = (int64_t)B * ((n_keep + aug_n) / d);
+    int64_t blocks = (items + 255) / 256;
+    if (blocks > 16384) blocks = 16384;
+    if (vec) k_postprocess_inv_bwd<4><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(y, gx, gy, items, n_keep / 4, (n_keep + aug_n) / 4, ybs, gybs, s12);
+    else k_postprocess_inv_bwd<1><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(y, gx, gy, items, n_keep, n_keep + aug_n, ybs, gybs, s12);
+    return 0;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -562,6 +602,15 @@ int cf_postprocess_inv_ld(const float* z, float* x, float* ld_acc, int B, int n_
     const float c0 = ldj_const + 0.5f * aug_n * kLog2Pi;
     if (clamp) launch_postprocess_inv_ld<true>(z, x, ld_acc, B, n_keep, aug_n, z_bstride, t2, s2, t1, s1, lo, hi, c0, cf_s(stream));
     else launch_postprocess_inv_ld<false>(z, x, ld_acc, B, n_keep, aug_n, z_bstride, t2, s2, t1, s1, 0.f, 0.f, c0, cf_s(stream));
+    CF_LAUNCH_CHECK();
+    return 0;
+}
+
+int cf_postprocess_inv_bwd(const float* y, const float* gx, float* gy, int B, int n_keep, int aug_n, int64_t y_bstride,
+                           int64_t gy_bstride, float s1s2, cf_stream_t stream) {
+    if (B == 0 || n_keep + aug_n == 0) return 0;
+    CF_REQUIRE(y && gx && gy && B > 0 && n_keep > 0 && aug_n >= 0 && y_bstride >= n_keep && gy_bstride >= (int64_t)n_keep + aug_n);
+    launch_postprocess_inv_bwd(y, gx, gy, B, n_keep, aug_n, y_bstride, gy_bstride, s1s2, cf_s(stream));
     CF_LAUNCH_CHECK();
     return 0;
 }

@@ -1382,6 +1382,21 @@ __global__ __launch_bounds__(256) void k_step_pack_inv(const float* __restrict__
     }
 }
 
+// table of the inverse step's vector-Jacobian product (cf_flow_step_inv_bwd_data): diag(e^{logs}) Wm^-T, the map from the upstream
+// d/dx to d/dy, as the A fragments of a dense_phase with the packed rows of phase 0 (OFF_A0 of k_step_pack) - Wm^-1 is the one
+// cf_flow_step_inv_prepare left at the head of wsi
+template <class G>
+__global__ __launch_bounds__(256) void k_step_pack_inv_bwd(const float* __restrict__ wsi, const float* __restrict__ logs,
+                                                           float* __restrict__ wsv) {
+    const int gtid = blockIdx.x * 256 + threadIdx.x, gsz = gridDim.x * 256;
+    const float* Winv = wsi + GeoInv<G>::OFF_WINV;
+    for (int e = gtid; e < G::NG0 * G::RT03 * 256; e += gsz) {
+        const int j = e & 3, lane = (e >> 2) & 63, q = e >> 8, rt = q % G::RT03, g = q / G::RT03;
+        const int ch = chan_of_row<G>(rt * 32 + (lane & 31)), k = 2 * (4 * g + j) + (lane >> 5);
+        wsv[e] = (ch >= 0 && k < G::C) ? expf(logs[ch]) * Winv[k * G::C + ch] : 0.f;
+    }
+}
+
 // LD (cf_flow_step_inv_ld): ld_acc[b] += ws[0] + sum log_s as well - what the forward step adds for its log-det at the recovered
 // input x - reduced as flow_step_phases reduces it: lane, shuffles over the lanes of a sample, one LDS hop where a sample spans
 // waves, then the one owner of sample b reads, adds and writes (no float atomics: the same bits in every run).  Without the
@@ -1909,6 +1924,31 @@ int cf_flow_step_inv_prepare(const float* Wm, const float* t, const float* logs,
         default: cf_set_error("cf_flow_step_inv_prepare: shape (%d,%d,%d) unsupported", C, H, W); return CF_ERR_UNSUPPORTED;
     }
     if (rc) return rc;
+    CF_LAUNCH_CHECK();
+    return 0;
+}
+
+int64_t cf_flow_step_inv_bwd_ws_bytes(int C, int H, int W) {
+    switch (shape_id(C, H, W)) {
+        case 0: return (int64_t)G8::NG0 * G8::RT03 * 256 * 4;
+        case 1: return (int64_t)G16::NG0 * G16::RT03 * 256 * 4;
+        case 2: return (int64_t)G32::NG0 * G32::RT03 * 256 * 4;
+        case 3: return (int64_t)G64::NG0 * G64::RT03 * 256 * 4;
+    }
+    return 0;
+}
+
+int cf_flow_step_inv_bwd_prepare(const void* wsi, const float* logs, void* wsv, int C, int H, int W, cf_stream_t stream) {
+    CF_REQUIRE(wsi && logs && wsv && (reinterpret_cast<uintptr_t>(wsv) & 15) == 0);
+    const float* wi = (const float*)wsi;
+    float* wv = (float*)wsv;
+    switch (shape_id(C, H, W)) {
+        case 0: k_step_pack_inv_bwd<G8><<<dim3(4), dim3(256), 0, cf_s(stream)>>>(wi, logs, wv); break;
+        case 1: k_step_pack_inv_bwd<G16><<<dim3(4), dim3(256), 0, cf_s(stream)>>>(wi, logs, wv); break;
+        case 2: k_step_pack_inv_bwd<G32><<<dim3(4), dim3(256), 0, cf_s(stream)>>>(wi, logs, wv); break;
+        case 3: k_step_pack_inv_bwd<G64><<<dim3(4), dim3(256), 0, cf_s(stream)>>>(wi, logs, wv); break;
+        default: cf_set_error("cf_flow_step_inv_bwd_prepare: shape (%d,%d,%d) unsupported", C, H, W); return CF_ERR_UNSUPPORTED;
+    }
     CF_LAUNCH_CHECK();
     return 0;
 }

@@ -240,7 +240,15 @@ __device__ __forceinline__ void adj_axis(int c, int d, int N, int (&src)[2], boo
 // DATA = true (cf_flow_step_bwd_data: the input gradient of log p(x) with frozen weights): none of the four operand planes of
 // the weight-gradient GEMMs is written (s_gh, s_gh2, s_gh1, s_gy may be null: 6 C HW of the 7 C HW floats the kernel stores per
 // sample); everything that leads to g_x is the same instruction stream, so g_x is bit for bit the training form's.
-template <class G, bool CTX, bool DATA = false>
+// INV = true (cf_flow_step_inv_bwd_data, recompute + data-only form without the per-sample bias): the vector-Jacobian product of
+// the INVERSE step  z -> x = W^-1 ((z0 | (z1 - t) e^{-ls}) e^{logs} + t)  at the recovered step input x.  `gz` is the upstream
+// d/dx, `gx` receives d/dz.  The forward is re-run from x as above (y0 = z0 conditions the net; y1, ls and the masks in
+// registers); the upstream of the coupling, g_y = e^{logs} (W^-T g_x), is one more dense phase over the upstream rows with the
+// fragments of wsv (packed as OFF_A0: cf_flow_step_inv_bwd_prepare; it arrives in the `sb` argument - this form has no per-sample
+// bias); then
+//     g_z1 = g_y1 e^{-ls},   g_h = [ -g_z1 ,  -g_y1 y1 (1 - (ls/2)^2) ],   g_z0 = g_y0 + NN^T g_h
+// through the same three transposed phases.  The last 1x1 phase (the forward step's transposed front matrix) is not run.
+template <class G, bool CTX, bool DATA = false, bool INV = false>
 __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
     const float* __restrict__ x, const float* __restrict__ gz, const float* __restrict__ gld,
     const float* __restrict__ ws, const float* __restrict__ wsb, float* __restrict__ gx,
@@ -248,6 +256,7 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
     float* __restrict__ s_gh2, float* __restrict__ s_gh1, float* __restrict__ s_gy, int B, int64_t xbs,
     const float* __restrict__ sb, StepTape tp, int gx_unsq) {
     using Bw = GeoBwd<G>;
+    static_assert(!INV || (CTX && DATA), "the inverse step's VJP is a recompute, data-only form");
     constexpr bool TAPED = !CTX;
     constexpr int C = G::C, HW = G::HW, W = G::W, H = G::H, RS = G::RS, HALF = G::HALF, HID = G::HID;   // RS: row stride of the LDS planes
     constexpr int PTW = G::PTW, RT03 = G::RT03, RT1 = G::RT1, NR = (HALF <= 16 ? 8 : 16);
@@ -273,6 +282,7 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
     // the upstream gradient of the transformed half, g_z1, in the same register layout (128 contiguous bytes per row and
     // half wave), and d L / d ld1 of this lane's samples - requested first, consumed after the tape / recompute below
     float g1v[PTW][NR], glv[PTW];
+    if constexpr (!INV) {
 #pragma unroll
     for (int q = 0; q < PTW; ++q) {
         const int smp = min(b0 + pix[q] / HW, B - 1);
@@ -283,6 +293,7 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
             const int idx = tile_row(r, lk);
             g1v[q][r] = (HALF >= 16 || idx < HALF) ? gzp[idx * HW] : 0.f;
         }
+    }
     }
     if constexpr (TAPED) {
 #pragma unroll
@@ -421,7 +432,8 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
             for (int r = 0; r < NR; ++r) {
                 float raw = (HALF <= 16) ? acc3[0][q][r + 8] : acc3[RT03 - 1][q][r];
                 const int idx = tile_row(r, lk);
-                if (idx < HALF) raw += sb[(int64_t)min(b0 + pix[q] / HW, B - 1) * C + HALF + idx];
+                if constexpr (!INV)
+                    if (idx < HALF) raw += sb[(int64_t)min(b0 + pix[q] / HW, B - 1) * C + HALF + idx];
                 ls[q][r] = cf_log_scale(raw);
             }
     }
@@ -431,8 +443,39 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
     // ---------------------------------------------------------------- backward
     // g_y1 = g_z1 e^{ls} is parked in the Y0 region (dead since phase 1) until the last phase; g_z0 is fetched separately
     // for the last phases: neither stays in registers across the transposed 3x3
+    f32x16 gy0k[INV ? PTW : 1];          // INV: g_y0, the start value of the g_z0 accumulators two phases on
     {
         float* GH = H1 + C * RS;                     // g_h plane: rows [0,HALF) = g_t, [HALF,C) = g_raw
+        if constexpr (INV) {
+            // g_y = e^{logs} (W^-T g_x): the upstream rows take the first C rows of the H region (h2 was consumed by phase 3, own
+            // columns; rows past the batch read 0), the product comes out in the packed rows of phase 0.  g_z1 is parked in the
+            // Y0 region, g_y0 waits in the accumulators of the last transposed phase.
+            rows_load_t<G, C, C>(gz, H1, b0, B, wave, lane);
+            f32x16 accg[RT03][PTW];
+#pragma unroll
+            for (int rt = 0; rt < RT03; ++rt)
+#pragma unroll
+                for (int q = 0; q < PTW; ++q)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) accg[rt][q][r] = 0.f;
+            dense_phase<G, G::KS0, G::NG0, RT03>(accg, ws_rsrc(sb, G::NG0 * RT03 * 256), 0, H1, pix, lane);
+#pragma unroll
+            for (int q = 0; q < PTW; ++q) {
+#pragma unroll
+                for (int r = 0; r < NR; ++r) {
+                    const int idx = tile_row(r, lk);
+                    if (idx < HALF) {
+                        const float gy1 = (HALF <= 16) ? accg[0][q][r + 8] : accg[RT03 - 1][q][r];
+                        const float g1 = gy1 * __expf(-ls[q][r]);
+                        Y0[idx * RS + pix[q]] = g1;                                     // g_z1
+                        GH[idx * RS + pix[q]] = -g1;                                    // d x / d t
+                        GH[(HALF + idx) * RS + pix[q]] = -gy1 * y1[q][r] * (1.0f - 0.25f * ls[q][r] * ls[q][r]);   // d x / d raw
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) gy0k[q][r] = (HALF >= 32 || tile_row(r, lk) < HALF) ? accg[0][q][r] : 0.f;
+            }
+        } else {
 #pragma unroll
         for (int q = 0; q < PTW; ++q) {
             const float gl = glv[q];
@@ -448,6 +491,7 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
                     GH[(HALF + idx) * RS + pix[q]] = gls * (1.0f - 0.25f * ls[q][r] * ls[q][r]);   // d log_s / d raw
                 }
             }
+        }
         }
         if constexpr (!DATA) rows_store_t<G, C, C>(s_gh, GH, b0, B, wave, lane);
         if constexpr (!CTX && !DATA) rows_store_t<G, HALF, C>(s_gy + HALF * HW, Y0, b0, B, wave, lane);   // g_y1 rows of the g_y plane
@@ -473,6 +517,10 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
     // g_z0, the start value of the g_y0 accumulators two phases on (rows of that single tile = channels 0..31 in natural
     // order; 128 contiguous bytes per row and half wave): in flight during the transposed 3x3
     f32x16 accy[1][PTW];
+    if constexpr (INV) {
+#pragma unroll
+        for (int q = 0; q < PTW; ++q) accy[0][q] = gy0k[q];
+    } else {
 #pragma unroll
     for (int q = 0; q < PTW; ++q) {
         const float* gzp = gz + (int64_t)min(b0 + pix[q] / HW, B - 1) * C * HW + pin[q];
@@ -481,6 +529,7 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
             const int row = tile_row(r, lk);
             accy[0][q][r] = (HALF >= 32 || row < HALF) ? gzp[row * HW] : 0.f;
         }
+    }
     }
     __syncthreads();                     // g_h2 complete: the transposed 3x3 reads neighbouring waves' columns
     {   // g_h1 = (NN.2^T (*) g_h2) * [h1 > 0]: adjoint of the reflect-padded gather.  Output pixel p of tap (dy,dx)
@@ -622,6 +671,11 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
                 if (row < HALF) H1[row * RS + pix[q]] = acc[0][q][r];
             }
         if constexpr (!CTX && !DATA) rows_store_t<G, HALF, C>(s_gy, H1, b0, B, wave, lane);   // g_y0 rows (weight-gradient operand plane)
+        if constexpr (INV) {             // d/dz = [g_z0 ; g_z1]: no front matrix behind the coupling in this direction
+            rows_store_t<G, HALF, C>(gx, H1, b0, B, wave, lane);
+            rows_store_t<G, HALF, C>(gx + HALF * HW, Y0, b0, B, wave, lane);
+            return;
+        }
         // g_x = (e^{-logs} Wm)^T g_y
         f32x16 ax[Bw::RTI][PTW];
 #pragma unroll
@@ -849,16 +903,16 @@ int launch_prepare_bwd(const StepPackBwdBatch& pb, int n, hipStream_t s) {
     return 0;
 }
 
-template <class G, bool CTX, bool DATA = false>
+template <class G, bool CTX, bool DATA = false, bool INV = false>
 int launch_step_bwd(const float* x, const float* gz, const float* gld, const float* ws, const float* wsb, float* gx,
                     float* s_y0, float* s_h1, float* s_h2, float* s_gh, float* s_gh2, float* s_gh1, float* s_gy, int B,
                     int64_t xbs, hipStream_t s, const float* sb = nullptr, StepTape tp = kNoTape, int gx_unsq = 0) {
     constexpr size_t lds_bytes = (size_t)G::LDS_FLOATS * sizeof(float);
     if (lds_bytes > 64 * 1024) {
         static std::atomic<uint64_t> raised{0};
-        if (int rc_ = cf_raise_dynamic_lds((const void*)k_flow_step_bwd<G, CTX, DATA>, 160 * 1024, raised, __func__)) return rc_;
+        if (int rc_ = cf_raise_dynamic_lds((const void*)k_flow_step_bwd<G, CTX, DATA, INV>, 160 * 1024, raised, __func__)) return rc_;
     }
-    k_flow_step_bwd<G, CTX, DATA><<<dim3((B + G::SPW - 1) / G::SPW), dim3(256), lds_bytes, s>>>(
+    k_flow_step_bwd<G, CTX, DATA, INV><<<dim3((B + G::SPW - 1) / G::SPW), dim3(256), lds_bytes, s>>>(
         x, gz, gld, ws, wsb, gx, s_y0, s_h1, s_h2, s_gh, s_gh2, s_gh1, s_gy, B, xbs, sb, tp, gx_unsq);
     return 0;
 }
@@ -871,6 +925,8 @@ using B32 = Geo<32, 8, 8, 2, 1, 0, 1>;
 using B64 = Geo<64, 4, 4, 8, 1>;
 
 }  // namespace
+
+#ifndef CF_STEP_BWD_KERNELS_ONLY         // cf_step_inv_bwd.hip instantiates the INV form from this text in a unit of its own
 
 extern "C" {
 
@@ -1032,3 +1088,5 @@ int cf_flow_step_bwd_ctx_data(const float* x, const float* gz, const float* gld,
 }
 
 }  // extern "C"
+
+#endif  // CF_STEP_BWD_KERNELS_ONLY

@@ -69,6 +69,10 @@ SIGNATURES = {
     "cf_flow_step_inv_prepare": (_c_int, [_c_p] * 4 + [_c_int] * 3 + [_c_p]),
     "cf_flow_step_inv": (_c_int, [_c_p] * 4 + [_c_int] * 4 + [_c_i64, _c_int, _c_p]),
     "cf_flow_step_inv_ld": (_c_int, [_c_p] * 5 + [_c_int] * 4 + [_c_i64, _c_int, _c_p]),
+    "cf_flow_step_inv_bwd_ws_bytes": (_c_i64, [_c_int] * 3),
+    "cf_flow_step_inv_bwd_prepare": (_c_int, [_c_p] * 3 + [_c_int] * 3 + [_c_p]),
+    "cf_flow_step_inv_bwd_data": (_c_int, [_c_p] * 6 + [_c_int] * 4 + [_c_i64, _c_p]),
+    "cf_postprocess_inv_bwd": (_c_int, [_c_p] * 3 + [_c_int] * 3 + [_c_i64, _c_i64, _c_f, _c_p]),
     "cf_gmm_bwd_coeffs": (_c_int, [_c_p] * 4 + [_c_int, _c_int, _c_int, _c_p]),
     "cf_gmm_bwd_gx": (_c_int, [_c_p] * 4 + [_c_int, _c_int, _c_i64, _c_p]),
     "cf_gmm_bwd_params": (_c_int, [_c_p] * 8 + [_c_int, _c_int, _c_p]),

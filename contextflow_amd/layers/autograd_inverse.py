@@ -1,0 +1,221 @@
+"""The differentiable backward walk: `FlowSequential.inverse / decode(..., differentiable=True)`.
+
+The walk runs the layers' reverses as `_inverse` does, but returns the CONTINUOUS point - for a flow whose first layer is a
+Dequantization the chain stops in front of it - and keeps, per inverted group, what the vector-Jacobian product (VJP) of that
+group needs: references to tensors the walk produces anyway (the recovered input of a fused step, the logits of the tail, the
+output of a layer-path coupling).  `backward` then walks the groups in forward order.  It is a data-only walk: the gradient with
+respect to z and to every half `decode` put back, no parameter gradient.
+
+Rules (g: the gradient at the group's output in the backward walk, i.e. at the FORWARD input of the layers):
+  SplitPrior (a concatenate here)     slice: the upper half is that latent's gradient
+  Squeeze / PermuteAxes               the index map (squeeze_op / permute)
+  Conv1x1                             g <- W^-T g            (conv1x1_apply with the transposed cached inverse)
+  ActNorm                             g <- g e^{logs}
+  Normalization                       g <- g scale
+  Augment.reverse                     zeros into the dropped channels
+  the pre-processing tail             cf_postprocess_inv_bwd, one pass
+  Coupling / CouplingFC (layer path)  with F the forward coupling at the recovered y: J_F^-T g = (g0 - A^T u, u), u = g1 e^{-s}
+                                      (cf_coupling_apply in inverse mode on g with the shift half of h zeroed); A^T u is the first
+                                      half of the forward coupling's data backward on upstream (0, u) with gld = 0
+  fused step                          cf_flow_step_inv_bwd_data, one launch
+Anything else raises NotImplementedError naming the layer."""
+import torch
+
+from . import _derived, _hip
+from .actnorm import ActNorm
+from .augment import Augment
+from .conv1x1 import Conv1x1, conv1x1_apply, slogdet_inverse
+from . import coupling as _cpl
+from .coupling import Coupling, coupling_apply
+from .dequantize import Dequantization
+from .normalize import Normalization
+from .permute_axes import PermuteAxes
+from .splitprior import SplitPrior
+from .squeeze import Squeeze, squeeze_op
+
+
+def _step_vjp_tables(flow, conv, act, cpl, shape, dev):
+    """(ws, wsb, wsv) of a fused step: the forward tables `_inverse_step` keeps, the transposed fragments of the backward kernel and
+    the fragments of diag(e^{logs}) Wm^-T (cf_flow_step_inv_bwd_prepare, from the Wm^-1 in wsi) - kept while the step's parameters
+    are unchanged, as the tables of `_inverse_step`."""
+    C, H, W = shape
+    ws, wsi = flow._inverse_tables(conv, act, cpl, shape, dev)
+    f, pp = _hip.f32, _hip.p
+    c1, c2, c3 = cpl.NN[0], cpl.NN[2], cpl.NN[4]
+
+    def build():
+        L, st = _hip.lib(), _hip.stream()
+        wsb = torch.empty(L.cf_flow_step_bwd_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
+        _hip.call("cf_flow_step_bwd_prepare", pp(f(conv.NN.detach())), pp(f(act.NN_logs.detach())), pp(f(c1.weight.detach())),
+                  pp(f(c2.weight.detach())), pp(f(c3.weight.detach())), pp(wsb), C, H, W, st)
+        wsv = torch.empty(L.cf_flow_step_inv_bwd_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
+        _hip.call("cf_flow_step_inv_bwd_prepare", pp(wsi), pp(f(act.NN_logs.detach())), pp(wsv), C, H, W, st)
+        return wsb, wsv
+    wsb, wsv = _derived.get(flow, ("inv_bwd_ws", id(cpl)), _derived.key(flow._inverse_step_sources(conv, act, cpl), C, H, W, str(dev)),
+                            build, dev)
+    return ws, wsb, wsv
+
+
+def _coupling_vjp(m, y, g):
+    """J_F^-T g of a context-free Coupling / CouplingFC at its recovered input y, from existing kernels only."""
+    from .autograd_layers import coupling_conv_backward
+    shape = g.shape
+    if y.dim() == 2:
+        y, g = y.view(-1, m.D, 1, 1), g.reshape(-1, m.D, 1, 1)
+    half = y.shape[1] // 2
+    h = m.net(y[:, :half])
+    h[:, :half].zero_()                                   # no shift: (g0, (g1 - 0) e^{-s})
+    u = coupling_apply(_hip.f32(g).contiguous(), h, True)[0]
+    up = u.clone()
+    up[:, :half].zero_()
+    gld = torch.zeros(y.shape[0], device=y.device, dtype=torch.float32)
+    at_u = coupling_conv_backward(m, y, up, gld, params=False)[0][:, :half]
+    u[:, :half] -= at_u
+    return u.view(shape)
+
+
+def walk(flow, z, latents):
+    """(x, records): the continuous backward walk from z (latents: `decode`'s halves in forward order, or None - every SplitPrior
+    then draws) and one record per inverted group, in walk order."""
+    mods = flow.sequence_modules
+    latents = None if latents is None else list(latents)
+    rec = []
+    i = len(mods) - 1
+    while i >= 0:
+        m = mods[i]
+        if i == 0 and isinstance(m, Dequantization):
+            break                                         # the continuous point: the tensor floor() would be applied to
+        if (flow.fused and i >= 2 and z.dim() == 4 and isinstance(mods[i - 1], ActNorm) and mods[i - 1].is_initialized()
+                and flow._step_supported(mods[i - 2], mods[i - 1], m, tuple(z.shape[1:]))):
+            z = flow._inverse_step(z, mods[i - 2], mods[i - 1], m)       # the Squeeze in front, if any, runs as its own launch
+            rec.append(("step", mods[i - 2], mods[i - 1], m, z))
+            i -= 3
+            continue
+        if flow._tail_fusable(i, z):
+            y, n1, n2 = z, mods[1], mods[2]
+            keep = y.shape[1] - (mods[4].aug_size if i == 4 else 0)
+            z = n1.reverse(n2.reverse(mods[3].reverse(y[:, :keep])))
+            rec.append(("tail", y, keep, n1._s * n2._s))
+            break
+        if isinstance(m, SplitPrior):
+            c = z.shape[1]
+            if latents is not None:
+                if not latents:
+                    raise ValueError("decode: no latent left for the SplitPrior at layer %d" % i)
+                z = m.reverse(z, None, latent=latents.pop())
+            else:
+                z = m.reverse(z, None)
+            rec.append(("split", c, latents is not None))
+        elif isinstance(m, Squeeze):
+            z = m.reverse(z)
+            rec.append(("squeeze", tuple(m.p)))
+        elif isinstance(m, PermuteAxes):
+            z = m.reverse(z)
+            rec.append(("permute", m.permutation))
+        elif isinstance(m, Conv1x1) and not m.context_net:
+            z = m.reverse(z)
+            rec.append(("conv", m))
+        elif isinstance(m, ActNorm) and not m.context_net:
+            z = m.reverse(z)
+            rec.append(("act", m))
+        elif isinstance(m, Normalization):
+            z = m.reverse(z)
+            rec.append(("scale", m._s))
+        elif isinstance(m, Augment) and m.split_dim == 1:
+            rec.append(("augment", z.shape[1]))
+            z = m.reverse(z)
+        elif type(m) in (Coupling, _cpl.CouplingFC) and not m.context_net:
+            z = m.reverse(z)
+            rec.append(("coupling", m, z))
+        else:
+            raise NotImplementedError("differentiable inverse: no vector-Jacobian rule for the reverse of %s (layer %d)"
+                                      % (type(m).__name__, i))
+        i -= 1
+    return z, rec
+
+
+def vjp(flow, rec, g):
+    """(gz, [gradient of every half put back, in forward order]) from g = dL/dx, walking the groups in forward order."""
+    halves = []
+    pp, st = _hip.p, _hip.stream()
+    g = _hip.f32(g)
+    for r in reversed(rec):
+        kind = r[0]
+        if kind == "tail":
+            _, y, keep, s12 = r
+            yv, ybs = _hip.bview(y)
+            B, C, H, W = yv.shape
+            g = g.contiguous()
+            gy = torch.empty(B, C, H, W, device=g.device, dtype=torch.float32)
+            _hip.call("cf_postprocess_inv_bwd", pp(yv), pp(g), pp(gy), B, keep * H * W, (C - keep) * H * W, ybs, C * H * W, s12, st)
+            g = gy
+        elif kind == "step":
+            _, conv, act, cpl, x = r
+            xv, xbs = _hip.bview(x)
+            B, C, H, W = xv.shape
+            ws, wsb, wsv = _step_vjp_tables(flow, conv, act, cpl, (C, H, W), xv.device)
+            g = g.contiguous()
+            gz = torch.empty(B, C, H, W, device=g.device, dtype=torch.float32)
+            _hip.call("cf_flow_step_inv_bwd_data", pp(xv), pp(g), pp(ws), pp(wsb), pp(wsv), pp(gz), B, C, H, W, xbs, st)
+            g = gz
+        elif kind == "split":
+            c = r[1]
+            if r[2]:
+                halves.append(g[:, c:].contiguous())
+            g = g[:, :c]
+        elif kind == "squeeze":
+            g = squeeze_op(g, r[1], False)
+        elif kind == "permute":
+            g = g.permute(r[1]).contiguous()
+        elif kind == "conv":
+            m = r[1]
+            inv = _derived.get(m, "winv", _derived.key((m.NN,), str(g.device)),
+                               lambda: slogdet_inverse(_hip.f32(m.NN.detach()), True)[1], g.device)
+            shape = g.shape
+            if g.dim() == 2:
+                g = g.reshape(-1, m.D, 1, 1)
+            g = conv1x1_apply(g, inv.t().contiguous()).view(shape)
+        elif kind == "act":
+            logs = _hip.f32(r[1].NN_logs.detach())
+            g = g * torch.exp(logs).view([1, -1] + [1] * (g.dim() - 2))
+        elif kind == "scale":
+            g = g * r[1]
+        elif kind == "augment":
+            full = g.new_zeros((g.shape[0], r[1]) + tuple(g.shape[2:]))
+            full[:, : g.shape[1]] = g
+            g = full
+        elif kind == "coupling":
+            g = _coupling_vjp(r[1], r[2], g)
+    return g.contiguous(), halves
+
+
+class InverseWalk(torch.autograd.Function):
+    """x = the continuous backward walk of (z, *halves); backward: the data-only VJP above.  Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, flow, n_halves, z, *halves):
+        with torch.no_grad():
+            x, rec = walk(flow, z, list(halves) if n_halves is not None else None)
+        ctx.flow, ctx.rec, ctx.n = flow, rec, len(halves)
+        ctx.shapes = [tuple(z.shape)] + [tuple(h.shape) for h in halves]
+        return x.clone() if x.data_ptr() == z.data_ptr() else x
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gx):
+        gz, gh = vjp(ctx.flow, ctx.rec, gx)
+        assert len(gh) == ctx.n and tuple(gz.shape) == ctx.shapes[0]
+        out = [gz.view(ctx.shapes[0])] + [h.view(s) for h, s in zip(gh, ctx.shapes[1:])]
+        need = ctx.needs_input_grad[2:]
+        return (None, None) + tuple(o if n else None for o, n in zip(out, need))
+
+
+def run(flow, z, latents):
+    """The differentiable walk: with grad mode on and a latent that requires a gradient the result carries a grad_fn; otherwise
+    the same continuous result, detached."""
+    _hip.require_device(z)
+    halves = [] if latents is None else list(latents)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in [z] + halves):
+        return InverseWalk.apply(flow, None if latents is None else len(halves), z, *halves)
+    with torch.no_grad():
+        return walk(flow, z.detach(), None if latents is None else [h.detach() for h in halves])[0]

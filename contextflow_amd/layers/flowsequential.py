@@ -924,6 +924,27 @@ class FlowSequential(nn.Module):
         `g(x) -> (z, logp)` (static output buffers, overwritten by the next replay)."""
         return GraphedFlow(self, example_input)
 
+    @staticmethod
+    def _inverse_step_sources(conv, act, cpl):
+        return (conv.NN, act.NN_t, act.NN_logs, cpl.NN[0].weight, cpl.NN[0].bias, cpl.NN[2].weight, cpl.NN[2].bias, cpl.NN[4].weight,
+                cpl.NN[4].bias)
+
+    def _inverse_tables(self, conv, act, cpl, shape, dev):
+        """(ws, wsi) of a fused step for the inverse kernel."""
+        C, H, W = shape
+        f, pp, st = _hip.f32, _hip.p, _hip.stream()
+        # the packed tables of the step (forward fragments of the conditioner, W^-1 and the inverse ActNorm) are kept while the
+        # parameters they derive from are unchanged - version counter and storage of every source tensor, as the forward's tables
+        # (two factorisations + two packing launches per step and call before: 13 - 17 % of a `sample` call at 16 384 samples)
+        srcs = self._inverse_step_sources(conv, act, cpl)
+        def build():
+            ws = self._prepare_step(conv, act, cpl, (C, H, W), dev)
+            wsi = torch.empty(_hip.lib().cf_flow_step_inv_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
+            _hip.call("cf_flow_step_inv_prepare", pp(f(conv.NN.detach())), pp(f(act.NN_t.detach())), pp(f(act.NN_logs.detach())),
+                      pp(wsi), C, H, W, st)
+            return ws, wsi
+        return _derived.get(self, ("inv_ws", id(cpl)), _derived.key(srcs, C, H, W, str(dev)), build, dev)
+
     def _inverse_step(self, z, conv, act, cpl, unsqueeze=False, ld=None):
         """Conv1x1^-1 o ActNorm^-1 o Coupling^-1 in one MFMA kernel (cf_flow_step_inv); unsqueeze: the Squeeze((2,2)) in front of
         the step is inverted by the kernel's stores.  ld (B,): the step's forward log-det at the recovered input is added to it
@@ -931,19 +952,8 @@ class FlowSequential(nn.Module):
         z, zbs = _hip.bview(z)
         B, C, H, W = z.shape
         dev = z.device
-        f, pp, st = _hip.f32, _hip.p, _hip.stream()
-        # the packed tables of the step (forward fragments of the conditioner, W^-1 and the inverse ActNorm) are kept while the
-        # parameters they derive from are unchanged - version counter and storage of every source tensor, as the forward's tables
-        # (two factorisations + two packing launches per step and call before: 13 - 17 % of a `sample` call at 16 384 samples)
-        srcs = (conv.NN, act.NN_t, act.NN_logs, cpl.NN[0].weight, cpl.NN[0].bias, cpl.NN[2].weight, cpl.NN[2].bias, cpl.NN[4].weight,
-                cpl.NN[4].bias)
-        def build():
-            ws = self._prepare_step(conv, act, cpl, (C, H, W), dev)
-            wsi = torch.empty(_hip.lib().cf_flow_step_inv_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
-            _hip.call("cf_flow_step_inv_prepare", pp(f(conv.NN.detach())), pp(f(act.NN_t.detach())), pp(f(act.NN_logs.detach())),
-                      pp(wsi), C, H, W, st)
-            return ws, wsi
-        ws, wsi = _derived.get(self, ("inv_ws", id(cpl)), _derived.key(srcs, C, H, W, str(dev)), build, dev)
+        pp, st = _hip.p, _hip.stream()
+        ws, wsi = self._inverse_tables(conv, act, cpl, (C, H, W), dev)
         x = torch.empty((B, C // 4, 2 * H, 2 * W) if unsqueeze else (B, C, H, W), device=dev, dtype=torch.float32)
         events = self.inv_events
         if events is not None:               # HIP events on the launch stream, bracketing exactly this kernel
@@ -1009,7 +1019,17 @@ class FlowSequential(nn.Module):
         if context is None and self._has_context_nets():
             raise ValueError("%s: a context-conditioned (specialist) flow needs its context" % what)
 
-    def inverse(self, z, context=None, noise=None, return_logp=False):
+    def _refuse_differentiable(self, what, context, clamp, return_logp):
+        """What `inverse` / `decode` with differentiable=True (layers/autograd_inverse.py) do not take."""
+        if clamp:
+            raise ValueError("%s: clamp=True together with differentiable=True - the clamp is about pixels, the differentiable walk "
+                             "returns the continuous point in front of the floor" % what)
+        if return_logp:
+            raise NotImplementedError("%s: return_logp=True together with differentiable=True" % what)
+        if self._has_context_nets() or context is not None:
+            raise NotImplementedError("%s: differentiable=True for a flow with context nets (a specialist flow)" % what)
+
+    def inverse(self, z, context=None, noise=None, return_logp=False, differentiable=False):
         """Run every layer's `reverse` from the last to the first (the loop of flowsequential.py:35-37); groups
         Coupling <- ActNorm <- Conv1x1 of a supported shape run as one fused kernel.  A specialist flow takes its `context`
         (ValueError without): ActNorm(c) <- Conv1x1(c) pairs, with the Squeeze((2,2)) in front of them, run as one
@@ -1018,7 +1038,16 @@ class FlowSequential(nn.Module):
         the noise layers given the noise this walk implies (the dequantisation noise is the fractional part the floor drops, the
         Augment noise the channels Augment.reverse drops): log p_prior(z | m) + the SplitPriors' log p(half | m) + the forward
         log-det of every inverted layer at its recovered input - log N(dropped Augment channels).  x is the plain call's bit for
-        bit.  NotImplementedError for a specialist flow and for a layer without a rule (activation layers, MaskedCoupling)."""
+        bit.  NotImplementedError for a specialist flow and for a layer without a rule (activation layers, MaskedCoupling).
+        differentiable=True: the CONTINUOUS point of the walk - a flow that starts with a Dequantization stops in front of it: the
+        tensor floor() would be applied to - and, when grad mode is on and z requires a gradient, with a grad_fn whose backward
+        returns dL/dz (a data-only walk: no parameter gradient is formed; once differentiable).  The forward values may differ from
+        the plain walk's in rounding.  NotImplementedError with return_logp, for a flow with context nets and for a layer without a
+        rule (TransCoupling, MaskedCoupling, the activation and spline layers, an Augment over another axis)."""
+        if differentiable:
+            from . import autograd_inverse
+            self._refuse_differentiable("inverse", context, False, return_logp)
+            return autograd_inverse.run(self, z, None)
         self._refuse_logp(return_logp)
         self._need_context("inverse", context)
         with self._pinned(noise, context):
@@ -1222,12 +1251,16 @@ class FlowSequential(nn.Module):
             latents = [h.clone(memory_format=torch.contiguous_format) for h in halves + [z]]
         return latents, logp
 
-    def decode(self, latents, context=None, clamp=False, noise=None, return_logp=False):
+    def decode(self, latents, context=None, clamp=False, noise=None, return_logp=False, differentiable=False):
         """The reverse chain on a complete latent (`encode`'s list: one half per SplitPrior in forward order, then z): every
         SplitPrior puts its half back instead of drawing one.  clamp=True: the projection into the pixel range that `sample`
         applies.  ValueError for a wrong number of latents or a latent whose shape is not its level's.  A specialist flow takes
         its `context` (ValueError without) and `noise` as `encode`.  return_logp: (x, logp) as `inverse` - the halves given
-        here are the ones scored; with clamp=True logp stays the density of the unclamped continuous point."""
+        here are the ones scored; with clamp=True logp stays the density of the unclamped continuous point.
+        differentiable=True: as `inverse` - the continuous point, and backward returns the gradient with respect to z and to every
+        half that requires one, each in the layout of its latent.  ValueError together with clamp=True."""
+        if differentiable:
+            self._refuse_differentiable("decode", context, clamp, return_logp)
         self._refuse_logp(return_logp)
         self._need_context("decode", context)
         latents = list(latents)
@@ -1239,6 +1272,9 @@ class FlowSequential(nn.Module):
             raise ValueError("decode: latents of different batch sizes %s" % [h.shape[0] for h in latents])
         if isinstance(self.dist, GaussianMixtureDistribution) and tuple(z.shape[1:]) != tuple(self.dist.mG.shape[2:]):
             raise ValueError("decode: z of shape %s, the prior is over %s" % (tuple(z.shape), tuple(self.dist.mG.shape[2:])))
+        if differentiable:
+            from . import autograd_inverse
+            return autograd_inverse.run(self, z, latents[:-1])
         with self._pinned(noise, context):
             return self._inverse(z, context, self._pixel_range() if clamp else None, latents=latents[:-1], return_logp=return_logp)
 

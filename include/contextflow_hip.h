@@ -73,6 +73,13 @@ int cf_postprocess_inv_clamped(const float* z, float* x, int B, int n_keep, int6
  * cf_postprocess_inv[_clamped]'s.  (Adds a symbol only: ABI 15.)                                                         */
 int cf_postprocess_inv_ld(const float* z, float* x, float* ld_acc, int B, int n_keep, int aug_n, int64_t z_bstride, float t2, float s2,
                           float t1, float s1, float ldj_const, int clamp, float lo, float hi, cf_stream_t stream);
+/* vector-Jacobian product of the CONTINUOUS tail (cf_postprocess_inv in front of its floor: FlowSequential.inverse / decode with
+ * differentiable=True), x = ((sigmoid(y) - t2) s2 - t1) s1:  gy[b, i] = gx[b, i] * s1s2 * v (1 - v), v = sigmoid(y[b, i]), for
+ * i < n_keep, and an exact 0 for the aug_n elements behind them (the channels Augment.reverse drops).  s1s2 = s1 * s2, the two
+ * Normalization scales (normalize.py: reverse multiplies by scale).  y, gy: rows of y_bstride / gy_bstride floats; gx dense
+ * (B, n_keep).  Any alignment.  (Adds a symbol only: CF_ABI_VERSION stays.)                                        */
+int cf_postprocess_inv_bwd(const float* y, const float* gx, float* gy, int B, int n_keep, int aug_n, int64_t y_bstride,
+                           int64_t gy_bstride, float s1s2, cf_stream_t stream);
 /* y = min(max(x, lo), hi)                                       the same projection behind the layer-by-layer chain */
 int cf_clamp(const float* x, float* y, int64_t n, float lo, float hi, cf_stream_t stream);
 /* Fused layers 0-3 of the image flows (model.py:97-100): v = ((x+u)/s1 + t1)/s2 + t2,
@@ -323,6 +330,21 @@ int cf_flow_step_inv(const float* z, float* x, const void* ws, const void* wsi, 
  * one owner (no float atomics): the same bits in every run.  (Adds a symbol only: ABI 15.)                              */
 int cf_flow_step_inv_ld(const float* z, float* x, float* ld_acc, const void* ws, const void* wsi, int B, int C, int H, int W,
                         int64_t z_bstride, int x_unsqueezed, cf_stream_t stream);
+
+/* Vector-Jacobian product of the inverse step (FlowSequential.inverse / decode with differentiable=True), data only: no
+ * parameter gradient is formed.  For  z -> x = cf_flow_step_inv(z):  given x (B,C,H,W; rows of x_bstride floats), the step
+ * input the inverse recovered, and gx = dL/dx (dense), writes gz = dL/dz (dense) in ONE launch:
+ *     gy = e^{logs} (Wm^-T gx),  gz1 = gy1 e^{-s},  gz0 = gy0 + (dNN/dz0)^T [ -gz1 | -gy1 y1 (1 - tanh^2(raw/2)) ]
+ * with y = ActNorm(Conv1x1(x)), [tau | raw] = NN(y0), s = 2 tanh(raw/2) recomputed from x (ReLU masks in registers).
+ * ws: cf_flow_step_prepare; wsb: cf_flow_step_bwd_prepare; wsv (cf_flow_step_inv_bwd_ws_bytes bytes, 16-byte aligned):
+ * the fragments of diag(e^{logs}) Wm^-T, packed by cf_flow_step_inv_bwd_prepare from the Wm^-1 that cf_flow_step_inv_prepare
+ * left in wsi (run it first, on the same stream).  Shapes: those of cf_flow_step_bwd_ws_bytes.  x, gx, gz 16-byte aligned,
+ * x_bstride % 4 == 0.  No float atomics: two launches give the same bits.  B == 0: no-op.
+ * (Adds symbols only: CF_ABI_VERSION stays.)                                                                       */
+int64_t cf_flow_step_inv_bwd_ws_bytes(int C, int H, int W);
+int cf_flow_step_inv_bwd_prepare(const void* wsi, const float* logs, void* wsv, int C, int H, int W, cf_stream_t stream);
+int cf_flow_step_inv_bwd_data(const float* x, const float* gx, const void* ws, const void* wsb, const void* wsv, float* gz,
+                              int B, int C, int H, int W, int64_t x_bstride, cf_stream_t stream);
 
 /* ---- backward of the fused step (training: experiment_cl.py:130-136) ------------------------------
  * cf_flow_step_bwd_prepare packs the TRANSPOSED weight fragments of the data-gradient chain (workspace of
