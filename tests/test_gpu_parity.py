@@ -982,6 +982,14 @@ def test_abi_errors(L):
     assert lib.cf_attention(N, N, 0, 4, 64, 0.125, N) == 0
     # shapes outside a kernel's range are refused with a message, not launched
     assert lib.cf_slogdet_inverse(ctypes.c_void_p(16), 193, ctypes.c_void_p(16), N, N) == -2 and b"193" in lib.cf_last_error()
+    # the transformer step backward: depth outside 1 .. 6 and channel counts other than 26 (host-side argument checks)
+    q = ctypes.c_void_p(16)
+    for depth in (0, 7):
+        assert lib.cf_vit_step_bwd(q, q, q, q, q, q, q, q, N, 4, 26, depth, 26 * 8, N) == -1 and b"cf_vit_step_bwd" in lib.cf_last_error()
+        assert lib.cf_vit_step_bwd_prepare_batch(0, q, q, q, q, 26, depth, N) == -1 and b"cf_vit_step_bwd_prepare_batch" in lib.cf_last_error()
+    assert lib.cf_vit_step_bwd(q, q, q, q, q, q, q, q, N, 4, 24, 6, 24 * 8, N) == -2 and b"C=24" in lib.cf_last_error()
+    assert lib.cf_vit_step_bwd_prepare_batch(0, q, q, q, q, 24, 6, N) == -2 and b"C=24" in lib.cf_last_error()
+    assert lib.cf_vit_step_bwd_prepare_batch(0, q, q, q, q, 26, 6, N) == 0
 
 
 @pytest.mark.parametrize("tag,indiv", [("spline_shared", False), ("spline_indiv", True)])
