@@ -853,7 +853,12 @@ struct CtxInvLds {
 // times y errs by cond(W_b) eps - 1e-4 of scale at the condition numbers of 1e3 .. 1e4 that trained contextflow layers reach, and
 // up to 20 x what an fp32 LU solve loses on the lower triangular W_b without contextflow - and the chain multiplies such steps;
 // the refined x is within eps + (cond eps)^2 of the exact one.  It costs two more products over data that is in LDS already.
-template <bool USQ>
+// TR (cf_affine_ctx_inv_bwd_data): the vector-Jacobian product of that map, which is affine in z:  gz[b] = e^{l_b} (.) (W_b^-T gx[b]).
+// `z` is gx, `x` receives gz, t is not read.  The same W_b is inverted by the same elimination - the inverse of the transpose is the
+// transpose of the inverse - and only the READS change: the product takes A = W_b^-1 row by row where the plain form takes its
+// transpose, the fp64 residual gx - W_b^T g0 walks W_b by columns; the scale moves from the load to the store, there is no shift.
+// USQ then says that gx ARRIVES in the (C/4, 2H, 2W) layout (the walk's output): the index map folds into the staging loads.
+template <bool USQ, bool TR = false>
 __global__ __launch_bounds__(256) void k_affine_ctx_inv(const float* __restrict__ z, const float* __restrict__ m1,
                                                         const float* __restrict__ Wm, const float* __restrict__ m2,
                                                         const float* __restrict__ t, const float* __restrict__ logs,
@@ -869,8 +874,12 @@ __global__ __launch_bounds__(256) void k_affine_ctx_inv(const float* __restrict_
     for (int c = tid; c < C; c += 256) {
         float tv = 0.f, ev = 1.f;
         if (m2 != nullptr) {
+            if constexpr (TR) {
+                ev = expf(actnorm_ctx_terms<false>(m2, b, nullptr, logs, C, c).l);
+            } else {
             const ActNormCtxTerms a = actnorm_ctx_terms(m2, b, t, logs, C, c);
             tv = a.t; ev = expf(a.l);
+            }
         }
         tb[c] = tv; eb[c] = ev;
     }
@@ -879,11 +888,18 @@ __global__ __launch_bounds__(256) void k_affine_ctx_inv(const float* __restrict_
         for (int e0 = tid; e0 < C * HW; e0 += 4 * 256) {
             float zv[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) zv[i] = zb[min(e0 + i * 256, C * HW - 1)];
+            for (int i = 0; i < 4; ++i) {
+                const int e = min(e0 + i * 256, C * HW - 1);
+                zv[i] = zb[(TR && USQ) ? squeeze_index(e / HW, e % HW, W, HW) : e];
+            }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int e = e0 + i * 256;
-                if (e < C * HW) { const int c = e / HW, p = e - c * HW; xb[USQ ? squeeze_index(c, p, W, HW) : e] = fmaf(zv[i], eb[c], tb[c]); }
+                if (e < C * HW) {
+                    const int c = e / HW, p = e - c * HW;
+                    if constexpr (TR) xb[e] = zv[i] * eb[c];
+                    else xb[USQ ? squeeze_index(c, p, W, HW) : e] = fmaf(zv[i], eb[c], tb[c]);
+                }
             }
         }
         return;
@@ -896,11 +912,14 @@ __global__ __launch_bounds__(256) void k_affine_ctx_inv(const float* __restrict_
     for (int e0 = tid; e0 < C * HW; e0 += 8 * 256) {
         float zv[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) zv[i] = zb[min(e0 + i * 256, C * HW - 1)];
+        for (int i = 0; i < 8; ++i) {
+            const int e = min(e0 + i * 256, C * HW - 1);
+            zv[i] = zb[(TR && USQ) ? squeeze_index(e / HW, e % HW, W, HW) : e];
+        }
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int e = e0 + i * 256;
-            if (e < C * HW) { const int c = e / HW; ys[e] = fmaf(zv[i], eb[c], tb[c]); }
+            if (e < C * HW) { const int c = e / HW; ys[e] = TR ? zv[i] : fmaf(zv[i], eb[c], tb[c]); }
         }
     }
     build_wb_rowmajor<false>(A, m1 + (int64_t)b * C * C, Wm, nullptr, C, S, tid);
@@ -958,7 +977,7 @@ __global__ __launch_bounds__(256) void k_affine_ctx_inv(const float* __restrict_
     }
     // At[k][c] = W_b^-1[c][k]: lanes walk c (A at stride S, At contiguous), padding columns zero
     for (int kk = r0, c = c0; kk < C;) {
-        At[kk * CP + c] = A[c * S + kk];
+        At[kk * CP + c] = TR ? A[kk * S + c] : A[c * S + kk];             // (TR: W_b^-T[c][k], a straight copy)
         kk += dr; c += dc;
         if (c >= C) { c -= C; ++kk; }
     }
@@ -967,17 +986,17 @@ __global__ __launch_bounds__(256) void k_affine_ctx_inv(const float* __restrict_
     build_wb_rowmajor<false>(A, m1 + (int64_t)b * C * C, Wm, nullptr, C, S, tid);          // W_b again, for the residual
     pixel8_product(At, ys, C, CP, HW, HW, tid, [=](int c, int p, float acc) { xs[c * HW + p] = acc; });
     __syncthreads();
-    // ys <- y - W_b x0 in fp64: a thread owns a pixel and 8 rows of W_b, and is the only reader of the y it replaces
+    // ys <- y - W_b x0 in fp64: a thread owns a pixel and 8 rows of W_b (TR: columns, W_b^T), and is the only reader of the y it replaces
     for (int e = tid; e < (CP >> 3) * HW; e += 256) {
         const int cb = e / HW, p = e - cb * HW, c0 = cb * 8;
         double acc[8];
         int row[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) { row[k] = min(c0 + k, C - 1) * S; acc[k] = (double)ys[min(c0 + k, C - 1) * HW + p]; }
+        for (int k = 0; k < 8; ++k) { row[k] = min(c0 + k, C - 1) * (TR ? 1 : S); acc[k] = (double)ys[min(c0 + k, C - 1) * HW + p]; }
         for (int i = 0; i < C; ++i) {
             const double xv = (double)xs[i * HW + p];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) acc[k] = fma(-(double)A[row[k] + i], xv, acc[k]);
+            for (int k = 0; k < 8; ++k) acc[k] = fma(-(double)(TR ? A[i * S + row[k]] : A[row[k] + i]), xv, acc[k]);
         }
 #pragma unroll
         for (int k = 0; k < 8; ++k)
@@ -985,7 +1004,10 @@ __global__ __launch_bounds__(256) void k_affine_ctx_inv(const float* __restrict_
     }
     __syncthreads();
     pixel8_product(At, ys, C, CP, HW, HW, tid,
-                   [=](int c, int p, float acc) { xb[USQ ? squeeze_index(c, p, W, HW) : c * HW + p] = xs[c * HW + p] + acc; });
+                   [=](int c, int p, float acc) {
+                       if constexpr (TR) xb[c * HW + p] = eb[c] * (xs[c * HW + p] + acc);
+                       else xb[USQ ? squeeze_index(c, p, W, HW) : c * HW + p] = xs[c * HW + p] + acc;
+                   });
 }
 
 // The three levels of the image flows: k_affine_ctx_wave transposed - one wave per sample, no LDS, no barrier, 64
@@ -1538,6 +1560,24 @@ int cf_affine_ctx_inv(const float* z, const float* m1, const float* Wm, const fl
                                                                            x_out, C, H, W, z_bstride)
                                : launch_per_sample<k_affine_ctx_inv<false>>(__func__, B, C, H * W, floats, cf_s(stream), z, m1, Wm, m2, t, logs,
                                                                             x_out, C, H, W, z_bstride)) return rc;
+    CF_LAUNCH_CHECK();
+    return 0;
+}
+
+// the vector-Jacobian product of cf_affine_ctx_inv: gz = e^{l_b} (.) (W_b^-T gx); gx_unsqueezed: gx in the layout of the twin's
+// out_unsqueeze output; m1 / m2 NULL as there
+int cf_affine_ctx_inv_bwd_data(const float* gx, const float* m1, const float* Wm, const float* m2, const float* logs, float* gz,
+                               int B, int C, int H, int W, int gx_unsqueezed, cf_stream_t stream) {
+    if (B == 0) return 0;
+    CF_REQUIRE(gx && gz && (m1 || m2) && B >= 0 && C > 0 && C <= 256 && H > 0 && W > 0 && (m1 || !Wm) && (m2 || !logs) &&
+               (!gx_unsqueezed || C % 4 == 0));
+    const int floats = CtxInvLds(C, H * W, m1 != nullptr).floats();
+    const float* no_t = nullptr;
+    const int64_t gbs = (int64_t)C * H * W;
+    if (int rc = gx_unsqueezed ? launch_per_sample<k_affine_ctx_inv<true, true>>(__func__, B, C, H * W, floats, cf_s(stream), gx, m1, Wm, m2,
+                                                                                 no_t, logs, gz, C, H, W, gbs)
+                               : launch_per_sample<k_affine_ctx_inv<false, true>>(__func__, B, C, H * W, floats, cf_s(stream), gx, m1, Wm, m2,
+                                                                                  no_t, logs, gz, C, H, W, gbs)) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }

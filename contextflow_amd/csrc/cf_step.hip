@@ -1401,7 +1401,11 @@ __global__ __launch_bounds__(256) void k_step_pack_inv_bwd(const float* __restri
 // input x - reduced as flow_step_phases reduces it: lane, shuffles over the lanes of a sample, one LDS hop where a sample spans
 // waves, then the one owner of sample b reads, adds and writes (no float atomics: the same bits in every run).  Without the
 // flag ld_acc is not read (NULL) and the kernel is the one it was.
-template <class G, bool LD = false>
+// CTX (cf_flow_step_inv_ctx, instantiated in cf_step_inv_ctx.hip): the specialist coupling ALONE backwards - the conditioner takes
+// the per-sample bias of conditioner_net's modes 1 / 2, which arrives in the `wsi` argument: no Conv1x1 / ActNorm sits behind that
+// coupling, so there is no inverse table, the last dense phase is not run and x = [z0 | (z1 - t) e^{-log_s}] goes from the y plane
+// to memory (no un-squeeze: a coupling never sits directly behind a Squeeze).
+template <class G, bool LD = false, int CTX = 0>
 #ifndef CF_INV16_MINW
 #define CF_INV16_MINW 3          // (4 waves per SIMD: 12 spilled registers, 6.55 vs 6.49 ms per cifar10 sample(16384))
 #endif
@@ -1409,6 +1413,7 @@ __global__ __launch_bounds__(256, (G::WINO && G::C == 16) ? CF_INV16_MINW : G::M
                                                        const float* __restrict__ ws, const float* __restrict__ wsi, int B,
                                                        int64_t zbs, int x_unsq, float* __restrict__ ld_acc) {
     using I = GeoInv<G>;
+    static_assert(CTX == 0 || !LD, "the specialist coupling's inverse has no log-det output");
     constexpr int C = G::C, HW = G::HW, PIX = G::PIX, HALF = G::HALF;
     constexpr int PTW = G::PTW, RT03 = G::RT03, NR = (HALF <= 16 ? 8 : 16);
     constexpr int XI = C * PTW / 8;
@@ -1445,7 +1450,14 @@ __global__ __launch_bounds__(256, (G::WINO && G::C == 16) ? CF_INV16_MINW : G::M
         cf_wave_sync();
     }
     f32x16 acc3[RT03][PTW];
-    conditioner_net<G>(acc3, lds, ws, pix, pin, lane, tid, nullptr, 0, tile);
+    if constexpr (CTX == 0) {
+        conditioner_net<G>(acc3, lds, ws, pix, pin, lane, tid, nullptr, 0, tile);
+    } else {
+        int soff[PTW];
+#pragma unroll
+        for (int q = 0; q < PTW; ++q) soff[q] = min(b0 + pix[q] / HW, B - 1) * (CTX == 1 ? C : G::HID);
+        conditioner_net<G, CTX>(acc3, lds, ws, pix, pin, lane, tid, nullptr, 0, tile, wsi, soff);
+    }
     cf_wave_sync();                      // phase 3 has read h2: its words are reused for the y plane
     // y = [z0 | (z1 - t) e^{-log_s}] as the operand plane of the last phase (this wave's columns of the H region).  z is read a
     // SECOND time here (L2-resident: this workgroup read it a few microseconds ago) instead of being carried in registers
@@ -1514,6 +1526,10 @@ __global__ __launch_bounds__(256, (G::WINO && G::C == 16) ? CF_INV16_MINW : G::M
             }
         }
     }
+    if constexpr (CTX != 0) {            // the identity front: the y plane (this wave's own columns) is x
+        rows_store<G, C>(x, H1, b0, 0, B, wave, lane);
+        return;
+    }
     f32x16 acc[I::RTI][PTW];
 #pragma unroll
     for (int rt = 0; rt < I::RTI; ++rt)
@@ -1570,6 +1586,8 @@ int launch_step_inv_ld(const float* z, float* x, float* ld_acc, const float* ws,
 
 
 }  // namespace
+
+#ifndef CF_STEP_KERNELS_ONLY             // cf_step_inv_ctx.hip instantiates the CTX form of k_flow_step_inv from this text in a unit of its own
 
 static bool direct_conv_only() {
     static const bool v = [] { const char* e = getenv("CONTEXTFLOW_DIRECT_CONV"); return e && e[0] == '1'; }();
@@ -2143,3 +2161,5 @@ int cf_flow_step_fwd_ctx_taped(const float* x, float* z, float* ldj_acc, const v
 }
 
 }  // extern "C"
+
+#endif  // CF_STEP_KERNELS_ONLY

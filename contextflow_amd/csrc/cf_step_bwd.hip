@@ -248,7 +248,12 @@ __device__ __forceinline__ void adj_axis(int c, int d, int N, int (&src)[2], boo
 // bias); then
 //     g_z1 = g_y1 e^{-ls},   g_h = [ -g_z1 ,  -g_y1 y1 (1 - (ls/2)^2) ],   g_z0 = g_y0 + NN^T g_h
 // through the same three transposed phases.  The last 1x1 phase (the forward step's transposed front matrix) is not run.
-template <class G, bool CTX, bool DATA = false, bool INV = false>
+// IB (INV only; cf_flow_step_inv_bwd_ctx_data, instantiated in cf_step_inv_ctx_bwd.hip): the specialist coupling backwards, whose
+// conditioner carries the per-sample bias of conditioner_net's CTX modes - 1: sb (B, C) on the conditioner output (only its raw
+// half enters), 2: sb (B, 2C) at the accumulator start of phase 1, so the ReLU masks are the forward's.  No Conv1x1 / ActNorm sits
+// behind that coupling: ws is packed with an identity front, and the g_y phase runs on ws's OWN identity fragments at OFF_A0 (the
+// packing of wsv for W = I, logs = 0) - `sb` is free for the bias, no further table, no other instruction stream.
+template <class G, bool CTX, bool DATA = false, bool INV = false, int IB = 0>
 __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
     const float* __restrict__ x, const float* __restrict__ gz, const float* __restrict__ gld,
     const float* __restrict__ ws, const float* __restrict__ wsb, float* __restrict__ gx,
@@ -257,6 +262,7 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
     const float* __restrict__ sb, StepTape tp, int gx_unsq) {
     using Bw = GeoBwd<G>;
     static_assert(!INV || (CTX && DATA), "the inverse step's VJP is a recompute, data-only form");
+    static_assert(IB == 0 || INV, "IB: the bias mode of the inverse form");
     constexpr bool TAPED = !CTX;
     constexpr int C = G::C, HW = G::HW, W = G::W, H = G::H, RS = G::RS, HALF = G::HALF, HID = G::HID;   // RS: row stride of the LDS planes
     constexpr int PTW = G::PTW, RT03 = G::RT03, RT1 = G::RT1, NR = (HALF <= 16 ? 8 : 16);
@@ -341,6 +347,19 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
         for (int rt = 0; rt < RT1; ++rt)
 #pragma unroll
             for (int q = 0; q < PTW; ++q) acc[rt][q] = bias_tile(ws + G::OFF_B1 + rt * 32, lk);
+        if constexpr (IB == 2) {
+#pragma unroll
+            for (int q = 0; q < PTW; ++q) {
+                const float* sbq = sb + (int64_t)min(b0 + pix[q] / HW, B - 1) * HID;
+#pragma unroll
+                for (int rt = 0; rt < RT1; ++rt)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int row = rt * 32 + tile_row(r, lk);
+                        if (row < HID) acc[rt][q][r] += sbq[row];
+                    }
+            }
+        }
         dense_phase<G, G::KS1, G::NG1, RT1>(acc, rsw, G::OFF_A1, Y0, pix, lane);
 #pragma unroll
         for (int rt = 0; rt < RT1; ++rt)
@@ -432,7 +451,7 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
             for (int r = 0; r < NR; ++r) {
                 float raw = (HALF <= 16) ? acc3[0][q][r + 8] : acc3[RT03 - 1][q][r];
                 const int idx = tile_row(r, lk);
-                if constexpr (!INV)
+                if constexpr (!INV || IB == 1)
                     if (idx < HALF) raw += sb[(int64_t)min(b0 + pix[q] / HW, B - 1) * C + HALF + idx];
                 ls[q][r] = cf_log_scale(raw);
             }
@@ -458,7 +477,8 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
                 for (int q = 0; q < PTW; ++q)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) accg[rt][q][r] = 0.f;
-            dense_phase<G, G::KS0, G::NG0, RT03>(accg, ws_rsrc(sb, G::NG0 * RT03 * 256), 0, H1, pix, lane);
+            if constexpr (IB != 0) dense_phase<G, G::KS0, G::NG0, RT03>(accg, rsw, G::OFF_A0, H1, pix, lane);
+            else dense_phase<G, G::KS0, G::NG0, RT03>(accg, ws_rsrc(sb, G::NG0 * RT03 * 256), 0, H1, pix, lane);
 #pragma unroll
             for (int q = 0; q < PTW; ++q) {
 #pragma unroll
@@ -903,16 +923,16 @@ int launch_prepare_bwd(const StepPackBwdBatch& pb, int n, hipStream_t s) {
     return 0;
 }
 
-template <class G, bool CTX, bool DATA = false, bool INV = false>
+template <class G, bool CTX, bool DATA = false, bool INV = false, int IB = 0>
 int launch_step_bwd(const float* x, const float* gz, const float* gld, const float* ws, const float* wsb, float* gx,
                     float* s_y0, float* s_h1, float* s_h2, float* s_gh, float* s_gh2, float* s_gh1, float* s_gy, int B,
                     int64_t xbs, hipStream_t s, const float* sb = nullptr, StepTape tp = kNoTape, int gx_unsq = 0) {
     constexpr size_t lds_bytes = (size_t)G::LDS_FLOATS * sizeof(float);
     if (lds_bytes > 64 * 1024) {
         static std::atomic<uint64_t> raised{0};
-        if (int rc_ = cf_raise_dynamic_lds((const void*)k_flow_step_bwd<G, CTX, DATA, INV>, 160 * 1024, raised, __func__)) return rc_;
+        if (int rc_ = cf_raise_dynamic_lds((const void*)k_flow_step_bwd<G, CTX, DATA, INV, IB>, 160 * 1024, raised, __func__)) return rc_;
     }
-    k_flow_step_bwd<G, CTX, DATA, INV><<<dim3((B + G::SPW - 1) / G::SPW), dim3(256), lds_bytes, s>>>(
+    k_flow_step_bwd<G, CTX, DATA, INV, IB><<<dim3((B + G::SPW - 1) / G::SPW), dim3(256), lds_bytes, s>>>(
         x, gz, gld, ws, wsb, gx, s_y0, s_h1, s_h2, s_gh, s_gh2, s_gh1, s_gy, B, xbs, sb, tp, gx_unsq);
     return 0;
 }
@@ -926,7 +946,7 @@ using B64 = Geo<64, 4, 4, 8, 1>;
 
 }  // namespace
 
-#ifndef CF_STEP_BWD_KERNELS_ONLY         // cf_step_inv_bwd.hip instantiates the INV form from this text in a unit of its own
+#ifndef CF_STEP_BWD_KERNELS_ONLY         // cf_step_inv_bwd.hip / cf_step_inv_ctx_bwd.hip instantiate the INV forms from this text in units of their own
 
 extern "C" {
 

@@ -161,6 +161,9 @@ SIGNATURES = {
     "cf_affine_ctx_bwd_data": (_c_int, [_c_p] * 6 + [_c_int] * 4 + [_c_i64, _c_int, _c_p]),
     "cf_affine_ctx_inv": (_c_int, [_c_p] * 7 + [_c_int] * 4 + [_c_i64, _c_int, _c_p]),
     "cf_gmm_ctx_draw": (_c_int, [_c_p] * 5 + [_c_int] + [_c_p] * 3 + [ctypes.c_uint64, _c_p, _c_i64, _c_int, _c_p] + [_c_int] * 5 + [_c_f, _c_p]),
+    "cf_affine_ctx_inv_bwd_data": (_c_int, [_c_p] * 6 + [_c_int] * 5 + [_c_p]),
+    "cf_flow_step_inv_ctx": (_c_int, [_c_p] * 4 + [_c_int] * 5 + [_c_i64, _c_p]),
+    "cf_flow_step_inv_bwd_ctx_data": (_c_int, [_c_p] * 5 + [_c_int, _c_p] + [_c_int] * 4 + [_c_i64, _c_p]),
     "cf_flow_step_bwd_ctx_data": (_c_int, [_c_p] * 7 + [_c_int] * 4 + [_c_i64, _c_p]),
     "cf_gmm_ctx_bwd_data": (_c_int, [_c_p] * 11 + [_c_int] * 5 + [_c_i64, _c_p]),
     "cf_add_repeat": (_c_int, [_c_p] * 2 + [_c_int] * 4 + [_c_p]),

@@ -17,7 +17,7 @@ from typing import Any, NamedTuple
 
 import torch
 
-from . import _derived, _hip, _tape
+from . import _hip, _tape
 from .actnorm import ActNorm
 from .augment import Augment
 from .autograd_layers import _new, _relu_mask
@@ -265,21 +265,9 @@ def _cn_chain_backward(rec, gcn, ldscale, bw):
 
 
 def _coupling_wsb(rec, C, H, W, dev):
-    """Transposed fragments of the step-backward kernel for a coupling record (identity 1x1 / ActNorm in front): kept while the
-    three weights are unchanged (frozen under contextflow)."""
-    m, f, pp = rec.module, _hip.f32, _hip.p
-    c1, c2, c3 = m.NN[0], m.NN[2], m.NN[4]
-
-    def build():
-        eye = torch.eye(C, device=dev, dtype=torch.float32)
-        zero = torch.zeros(C, device=dev, dtype=torch.float32)
-        wsb = torch.empty(_hip.lib().cf_flow_step_bwd_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
-        w1 = f(c1.weight.detach())
-        w1x = w1 if rec.mode == 1 else w1[:, :C // 2].contiguous()
-        _hip.call("cf_flow_step_bwd_prepare", pp(eye), pp(zero), pp(w1x), pp(f(c2.weight.detach())),
-                  pp(f(c3.weight.detach())), pp(wsb), C, H, W, _hip.stream())
-        return wsb
-    return _derived.get(m, "ctx_wsb", _derived.key((c1.weight, c2.weight, c3.weight), rec.mode, C, H, W, str(dev)), build, dev)
+    """Transposed fragments of the step-backward kernel for a coupling record (Coupling._ctx_step_bwd_tables: kept while the three
+    weights are unchanged, frozen under contextflow)."""
+    return rec.module._ctx_step_bwd_tables(rec.mode, C, H, W, dev)
 
 
 def coupling_ctx_backward(rec, gz, bw):

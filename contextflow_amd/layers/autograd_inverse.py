@@ -18,13 +18,23 @@ Rules (g: the gradient at the group's output in the backward walk, i.e. at the F
                                       (cf_coupling_apply in inverse mode on g with the shift half of h zeroed); A^T u is the first
                                       half of the forward coupling's data backward on upstream (0, u) with gld = 0
   fused step                          cf_flow_step_inv_bwd_data, one launch
+A specialist flow under its context - the codes are formed ONCE, in the walk, and the records keep the tensors the
+VJP needs (m1, m2, the coupling's per-sample bias), not the encoders: backward differentiates the map the forward applied,
+whatever a stochastic encoder would draw next:
+  [Squeeze <-] Conv1x1(c) <- ActNorm(c')   cf_affine_ctx_inv forward (as the plain walk), cf_affine_ctx_inv_bwd_data backward:
+                                      g <- e^{l_b} (W_b^-T g), the un-squeeze folded into its loads; a lone context Conv1x1 /
+                                      ActNorm is the same pair of entry points with one side NULL
+  Coupling(c), fused geometry         cf_flow_step_inv_ctx forward - ONE launch where the plain walk runs six - keeping x, the bias
+                                      and its mode; cf_flow_step_inv_bwd_ctx_data backward
+No gradient with respect to a parameter, a code or the context is formed.
 Anything else raises NotImplementedError naming the layer."""
 import torch
 
 from . import _derived, _hip
 from .actnorm import ActNorm
 from .augment import Augment
-from .conv1x1 import Conv1x1, conv1x1_apply, slogdet_inverse
+from .context import cn_chain
+from .conv1x1 import Conv1x1, affine_ctx_inverse, affine_ctx_inverse_vjp, affine_ctx_operands, conv1x1_apply, slogdet_inverse
 from . import coupling as _cpl
 from .coupling import Coupling, coupling_apply
 from .dequantize import Dequantization
@@ -74,18 +84,52 @@ def _coupling_vjp(m, y, g):
     return u.view(shape)
 
 
-def walk(flow, z, latents):
+def _coupling_ctx_inverse(m, z, context):
+    """(x, record) of a specialist Coupling in the fused geometry: cf_flow_step_inv_ctx, one launch."""
+    cn = cn_chain(m, context).cn
+    zv, zbs = _hip.bview(z)
+    B, C, H, W = zv.shape
+    mode, sbias, ws = m._ctx_step_operands(cn, C, H, W, zv.device)
+    x = torch.empty(B, C, H, W, device=zv.device, dtype=torch.float32)
+    _hip.call("cf_flow_step_inv_ctx", _hip.p(zv), _hip.p(x), _hip.p(ws), _hip.p(sbias), mode, B, C, H, W, zbs, _hip.stream())
+    return x, ("coupling_ctx", m, x, sbias, mode, ws)
+
+
+def walk(flow, z, latents, context=None):
     """(x, records): the continuous backward walk from z (latents: `decode`'s halves in forward order, or None - every SplitPrior
-    then draws) and one record per inverted group, in walk order."""
+    then draws) and one record per inverted group, in walk order.  context: that of a specialist flow (the caller pins the
+    encoders' noise); its layers then take the rules of the context kernels."""
     mods = flow.sequence_modules
     latents = None if latents is None else list(latents)
+    spec = context is not None
     rec = []
     i = len(mods) - 1
     while i >= 0:
         m = mods[i]
         if i == 0 and isinstance(m, Dequantization):
             break                                         # the continuous point: the tensor floor() would be applied to
-        if (flow.fused and i >= 2 and z.dim() == 4 and isinstance(mods[i - 1], ActNorm) and mods[i - 1].is_initialized()
+        if spec and z.dim() == 4 and isinstance(m, (ActNorm, Conv1x1)) and m.context_net:
+            # the groups of FlowSequential._inverse: ActNorm(c') <- Conv1x1(c) with the Squeeze((2,2)) in front, or either layer alone
+            act = m if isinstance(m, ActNorm) else None
+            conv = m if act is None else None
+            n = 1
+            if (act is not None and i >= 1 and isinstance(mods[i - 1], Conv1x1) and mods[i - 1].context_net
+                    and mods[i - 1].D == z.shape[1]):
+                conv, n = mods[i - 1], 2
+            sq = (n == 2 and i >= 2 and isinstance(mods[i - 2], Squeeze) and tuple(mods[i - 2].p) == (2, 2)
+                  and z.shape[1] % 4 == 0)
+            ops = affine_ctx_operands(conv, act, context)
+            shape = tuple(z.shape)
+            z = affine_ctx_inverse(z, operands=ops, unsqueeze=sq)
+            rec.append(("affine_ctx", ops, shape, sq))
+            i -= n + int(sq)
+            continue
+        if spec and type(m) is Coupling and m.context_net and m._fused_ctx_ok(z):
+            z, r = _coupling_ctx_inverse(m, z, context)
+            rec.append(r)
+            i -= 1
+            continue
+        if (not spec and flow.fused and i >= 2 and z.dim() == 4 and isinstance(mods[i - 1], ActNorm) and mods[i - 1].is_initialized()
                 and flow._step_supported(mods[i - 2], mods[i - 1], m, tuple(z.shape[1:]))):
             z = flow._inverse_step(z, mods[i - 2], mods[i - 1], m)       # the Squeeze in front, if any, runs as its own launch
             rec.append(("step", mods[i - 2], mods[i - 1], m, z))
@@ -102,9 +146,9 @@ def walk(flow, z, latents):
             if latents is not None:
                 if not latents:
                     raise ValueError("decode: no latent left for the SplitPrior at layer %d" % i)
-                z = m.reverse(z, None, latent=latents.pop())
+                z = m.reverse(z, context, latent=latents.pop())
             else:
-                z = m.reverse(z, None)
+                z = m.reverse(z, context)
             rec.append(("split", c, latents is not None))
         elif isinstance(m, Squeeze):
             z = m.reverse(z)
@@ -128,8 +172,8 @@ def walk(flow, z, latents):
             z = m.reverse(z)
             rec.append(("coupling", m, z))
         else:
-            raise NotImplementedError("differentiable inverse: no vector-Jacobian rule for the reverse of %s (layer %d)"
-                                      % (type(m).__name__, i))
+            raise NotImplementedError("differentiable inverse: no vector-Jacobian rule for the reverse of %s%s (layer %d)"
+                                      % (type(m).__name__, " with a context net" if getattr(m, "context_net", None) else "", i))
         i -= 1
     return z, rec
 
@@ -186,6 +230,16 @@ def vjp(flow, rec, g):
             g = full
         elif kind == "coupling":
             g = _coupling_vjp(r[1], r[2], g)
+        elif kind == "affine_ctx":
+            g = affine_ctx_inverse_vjp(g, r[1], r[2], r[3])
+        elif kind == "coupling_ctx":
+            _, m, x, sbias, mode, ws = r
+            B, C, H, W = x.shape
+            wsb = m._ctx_step_bwd_tables(mode, C, H, W, x.device)
+            g = g.contiguous()
+            gz = torch.empty(B, C, H, W, device=g.device, dtype=torch.float32)
+            _hip.call("cf_flow_step_inv_bwd_ctx_data", pp(x), pp(g), pp(ws), pp(wsb), pp(sbias), mode, pp(gz), B, C, H, W, C * H * W, st)
+            g = gz
     return g.contiguous(), halves
 
 
@@ -193,29 +247,34 @@ class InverseWalk(torch.autograd.Function):
     """x = the continuous backward walk of (z, *halves); backward: the data-only VJP above.  Once differentiable."""
 
     @staticmethod
-    def forward(ctx, flow, n_halves, z, *halves):
+    def forward(ctx, flow, n_halves, context, z, *halves):
         with torch.no_grad():
-            x, rec = walk(flow, z, list(halves) if n_halves is not None else None)
+            x, rec = walk(flow, z, list(halves) if n_halves is not None else None, context)
         ctx.flow, ctx.rec, ctx.n = flow, rec, len(halves)
+        ctx.spec = context is not None
+        if ctx.spec:                     # autograd's own guard: a second backward without retain_graph raises, as for any graph
+            ctx.save_for_backward(z)
         ctx.shapes = [tuple(z.shape)] + [tuple(h.shape) for h in halves]
         return x.clone() if x.data_ptr() == z.data_ptr() else x
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gx):
+        if ctx.spec:
+            ctx.saved_tensors
         gz, gh = vjp(ctx.flow, ctx.rec, gx)
         assert len(gh) == ctx.n and tuple(gz.shape) == ctx.shapes[0]
         out = [gz.view(ctx.shapes[0])] + [h.view(s) for h, s in zip(gh, ctx.shapes[1:])]
-        need = ctx.needs_input_grad[2:]
-        return (None, None) + tuple(o if n else None for o, n in zip(out, need))
+        need = ctx.needs_input_grad[3:]
+        return (None, None, None) + tuple(o if n else None for o, n in zip(out, need))
 
 
-def run(flow, z, latents):
+def run(flow, z, latents, context=None):
     """The differentiable walk: with grad mode on and a latent that requires a gradient the result carries a grad_fn; otherwise
-    the same continuous result, detached."""
+    the same continuous result, detached.  context: a specialist flow's, the caller holds the encoders' noise pinned."""
     _hip.require_device(z)
     halves = [] if latents is None else list(latents)
     if torch.is_grad_enabled() and any(t.requires_grad for t in [z] + halves):
-        return InverseWalk.apply(flow, None if latents is None else len(halves), z, *halves)
+        return InverseWalk.apply(flow, None if latents is None else len(halves), context, z, *halves)
     with torch.no_grad():
-        return walk(flow, z.detach(), None if latents is None else [h.detach() for h in halves])[0]
+        return walk(flow, z.detach(), None if latents is None else [h.detach() for h in halves], context)[0]

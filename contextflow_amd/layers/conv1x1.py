@@ -26,12 +26,9 @@ def conv1x1_apply(x, W, bias=None):
     return out
 
 
-def affine_ctx_inverse(z, conv=None, act=None, context=None, unsqueeze=False):
-    """[Squeeze(2,2) <-] Conv1x1(c) <- ActNorm(c') backwards in one cf_affine_ctx_inv launch: x = W_b^-1 (z exp(l_b) + t_b).  conv /
-    act: the layers (either may be None: the other one alone); each forms its code through cn_linear, exactly as its forward
-    does.  NotImplementedError where the per-sample matrix and the sample do not fit the LDS of a CU."""
-    zv, zbs = _hip.bview(z)
-    B, C, H, W = zv.shape
+def affine_ctx_operands(conv=None, act=None, context=None):
+    """(m1, Wm, m2, t, logs) of cf_affine_ctx_inv for the layers given (either may be None): each forms its code through cn_linear,
+    exactly as its forward does."""
     m1 = Wm = m2 = t = logs = None
     if act is not None:
         if act.contextflow and not act.is_initialized():
@@ -42,15 +39,41 @@ def affine_ctx_inverse(z, conv=None, act=None, context=None, unsqueeze=False):
     if conv is not None:
         m1 = cn_linear(conv, context).m
         Wm = _hip.f32(conv.NN.detach()) if conv.contextflow else None
-    x = torch.empty((B, C // 4, 2 * H, 2 * W) if unsqueeze else (B, C, H, W), device=zv.device, dtype=torch.float32)
+    return m1, Wm, m2, t, logs
+
+
+def _lds_refusal(call):
     try:
-        _hip.call("cf_affine_ctx_inv", _hip.p(zv), _hip.p(m1), _hip.p(Wm), _hip.p(m2), _hip.p(t), _hip.p(logs), _hip.p(x), B, C, H, W, zbs,
-                  int(unsqueeze), _hip.stream())
+        return call()
     except RuntimeError as e:
         if "(code -2)" in str(e):              # CF_ERR_UNSUPPORTED: the shape needs more LDS than a CU has
             raise NotImplementedError(str(e)) from None
         raise
+
+
+def affine_ctx_inverse(z, conv=None, act=None, context=None, unsqueeze=False, operands=None):
+    """[Squeeze(2,2) <-] Conv1x1(c) <- ActNorm(c') backwards in one cf_affine_ctx_inv launch: x = W_b^-1 (z exp(l_b) + t_b).  conv /
+    act: the layers (either may be None: the other one alone); operands: what affine_ctx_operands returned for them, where the
+    caller keeps it.  NotImplementedError where the per-sample matrix and the sample do not fit the LDS of a CU."""
+    zv, zbs = _hip.bview(z)
+    B, C, H, W = zv.shape
+    m1, Wm, m2, t, logs = operands if operands is not None else affine_ctx_operands(conv, act, context)
+    x = torch.empty((B, C // 4, 2 * H, 2 * W) if unsqueeze else (B, C, H, W), device=zv.device, dtype=torch.float32)
+    _lds_refusal(lambda: _hip.call("cf_affine_ctx_inv", _hip.p(zv), _hip.p(m1), _hip.p(Wm), _hip.p(m2), _hip.p(t), _hip.p(logs), _hip.p(x),
+                                   B, C, H, W, zbs, int(unsqueeze), _hip.stream()))
     return x
+
+
+def affine_ctx_inverse_vjp(gx, operands, shape, unsqueezed=False):
+    """The vector-Jacobian product of affine_ctx_inverse, one cf_affine_ctx_inv_bwd_data launch: gz = exp(l_b) (W_b^-T gx) in the
+    (B, C, H, W) = shape of the z that call was given; unsqueezed: gx has the layout of its unsqueeze=True output."""
+    B, C, H, W = shape
+    m1, Wm, m2, _, logs = operands
+    gx = _hip.f32(gx).contiguous()
+    gz = torch.empty(B, C, H, W, device=gx.device, dtype=torch.float32)
+    _lds_refusal(lambda: _hip.call("cf_affine_ctx_inv_bwd_data", _hip.p(gx), _hip.p(m1), _hip.p(Wm), _hip.p(m2), _hip.p(logs), _hip.p(gz),
+                                   B, C, H, W, int(unsqueezed), _hip.stream()))
+    return gz
 
 
 class Conv1x1(FlowLayer):

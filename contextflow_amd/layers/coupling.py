@@ -132,16 +132,12 @@ class Coupling(_AffineCoupling):
         h = conv2d_reflect(h1, self.NN[2], True)
         return conv2d_reflect(h, self.NN[4], False), logp_c
 
-    def _fused_ctx(self, x, context, tape=None, pre=None):
-        """The Coupling layer as ONE fp32-MFMA kernel (the fused flow-step kernel with an identity 1x1 / ActNorm in
-        front) with the CN(c) term as a per-sample bias: on the conditioner output (contextflow) or before its first
-        ReLU (CN(c) concatenated to the conditioner input: W[:, D:] CN(c))."""
-        code = cn_chain(self, context, pre)         # pre: formed by the grouped front end (layers/specialist.py)
-        cn = code.cn                                                                              # (B, O)
-        x, xbs = _hip.bview(x)
-        B, C, H, W = x.shape
-        D = C // 2
-        dev, st, f, pp = x.device, _hip.stream(), _hip.f32, _hip.p
+    def _ctx_step_operands(self, cn, C, H, W, dev):
+        """(mode, sbias, ws) of the fused coupling step under the code's CN(c) = cn (B, O): the per-sample bias - mode 1, cn itself on
+        the conditioner output (contextflow); mode 2, W[:, D:] cn before the first ReLU - and the packed tables with an identity
+        front, shared by the forward kernel, the inverse kernel and their backward kernels."""
+        B, D = cn.shape[0], C // 2
+        st, f, pp = _hip.stream(), _hip.f32, _hip.p
         c1, c2, c3 = self.NN[0], self.NN[2], self.NN[4]
         w1 = f(c1.weight.detach())
         if self.contextflow:
@@ -156,6 +152,35 @@ class Coupling(_AffineCoupling):
         srcs = (c1.weight, c1.bias, c2.weight, c2.bias, c3.weight, c3.bias)
         ws = _derived.get(self, "ctx_ws", _derived.key(srcs, mode, C, H, W, str(dev)),
                           lambda: identity_front_step_tables(self, w1, C, H, W, dev), dev)
+        return mode, sbias, ws
+
+    def _ctx_step_bwd_tables(self, mode, C, H, W, dev):
+        """Transposed fragments of the step-backward kernel for this coupling (identity 1x1 / ActNorm in front), kept while the three
+        weights are unchanged."""
+        f, pp = _hip.f32, _hip.p
+        c1, c2, c3 = self.NN[0], self.NN[2], self.NN[4]
+
+        def build():
+            eye = torch.eye(C, device=dev, dtype=torch.float32)
+            zero = torch.zeros(C, device=dev, dtype=torch.float32)
+            wsb = torch.empty(_hip.lib().cf_flow_step_bwd_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
+            w1 = f(c1.weight.detach())
+            w1x = w1 if mode == 1 else w1[:, :C // 2].contiguous()
+            _hip.call("cf_flow_step_bwd_prepare", pp(eye), pp(zero), pp(w1x), pp(f(c2.weight.detach())),
+                      pp(f(c3.weight.detach())), pp(wsb), C, H, W, _hip.stream())
+            return wsb
+        return _derived.get(self, "ctx_wsb", _derived.key((c1.weight, c2.weight, c3.weight), mode, C, H, W, str(dev)), build, dev)
+
+    def _fused_ctx(self, x, context, tape=None, pre=None):
+        """The Coupling layer as ONE fp32-MFMA kernel (the fused flow-step kernel with an identity 1x1 / ActNorm in
+        front) with the CN(c) term as a per-sample bias: on the conditioner output (contextflow) or before its first
+        ReLU (CN(c) concatenated to the conditioner input: W[:, D:] CN(c))."""
+        code = cn_chain(self, context, pre)         # pre: formed by the grouped front end (layers/specialist.py)
+        cn = code.cn                                                                              # (B, O)
+        x, xbs = _hip.bview(x)
+        B, C, H, W = x.shape
+        dev, st, pp = x.device, _hip.stream(), _hip.p
+        mode, sbias, ws = self._ctx_step_operands(cn, C, H, W, dev)
         z = torch.empty(B, C, H, W, device=dev, dtype=torch.float32)
         ldj = torch.zeros(B, device=dev, dtype=torch.float32)
         planes = None

@@ -1026,8 +1026,19 @@ class FlowSequential(nn.Module):
                              "returns the continuous point in front of the floor" % what)
         if return_logp:
             raise NotImplementedError("%s: return_logp=True together with differentiable=True" % what)
-        if self._has_context_nets() or context is not None:
-            raise NotImplementedError("%s: differentiable=True for a flow with context nets (a specialist flow)" % what)
+        if self._has_context_nets():
+            # a specialist flow: its context is required as everywhere; the walk refuses, by name and index, a context
+            # layer it has no rule for (TransCoupling, a Coupling outside the fused geometry)
+            self._need_context(what, context)
+        elif context is not None:
+            raise NotImplementedError("%s: differentiable=True with a context for a flow without context nets" % what)
+
+    def _run_differentiable(self, z, latents, context, noise):
+        from . import autograd_inverse
+        if not self._has_context_nets():
+            return autograd_inverse.run(self, z, latents)
+        with self._pinned(noise, context):               # the codes are formed once, here; backward reads the records
+            return autograd_inverse.run(self, z, latents, context)
 
     def inverse(self, z, context=None, noise=None, return_logp=False, differentiable=False):
         """Run every layer's `reverse` from the last to the first (the loop of flowsequential.py:35-37); groups
@@ -1042,12 +1053,14 @@ class FlowSequential(nn.Module):
         differentiable=True: the CONTINUOUS point of the walk - a flow that starts with a Dequantization stops in front of it: the
         tensor floor() would be applied to - and, when grad mode is on and z requires a gradient, with a grad_fn whose backward
         returns dL/dz (a data-only walk: no parameter gradient is formed; once differentiable).  The forward values may differ from
-        the plain walk's in rounding.  NotImplementedError with return_logp, for a flow with context nets and for a layer without a
-        rule (TransCoupling, MaskedCoupling, the activation and spline layers, an Augment over another axis)."""
+        the plain walk's in rounding.  A specialist flow takes its context and `noise` here too: the codes are formed once, in the
+        walk, the couplings run as one cf_flow_step_inv_ctx launch each, and no gradient with respect to a code or the context is
+        formed.  NotImplementedError with return_logp, with a context for a flow without context nets, and for a layer without a rule
+        (TransCoupling, MaskedCoupling, a context Coupling outside the fused geometry, the activation and spline layers, an Augment
+        over another axis)."""
         if differentiable:
-            from . import autograd_inverse
             self._refuse_differentiable("inverse", context, False, return_logp)
-            return autograd_inverse.run(self, z, None)
+            return self._run_differentiable(z, None, context, noise)
         self._refuse_logp(return_logp)
         self._need_context("inverse", context)
         with self._pinned(noise, context):
@@ -1273,8 +1286,7 @@ class FlowSequential(nn.Module):
         if isinstance(self.dist, GaussianMixtureDistribution) and tuple(z.shape[1:]) != tuple(self.dist.mG.shape[2:]):
             raise ValueError("decode: z of shape %s, the prior is over %s" % (tuple(z.shape), tuple(self.dist.mG.shape[2:])))
         if differentiable:
-            from . import autograd_inverse
-            return autograd_inverse.run(self, z, latents[:-1])
+            return self._run_differentiable(z, latents[:-1], context, noise)
         with self._pinned(noise, context):
             return self._inverse(z, context, self._pixel_range() if clamp else None, latents=latents[:-1], return_logp=return_logp)
 

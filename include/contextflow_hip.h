@@ -709,6 +709,28 @@ int cf_affine_ctx_bwd_data(const float* gz, const float* m1, const float* Wm, co
  * of LDS (4 (C (2C + 9) + 2 C H W) bytes, about).  Any alignment; z may be batch-strided.  B == 0: no-op.          */
 int cf_affine_ctx_inv(const float* z, const float* m1, const float* Wm, const float* m2, const float* t, const float* logs,
                       float* x_out, int B, int C, int H, int W, int64_t z_bstride, int out_unsqueeze, cf_stream_t stream);
+/* ---- the differentiable backward walk of a specialist flow (FlowSequential.inverse / decode with a context and
+ * differentiable=True).  Three entry points; they add symbols only: CF_ABI_VERSION stays.
+ * The vector-Jacobian product of cf_affine_ctx_inv, which is affine in z:  gz[b] = exp(l_b) * (W_b^-T gx[b])  per pixel; W_b, l_b,
+ * m1 / m2 NULL as there (no t: the shift has no gradient).  gx_unsqueezed: gx (dense) arrives in the (B, C/4, 2H, 2W) layout of the
+ * twin's out_unsqueeze output; gz is (B, C, H, W) dense.  The same in-LDS elimination of the same W_b and one refinement step
+ * g0 + W_b^-T (gx - W_b^T g0) with the residual in fp64.  C <= 256, CF_ERR_UNSUPPORTED under the twin's LDS condition.  Any
+ * alignment.  B == 0: no-op.                                                                                       */
+int cf_affine_ctx_inv_bwd_data(const float* gx, const float* m1, const float* Wm, const float* m2, const float* logs, float* gz,
+                               int B, int C, int H, int W, int gx_unsqueezed, cf_stream_t stream);
+/* The specialist Coupling backwards in ONE launch, the inverse of cf_flow_step_fwd_ctx:
+ *     x = [z0 | (z1 - tau) e^{-s}],  [tau | raw] = NN(z0) (+) CN(c),  s = 2 tanh(raw/2)
+ * ws: cf_flow_step_prepare with an identity matrix and zero t / logs; sbias / mode as cf_flow_step_fwd_ctx (1: (B, C) on the
+ * conditioner output, 2: (B, 2C) before the first ReLU).  No un-squeeze.  z, x 16-byte aligned, z_bstride % 4 == 0 (z may be a
+ * channel slice).  Shapes: those of cf_flow_step_inv.  B == 0: no-op.                                               */
+int cf_flow_step_inv_ctx(const float* z, float* x, const void* ws, const float* sbias, int mode, int B, int C, int H, int W,
+                         int64_t z_bstride, cf_stream_t stream);
+/* ... and its vector-Jacobian product at the recovered input x, gx = dL/dx (dense) -> gz = dL/dz (dense), data only:
+ *     gz1 = gx1 e^{-s},  gz0 = gx0 + (dNN/dz0)^T [ -gz1 | -gx1 x1 (1 - tanh^2(raw/2)) ]
+ * with the conditioner, bias included, recomputed from x.  wsb: cf_flow_step_bwd_prepare with an identity matrix and zero logs.
+ * x, gx, gz 16-byte aligned, x_bstride % 4 == 0.  No float atomics: two launches give the same bits.  B == 0: no-op. */
+int cf_flow_step_inv_bwd_ctx_data(const float* x, const float* gx, const void* ws, const void* wsb, const float* sbias, int mode,
+                                  float* gz, int B, int C, int H, int W, int64_t x_bstride, cf_stream_t stream);
 /* cf_flow_step_bwd_ctx without its operand planes: s_gh is not written either, gx is bitwise the same.           */
 int cf_flow_step_bwd_ctx_data(const float* x, const float* gz, const float* gld, const void* ws, const void* wsb,
                               const float* sbias, float* gx, int B, int C, int H, int W, int64_t x_bstride, cf_stream_t stream);
