@@ -1562,33 +1562,34 @@ int launch_prepare_inv(const float* Wm, const float* t, const float* logs, float
     return 0;
 }
 
-template <class G>
-int launch_step_inv(const float* z, float* x, const float* ws, const float* wsi, int B, int64_t zbs, int x_unsq, hipStream_t s) {
-    constexpr size_t lds_bytes = (size_t)G::LDS_FLOATS * sizeof(float);
-    if (lds_bytes > 64 * 1024) {
-        static std::atomic<uint64_t> raised{0};
-        if (int rc_ = cf_raise_dynamic_lds((const void*)k_flow_step_inv<G>, 160 * 1024, raised, __func__)) return rc_;
-    }
-    k_flow_step_inv<G><<<dim3((B + G::SPW - 1) / G::SPW), dim3(256), lds_bytes, s>>>(z, x, ws, wsi, B, zbs, x_unsq, nullptr);
-    return 0;
-}
-template <class G>
-int launch_step_inv_ld(const float* z, float* x, float* ld_acc, const float* ws, const float* wsi, int B, int64_t zbs, int x_unsq,
-                       hipStream_t s) {
-    constexpr size_t lds_bytes = (size_t)G::LDS_FLOATS * sizeof(float);
-    if (lds_bytes > 64 * 1024) {
-        static std::atomic<uint64_t> raised{0};
-        if (int rc_ = cf_raise_dynamic_lds((const void*)k_flow_step_inv<G, true>, 160 * 1024, raised, __func__)) return rc_;
-    }
-    k_flow_step_inv<G, true><<<dim3((B + G::SPW - 1) / G::SPW), dim3(256), lds_bytes, s>>>(z, x, ws, wsi, B, zbs, x_unsq, ld_acc);
-    return 0;
-}
+// The operands of one k_flow_step_inv launch by name - the inverse's StepArgs.  ld: the log-det accumulator of the LD form; behind ws a
+// form reads the inverse tables wsi (cf_flow_step_inv_prepare; CTX = 0) or the per-sample bias sb (CTX forms: no un-squeeze).
+struct StepInvArgs {
+    const float* z;
+    float *x, *ld = nullptr;
+    const float *ws, *wsi = nullptr, *sb = nullptr;
+    int B;
+    int64_t zbs;
+    int x_unsq = 0;
+    hipStream_t s;
+};
 
+template <class G, bool LD = false, int CTX = 0>
+int launch_step_inv(const StepInvArgs& a) {
+    constexpr size_t lds_bytes = (size_t)G::LDS_FLOATS * sizeof(float);
+    if (lds_bytes > 64 * 1024) {
+        static std::atomic<uint64_t> raised{0};
+        if (int rc_ = cf_raise_dynamic_lds((const void*)k_flow_step_inv<G, LD, CTX>, 160 * 1024, raised, __func__)) return rc_;
+    }
+    k_flow_step_inv<G, LD, CTX><<<dim3((a.B + G::SPW - 1) / G::SPW), dim3(256), lds_bytes, a.s>>>(a.z, a.x, a.ws, CTX ? a.sb : a.wsi, a.B,
+                                                                                                 a.zbs, a.x_unsq, a.ld);
+    return 0;
+}
 
 }  // namespace
 
-#ifndef CF_STEP_KERNELS_ONLY             // cf_step_inv_ctx.hip instantiates the CTX form of k_flow_step_inv from this text in a unit of its own
-
+// (host only from here.  The dispatch stands in front of the CF_STEP_KERNELS_ONLY guard: cf_step_inv_ctx.hip, which instantiates the
+// CTX form of k_flow_step_inv from this text in a unit of its own, asks the same select() for its kernel.)
 static bool direct_conv_only() {
     static const bool v = [] { const char* e = getenv("CONTEXTFLOW_DIRECT_CONV"); return e && e[0] == '1'; }();
     return v;
@@ -1603,8 +1604,9 @@ enum class Kernel {
     Rs16_G64,                                                                                                      // k_flow_step_rs16
     Inv_G8, Inv_G8w, Inv_G16, Inv_G16w, Inv_G32, Inv_G32w, Inv_G64, Inv_G64w2,                                     // k_flow_step_inv
 };
-// CtxDirect: cf_flow_step_fwd_ctx with mode | 4; Chain: cf_flow_step_fwd_chain (the kernel whose chained form runs)
-enum class Pass { Eval, Taped, Ctx, CtxDirect, CtxTaped, Chain, Inverse };
+// CtxDirect: cf_flow_step_fwd_ctx with mode | 4; Chain: cf_flow_step_fwd_chain (the kernel whose chained form runs);
+// InverseCtx: cf_flow_step_inv_ctx (cf_step_inv_ctx.hip)
+enum class Pass { Eval, Taped, Ctx, CtxDirect, CtxTaped, Chain, Inverse, InverseCtx };
 
 // Batch thresholds.  Small batches are latency-bound by the serial work of ONE workgroup (a launch of < 256 workgroups leaves CUs
 // idle anyway): below these, the geometry with half the samples per workgroup (same packed-weight workspace) ...
@@ -1637,14 +1639,17 @@ static int chain_max_batch(int sid) {
 static Kernel select(Pass pass, int sid, int B) {
     const bool direct = direct_conv_only() || pass == Pass::CtxDirect;
     const bool eval = pass == Pass::Eval, ctx = pass == Pass::Ctx || pass == Pass::CtxDirect;
-    if (pass == Pass::Inverse)           // the conditioner is the forward's: Winograd form of its 3x3 at every batch size
-        switch (sid) {
-            case 0: return direct ? Kernel::Inv_G8 : Kernel::Inv_G8w;
-            case 1: return direct ? Kernel::Inv_G16 : Kernel::Inv_G16w;
-            case 2: return direct ? Kernel::Inv_G32 : Kernel::Inv_G32w;
-            case 3: return direct ? Kernel::Inv_G64 : Kernel::Inv_G64w2;
+    if (pass == Pass::Inverse || pass == Pass::InverseCtx) {      // the conditioner is the forward's: Winograd form of its 3x3 at every
+        const bool ictx = pass == Pass::InverseCtx;               // batch size.  InverseCtx: whatever CONTEXTFLOW_DIRECT_CONV says, and the
+        const bool d = direct && !ictx;                           // direct geometry at C = 8, whose Winograd geometry (16-row phases) has no
+        switch (sid) {                                            // bias path - as the forward's launch_fwd_ctx
+            case 0: return d || ictx ? Kernel::Inv_G8 : Kernel::Inv_G8w;
+            case 1: return d ? Kernel::Inv_G16 : Kernel::Inv_G16w;
+            case 2: return d ? Kernel::Inv_G32 : Kernel::Inv_G32w;
+            case 3: return d ? Kernel::Inv_G64 : Kernel::Inv_G64w2;
             default: return Kernel::None;
         }
+    }
     if (pass == Pass::CtxTaped)          // (its backward is cf_flow_step_bwd_taped: direct, one geometry per shape)
         switch (sid) {
             case 0: return Kernel::Step_G8;
@@ -1676,6 +1681,18 @@ static Kernel select(Pass pass, int sid, int B) {
     return Kernel::None;
 }
 
+// A kernel that a pass's launch list does not hold is a bug in select().
+static int not_built(const char* fn, Kernel k) {
+    cf_set_error("%s: kernel %d is not built for this pass", fn, (int)k);
+    return CF_ERR_UNSUPPORTED;
+}
+static int unsupported_shape(const char* fn, int C, int H, int W) {
+    cf_set_error("%s: shape (%d,%d,%d) unsupported", fn, C, H, W);
+    return CF_ERR_UNSUPPORTED;
+}
+
+#ifndef CF_STEP_KERNELS_ONLY             // cf_step_inv_ctx.hip: the kernels and the dispatch above, a launch list of its own
+
 // Multiply-adds per pixel and C^2 of a kernel's step, from its geometry's own traits: the direct form runs C^2 (Conv1x1) + C^2 +
 // 36 C^2 + 2 C^2 = 40 C^2, the Winograd form of the 3x3 runs 16 instead of 36 C^2 (F(2x2, 3x3)) or 12 C^2 (F(2x4, 3x3)).
 template <class G> constexpr int step_macs_c2hw() { return G::W24 ? 16 : G::WINO ? 20 : 40; }
@@ -1701,11 +1718,7 @@ static int step_macs_c2hw(Kernel k) {
 }
 
 // Launch lists, one per pass: exactly the template combinations the library builds (a 160 KB k_flow_step instantiation is
-// minutes of compile time).  A kernel that a pass does not list is a bug in select().
-static int not_built(const char* fn, Kernel k) {
-    cf_set_error("%s: kernel %d is not built for this pass", fn, (int)k);
-    return CF_ERR_UNSUPPORTED;
-}
+// minutes of compile time).  A kernel that a pass does not list is a bug in select() (not_built).
 static int launch_fwd(Kernel k, const StepArgs& a) {         // evaluation forward, and the test hook without dumps
     switch (k) {
         case Kernel::Small_G8s: return launch_step_small<G8s>(a);
@@ -1804,38 +1817,24 @@ static int level_min_batch(int sid) {
     }
     return 0;
 }
-static int launch_inv(Kernel k, const float* z, float* x, const float* ws, const float* wsi, int B, int64_t zbs, int x_unsq, hipStream_t s) {
+// the inverse step; LD: with the log-det of the step next to x (cf_flow_step_inv_ld) - the dispatch's choice, its flagged twin
+template <bool LD>
+static int launch_inv(Kernel k, const StepInvArgs& a) {
     switch (k) {
-        case Kernel::Inv_G8: return launch_step_inv<G8>(z, x, ws, wsi, B, zbs, x_unsq, s);
-        case Kernel::Inv_G8w: return launch_step_inv<G8w>(z, x, ws, wsi, B, zbs, x_unsq, s);
-        case Kernel::Inv_G16: return launch_step_inv<G16>(z, x, ws, wsi, B, zbs, x_unsq, s);
-        case Kernel::Inv_G16w: return launch_step_inv<G16w>(z, x, ws, wsi, B, zbs, x_unsq, s);
-        case Kernel::Inv_G32: return launch_step_inv<G32>(z, x, ws, wsi, B, zbs, x_unsq, s);
-        case Kernel::Inv_G32w: return launch_step_inv<G32w>(z, x, ws, wsi, B, zbs, x_unsq, s);
-        case Kernel::Inv_G64: return launch_step_inv<G64>(z, x, ws, wsi, B, zbs, x_unsq, s);
-        case Kernel::Inv_G64w2: return launch_step_inv<G64w2>(z, x, ws, wsi, B, zbs, x_unsq, s);
+        case Kernel::Inv_G8: return launch_step_inv<G8, LD>(a);
+        case Kernel::Inv_G8w: return launch_step_inv<G8w, LD>(a);
+        case Kernel::Inv_G16: return launch_step_inv<G16, LD>(a);
+        case Kernel::Inv_G16w: return launch_step_inv<G16w, LD>(a);
+        case Kernel::Inv_G32: return launch_step_inv<G32, LD>(a);
+        case Kernel::Inv_G32w: return launch_step_inv<G32w, LD>(a);
+        case Kernel::Inv_G64: return launch_step_inv<G64, LD>(a);
+        case Kernel::Inv_G64w2: return launch_step_inv<G64w2, LD>(a);
         default: return not_built(__func__, k);
     }
 }
-// the same kernel with the log-det of the step next to x (cf_flow_step_inv_ld): the dispatch's choice, its flagged twin
-static int launch_inv_ld(Kernel k, const float* z, float* x, float* ld, const float* ws, const float* wsi, int B, int64_t zbs, int x_unsq,
-                         hipStream_t s) {
-    switch (k) {
-        case Kernel::Inv_G8: return launch_step_inv_ld<G8>(z, x, ld, ws, wsi, B, zbs, x_unsq, s);
-        case Kernel::Inv_G8w: return launch_step_inv_ld<G8w>(z, x, ld, ws, wsi, B, zbs, x_unsq, s);
-        case Kernel::Inv_G16: return launch_step_inv_ld<G16>(z, x, ld, ws, wsi, B, zbs, x_unsq, s);
-        case Kernel::Inv_G16w: return launch_step_inv_ld<G16w>(z, x, ld, ws, wsi, B, zbs, x_unsq, s);
-        case Kernel::Inv_G32: return launch_step_inv_ld<G32>(z, x, ld, ws, wsi, B, zbs, x_unsq, s);
-        case Kernel::Inv_G32w: return launch_step_inv_ld<G32w>(z, x, ld, ws, wsi, B, zbs, x_unsq, s);
-        case Kernel::Inv_G64: return launch_step_inv_ld<G64>(z, x, ld, ws, wsi, B, zbs, x_unsq, s);
-        case Kernel::Inv_G64w2: return launch_step_inv_ld<G64w2>(z, x, ld, ws, wsi, B, zbs, x_unsq, s);
-        default: return not_built(__func__, k);
-    }
-}
-static int unsupported_shape(const char* fn, int C, int H, int W) {
-    cf_set_error("%s: shape (%d,%d,%d) unsupported", fn, C, H, W);
-    return CF_ERR_UNSUPPORTED;
-}
+// (instantiated here, the plain form first: the sixteen kernels keep their place in the code object, whose assembly is what it was)
+template int launch_inv<false>(Kernel, const StepInvArgs&);
+template int launch_inv<true>(Kernel, const StepInvArgs&);
 
 // test hook: (shape, variant = flags bits 16..19) -> kernel.  0: the default geometry of the shape in k_flow_step (the only one
 // with per-phase dumps besides 3), 2: half the samples per workgroup, 3: k_flow_step_small in the direct form, 4: Winograd
@@ -1978,7 +1977,9 @@ int cf_flow_step_inv(const float* z, float* x, const void* ws, const void* wsi, 
     CF_REQUIRE((reinterpret_cast<uintptr_t>(z) & 15) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0);
     const Kernel k = select(Pass::Inverse, shape_id(C, H, W), B);
     if (k == Kernel::None) return unsupported_shape(__func__, C, H, W);
-    if (int rc = launch_inv(k, z, x, (const float*)ws, (const float*)wsi, B, z_bstride, x_unsqueezed, cf_s(stream))) return rc;
+    if (int rc = launch_inv<false>(k, StepInvArgs{.z = z, .x = x, .ws = (const float*)ws, .wsi = (const float*)wsi, .B = B, .zbs = z_bstride,
+                                                  .x_unsq = x_unsqueezed, .s = cf_s(stream)}))
+        return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }
@@ -1990,7 +1991,9 @@ int cf_flow_step_inv_ld(const float* z, float* x, float* ld_acc, const void* ws,
     CF_REQUIRE((reinterpret_cast<uintptr_t>(z) & 15) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0);
     const Kernel k = select(Pass::Inverse, shape_id(C, H, W), B);
     if (k == Kernel::None) return unsupported_shape(__func__, C, H, W);
-    if (int rc = launch_inv_ld(k, z, x, ld_acc, (const float*)ws, (const float*)wsi, B, z_bstride, x_unsqueezed, cf_s(stream))) return rc;
+    if (int rc = launch_inv<true>(k, StepInvArgs{.z = z, .x = x, .ld = ld_acc, .ws = (const float*)ws, .wsi = (const float*)wsi, .B = B,
+                                                 .zbs = z_bstride, .x_unsq = x_unsqueezed, .s = cf_s(stream)}))
+        return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }

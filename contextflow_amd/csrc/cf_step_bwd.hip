@@ -923,20 +923,6 @@ int launch_prepare_bwd(const StepPackBwdBatch& pb, int n, hipStream_t s) {
     return 0;
 }
 
-template <class G, bool CTX, bool DATA = false, bool INV = false, int IB = 0>
-int launch_step_bwd(const float* x, const float* gz, const float* gld, const float* ws, const float* wsb, float* gx,
-                    float* s_y0, float* s_h1, float* s_h2, float* s_gh, float* s_gh2, float* s_gh1, float* s_gy, int B,
-                    int64_t xbs, hipStream_t s, const float* sb = nullptr, StepTape tp = kNoTape, int gx_unsq = 0) {
-    constexpr size_t lds_bytes = (size_t)G::LDS_FLOATS * sizeof(float);
-    if (lds_bytes > 64 * 1024) {
-        static std::atomic<uint64_t> raised{0};
-        if (int rc_ = cf_raise_dynamic_lds((const void*)k_flow_step_bwd<G, CTX, DATA, INV, IB>, 160 * 1024, raised, __func__)) return rc_;
-    }
-    k_flow_step_bwd<G, CTX, DATA, INV, IB><<<dim3((B + G::SPW - 1) / G::SPW), dim3(256), lds_bytes, s>>>(
-        x, gz, gld, ws, wsb, gx, s_y0, s_h1, s_h2, s_gh, s_gh2, s_gh1, s_gy, B, xbs, sb, tp, gx_unsq);
-    return 0;
-}
-
 // the backward uses the smaller tiles (2 workgroups/CU at C = 64): its register footprint is larger than the forward's
 // 16x16 / 8x8: fold slots behind every plane row (PATCH); 8x8 with 2 samples per workgroup so that two workgroups share a CU
 using B8 = Geo<8, 16, 16, 1, 1, 0, 1>;
@@ -944,9 +930,89 @@ using B16 = Geo<16, 16, 16, 1, 1, 0, 1>;
 using B32 = Geo<32, 8, 8, 2, 1, 0, 1>;
 using B64 = Geo<64, 4, 4, 8, 1>;
 
+// ---- launch: one argument record, one check and one dispatch for every entry point of the family ------------------------------
+// The operands of k_flow_step_bwd by name (the comment above the kernel says which form reads which; INV: gz is d/dx, gx d/dz).
+struct StepBwdArgs {
+    const float *x = nullptr, *gz = nullptr, *gld = nullptr, *ws = nullptr, *wsb = nullptr;
+    float* gx = nullptr;
+    float *s_y0 = nullptr, *s_h1 = nullptr, *s_h2 = nullptr, *s_gh = nullptr, *s_gh2 = nullptr, *s_gh1 = nullptr, *s_gy = nullptr;
+    int B = 0;
+    int64_t xbs = 0;
+    hipStream_t s = nullptr;
+    // The kernel's `sb`: the per-sample bias CN(c), (B, C) or (B, 2C), of the CTX forms and of INV with IB = 1 / 2; in INV with IB = 0
+    // (no per-sample bias) the fragments of diag(e^{logs}) Wm^-T that cf_flow_step_inv_bwd_prepare packs (wsv).  The launch casts.
+    const void* bias_or_wsv = nullptr;
+    StepTape tp = kNoTape;          // taped forms: the aux buffer of the training forward's tape (the planes are cf_wgrad's operands)
+    int gx_unsq = 0;
+};
+
+// What the form <CTX, DATA, INV, IB> requires of its record and of the shape; the error text names the entry point `fn`.  Every
+// pointer the form dereferences is there; x, gz, gx, the aux buffer and wsv are read or written as float4, across samples too.
+template <bool CTX, bool DATA, bool INV, int IB>
+int check_step_bwd(const char* fn, const StepBwdArgs& a, int C, int H, int W) {
+    auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const bool ptrs = a.gz && a.wsb && a.gx && (INV || a.gld) &&
+                      (CTX ? a.x && a.ws && a.bias_or_wsv && (DATA || a.s_gh)          // (the other planes are not written in this mode)
+                           : a.tp.ls && (DATA || (a.s_gh && a.s_gh2 && a.s_gh1 && a.s_gy)));
+    const bool layout = al(a.gz) && al(a.gx) &&
+                        (CTX ? al(a.x) && a.xbs >= (int64_t)C * H * W && a.xbs % 4 == 0 && (!INV || IB || al(a.bias_or_wsv))
+                             : al(a.tp.ls) && (!a.gx_unsq || C % 4 == 0));
+    if (!ptrs || !layout) {
+        cf_set_error("%s: requirement failed: %s", fn, !ptrs ? "an operand of this form is null" : "stride, layout or 16-byte alignment");
+        return CF_ERR_ARG;
+    }
+    if (shape_id(C, H, W) >= 0) return 0;
+    cf_set_error("%s: shape (%d,%d,%d) unsupported", fn, C, H, W);
+    return CF_ERR_UNSUPPORTED;
+}
+
+template <class G, bool CTX, bool DATA = false, bool INV = false, int IB = 0>
+int launch_step_bwd(const StepBwdArgs& a) {
+    constexpr size_t lds_bytes = (size_t)G::LDS_FLOATS * sizeof(float);
+    if (lds_bytes > 64 * 1024) {
+        static std::atomic<uint64_t> raised{0};
+        if (int rc_ = cf_raise_dynamic_lds((const void*)k_flow_step_bwd<G, CTX, DATA, INV, IB>, 160 * 1024, raised, __func__)) return rc_;
+    }
+    k_flow_step_bwd<G, CTX, DATA, INV, IB><<<dim3((a.B + G::SPW - 1) / G::SPW), dim3(256), lds_bytes, a.s>>>(
+        a.x, a.gz, a.gld, a.ws, a.wsb, a.gx, a.s_y0, a.s_h1, a.s_h2, a.s_gh, a.s_gh2, a.s_gh1, a.s_gy, a.B, a.xbs, (const float*)a.bias_or_wsv, a.tp,
+        a.gx_unsq);
+    return 0;
+}
+
+// The 4x4 level of the taped forms up to CF_BWD_RS16_MAXB samples: one sample per workgroup, B workgroups instead of B / 8.
+// false: the batch is the tile form's, nothing was launched.
+template <bool DATA>
+bool launch_step_bwd_rs16(const StepBwdArgs& a) {
+    if (a.B > CF_BWD_RS16_MAXB) return false;
+    k_flow_step_bwd_rs16<B64, DATA><<<dim3(a.B), dim3(256), 0, a.s>>>(a.gz, a.gld, a.wsb, a.gx, a.s_gh, a.s_gh2, a.s_gh1, a.s_gy, a.B, a.tp,
+                                                                    a.gx_unsq);
+    return true;
+}
+
+// One geometry per shape id (check_step_bwd has refused the others); the taped forms have a second kernel at 4x4.
+template <bool CTX, bool DATA = false, bool INV = false, int IB = 0>
+int launch_bwd(int sid, const StepBwdArgs& a) {
+    switch (sid) {
+        case 0: return launch_step_bwd<B8, CTX, DATA, INV, IB>(a);
+        case 1: return launch_step_bwd<B16, CTX, DATA, INV, IB>(a);
+        case 2: return launch_step_bwd<B32, CTX, DATA, INV, IB>(a);
+        case 3:
+            if constexpr (!CTX)
+                if (launch_step_bwd_rs16<DATA>(a)) return 0;
+            return launch_step_bwd<B64, CTX, DATA, INV, IB>(a);
+    }
+    return CF_ERR_UNSUPPORTED;
+}
+
 }  // namespace
 
 #ifndef CF_STEP_BWD_KERNELS_ONLY         // cf_step_inv_bwd.hip / cf_step_inv_ctx_bwd.hip instantiate the INV forms from this text in units of their own
+
+// the tape as the backward kernels see it: the aux buffer alone
+static StepTape aux_tape(const void* t_aux, int B, int C, int H, int W) {
+    constexpr float* none = nullptr;
+    return t_aux ? make_tape(none, none, none, const_cast<void*>(t_aux), B, C, H, W) : kNoTape;
+}
 
 extern "C" {
 
@@ -998,28 +1064,11 @@ int cf_flow_step_bwd_taped(const float* gz, const float* gld, const void* wsb, c
                            float* s_gh2, float* s_gh1, float* s_gy, int B, int C, int H, int W, int gx_unsqueezed,
                            cf_stream_t stream) {
     if (B == 0) return 0;
-    CF_REQUIRE(gz && gld && wsb && t_aux && gx && s_gh && s_gh2 && s_gh1 && s_gy && (!gx_unsqueezed || C % 4 == 0));
-    CF_REQUIRE((reinterpret_cast<uintptr_t>(gz) & 15) == 0 && (reinterpret_cast<uintptr_t>(gx) & 15) == 0 &&
-               (reinterpret_cast<uintptr_t>(t_aux) & 15) == 0);
-    const float* wb = (const float*)wsb;
-    const StepTape tp = make_tape(nullptr, nullptr, nullptr, const_cast<void*>(t_aux), B, C, H, W);
-    int rc = 0;
-#define CF_BWDT(G) rc = launch_step_bwd<G, false>(nullptr, gz, gld, nullptr, wb, gx, nullptr, nullptr, nullptr, s_gh, s_gh2, \
-                                                s_gh1, s_gy, B, (int64_t)C * H * W, cf_s(stream), nullptr, tp, gx_unsqueezed != 0)
-    switch (shape_id(C, H, W)) {
-        case 0: CF_BWDT(B8); break;
-        case 1: CF_BWDT(B16); break;
-        case 2: CF_BWDT(B32); break;
-        case 3:
-            if (B <= CF_BWD_RS16_MAXB)      // one sample per workgroup: B workgroups instead of B / 8
-                k_flow_step_bwd_rs16<B64><<<dim3(B), dim3(256), 0, cf_s(stream)>>>(gz, gld, wb, gx, s_gh, s_gh2, s_gh1, s_gy, B, tp,
-                                                                                  gx_unsqueezed != 0);
-            else CF_BWDT(B64);
-            break;
-        default: cf_set_error("cf_flow_step_bwd_taped: shape (%d,%d,%d) unsupported", C, H, W); return CF_ERR_UNSUPPORTED;
-    }
-#undef CF_BWDT
-    if (rc) return rc;
+    const StepBwdArgs a{.gz = gz, .gld = gld, .wsb = (const float*)wsb, .gx = gx, .s_gh = s_gh, .s_gh2 = s_gh2, .s_gh1 = s_gh1,
+                        .s_gy = s_gy, .B = B, .xbs = (int64_t)C * H * W, .s = cf_s(stream), .tp = aux_tape(t_aux, B, C, H, W),
+                        .gx_unsq = gx_unsqueezed != 0};
+    if (int rc = check_step_bwd<false, false, false, 0>(__func__, a, C, H, W)) return rc;
+    if (int rc = launch_bwd<false>(shape_id(C, H, W), a)) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }
@@ -1029,28 +1078,10 @@ int cf_flow_step_bwd_taped(const float* gz, const float* gld, const void* wsb, c
 int cf_flow_step_bwd_data(const float* gz, const float* gld, const void* wsb, const void* t_aux, float* gx, int B, int C, int H,
                           int W, int gx_unsqueezed, cf_stream_t stream) {
     if (B == 0) return 0;
-    CF_REQUIRE(gz && gld && wsb && t_aux && gx && (!gx_unsqueezed || C % 4 == 0));
-    CF_REQUIRE((reinterpret_cast<uintptr_t>(gz) & 15) == 0 && (reinterpret_cast<uintptr_t>(gx) & 15) == 0 &&
-               (reinterpret_cast<uintptr_t>(t_aux) & 15) == 0);
-    const float* wb = (const float*)wsb;
-    const StepTape tp = make_tape(nullptr, nullptr, nullptr, const_cast<void*>(t_aux), B, C, H, W);
-    int rc = 0;
-#define CF_BWDD(G) rc = launch_step_bwd<G, false, true>(nullptr, gz, gld, nullptr, wb, gx, nullptr, nullptr, nullptr, nullptr, nullptr, \
-                                                      nullptr, nullptr, B, (int64_t)C * H * W, cf_s(stream), nullptr, tp, gx_unsqueezed != 0)
-    switch (shape_id(C, H, W)) {
-        case 0: CF_BWDD(B8); break;
-        case 1: CF_BWDD(B16); break;
-        case 2: CF_BWDD(B32); break;
-        case 3:
-            if (B <= CF_BWD_RS16_MAXB)      // one sample per workgroup, as cf_flow_step_bwd_taped
-                k_flow_step_bwd_rs16<B64, true><<<dim3(B), dim3(256), 0, cf_s(stream)>>>(gz, gld, wb, gx, nullptr, nullptr, nullptr, nullptr, B,
-                                                                                        tp, gx_unsqueezed != 0);
-            else CF_BWDD(B64);
-            break;
-        default: cf_set_error("cf_flow_step_bwd_data: shape (%d,%d,%d) unsupported", C, H, W); return CF_ERR_UNSUPPORTED;
-    }
-#undef CF_BWDD
-    if (rc) return rc;
+    const StepBwdArgs a{.gz = gz, .gld = gld, .wsb = (const float*)wsb, .gx = gx, .B = B, .xbs = (int64_t)C * H * W, .s = cf_s(stream),
+                        .tp = aux_tape(t_aux, B, C, H, W), .gx_unsq = gx_unsqueezed != 0};
+    if (int rc = check_step_bwd<false, true, false, 0>(__func__, a, C, H, W)) return rc;
+    if (int rc = launch_bwd<false, true>(shape_id(C, H, W), a)) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }
@@ -1061,22 +1092,11 @@ int cf_flow_step_bwd_ctx(const float* x, const float* gz, const float* gld, cons
                          const float* sbias, float* gx, float* s_y0, float* s_h1, float* s_h2, float* s_gh, float* s_gh2,
                          float* s_gh1, float* s_gy, int B, int C, int H, int W, int64_t x_bstride, cf_stream_t stream) {
     if (B == 0) return 0;
-    CF_REQUIRE(x && gz && gld && ws && wsb && sbias && gx && s_gh);     // the other planes are not written in this mode
-    CF_REQUIRE(x_bstride >= (int64_t)C * H * W && x_bstride % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-               (reinterpret_cast<uintptr_t>(gz) & 15) == 0 && (reinterpret_cast<uintptr_t>(gx) & 15) == 0);
-    const float* w = (const float*)ws;
-    const float* wb = (const float*)wsb;
-    int rc = 0;
-#define CF_BWDC(G) rc = launch_step_bwd<G, true>(x, gz, gld, w, wb, gx, s_y0, s_h1, s_h2, s_gh, s_gh2, s_gh1, s_gy, B, x_bstride, cf_s(stream), sbias)
-    switch (shape_id(C, H, W)) {
-        case 0: CF_BWDC(B8); break;
-        case 1: CF_BWDC(B16); break;
-        case 2: CF_BWDC(B32); break;
-        case 3: CF_BWDC(B64); break;
-        default: cf_set_error("cf_flow_step_bwd_ctx: shape (%d,%d,%d) unsupported", C, H, W); return CF_ERR_UNSUPPORTED;
-    }
-#undef CF_BWDC
-    if (rc) return rc;
+    const StepBwdArgs a{.x = x, .gz = gz, .gld = gld, .ws = (const float*)ws, .wsb = (const float*)wsb, .gx = gx, .s_y0 = s_y0,
+                        .s_h1 = s_h1, .s_h2 = s_h2, .s_gh = s_gh, .s_gh2 = s_gh2, .s_gh1 = s_gh1, .s_gy = s_gy, .B = B,
+                        .xbs = x_bstride, .s = cf_s(stream), .bias_or_wsv = sbias};
+    if (int rc = check_step_bwd<true, false, false, 0>(__func__, a, C, H, W)) return rc;
+    if (int rc = launch_bwd<true>(shape_id(C, H, W), a)) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }
@@ -1086,23 +1106,10 @@ int cf_flow_step_bwd_ctx(const float* x, const float* gz, const float* gld, cons
 int cf_flow_step_bwd_ctx_data(const float* x, const float* gz, const float* gld, const void* ws, const void* wsb,
                               const float* sbias, float* gx, int B, int C, int H, int W, int64_t x_bstride, cf_stream_t stream) {
     if (B == 0) return 0;
-    CF_REQUIRE(x && gz && gld && ws && wsb && sbias && gx);
-    CF_REQUIRE(x_bstride >= (int64_t)C * H * W && x_bstride % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-               (reinterpret_cast<uintptr_t>(gz) & 15) == 0 && (reinterpret_cast<uintptr_t>(gx) & 15) == 0);
-    const float* w = (const float*)ws;
-    const float* wb = (const float*)wsb;
-    int rc = 0;
-#define CF_BWDCD(G) rc = launch_step_bwd<G, true, true>(x, gz, gld, w, wb, gx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, \
-                                                       nullptr, B, x_bstride, cf_s(stream), sbias)
-    switch (shape_id(C, H, W)) {
-        case 0: CF_BWDCD(B8); break;
-        case 1: CF_BWDCD(B16); break;
-        case 2: CF_BWDCD(B32); break;
-        case 3: CF_BWDCD(B64); break;
-        default: cf_set_error("cf_flow_step_bwd_ctx_data: shape (%d,%d,%d) unsupported", C, H, W); return CF_ERR_UNSUPPORTED;
-    }
-#undef CF_BWDCD
-    if (rc) return rc;
+    const StepBwdArgs a{.x = x, .gz = gz, .gld = gld, .ws = (const float*)ws, .wsb = (const float*)wsb, .gx = gx, .B = B,
+                        .xbs = x_bstride, .s = cf_s(stream), .bias_or_wsv = sbias};
+    if (int rc = check_step_bwd<true, true, false, 0>(__func__, a, C, H, W)) return rc;
+    if (int rc = launch_bwd<true, true>(shape_id(C, H, W), a)) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }

@@ -1,7 +1,8 @@
 // The vector-Jacobian product of the inverse flow step: the INV form of k_flow_step_bwd (cf_step_bwd.hip), instantiated in a
 // translation unit of its own.  Built next to the training and score forms it moves the register allocation of one of THEM
 // (k_flow_step_bwd<B64, taped>: 190 -> 189 VGPRs; profiles/decode_grad.md) although no line of their bodies changes - here they
-// compile to what they were.
+// compile to what they were.  The argument record, the check and the dispatch (StepBwdArgs, check_step_bwd, launch_bwd) are the
+// family's, from that text: this unit holds the entry point alone.
 #define CF_STEP_BWD_KERNELS_ONLY 1
 #include "cf_step_bwd.hip"
 
@@ -14,24 +15,12 @@ extern "C" {
 int cf_flow_step_inv_bwd_data(const float* x, const float* gx, const void* ws, const void* wsb, const void* wsv, float* gz,
                               int B, int C, int H, int W, int64_t x_bstride, cf_stream_t stream) {
     if (B == 0) return 0;
-    CF_REQUIRE(x && gx && ws && wsb && wsv && gz && B >= 0);
-    CF_REQUIRE(x_bstride >= (int64_t)C * H * W && x_bstride % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-               (reinterpret_cast<uintptr_t>(gx) & 15) == 0 && (reinterpret_cast<uintptr_t>(gz) & 15) == 0 &&
-               (reinterpret_cast<uintptr_t>(wsv) & 15) == 0);
-    const float* w = (const float*)ws;
-    const float* wb = (const float*)wsb;
-    int rc = 0;
-#define CF_BWDI(G) rc = launch_step_bwd<G, true, true, true>(x, gx, nullptr, w, wb, gz, nullptr, nullptr, nullptr, nullptr, nullptr, \
-                                                             nullptr, nullptr, B, x_bstride, cf_s(stream), (const float*)wsv)
-    switch (shape_id(C, H, W)) {
-        case 0: CF_BWDI(B8); break;
-        case 1: CF_BWDI(B16); break;
-        case 2: CF_BWDI(B32); break;
-        case 3: CF_BWDI(B64); break;
-        default: cf_set_error("cf_flow_step_inv_bwd_data: shape (%d,%d,%d) unsupported", C, H, W); return CF_ERR_UNSUPPORTED;
-    }
-#undef CF_BWDI
-    if (rc) return rc;
+    CF_REQUIRE(B >= 0);
+    // the kernel's upstream / result slots: it is given d/dx and writes d/dz
+    const StepBwdArgs a{.x = x, .gz = gx, .ws = (const float*)ws, .wsb = (const float*)wsb, .gx = gz, .B = B, .xbs = x_bstride,
+                        .s = cf_s(stream), .bias_or_wsv = wsv};
+    if (int rc = check_step_bwd<true, true, true, 0>(__func__, a, C, H, W)) return rc;
+    if (int rc = launch_bwd<true, true, true>(shape_id(C, H, W), a)) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }

@@ -1,8 +1,21 @@
 // The vector-Jacobian product of the specialist coupling's inverse (cf_flow_step_inv_ctx): the INV form of k_flow_step_bwd
 // (cf_step_bwd.hip) with the per-sample bias in its recompute (IB), in a translation unit of its own for the reason
-// cf_step_inv_bwd.hip gives - the kernels of the other units compile to what they were.
+// cf_step_inv_bwd.hip gives - the kernels of the other units compile to what they were.  Record, check and dispatch are the
+// family's (StepBwdArgs, check_step_bwd, launch_bwd): this unit holds the entry point alone.
 #define CF_STEP_BWD_KERNELS_ONLY 1
 #include "cf_step_bwd.hip"
+
+namespace {
+// the eight instantiations of this unit, in the order their kernels have in its code object (the two modes of a geometry side by side)
+template int launch_step_bwd<B8, true, true, true, 1>(const StepBwdArgs&);
+template int launch_step_bwd<B8, true, true, true, 2>(const StepBwdArgs&);
+template int launch_step_bwd<B16, true, true, true, 1>(const StepBwdArgs&);
+template int launch_step_bwd<B16, true, true, true, 2>(const StepBwdArgs&);
+template int launch_step_bwd<B32, true, true, true, 1>(const StepBwdArgs&);
+template int launch_step_bwd<B32, true, true, true, 2>(const StepBwdArgs&);
+template int launch_step_bwd<B64, true, true, true, 1>(const StepBwdArgs&);
+template int launch_step_bwd<B64, true, true, true, 2>(const StepBwdArgs&);
+}  // namespace
 
 extern "C" {
 
@@ -15,26 +28,13 @@ extern "C" {
 int cf_flow_step_inv_bwd_ctx_data(const float* x, const float* gx, const void* ws, const void* wsb, const float* sbias,
                                   int mode, float* gz, int B, int C, int H, int W, int64_t x_bstride, cf_stream_t stream) {
     if (B == 0) return 0;
-    CF_REQUIRE(x && gx && ws && wsb && sbias && gz && B >= 0 && (mode == 1 || mode == 2));
-    CF_REQUIRE(x_bstride >= (int64_t)C * H * W && x_bstride % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-               (reinterpret_cast<uintptr_t>(gx) & 15) == 0 && (reinterpret_cast<uintptr_t>(gz) & 15) == 0);
-    const float* w = (const float*)ws;
-    const float* wb = (const float*)wsb;
-    int rc = 0;
-#define CF_BWDIC(G)                                                                                                                     \
-    rc = mode == 1 ? launch_step_bwd<G, true, true, true, 1>(x, gx, nullptr, w, wb, gz, nullptr, nullptr, nullptr, nullptr, nullptr,   \
-                                                            nullptr, nullptr, B, x_bstride, cf_s(stream), sbias)                      \
-                   : launch_step_bwd<G, true, true, true, 2>(x, gx, nullptr, w, wb, gz, nullptr, nullptr, nullptr, nullptr, nullptr,   \
-                                                            nullptr, nullptr, B, x_bstride, cf_s(stream), sbias)
-    switch (shape_id(C, H, W)) {
-        case 0: CF_BWDIC(B8); break;
-        case 1: CF_BWDIC(B16); break;
-        case 2: CF_BWDIC(B32); break;
-        case 3: CF_BWDIC(B64); break;
-        default: cf_set_error("cf_flow_step_inv_bwd_ctx_data: shape (%d,%d,%d) unsupported", C, H, W); return CF_ERR_UNSUPPORTED;
-    }
-#undef CF_BWDIC
-    if (rc) return rc;
+    CF_REQUIRE(B >= 0 && (mode == 1 || mode == 2));
+    // the kernel's upstream / result slots: it is given d/dx and writes d/dz
+    const StepBwdArgs a{.x = x, .gz = gx, .ws = (const float*)ws, .wsb = (const float*)wsb, .gx = gz, .B = B, .xbs = x_bstride,
+                        .s = cf_s(stream), .bias_or_wsv = sbias};
+    if (int rc = check_step_bwd<true, true, true, 1>(__func__, a, C, H, W)) return rc;          // (the two modes require the same)
+    const int sid = shape_id(C, H, W);
+    if (int rc = mode == 1 ? launch_bwd<true, true, true, 1>(sid, a) : launch_bwd<true, true, true, 2>(sid, a)) return rc;
     CF_LAUNCH_CHECK();
     return 0;
 }

@@ -96,7 +96,7 @@ class Layer(NamedTuple):
 # Gaussian draw of a flow-type encoder (flowlayer.encoder_noise) or None
 class Permute(NamedTuple):
     kind = "permute"
-    inverse: tuple           # PermuteAxes.inverse_permutation
+    inverse: tuple           # undoes the map the pass applied: PermuteAxes.inverse_permutation (.permutation on the backward walk)
 
 
 class CtxAffine(NamedTuple):
@@ -145,6 +145,79 @@ class CtxMixture(NamedTuple):
     context: Any
     lp: Any                  # per-component log-joints of the forward
     tab: Any                 # (key, inv, dsig, lsum) scale tables of the embedding-lookup form, or None
+
+
+# ---- the differentiable backward walk (autograd_inverse.walk writes one per inverted group, autograd_inverse.VJP holds the rule of
+# each kind).  Besides these the walk writes Squeeze, and Permute with the layer's FORWARD permutation - the inverse of the map the
+# walk applied.
+class InvStep(NamedTuple):
+    """Conv1x1 <- ActNorm <- Coupling inverted by one kernel (cf_flow_step_inv)"""
+    kind = "inv_step"
+    conv: Any
+    act: Any
+    cpl: Any
+    x: Any                   # the recovered step input
+
+
+class InvTail(NamedTuple):
+    """the pre-processing tail, in front of a Dequantization"""
+    kind = "inv_tail"
+    y: Any                   # the tail's input in the walk (the logits)
+    keep: int                # channels behind the Augment's reverse
+    s12: float               # product of the two Normalizations' scales
+
+
+class InvSplit(NamedTuple):
+    """SplitPrior.reverse: a concatenate"""
+    kind = "inv_split"
+    c: int                   # channels in front of the concatenate
+    given: bool              # the upper half was a latent of `decode` (it gets a gradient), not a draw
+
+
+class InvConv(NamedTuple):
+    kind = "inv_conv"
+    module: Any
+
+
+class InvAct(NamedTuple):
+    kind = "inv_act"
+    module: Any
+
+
+class InvScale(NamedTuple):
+    """Normalization"""
+    kind = "inv_scale"
+    s: float
+
+
+class InvAugment(NamedTuple):
+    kind = "inv_augment"
+    channels: int            # channels in front of Augment.reverse
+
+
+class InvCoupling(NamedTuple):
+    """Coupling / CouplingFC on the layer path"""
+    kind = "inv_coupling"
+    module: Any
+    y: Any                   # the recovered coupling input
+
+
+class InvCtxAffine(NamedTuple):
+    """[Squeeze <-] Conv1x1(c) <- ActNorm(c'), or either layer alone (cf_affine_ctx_inv)"""
+    kind = "inv_affine_ctx"
+    operands: Any            # conv1x1.affine_ctx_operands: the per-sample matrices and log-scales of the codes the walk formed
+    shape: tuple             # of the group's input in the walk
+    unsqueeze: bool
+
+
+class InvCtxCoupling(NamedTuple):
+    """Coupling with a context net inverted by one kernel (cf_flow_step_inv_ctx)"""
+    kind = "inv_coupling_ctx"
+    module: Any
+    x: Any                   # the recovered coupling input
+    sbias: Any               # per-sample bias CN(c)
+    mode: int                # as CtxCoupling.mode
+    ws: Any                  # packed forward tables (identity front)
 
 
 def data_only(rec):

@@ -6,31 +6,32 @@ group needs: references to tensors the walk produces anyway (the recovered input
 output of a layer-path coupling).  `backward` then walks the groups in forward order.  It is a data-only walk: the gradient with
 respect to z and to every half `decode` put back, no parameter gradient.
 
-Rules (g: the gradient at the group's output in the backward walk, i.e. at the FORWARD input of the layers):
-  SplitPrior (a concatenate here)     slice: the upper half is that latent's gradient
-  Squeeze / PermuteAxes               the index map (squeeze_op / permute)
-  Conv1x1                             g <- W^-T g            (conv1x1_apply with the transposed cached inverse)
-  ActNorm                             g <- g e^{logs}
-  Normalization                       g <- g scale
-  Augment.reverse                     zeros into the dropped channels
-  the pre-processing tail             cf_postprocess_inv_bwd, one pass
-  Coupling / CouplingFC (layer path)  with F the forward coupling at the recovered y: J_F^-T g = (g0 - A^T u, u), u = g1 e^{-s}
-                                      (cf_coupling_apply in inverse mode on g with the shift half of h zeroed); A^T u is the first
-                                      half of the forward coupling's data backward on upstream (0, u) with gld = 0
-  fused step                          cf_flow_step_inv_bwd_data, one launch
+The records are the NamedTuples of the last section of layers/_tape.py; `vjp` looks the rule of a record up by its `kind` in VJP.
+Rules (g: the gradient at the group's output in the backward walk, i.e. at the FORWARD input of the layers), by record:
+  InvSplit     SplitPrior (a concatenate here)     slice: the upper half is that latent's gradient
+  Squeeze / Permute                                the index map (squeeze_op / permute)
+  InvConv      Conv1x1                             g <- W^-T g            (conv1x1_apply with the transposed cached inverse)
+  InvAct       ActNorm                             g <- g e^{logs}
+  InvScale     Normalization                       g <- g scale
+  InvAugment   Augment.reverse                     zeros into the dropped channels
+  InvTail      the pre-processing tail             cf_postprocess_inv_bwd, one pass
+  InvCoupling  Coupling / CouplingFC (layer path)  with F the forward coupling at the recovered y: J_F^-T g = (g0 - A^T u, u),
+                                      u = g1 e^{-s} (cf_coupling_apply in inverse mode on g with the shift half of h zeroed); A^T u is
+                                      the first half of the forward coupling's data backward on upstream (0, u) with gld = 0
+  InvStep      fused step                          cf_flow_step_inv_bwd_data, one launch
 A specialist flow under its context - the codes are formed ONCE, in the walk, and the records keep the tensors the
 VJP needs (m1, m2, the coupling's per-sample bias), not the encoders: backward differentiates the map the forward applied,
 whatever a stochastic encoder would draw next:
-  [Squeeze <-] Conv1x1(c) <- ActNorm(c')   cf_affine_ctx_inv forward (as the plain walk), cf_affine_ctx_inv_bwd_data backward:
+  InvCtxAffine    [Squeeze <-] Conv1x1(c) <- ActNorm(c'):  cf_affine_ctx_inv forward (as the plain walk), cf_affine_ctx_inv_bwd_data backward:
                                       g <- e^{l_b} (W_b^-T g), the un-squeeze folded into its loads; a lone context Conv1x1 /
                                       ActNorm is the same pair of entry points with one side NULL
-  Coupling(c), fused geometry         cf_flow_step_inv_ctx forward - ONE launch where the plain walk runs six - keeping x, the bias
+  InvCtxCoupling  Coupling(c), fused geometry:     cf_flow_step_inv_ctx forward - ONE launch where the plain walk runs six - keeping x, the bias
                                       and its mode; cf_flow_step_inv_bwd_ctx_data backward
 No gradient with respect to a parameter, a code or the context is formed.
 Anything else raises NotImplementedError naming the layer."""
 import torch
 
-from . import _derived, _hip
+from . import _derived, _hip, _tape
 from .actnorm import ActNorm
 from .augment import Augment
 from .context import cn_chain
@@ -92,7 +93,7 @@ def _coupling_ctx_inverse(m, z, context):
     mode, sbias, ws = m._ctx_step_operands(cn, C, H, W, zv.device)
     x = torch.empty(B, C, H, W, device=zv.device, dtype=torch.float32)
     _hip.call("cf_flow_step_inv_ctx", _hip.p(zv), _hip.p(x), _hip.p(ws), _hip.p(sbias), mode, B, C, H, W, zbs, _hip.stream())
-    return x, ("coupling_ctx", m, x, sbias, mode, ws)
+    return x, _tape.InvCtxCoupling(m, x, sbias, mode, ws)
 
 
 def walk(flow, z, latents, context=None):
@@ -121,7 +122,7 @@ def walk(flow, z, latents, context=None):
             ops = affine_ctx_operands(conv, act, context)
             shape = tuple(z.shape)
             z = affine_ctx_inverse(z, operands=ops, unsqueeze=sq)
-            rec.append(("affine_ctx", ops, shape, sq))
+            rec.append(_tape.InvCtxAffine(ops, shape, sq))
             i -= n + int(sq)
             continue
         if spec and type(m) is Coupling and m.context_net and m._fused_ctx_ok(z):
@@ -132,14 +133,14 @@ def walk(flow, z, latents, context=None):
         if (not spec and flow.fused and i >= 2 and z.dim() == 4 and isinstance(mods[i - 1], ActNorm) and mods[i - 1].is_initialized()
                 and flow._step_supported(mods[i - 2], mods[i - 1], m, tuple(z.shape[1:]))):
             z = flow._inverse_step(z, mods[i - 2], mods[i - 1], m)       # the Squeeze in front, if any, runs as its own launch
-            rec.append(("step", mods[i - 2], mods[i - 1], m, z))
+            rec.append(_tape.InvStep(mods[i - 2], mods[i - 1], m, z))
             i -= 3
             continue
         if flow._tail_fusable(i, z):
             y, n1, n2 = z, mods[1], mods[2]
             keep = y.shape[1] - (mods[4].aug_size if i == 4 else 0)
             z = n1.reverse(n2.reverse(mods[3].reverse(y[:, :keep])))
-            rec.append(("tail", y, keep, n1._s * n2._s))
+            rec.append(_tape.InvTail(y, keep, n1._s * n2._s))
             break
         if isinstance(m, SplitPrior):
             c = z.shape[1]
@@ -149,28 +150,28 @@ def walk(flow, z, latents, context=None):
                 z = m.reverse(z, context, latent=latents.pop())
             else:
                 z = m.reverse(z, context)
-            rec.append(("split", c, latents is not None))
+            rec.append(_tape.InvSplit(c, latents is not None))
         elif isinstance(m, Squeeze):
             z = m.reverse(z)
-            rec.append(("squeeze", tuple(m.p)))
+            rec.append(_tape.Squeeze(tuple(m.p)))
         elif isinstance(m, PermuteAxes):
             z = m.reverse(z)
-            rec.append(("permute", m.permutation))
+            rec.append(_tape.Permute(m.permutation))
         elif isinstance(m, Conv1x1) and not m.context_net:
             z = m.reverse(z)
-            rec.append(("conv", m))
+            rec.append(_tape.InvConv(m))
         elif isinstance(m, ActNorm) and not m.context_net:
             z = m.reverse(z)
-            rec.append(("act", m))
+            rec.append(_tape.InvAct(m))
         elif isinstance(m, Normalization):
             z = m.reverse(z)
-            rec.append(("scale", m._s))
+            rec.append(_tape.InvScale(m._s))
         elif isinstance(m, Augment) and m.split_dim == 1:
-            rec.append(("augment", z.shape[1]))
+            rec.append(_tape.InvAugment(z.shape[1]))
             z = m.reverse(z)
         elif type(m) in (Coupling, _cpl.CouplingFC) and not m.context_net:
             z = m.reverse(z)
-            rec.append(("coupling", m, z))
+            rec.append(_tape.InvCoupling(m, z))
         else:
             raise NotImplementedError("differentiable inverse: no vector-Jacobian rule for the reverse of %s%s (layer %d)"
                                       % (type(m).__name__, " with a context net" if getattr(m, "context_net", None) else "", i))
@@ -178,68 +179,84 @@ def walk(flow, z, latents, context=None):
     return z, rec
 
 
+def _kernel_vjp(name, x, g, mid, rest):
+    """One data-only backward kernel: g made contiguous, gz allocated like x, the call name(x, g, *mid, gz, *rest, stream)."""
+    g = g.contiguous()
+    gz = torch.empty(x.shape, device=g.device, dtype=torch.float32)
+    _hip.call(name, _hip.p(x), _hip.p(g), *mid, _hip.p(gz), *rest, _hip.stream())
+    return gz
+
+
+def _tail_vjp(flow, r, g, halves):
+    yv, ybs = _hip.bview(r.y)
+    B, C, H, W = yv.shape
+    return _kernel_vjp("cf_postprocess_inv_bwd", yv, g, (), (B, r.keep * H * W, (C - r.keep) * H * W, ybs, C * H * W, r.s12))
+
+
+def _step_vjp(flow, r, g, halves):
+    xv, xbs = _hip.bview(r.x)
+    B, C, H, W = xv.shape
+    tables = _step_vjp_tables(flow, r.conv, r.act, r.cpl, (C, H, W), xv.device)
+    return _kernel_vjp("cf_flow_step_inv_bwd_data", xv, g, [_hip.p(t) for t in tables], (B, C, H, W, xbs))
+
+
+def _coupling_ctx_vjp(flow, r, g, halves):
+    B, C, H, W = r.x.shape
+    wsb = r.module._ctx_step_bwd_tables(r.mode, C, H, W, r.x.device)
+    return _kernel_vjp("cf_flow_step_inv_bwd_ctx_data", r.x, g, (_hip.p(r.ws), _hip.p(wsb), _hip.p(r.sbias), r.mode), (B, C, H, W, C * H * W))
+
+
+def _split_vjp(flow, r, g, halves):
+    if r.given:
+        halves.append(g[:, r.c:].contiguous())
+    return g[:, :r.c]
+
+
+def _conv_vjp(flow, r, g, halves):
+    m = r.module
+    inv = _derived.get(m, "winv", _derived.key((m.NN,), str(g.device)),
+                       lambda: slogdet_inverse(_hip.f32(m.NN.detach()), True)[1], g.device)
+    shape = g.shape
+    if g.dim() == 2:
+        g = g.reshape(-1, m.D, 1, 1)
+    return conv1x1_apply(g, inv.t().contiguous()).view(shape)
+
+
+def _act_vjp(flow, r, g, halves):
+    logs = _hip.f32(r.module.NN_logs.detach())
+    return g * torch.exp(logs).view([1, -1] + [1] * (g.dim() - 2))
+
+
+def _augment_vjp(flow, r, g, halves):
+    full = g.new_zeros((g.shape[0], r.channels) + tuple(g.shape[2:]))
+    full[:, : g.shape[1]] = g
+    return full
+
+
+# The rule of each kind `walk` appends: (flow, record, g at the group's output in the walk, halves) -> g at its input; the rule of
+# a half `decode` put back appends that half's gradient to `halves`
+VJP = {
+    "inv_tail": _tail_vjp,
+    "inv_step": _step_vjp,
+    "inv_split": _split_vjp,
+    "squeeze": lambda flow, r, g, halves: squeeze_op(g, r.p, False),
+    "permute": lambda flow, r, g, halves: g.permute(r.inverse).contiguous(),
+    "inv_conv": _conv_vjp,
+    "inv_act": _act_vjp,
+    "inv_scale": lambda flow, r, g, halves: g * r.s,
+    "inv_augment": _augment_vjp,
+    "inv_coupling": lambda flow, r, g, halves: _coupling_vjp(r.module, r.y, g),
+    "inv_affine_ctx": lambda flow, r, g, halves: affine_ctx_inverse_vjp(g, r.operands, r.shape, r.unsqueeze),
+    "inv_coupling_ctx": _coupling_ctx_vjp,
+}
+
+
 def vjp(flow, rec, g):
     """(gz, [gradient of every half put back, in forward order]) from g = dL/dx, walking the groups in forward order."""
     halves = []
-    pp, st = _hip.p, _hip.stream()
     g = _hip.f32(g)
     for r in reversed(rec):
-        kind = r[0]
-        if kind == "tail":
-            _, y, keep, s12 = r
-            yv, ybs = _hip.bview(y)
-            B, C, H, W = yv.shape
-            g = g.contiguous()
-            gy = torch.empty(B, C, H, W, device=g.device, dtype=torch.float32)
-            _hip.call("cf_postprocess_inv_bwd", pp(yv), pp(g), pp(gy), B, keep * H * W, (C - keep) * H * W, ybs, C * H * W, s12, st)
-            g = gy
-        elif kind == "step":
-            _, conv, act, cpl, x = r
-            xv, xbs = _hip.bview(x)
-            B, C, H, W = xv.shape
-            ws, wsb, wsv = _step_vjp_tables(flow, conv, act, cpl, (C, H, W), xv.device)
-            g = g.contiguous()
-            gz = torch.empty(B, C, H, W, device=g.device, dtype=torch.float32)
-            _hip.call("cf_flow_step_inv_bwd_data", pp(xv), pp(g), pp(ws), pp(wsb), pp(wsv), pp(gz), B, C, H, W, xbs, st)
-            g = gz
-        elif kind == "split":
-            c = r[1]
-            if r[2]:
-                halves.append(g[:, c:].contiguous())
-            g = g[:, :c]
-        elif kind == "squeeze":
-            g = squeeze_op(g, r[1], False)
-        elif kind == "permute":
-            g = g.permute(r[1]).contiguous()
-        elif kind == "conv":
-            m = r[1]
-            inv = _derived.get(m, "winv", _derived.key((m.NN,), str(g.device)),
-                               lambda: slogdet_inverse(_hip.f32(m.NN.detach()), True)[1], g.device)
-            shape = g.shape
-            if g.dim() == 2:
-                g = g.reshape(-1, m.D, 1, 1)
-            g = conv1x1_apply(g, inv.t().contiguous()).view(shape)
-        elif kind == "act":
-            logs = _hip.f32(r[1].NN_logs.detach())
-            g = g * torch.exp(logs).view([1, -1] + [1] * (g.dim() - 2))
-        elif kind == "scale":
-            g = g * r[1]
-        elif kind == "augment":
-            full = g.new_zeros((g.shape[0], r[1]) + tuple(g.shape[2:]))
-            full[:, : g.shape[1]] = g
-            g = full
-        elif kind == "coupling":
-            g = _coupling_vjp(r[1], r[2], g)
-        elif kind == "affine_ctx":
-            g = affine_ctx_inverse_vjp(g, r[1], r[2], r[3])
-        elif kind == "coupling_ctx":
-            _, m, x, sbias, mode, ws = r
-            B, C, H, W = x.shape
-            wsb = m._ctx_step_bwd_tables(mode, C, H, W, x.device)
-            g = g.contiguous()
-            gz = torch.empty(B, C, H, W, device=g.device, dtype=torch.float32)
-            _hip.call("cf_flow_step_inv_bwd_ctx_data", pp(x), pp(g), pp(ws), pp(wsb), pp(sbias), mode, pp(gz), B, C, H, W, C * H * W, st)
-            g = gz
+        g = VJP[r.kind](flow, r, g, halves)
     return g.contiguous(), halves
 
 

@@ -156,7 +156,7 @@ def test_flow_step_inv_ctx_against_the_layer_path(L, fxname):
             assert type(m) is L.Coupling and m.context_net and m._fused_ctx_ok(z)
             one, rec = _coupling_ctx_inverse(m, z, cd)
             layers = m.reverse(z, cd)
-            assert rec[0] == "coupling_ctx" and rec[4] == (1 if p.ctx["contextflow"] else 2)
+            assert rec.kind == "inv_coupling_ctx" and rec.mode == (1 if p.ctx["contextflow"] else 2)
             seen.add(tuple(z.shape[1:]))
             e = SU.err_of(one, layers)
             worst = max(worst, e)

@@ -111,7 +111,7 @@ def kernels(B, iters, warmup):
             m = by_width[C]
             z, g, out = r(B, C, H, H), r(B, C, H, H), torch.empty(B, C, H, H, device=dev)
             x, rec = _coupling_ctx_inverse(m, z, c)
-            _, _, _, sbias, mode, ws = rec
+            sbias, mode, ws = rec.sbias, rec.mode, rec.ws
             wsb = m._ctx_step_bwd_tables(mode, C, H, H, dev)
             # the generalist's step on the same conditioner: an orthogonal 1x1 and an ActNorm in front
             Wm, t, logs = torch.linalg.qr(r(C, C).cpu())[0].contiguous().to(dev), 0.1 * r(C), 0.1 * r(C)
