@@ -112,7 +112,15 @@ __device__ __forceinline__ float gelu_d(float x) {                    // d/dx of
 // TAPED: the residual stream at the layer boundaries comes from the training forward (cf_vit_step_fwd with xtape:
 // [depth + 1][DIM][T], feature-major) - phase A then runs the Conv1x1 / ActNorm / patch embedding only (their statistics and
 // planes are needed on the way back) and skips the six layers, a quarter of this kernel's work.
-template <class V, bool TAPED = false>
+// DATA: data gradient only - no token-major operand plane and no LayerNorm partial row is written (tp / lnp: NULL), nor are the
+// planes that only those stores read.
+// INV (with DATA; cf_vit_rs_inv_bwd.hip): the vector-Jacobian product of the INVERSE step at its output.  x is the step input the
+// inverse recovered; the `gz` slot takes gx = dL/dx (dense), the `gx` slot receives gz = J_F^-T gx (dense), the `gld` slot carries
+// wsv, the fragments of diag(e^{logs}) Wm^-T (k_vit_rs_pack_inv_bwd).  Phase A is the same; one product in front makes the plane
+// GYP holds in the forward form (g_y = e^{logs} Wm^-T g_x), the epilogue forms g_z1 = g_y1 e^{-s}, g_t = -g_z1 and
+// g_raw = -g_y1 y1 (1 - tanh^2(raw / 2)), the walk through the conditioner is the forward form's - its last read-modify-write
+// leaves g_z0 = g_y0 + (dViT/dy0)^T g_h in the y0 rows of GYP - and the Conv1x1 + ActNorm product at the end is not run.
+template <class V, bool TAPED = false, bool DATA = false, bool INV = false>
 __global__ __launch_bounds__(256, 3) void k_vit_step_bwd_rs(const float* __restrict__ x, const float* __restrict__ gz,
                                                             const float* __restrict__ gld, float* __restrict__ gx,
                                                             const float* __restrict__ ws, const float* __restrict__ wsb,
@@ -120,6 +128,7 @@ __global__ __launch_bounds__(256, 3) void k_vit_step_bwd_rs(const float* __restr
                                                             int64_t xbs, int depth, const float* __restrict__ xtape = nullptr,
                                                             int64_t T = 0) {
     using R = RSB<V>;
+    static_assert(!INV || DATA, "the inverse form is data-only");
     constexpr int C = V::C, CIN = V::CIN, HW = V::HW, DIM = V::DIM, PD = V::PD, TS = R::TS, PS = R::PS;
     extern __shared__ __align__(16) float lds[];
     float* XIN = lds + R::P_XIN;   // [4 KS_C][PS]  step input, channel-major
@@ -168,6 +177,7 @@ __global__ __launch_bounds__(256, 3) void k_vit_step_bwd_rs(const float* __restr
     // plane [nrows][TS] -> token-major rows of `dst` (row stride ld): lane = feature (coalesced, conflict-free LDS reads),
     // wave w takes tokens w, w + 4, ..; no integer divisions
     auto store_T = [&](const float* P, int nrows, float* dst, int ld) {
+        if constexpr (DATA) return;
         for (int f0 = 0; f0 < nrows; f0 += 64) {
             const int f = f0 + lane;
             if (f < nrows) {
@@ -210,6 +220,7 @@ __global__ __launch_bounds__(256, 3) void k_vit_step_bwd_rs(const float* __restr
     };
     // LayerNorm weight / bias gradient of this workgroup's 16 tokens: rows of the owner's tile
     auto ln_partial = [&](int off, const f32x4& gu, const f32x4& uh) {
+        if constexpr (DATA) return;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float a = row_sum16(gu[r] * uh[r]), b = row_sum16(gu[r]);
@@ -287,6 +298,7 @@ __global__ __launch_bounds__(256, 3) void k_vit_step_bwd_rs(const float* __restr
     for (int i = tid; i < 6 * PS; i += 256) GYP[26 * PS + i] = 0.f;            // channel rows past C: zero operands
     for (int i = tid; i < 12 * TS; i += 256) PG[52 * TS + i] = 0.f;
     __syncthreads();
+    if constexpr (!DATA)
     for (int it = tid; it < V::POSC * C; it += 256) {                          // x, position-major (operand of the Conv1x1 weight gradient)
         const int c = it % C, pc = it / C;
         tXT[(int64_t)(pos0 + pc) * C + c] = XIN[c * PS + pc];
@@ -407,12 +419,35 @@ __global__ __launch_bounds__(256, 3) void k_vit_step_bwd_rs(const float* __restr
         for (int r = 0; r < 4; ++r) hn[r] = fmaf(un[r], gn[r], bn[r]);
         put(PH, hn);
     }
+    if constexpr (INV) {
+        // the upstream rows g_x, channel-major as XIN was, on the attention-output plane (dead since the last layer's out-proj)
+        float* GXP = PO;
+        for (int i = tid; i < 4 * V::KS_C * V::POSC; i += 256) {
+            const int c = i / V::POSC, pc = i % V::POSC, b = s0 + pc / HW;
+            GXP[c * PS + pc] = (c < C && b < B) ? gz[(int64_t)b * C * HW + c * HW + pc % HW] : 0.f;
+        }
+        load_frags(fconv, make_rsrc(gld, 2 * V::NG_C * 256), lane, (w & 1) * V::NG_C * 256);
+        __syncthreads();
+        // g_y = e^{logs} Wm^-T g_x: the Conv1x1 + ActNorm product's tiling (row tile w & 1, column tile w >> 1)
+        const int rt = w & 1, ct = w >> 1;
+        const f32x4 a = gemm1<V::KS_C>(f32x4{0.f, 0.f, 0.f, 0.f}, fconv, [&](int s) { return GXP[(4 * s + g) * PS + 16 * ct + col]; });
+#pragma unroll
+        for (int r = 0; r < 4; ++r) GYP[(16 * rt + 4 * g + r) * PS + 16 * ct + col] = a[r];    // (rows past C: zero fragments)
+    }
     __syncthreads();
     for (int it = tid; it < CIN * 2 * V::TOK; it += 256) {
         const int tc = it % V::TOK, ci = it / V::TOK, ii = ci / CIN, c = ci - ii * CIN;
         const int s = tc >> 2, pos = 2 * (tc & 3) + ii, b = s0 + s;
         const float raw = PH[(ii * C + CIN + c) * TS + tc], y1 = YP[(CIN + c) * PS + s * HW + pos];
-        const float ls = 2.0f * tanhf(0.5f * raw), es = expf(ls);
+        const float ls = 2.0f * tanhf(0.5f * raw);
+        if constexpr (INV) {
+            const float gy1 = GYP[(CIN + c) * PS + s * HW + pos], gz1 = gy1 * expf(-ls);
+            PG[(ii * C + c) * TS + tc] = -gz1;                                                 // d / d t: y1 = (z1 - t) e^{-log_s}
+            PG[(ii * C + CIN + c) * TS + tc] = -gy1 * y1 * (1.0f - 0.25f * ls * ls);           // d / d raw
+            GYP[(CIN + c) * PS + s * HW + pos] = gz1;                                          // (the y0 rows hold g_y0 already)
+            continue;
+        }
+        const float es = expf(ls);
         float gz0 = 0.f, gz1 = 0.f, gl = 0.f;
         if (b < B) {
             gz0 = gz[(int64_t)b * C * HW + c * HW + pos];
@@ -450,7 +485,7 @@ __global__ __launch_bounds__(256, 3) void k_vit_step_bwd_rs(const float* __restr
         f32x4 q, k, v, o;
         layer_front(l, mean1, rstd1, q, k, v, p, o);
         const f32x4 u1h = normalised(Xin, mean1, rstd1);
-        {
+        if constexpr (!DATA) {                                                 // (the LayerNorm outputs are weight-gradient operands only)
             const f32x4 ga = vec4(wsb + bl + R::LB_GA, w, g), ba = vec4(wsb + bl + R::LB_BA, w, g);
             f32x4 u1;
 #pragma unroll
@@ -480,12 +515,14 @@ __global__ __launch_bounds__(256, 3) void k_vit_step_bwd_rs(const float* __restr
             load_frags(f2T, rb, lane, bl + R::LB_W2T + w * V::NG_D * 256);          // transposed fragments: one product ahead
             __builtin_amdgcn_sched_barrier(0);
             u2h = normalised(Xm, mean2, rstd2);
-            const f32x4 gf = vec4(wsb + bl + R::LB_GF, w, g), bf = vec4(wsb + bl + R::LB_BF, w, g);
-            f32x4 u2, h;
+            if constexpr (!DATA) {
+                const f32x4 gf = vec4(wsb + bl + R::LB_GF, w, g), bf = vec4(wsb + bl + R::LB_BF, w, g);
+                f32x4 u2, h;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { u2[r] = fmaf(u2h[r], gf[r], bf[r]); h[r] = gelu_f(hp[r]); }
-            put(PB, u2);
-            put(PH, h);
+                for (int r = 0; r < 4; ++r) { u2[r] = fmaf(u2h[r], gf[r], bf[r]); h[r] = gelu_f(hp[r]); }
+                put(PB, u2);
+                put(PH, h);
+            }
         }
         __syncthreads();
         store_T(PB, DIM, tl + R4 * R::TL_U2, DIM);
@@ -578,10 +615,10 @@ __global__ __launch_bounds__(256, 3) void k_vit_step_bwd_rs(const float* __restr
         ln_partial(R::LN_1, gX, eh);
         const f32x4 ge = ln_bwd(gX * g1, eh, rstd_e, DIM);
         load_frags(foT, rb, lane, R::OFF_WET + (w & 1) * V::NG_D * 256);       // (waves 2, 3: unused copies)
-        load_frags(fconv, rb, lane, R::OFF_CT + (w & 1) * V::NG_C * 256);
+        if constexpr (!INV) load_frags(fconv, rb, lane, R::OFF_CT + (w & 1) * V::NG_C * 256);
         put(PA, ge);
         // LayerNorm(pd) output u0 (operand of the embedding weight gradient): lane group g holds features g, g + 4, .. of its token
-        if (w == 0) {
+        if (!DATA && w == 0) {
 #pragma unroll
             for (int i = 0; i < V::KS_PD; ++i) {
                 const int f = g + 4 * i, ii = f / CIN, c = f - ii * CIN;
@@ -603,7 +640,7 @@ __global__ __launch_bounds__(256, 3) void k_vit_step_bwd_rs(const float* __restr
             ph[r] = vp[r] ? (YP[c * PS + pcol + ii] - mean0) * rstd0 : 0.f;
             if (!vp[r]) gu0[r] = 0.f;
         }
-        if (w < 2) {
+        if (!DATA && w < 2) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float a = row_sum16(gu0[r] * ph[r]), b = row_sum16(gu0[r]);
@@ -621,7 +658,15 @@ __global__ __launch_bounds__(256, 3) void k_vit_step_bwd_rs(const float* __restr
         }
     }
     __syncthreads();
+    if constexpr (INV) {                                                       // g_z = [g_z0 | g_z1]: the rows of GYP, valid samples only
+        for (int it = tid; it < C * V::POSC; it += 256) {
+            const int c = it / V::POSC, pc = it % V::POSC, b = s0 + pc / HW;
+            if (b < B) gx[(int64_t)b * C * HW + c * HW + pc % HW] = GYP[c * PS + pc];
+        }
+        return;
+    }
     // ---- Conv1x1 + ActNorm backwards: g_x = (e^{-logs} Wm)^T g_y; g_y position-major for the weight gradient
+    if constexpr (!DATA)
     for (int it = tid; it < V::POSC * C; it += 256) {
         const int c = it % C, pc = it / C;
         tGYT[(int64_t)(pos0 + pc) * C + c] = GYP[c * PS + pc];
@@ -643,6 +688,7 @@ using RB26 = RSB<RS26>;
 
 }  // namespace
 
+#ifndef CF_VIT_RS_BWD_KERNELS_ONLY       // cf_vit_rs_inv_bwd.hip instantiates the INV form from this text in a unit of its own
 extern "C" {
 
 int64_t cf_vit_step_bwd_ws_bytes(int C, int depth) { return C == 26 ? (int64_t)wsb_floats<RS26>(depth) * 4 : 0; }
@@ -697,3 +743,4 @@ int cf_vit_step_bwd(const float* x, const float* gz, const float* gld, float* gx
 }
 
 }  // extern "C"
+#endif  // CF_VIT_RS_BWD_KERNELS_ONLY

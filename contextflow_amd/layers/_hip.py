@@ -134,6 +134,9 @@ SIGNATURES = {
     "cf_vit_step_bwd_ln_floats": (_c_i64, [_c_int] * 3),
     "cf_vit_step_bwd_prepare_batch": (_c_int, [_c_int] + [_c_p] * 4 + [_c_int] * 2 + [_c_p]),
     "cf_vit_step_bwd": (_c_int, [_c_p] * 9 + [_c_int] * 3 + [_c_i64, _c_p]),
+    "cf_vit_inv_step_bwd_ws_bytes": (_c_i64, [_c_int]),
+    "cf_vit_inv_step_bwd_prepare": (_c_int, [_c_p] * 3 + [_c_int, _c_p]),
+    "cf_vit_inv_step_bwd_data": (_c_int, [_c_p] * 6 + [_c_int] * 3 + [_c_i64, _c_p]),
     "cf_linear_wgrad_group_ws_bytes": (_c_i64, [_c_p] * 3 + [_c_int]),
     "cf_linear_wgrad_group": (_c_int, [_c_p] * 7 + [_c_int, _c_p, _c_p]),
     "cf_spline_table_floats": (_c_i64, [_c_int, _c_int]),

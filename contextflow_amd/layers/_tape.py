@@ -202,6 +202,23 @@ class InvCoupling(NamedTuple):
     y: Any                   # the recovered coupling input
 
 
+class InvVitStep(NamedTuple):
+    """Conv1x1 <- ActNorm <- TransCoupling in the one-kernel geometry: inverted by the plain walk's three launches, its
+    vector-Jacobian product one kernel (cf_vit_inv_step_bwd_data)"""
+    kind = "inv_vstep"
+    conv: Any
+    act: Any
+    cpl: Any
+    x: Any                   # the recovered step input
+
+
+class InvTransCoupling(NamedTuple):
+    """TransCoupling on the layer path (any other geometry, fused = False, an uninitialised ActNorm in front)"""
+    kind = "inv_transcoupling"
+    module: Any
+    y: Any                   # the recovered coupling input
+
+
 class InvCtxAffine(NamedTuple):
     """[Squeeze <-] Conv1x1(c) <- ActNorm(c'), or either layer alone (cf_affine_ctx_inv)"""
     kind = "inv_affine_ctx"

@@ -19,6 +19,14 @@ Rules (g: the gradient at the group's output in the backward walk, i.e. at the F
                                       u = g1 e^{-s} (cf_coupling_apply in inverse mode on g with the shift half of h zeroed); A^T u is
                                       the first half of the forward coupling's data backward on upstream (0, u) with gld = 0
   InvStep      fused step                          cf_flow_step_inv_bwd_data, one launch
+The transformer flows:
+  InvVitStep   TransCoupling <- ActNorm <- Conv1x1 in the one-kernel geometry (smap: C = 26 on 8 x 1 windows; no context nets, an
+                                      initialised ActNorm, flow.fused): the walk runs the plain walk's three reverses - its value is
+                                      the plain inverse's bit for bit - and keeps the recovered step input; backward is
+                                      cf_vit_inv_step_bwd_data, one launch
+  InvTransCoupling  a context-free TransCoupling anywhere else (msl, smd, atm; fused = False; an uninitialised ActNorm in front):
+                                      the InvCoupling rule with transcoupling_backward for A^T u; the Conv1x1 / ActNorm around it keep
+                                      InvConv / InvAct
 A specialist flow under its context - the codes are formed ONCE, in the walk, and the records keep the tensors the
 VJP needs (m1, m2, the coupling's per-sample bias), not the encoders: backward differentiates the map the forward applied,
 whatever a stochastic encoder would draw next:
@@ -37,7 +45,7 @@ from .augment import Augment
 from .context import cn_chain
 from .conv1x1 import Conv1x1, affine_ctx_inverse, affine_ctx_inverse_vjp, affine_ctx_operands, conv1x1_apply, slogdet_inverse
 from . import coupling as _cpl
-from .coupling import Coupling, coupling_apply
+from .coupling import Coupling, TransCoupling, coupling_apply
 from .dequantize import Dequantization
 from .normalize import Normalization
 from .permute_axes import PermuteAxes
@@ -83,6 +91,43 @@ def _coupling_vjp(m, y, g):
     at_u = coupling_conv_backward(m, y, up, gld, params=False)[0][:, :half]
     u[:, :half] -= at_u
     return u.view(shape)
+
+
+def _vit_step_matches(flow, conv, act, cpl, z):
+    """The group TransCoupling <- ActNorm <- Conv1x1 that the forward runs as one kernel (FlowSequential._build_plan, "vstep")."""
+    return (flow.fused and z.dim() == 4 and isinstance(cpl, TransCoupling) and isinstance(act, ActNorm) and isinstance(conv, Conv1x1)
+            and not conv.context_net and not act.context_net and conv.D == z.shape[1] and act.D == z.shape[1]
+            and act.is_initialized() and cpl.step_supported(tuple(z.shape[1:])))
+
+
+def _vit_step_vjp_tables(flow, conv, act, cpl, dev):
+    """(ws, wsb, wsv) of a transformer step: the row-split forward tables, the backward kernel's and the fragments of
+    diag(e^{logs}) Wm^-T (cf_vit_inv_step_bwd_prepare, from the Wm^-1 of the same packing call) - kept while the step's parameters
+    are unchanged."""
+    C = cpl.in_sz[0]
+    srcs = (conv.NN, act.NN_t, act.NN_logs) + tuple(cpl.step_sources())
+
+    def build():
+        t = TransCoupling.step_tables([(cpl, conv.NN, act.NN_t, act.NN_logs)], dev, "rs", winv=True, bwd=True)[0]
+        wsv = torch.empty(_hip.lib().cf_vit_inv_step_bwd_ws_bytes(C), device=dev, dtype=torch.uint8)
+        _hip.call("cf_vit_inv_step_bwd_prepare", _hip.p(t.winv), _hip.p(_hip.f32(act.NN_logs.detach())), _hip.p(wsv), C, _hip.stream())
+        return t.ws, t.wsb, wsv
+    return _derived.get(flow, ("inv_vstep_ws", id(cpl)), _derived.key(srcs, C, str(dev)), build, dev)
+
+
+def _transcoupling_vjp(m, y, g):
+    """J_F^-T g of a context-free TransCoupling at its recovered input y, from existing kernels only (as _coupling_vjp)."""
+    from .autograd_layers import transcoupling_backward
+    half = y.shape[1] // 2
+    h = m.net(y[:, :half])
+    h[:, :half].zero_()                                   # no shift: (g0, (g1 - 0) e^{-s})
+    u = coupling_apply(_hip.f32(g).contiguous(), h, True)[0]
+    up = u.clone()
+    up[:, :half].zero_()
+    gld = torch.zeros(y.shape[0], device=y.device, dtype=torch.float32)
+    at_u = transcoupling_backward(m, y, up, gld, params=False)[0][:, :half]
+    u[:, :half] -= at_u
+    return u
 
 
 def _coupling_ctx_inverse(m, z, context):
@@ -136,6 +181,11 @@ def walk(flow, z, latents, context=None):
             rec.append(_tape.InvStep(mods[i - 2], mods[i - 1], m, z))
             i -= 3
             continue
+        if not spec and i >= 2 and _vit_step_matches(flow, mods[i - 2], mods[i - 1], m, z):
+            z = mods[i - 2].reverse(mods[i - 1].reverse(m.reverse(z)))       # the plain walk's three launches: its values bit for bit
+            rec.append(_tape.InvVitStep(mods[i - 2], mods[i - 1], m, z))
+            i -= 3
+            continue
         if flow._tail_fusable(i, z):
             y, n1, n2 = z, mods[1], mods[2]
             keep = y.shape[1] - (mods[4].aug_size if i == 4 else 0)
@@ -172,6 +222,9 @@ def walk(flow, z, latents, context=None):
         elif type(m) in (Coupling, _cpl.CouplingFC) and not m.context_net:
             z = m.reverse(z)
             rec.append(_tape.InvCoupling(m, z))
+        elif isinstance(m, TransCoupling) and not m.context_net and z.dim() == 4:
+            z = m.reverse(z)
+            rec.append(_tape.InvTransCoupling(m, z))
         else:
             raise NotImplementedError("differentiable inverse: no vector-Jacobian rule for the reverse of %s%s (layer %d)"
                                       % (type(m).__name__, " with a context net" if getattr(m, "context_net", None) else "", i))
@@ -198,6 +251,14 @@ def _step_vjp(flow, r, g, halves):
     B, C, H, W = xv.shape
     tables = _step_vjp_tables(flow, r.conv, r.act, r.cpl, (C, H, W), xv.device)
     return _kernel_vjp("cf_flow_step_inv_bwd_data", xv, g, [_hip.p(t) for t in tables], (B, C, H, W, xbs))
+
+
+def _vit_step_vjp(flow, r, g, halves):
+    xv, xbs = _hip.bview(r.x)
+    B, C = xv.shape[0], xv.shape[1]
+    tables = _vit_step_vjp_tables(flow, r.conv, r.act, r.cpl, xv.device)
+    return _kernel_vjp("cf_vit_inv_step_bwd_data", xv, g, [_hip.p(t) for t in tables],
+                       (B, C, len(r.cpl.NN[0].transformer.layers), xbs))
 
 
 def _coupling_ctx_vjp(flow, r, g, halves):
@@ -246,6 +307,8 @@ VJP = {
     "inv_scale": lambda flow, r, g, halves: g * r.s,
     "inv_augment": _augment_vjp,
     "inv_coupling": lambda flow, r, g, halves: _coupling_vjp(r.module, r.y, g),
+    "inv_vstep": _vit_step_vjp,
+    "inv_transcoupling": lambda flow, r, g, halves: _transcoupling_vjp(r.module, r.y, g),
     "inv_affine_ctx": lambda flow, r, g, halves: affine_ctx_inverse_vjp(g, r.operands, r.shape, r.unsqueeze),
     "inv_coupling_ctx": _coupling_ctx_vjp,
 }

@@ -1055,9 +1055,12 @@ class FlowSequential(nn.Module):
         returns dL/dz (a data-only walk: no parameter gradient is formed; once differentiable).  The forward values may differ from
         the plain walk's in rounding.  A specialist flow takes its context and `noise` here too: the codes are formed once, in the
         walk, the couplings run as one cf_flow_step_inv_ctx launch each, and no gradient with respect to a code or the context is
-        formed.  NotImplementedError with return_logp, with a context for a flow without context nets, and for a layer without a rule
-        (TransCoupling, MaskedCoupling, a context Coupling outside the fused geometry, the activation and spline layers, an Augment
-        over another axis)."""
+        formed.  The transformer flows: a Conv1x1 -> ActNorm -> TransCoupling step in the one-kernel geometry (smap) is
+        walked by the plain walk's launches - there the forward value IS the plain walk's, bit for bit - and its backward is one
+        cf_vit_inv_step_bwd_data launch; a context-free TransCoupling anywhere else (msl, smd, atm, fused = False) takes a layer rule
+        built from the training backward's kernels.  NotImplementedError with return_logp, with a context for a flow without context
+        nets, and for a layer without a rule (a TransCoupling with a context net, MaskedCoupling, a context Coupling outside the fused
+        geometry, the activation and spline layers, an Augment over another axis)."""
         if differentiable:
             self._refuse_differentiable("inverse", context, False, return_logp)
             return self._run_differentiable(z, None, context, noise)
@@ -1271,7 +1274,8 @@ class FlowSequential(nn.Module):
         its `context` (ValueError without) and `noise` as `encode`.  return_logp: (x, logp) as `inverse` - the halves given
         here are the ones scored; with clamp=True logp stays the density of the unclamped continuous point.
         differentiable=True: as `inverse` - the continuous point, and backward returns the gradient with respect to z and to every
-        half that requires one, each in the layout of its latent.  ValueError together with clamp=True."""
+        half that requires one, each in the layout of its latent; the conv flows, the specialist conv flows and the transformer
+        flows (smap: one launch per step in the backward; msl / smd / atm: a layer rule).  ValueError together with clamp=True."""
         if differentiable:
             self._refuse_differentiable("decode", context, clamp, return_logp)
         self._refuse_logp(return_logp)

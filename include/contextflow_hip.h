@@ -561,6 +561,20 @@ int cf_vit_step_bwd_prepare_batch(int n, const float* const* Wm, const float* co
 int cf_vit_step_bwd(const float* x, const float* gz, const float* gld, float* gx, const void* ws, const void* wsb, float* planes,
                     float* ln_partials, const float* xtape, int B, int C, int depth, int64_t x_bstride, cf_stream_t stream);
 
+/* The vector-Jacobian product of the INVERSE of that step (Conv1x1^-1 o ActNorm^-1 o TransCoupling^-1: the backward walk of the
+ * transformer flows, `decode(..., differentiable=True)`; csrc/cf_vit_rs_inv_bwd.hip): from x (B,C,8,1), the step input that the
+ * inverse recovered (batch stride x_bstride >= 8 C), and gx = dL/dx (dense) it writes gz = dL/dz = J_F^-T gx (dense) for the z the
+ * inverse was given.  Data only: no parameter gradient, no plane, no LayerNorm partial; one launch of ceil(B/4) workgroups of the
+ * same kernel text as cf_vit_step_bwd, no atomics - two calls give the same bits.  B == 0 is a no-op.
+ * ws / wsb: as cf_vit_step_bwd; wsv (cf_vit_inv_step_bwd_ws_bytes bytes, 16-byte aligned): the fragments of
+ * diag(e^{logs}) Wm^-T, packed by cf_vit_inv_step_bwd_prepare from the Wm^-1 (C,C) that cf_vit_step_prepare_batch (winv) writes
+ * and the ActNorm's logs (C,).  C = 26, depth 1 .. 6; anything else CF_ERR_UNSUPPORTED (cf_vit_inv_step_bwd_ws_bytes: 0).
+ * (Adds symbols only: CF_ABI_VERSION stays.)                                                                           */
+int64_t cf_vit_inv_step_bwd_ws_bytes(int C);
+int cf_vit_inv_step_bwd_prepare(const float* winv, const float* logs, void* wsv, int C, cf_stream_t stream);
+int cf_vit_inv_step_bwd_data(const float* x, const float* gx, const void* ws, const void* wsb, const void* wsv, float* gz, int B,
+                             int C, int depth, int64_t x_bstride, cf_stream_t stream);
+
 /* ---- SplineActivation: monotone rational-quadratic spline, linear tails (layers/activations.py:120-211,
  * layers/splines/rational_quadratic.py:21-176) ----------------------------------------------------- */
 /* knot tables: P parameter sets (1 = shared weights, C*H*W = individual_weights) of K bins;
