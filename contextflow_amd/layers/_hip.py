@@ -4,6 +4,7 @@ This is the only place the product touches native code.  There is NO CPU fallbac
 library is missing, or a tensor is not on a ROCm device, the call raises.  (The CPU oracle lives in
 `oracle/` and is test infrastructure only.)
 """
+import contextlib
 import ctypes
 import os
 
@@ -352,6 +353,26 @@ def p(t):
 
 
 _WRAPPED = (_Ptr, _PtrArray)             # the argument wrappers that carry tensors (device_of)
+
+
+@contextlib.contextmanager
+def _probe(events, stream, tag):
+    stream = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.current_stream(stream)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(stream)
+    yield
+    e1.record(stream)
+    events.append((e0, e1) + tag)
+
+
+_NO_PROBE = contextlib.nullcontext()
+
+
+def probe(events, stream, *tag):
+    """Context manager: two timing events on `stream` (a torch stream, or the device whose current stream is meant) bracket exactly
+    the launches of the block, and (e0, e1, *tag) is appended to the list `events`.  events None - no benchmark listens, the case of
+    every other call: nothing beyond this test, no stream looked up, no object built."""
+    return _NO_PROBE if events is None else _probe(events, stream, tag)
 
 
 NOISE_KEY = 0x243F6A8885A308D3           # Philox key of the in-kernel noise (the rank of a data-parallel process is folded in)

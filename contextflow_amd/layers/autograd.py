@@ -35,6 +35,7 @@ from torch.autograd.function import once_differentiable
 from . import _hip
 from ._tape import step_tape
 from .autograd_layers import layer_backward
+from .coupling import step_sources
 from .squeeze import squeeze_op
 
 
@@ -149,12 +150,11 @@ def step_backward(rec, gz, gld, gsum=None, side=None, keep=None, sink=None, coll
     B, dev = xv.shape[0], xv.device
     L = _hip.lib()
     f, pp, st = _hip.f32, _hip.p, _hip.stream()
-    c1, c2, c3 = cpl.NN[0], cpl.NN[2], cpl.NN[4]
-    Wm, t, logs = f(conv.NN.detach()), f(act.NN_t.detach()), f(act.NN_logs.detach())
+    srcs = step_sources(conv, act, cpl)
+    Wm, t, logs = (f(s.detach()) for s in srcs[:3])
     if wsb is None:                  # (the training forward packs the backward kernel's fragments on its side stream)
         wsb = torch.empty(L.cf_flow_step_bwd_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
-        _hip.call("cf_flow_step_bwd_prepare", pp(Wm), pp(logs), pp(f(c1.weight.detach())), pp(f(c2.weight.detach())),
-                  pp(f(c3.weight.detach())), pp(wsb), C, H, W, st)
+        _hip.call("cf_flow_step_bwd_prepare", pp(Wm), pp(logs), *[pp(f(w.detach())) for w in srcs[3::2]], pp(wsb), C, H, W, st)
     new = lambda rows: torch.empty(B, rows, HW, device=dev, dtype=torch.float32)
     # with a Squeeze in front of the step, dL/dx leaves the kernel in the un-squeezed layout of x (index map folded into its stores)
     gx = torch.empty((B, C // 4, 2 * H, 2 * W) if squeeze else (B, C, H, W), device=dev, dtype=torch.float32)
@@ -580,8 +580,7 @@ def _record_params(rec):
         d = rec.dist
         return [d.mG, d.sG, d.wG]
     if kind == "step":
-        c1, c2, c3 = rec.cpl.NN[0], rec.cpl.NN[2], rec.cpl.NN[4]
-        return [rec.conv.NN, rec.act.NN_t, rec.act.NN_logs, c1.weight, c1.bias, c2.weight, c2.bias, c3.weight, c3.bias]
+        return list(step_sources(rec.conv, rec.act, rec.cpl))
     if kind == "vstep":
         return [p for m in (rec.conv, rec.act, rec.cpl) for p in m.parameters()]
     if kind == "layer":

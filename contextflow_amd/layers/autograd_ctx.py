@@ -25,13 +25,11 @@ from .context import (ArgmaxCatDequantization, CatEmbeddings, EyeSampling, ProbS
                       VariationalCatDequantization)
 from .conv1x1 import Conv1x1
 from .coupling import Coupling, TransCoupling
-from .dequantize import Dequantization
+from .dequantize import preprocessing_group
 from .distributions.uniform import UniformDistribution
-from .normalize import Normalization
 from .permute_axes import PermuteAxes
 from .splitprior import SplitPrior
 from .squeeze import Squeeze, squeeze_op
-from .transforms import LogitTransform
 
 TRAINABLE_ENCODERS = (UniformCatDequantization, EyeSampling, VariationalCatDequantization, ArgmaxCatDequantization, ProbSampling)
 
@@ -465,13 +463,12 @@ def pre_ctx_backward(rec, gz, bw):
 def _pre_record(prefix, x_in, y):
     """The Pre record of a specialist tape from the modules that ran in front of its first record (x_in -> y)."""
     n = math.prod(x_in.shape[1:])
-    kinds = [type(m) for m in prefix]
-    if kinds and kinds[-1] is Augment and prefix[-1].split_dim == 1:       # its channels sit behind the data and get no gradient
-        kinds = kinds[:-1]
-    if not kinds:                                                           # the time-series flows: nothing transforms x
-        return _tape.Pre(None, n)
-    if kinds == [Dequantization, Normalization, Normalization, LogitTransform] and isinstance(prefix[0].dist, UniformDistribution):
-        return _tape.Pre(y, n, prefix[1]._s, prefix[2]._s)
+    if not prefix or (len(prefix) == 1 and type(prefix[0]) is Augment and prefix[0].split_dim == 1):
+        return _tape.Pre(None, n)                                           # the time-series flows: nothing transforms x
+    # the group and nothing else; any Augment over the channels may close it, whatever it draws: they get no gradient
+    g = preprocessing_group(prefix)
+    if g is not None and g.count == len(prefix) and isinstance(g.deq.dist, UniformDistribution):
+        return _tape.Pre(y, n, g.n1._s, g.n2._s)
     return _tape.Pre()                                                      # n = 0: pre_ctx_backward raises
 
 

@@ -1,6 +1,6 @@
 """The differentiable backward walk: `FlowSequential.inverse / decode(..., differentiable=True)`.
 
-The walk runs the layers' reverses as `_inverse` does, but returns the CONTINUOUS point - for a flow whose first layer is a
+The walk runs the layers' reverses as the plain walk (layers/inverse.py) does, but returns the CONTINUOUS point - for a flow whose first layer is a
 Dequantization the chain stops in front of it - and keeps, per inverted group, what the vector-Jacobian product (VJP) of that
 group needs: references to tensors the walk produces anyway (the recovered input of a fused step, the logits of the tail, the
 output of a layer-path coupling).  `backward` then walks the groups in forward order.  It is a data-only walk: the gradient with
@@ -45,8 +45,9 @@ from .augment import Augment
 from .context import cn_chain
 from .conv1x1 import Conv1x1, affine_ctx_inverse, affine_ctx_inverse_vjp, affine_ctx_operands, conv1x1_apply, slogdet_inverse
 from . import coupling as _cpl
-from .coupling import Coupling, TransCoupling, coupling_apply
+from .coupling import Coupling, TransCoupling, coupling_apply, step_sources
 from .dequantize import Dequantization
+from .inverse import _inverse_step, _inverse_tables, _step_fusable, _tail_fusable
 from .normalize import Normalization
 from .permute_axes import PermuteAxes
 from .splitprior import SplitPrior
@@ -58,26 +59,25 @@ def _step_vjp_tables(flow, conv, act, cpl, shape, dev):
     the fragments of diag(e^{logs}) Wm^-T (cf_flow_step_inv_bwd_prepare, from the Wm^-1 in wsi) - kept while the step's parameters
     are unchanged, as the tables of `_inverse_step`."""
     C, H, W = shape
-    ws, wsi = flow._inverse_tables(conv, act, cpl, shape, dev)
+    ws, wsi = _inverse_tables(flow, conv, act, cpl, shape, dev)
     f, pp = _hip.f32, _hip.p
-    c1, c2, c3 = cpl.NN[0], cpl.NN[2], cpl.NN[4]
+    srcs = step_sources(conv, act, cpl)
 
     def build():
         L, st = _hip.lib(), _hip.stream()
         wsb = torch.empty(L.cf_flow_step_bwd_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
-        _hip.call("cf_flow_step_bwd_prepare", pp(f(conv.NN.detach())), pp(f(act.NN_logs.detach())), pp(f(c1.weight.detach())),
-                  pp(f(c2.weight.detach())), pp(f(c3.weight.detach())), pp(wsb), C, H, W, st)
+        _hip.call("cf_flow_step_bwd_prepare", *[pp(f(t.detach())) for t in (srcs[0], srcs[2]) + srcs[3::2]], pp(wsb), C, H, W, st)
         wsv = torch.empty(L.cf_flow_step_inv_bwd_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
-        _hip.call("cf_flow_step_inv_bwd_prepare", pp(wsi), pp(f(act.NN_logs.detach())), pp(wsv), C, H, W, st)
+        _hip.call("cf_flow_step_inv_bwd_prepare", pp(wsi), pp(f(srcs[2].detach())), pp(wsv), C, H, W, st)
         return wsb, wsv
-    wsb, wsv = _derived.get(flow, ("inv_bwd_ws", id(cpl)), _derived.key(flow._inverse_step_sources(conv, act, cpl), C, H, W, str(dev)),
-                            build, dev)
+    wsb, wsv = _derived.get(flow, ("inv_bwd_ws", id(cpl)), _derived.key(srcs, C, H, W, str(dev)), build, dev)
     return ws, wsb, wsv
 
 
 def _coupling_vjp(m, y, g):
-    """J_F^-T g of a context-free Coupling / CouplingFC at its recovered input y, from existing kernels only."""
-    from .autograd_layers import coupling_conv_backward
+    """J_F^-T g of a context-free Coupling / CouplingFC / TransCoupling at its recovered input y, from existing kernels only."""
+    from .autograd_layers import coupling_conv_backward, transcoupling_backward
+    backward = transcoupling_backward if isinstance(m, TransCoupling) else coupling_conv_backward
     shape = g.shape
     if y.dim() == 2:
         y, g = y.view(-1, m.D, 1, 1), g.reshape(-1, m.D, 1, 1)
@@ -88,7 +88,7 @@ def _coupling_vjp(m, y, g):
     up = u.clone()
     up[:, :half].zero_()
     gld = torch.zeros(y.shape[0], device=y.device, dtype=torch.float32)
-    at_u = coupling_conv_backward(m, y, up, gld, params=False)[0][:, :half]
+    at_u = backward(m, y, up, gld, params=False)[0][:, :half]
     u[:, :half] -= at_u
     return u.view(shape)
 
@@ -113,21 +113,6 @@ def _vit_step_vjp_tables(flow, conv, act, cpl, dev):
         _hip.call("cf_vit_inv_step_bwd_prepare", _hip.p(t.winv), _hip.p(_hip.f32(act.NN_logs.detach())), _hip.p(wsv), C, _hip.stream())
         return t.ws, t.wsb, wsv
     return _derived.get(flow, ("inv_vstep_ws", id(cpl)), _derived.key(srcs, C, str(dev)), build, dev)
-
-
-def _transcoupling_vjp(m, y, g):
-    """J_F^-T g of a context-free TransCoupling at its recovered input y, from existing kernels only (as _coupling_vjp)."""
-    from .autograd_layers import transcoupling_backward
-    half = y.shape[1] // 2
-    h = m.net(y[:, :half])
-    h[:, :half].zero_()                                   # no shift: (g0, (g1 - 0) e^{-s})
-    u = coupling_apply(_hip.f32(g).contiguous(), h, True)[0]
-    up = u.clone()
-    up[:, :half].zero_()
-    gld = torch.zeros(y.shape[0], device=y.device, dtype=torch.float32)
-    at_u = transcoupling_backward(m, y, up, gld, params=False)[0][:, :half]
-    u[:, :half] -= at_u
-    return u
 
 
 def _coupling_ctx_inverse(m, z, context):
@@ -155,7 +140,7 @@ def walk(flow, z, latents, context=None):
         if i == 0 and isinstance(m, Dequantization):
             break                                         # the continuous point: the tensor floor() would be applied to
         if spec and z.dim() == 4 and isinstance(m, (ActNorm, Conv1x1)) and m.context_net:
-            # the groups of FlowSequential._inverse: ActNorm(c') <- Conv1x1(c) with the Squeeze((2,2)) in front, or either layer alone
+            # the groups of inverse._inverse: ActNorm(c') <- Conv1x1(c) with the Squeeze((2,2)) in front, or either layer alone
             act = m if isinstance(m, ActNorm) else None
             conv = m if act is None else None
             n = 1
@@ -175,9 +160,8 @@ def walk(flow, z, latents, context=None):
             rec.append(r)
             i -= 1
             continue
-        if (not spec and flow.fused and i >= 2 and z.dim() == 4 and isinstance(mods[i - 1], ActNorm) and mods[i - 1].is_initialized()
-                and flow._step_supported(mods[i - 2], mods[i - 1], m, tuple(z.shape[1:]))):
-            z = flow._inverse_step(z, mods[i - 2], mods[i - 1], m)       # the Squeeze in front, if any, runs as its own launch
+        if not spec and _step_fusable(flow, i, z):
+            z = _inverse_step(flow, z, mods[i - 2], mods[i - 1], m)      # the Squeeze in front, if any, runs as its own launch
             rec.append(_tape.InvStep(mods[i - 2], mods[i - 1], m, z))
             i -= 3
             continue
@@ -186,7 +170,7 @@ def walk(flow, z, latents, context=None):
             rec.append(_tape.InvVitStep(mods[i - 2], mods[i - 1], m, z))
             i -= 3
             continue
-        if flow._tail_fusable(i, z):
+        if _tail_fusable(flow, i, z):
             y, n1, n2 = z, mods[1], mods[2]
             keep = y.shape[1] - (mods[4].aug_size if i == 4 else 0)
             z = n1.reverse(n2.reverse(mods[3].reverse(y[:, :keep])))
@@ -308,7 +292,7 @@ VJP = {
     "inv_augment": _augment_vjp,
     "inv_coupling": lambda flow, r, g, halves: _coupling_vjp(r.module, r.y, g),
     "inv_vstep": _vit_step_vjp,
-    "inv_transcoupling": lambda flow, r, g, halves: _transcoupling_vjp(r.module, r.y, g),
+    "inv_transcoupling": lambda flow, r, g, halves: _coupling_vjp(r.module, r.y, g),
     "inv_affine_ctx": lambda flow, r, g, halves: affine_ctx_inverse_vjp(g, r.operands, r.shape, r.unsqueeze),
     "inv_coupling_ctx": _coupling_ctx_vjp,
 }

@@ -42,16 +42,26 @@ def coupling_apply(x, h, inverse, inverse_ldj=False):
     return z, ldj
 
 
+def conditioner_sources(cpl):
+    """The six parameters of a Coupling's conditioner in the packing kernels' order: weight and bias of its 1x1, 3x3 and last 1x1."""
+    c1, c2, c3 = cpl.NN[0], cpl.NN[2], cpl.NN[4]
+    return c1.weight, c1.bias, c2.weight, c2.bias, c3.weight, c3.bias
+
+
+def step_sources(conv, act, cpl):
+    """The nine parameters a Conv1x1 -> ActNorm -> Coupling step derives its tables from, in the packing kernels' order.  Every
+    cache key of such tables and every launch that packs them takes the tuple, or a slice, from here: both name the same tensors."""
+    return (conv.NN, act.NN_t, act.NN_logs) + conditioner_sources(cpl)
+
+
 def identity_front_step_tables(cpl, w1, C, H, W, dev):
     """Packed tables of the fused flow-step kernel for the Coupling `cpl` alone: an identity 1x1 and a zero ActNorm in front of
     its conditioner.  w1: the weight of the conditioner's first 1x1 (its data columns when CN(c) is concatenated to the input)."""
     f, pp = _hip.f32, _hip.p
-    c1, c2, c3 = cpl.NN[0], cpl.NN[2], cpl.NN[4]
     eye = torch.eye(C, device=dev, dtype=torch.float32)
     zero = torch.zeros(C, device=dev, dtype=torch.float32)
     ws = torch.empty(_hip.lib().cf_flow_step_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
-    _hip.call("cf_flow_step_prepare", pp(eye), pp(zero), pp(zero), pp(w1), pp(f(c1.bias.detach())),
-              pp(f(c2.weight.detach())), pp(f(c2.bias.detach())), pp(f(c3.weight.detach())), pp(f(c3.bias.detach())),
+    _hip.call("cf_flow_step_prepare", pp(eye), pp(zero), pp(zero), pp(w1), *[pp(f(t.detach())) for t in conditioner_sources(cpl)[1:]],
               pp(ws), C, H, W, _hip.stream())
     return ws
 
@@ -358,15 +368,9 @@ class TransCoupling(_AffineCoupling):
         B, C = x.shape[0], x.shape[1]
         depth = len(self.NN[0].transformer.layers)
         z = torch.empty(B, C, x.shape[2], x.shape[3], device=x.device, dtype=torch.float32)
-        events = VIT_EVENTS if xtape is None else None
-        if events is not None:               # bench.py: HIP events on the launch stream around exactly this kernel
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(torch.cuda.current_stream(x.device))
-        _hip.call("cf_vit_step_fwd", _hip.p(x), _hip.p(z), _hip.p(ld1), _hip.p(tables.ws), _hip.p(h_out), _hip.p(xtape), B, C, depth,
-                  xbs, self.STEP_FORMS[tables.form], _hip.stream())
-        if events is not None:
-            e1.record(torch.cuda.current_stream(x.device))
-            events.append((e0, e1, B))
+        with _hip.probe(VIT_EVENTS if xtape is None else None, x.device, B):      # bench.py
+            _hip.call("cf_vit_step_fwd", _hip.p(x), _hip.p(z), _hip.p(ld1), _hip.p(tables.ws), _hip.p(h_out), _hip.p(xtape), B, C, depth,
+                      xbs, self.STEP_FORMS[tables.form], _hip.stream())
         return z
 
     def _flat_params(self):
@@ -408,15 +412,9 @@ class TransCoupling(_AffineCoupling):
             vit.pos_embedding = vit.pos_embedding.to(x.device).contiguous()
         z = torch.empty(B, C, H, W, device=x.device, dtype=torch.float32)
         ldj = None if inverse and not inverse_ldj else torch.empty(B, device=x.device, dtype=torch.float32)
-        events = VIT_EVENTS
-        if events is not None:               # bench.py: HIP events on the launch stream around exactly this kernel
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(torch.cuda.current_stream(x.device))
-        _hip.call("cf_vit_coupling", _hip.p(x), _hip.p(z), _hip.p(ldj), _hip.p(ws), _hip.p(vit.pos_embedding),
-                  B, C, H, W, p1, p2, dim, depth, xbs, int(inverse), st)
-        if events is not None:
-            e1.record(torch.cuda.current_stream(x.device))
-            events.append((e0, e1, B))
+        with _hip.probe(VIT_EVENTS, x.device, B):                                  # bench.py
+            _hip.call("cf_vit_coupling", _hip.p(x), _hip.p(z), _hip.p(ldj), _hip.p(ws), _hip.p(vit.pos_embedding),
+                      B, C, H, W, p1, p2, dim, depth, xbs, int(inverse), st)
         return z, ldj
 
     def forward(self, x, context=None):

@@ -12,28 +12,31 @@ Two execution modes produce the same numbers:
     The per-call parameter transforms (log|det W|, ActNorm folding, MFMA-fragment packing, GMM
     1/sigma tables) are tiny one-workgroup kernels: they are enqueued on a side HIP stream at the
     start of the call and joined by events, so they overlap the main stream's kernels.
-Set `fused = False` on the instance to force the layer-by-layer mode."""
+Set `fused = False` on the instance to force the layer-by-layer mode.
+
+The backward walk behind `inverse` / `sample` / `decode` is layers/inverse.py; the HIP-graph classes and the policy by which `forward`
+captures and replays on its own are layers/graphs.py."""
+import functools
 import math
 
 import torch
 import torch.nn as nn
 
-from . import _derived, _hip, _tape
+from . import _derived, _hip, _tape, graphs, inverse as _inv
 from ._tape import step_tape
 from .actnorm import ActNorm
 from .augment import Augment
-from .conv1x1 import Conv1x1, affine_ctx_inverse
+from .conv1x1 import Conv1x1
 from . import coupling as _cpl
-from .coupling import Coupling, TransCoupling
-from .dequantize import Dequantization
+from .coupling import Coupling, TransCoupling, step_sources
+from .dequantize import preprocess_rng_fwd, preprocessing_group
 from .distributions.gaussian import (GaussianMixtureDistribution, StandardNormal, gmm_logprob, gmm_levels_ok,
                                      gmm_logprob_levels, GMM_LEVELS_MAX_BATCH)
 from .distributions.uniform import UniformDistribution
-from .normalize import Normalization
+from .graphs import GraphedFlow, GraphedTrainStep
 from .permute_axes import PermuteAxes
 from .splitprior import SplitPrior
 from .squeeze import Squeeze, squeeze_op
-from .transforms import LogitTransform
 
 # training: the forward step kernel tapes y0 / h1 / h2 and the backward kernel loads them (no recompute of the two big
 # contractions).  False = the tape is dropped after the forward and rebuilt per step at backward time by the same kernel
@@ -59,6 +62,12 @@ def _on_parameter_registration(module, name, param):
 torch.nn.modules.module.register_module_parameter_registration_hook(_on_parameter_registration)
 
 
+@functools.lru_cache(maxsize=None)
+def _shape_query(name, C, H, W):
+    """A host-only query of the library about a step shape, asked once per process."""
+    return int(getattr(_hip.lib(), name)(C, H, W))
+
+
 class ContextNoise:
     """The noise of the stochastic context encoders of one flow for one batch (FlowSequential.context_noise): `tensors`, one per
     encoder in `flow.modules()` order."""
@@ -71,54 +80,6 @@ class ContextNoise:
 
     def __iter__(self):
         return iter(self.tensors)
-
-
-class _WalkDensity:
-    """What a backward walk gathers for the log-density of the point it produces (FlowSequential._inverse, return_logp):
-    ld1 (B,) - the forward log-det of every inverted layer at its recovered input and -log q of the channels an Augment drops,
-    added by the inverse kernels themselves - and the tensors the priors score, in place: the final z and every split-off half.
-    finish(): log p (B, M) = the mixtures' log-densities + ld1, through the kernels the forward uses."""
-
-    def __init__(self, z):
-        self.B, self.dev = z.shape[0], z.device
-        self.ld1 = torch.zeros(self.B, device=z.device, dtype=torch.float32)
-        self.levels = []              # (tensor, prepared mixture tables) in walk order: the prior first
-        self.terms = []               # (B, M) log-densities of priors that are no mixtures
-
-    def score(self, dist, x):
-        if isinstance(dist, GaussianMixtureDistribution) and not dist.context_net:
-            srcs = (dist.mG, dist.sG, dist.wG)
-            self.levels.append((x, _derived.get(dist, "walk_prep", _derived.key(srcs, str(self.dev)), dist.prepared, self.dev)))
-        elif callable(getattr(dist, "log_prob", None)) and not getattr(dist, "context_net", None):
-            lp = dist.log_prob(x)
-            self.terms.append(lp.reshape(self.B, -1))
-        else:
-            raise NotImplementedError("return_logp: no log-density rule for the prior %s" % type(dist).__name__)
-
-    def finish(self, M):
-        B, dev = self.B, self.dev
-        levels = self.levels[::-1]    # forward order: the halves, then the prior
-        ldM = None
-        for t in self.terms:
-            if t.shape[1] == 1:
-                self.ld1 += t[:, 0]
-            else:
-                ldM = t.clone() if ldM is None else ldM + t
-        if not levels:
-            return self.ld1.unsqueeze(-1).expand(B, M).clone() if ldM is None else ldM + self.ld1.unsqueeze(-1)
-        if B <= GMM_LEVELS_MAX_BATCH and gmm_levels_ok(levels):
-            return gmm_logprob_levels(levels, ldM, self.ld1)
-        if ldM is None:
-            ldM = torch.empty(B, M, device=dev, dtype=torch.float32)
-            acc = False
-        else:
-            acc = True
-        for x, prep in levels:
-            gmm_logprob(x, prep, out=ldM, accumulate=acc)
-            acc = True
-        logp = torch.empty(B, M, device=dev, dtype=torch.float32)
-        _hip.call("cf_logdet_combine", _hip.p(ldM), _hip.p(self.ld1), _hip.p(logp), B, M, _hip.stream())
-        return logp
 
 
 class FlowSequential(nn.Module):
@@ -143,7 +104,6 @@ class FlowSequential(nn.Module):
         self._graphs = {}            # (shape, device) -> [stable calls, versions, GraphedFlow | None]
         self._graph_policy = {}      # (shape, device) -> replaying beat eager launches when it was measured (else: stay eager)
         self._tensors = None         # parameters + buffers, collected once (_versions)
-        self._rng_key = 0            # Philox key of the in-kernel noise (rank folded in); the stream position is drawn per call
         # data-parallel training (dist.GradBucket, layers/autograd.py): the backward writes the gradients into one flat
         # bucket that p.grad views and all-reduces it segment by segment while it is still running
         self.data_parallel = False
@@ -282,13 +242,12 @@ class FlowSequential(nn.Module):
             return sh is not None and len(sh) == 3
         while i < n:
             m = mods[i]
-            if (isinstance(m, Dequantization) and isinstance(m.dist, UniformDistribution) and i + 3 < n
-                    and isinstance(mods[i + 1], Normalization) and isinstance(mods[i + 2], Normalization)
-                    and isinstance(mods[i + 3], LogitTransform) and is3(shape)):
-                aug = mods[i + 4] if (i + 4 < n and isinstance(mods[i + 4], Augment)
-                                      and isinstance(mods[i + 4].distribution, StandardNormal)
-                                      and mods[i + 4].split_dim == 1) else None
-                ops.append(("pre", m, mods[i + 1], mods[i + 2], aug))
+            g = preprocessing_group(mods, i) if is3(shape) else None
+            # the forward DRAWS the group's noise: uniform dequantisation noise only, and an Augment joins the group only when its
+            # channels are standard normals (any other one runs as a layer behind it).  Injected noise is looked at per call
+            if g is not None and isinstance(g.deq.dist, UniformDistribution):
+                aug = g.aug if g.aug is not None and isinstance(g.aug.distribution, StandardNormal) else None
+                ops.append(("pre", g, aug))
                 if aug is not None:
                     shape = (shape[0] + aug.aug_size,) + shape[1:]
                 i += 5 if aug is not None else 4
@@ -329,59 +288,22 @@ class FlowSequential(nn.Module):
             i += 1
         return ops
 
-    def _noise_nonce(self, dev):
-        """Per-call position of the in-kernel noise stream (dequantisation / Augment noise): `_hip.noise_nonce`, which the
-        tempered / class-conditional prior draws use too - one 63-bit draw from torch's CUDA generator per call; the Philox
-        key (rank folded in) goes to `_rng_key`."""
-        self._rng_key, nonce = _hip.noise_nonce(dev)
-        return nonce
-
     def _side_stream(self, dev, k=0):
         s = self._side.get((dev.index, k))
         if s is None:
             s = self._side[(dev.index, k)] = torch.cuda.Stream(device=dev)
         return s
 
-    @staticmethod
-    def _prepare_step(conv, act, cpl, shape, dev, winv=None):
-        """Packed weight tables of a flow step; winv (C, C): also Wm^-1 from the same factorisation (training)."""
-        C, H, W = shape
-        ws = torch.empty(_hip.lib().cf_flow_step_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
-        f, pp = _hip.f32, _hip.p
-        c1, c2, c3 = cpl.NN[0], cpl.NN[2], cpl.NN[4]
-        args = (pp(f(conv.NN.detach())), pp(f(act.NN_t.detach())), pp(f(act.NN_logs.detach())),
-                pp(f(c1.weight.detach())), pp(f(c1.bias.detach())), pp(f(c2.weight.detach())), pp(f(c2.bias.detach())),
-                pp(f(c3.weight.detach())), pp(f(c3.bias.detach())), pp(ws))
-        if winv is None:
-            _hip.call("cf_flow_step_prepare", *args, C, H, W, _hip.stream())
-        else:
-            _hip.call("cf_flow_step_prepare_train", *args, pp(winv), C, H, W, _hip.stream())
-        return ws
-
-    _chain_cache = {}
-
     @classmethod
     def _chain_max(cls, C, H, W):
         """largest batch at which cf_flow_step_fwd_chain covers this shape (0: never)"""
-        if not cls.CHAIN_STEPS:
-            return 0
-        v = cls._chain_cache.get((C, H, W))
-        if v is None:
-            v = cls._chain_cache[(C, H, W)] = int(_hip.lib().cf_flow_step_chain_max_batch(C, H, W))
-        return v
+        return _shape_query("cf_flow_step_chain_max_batch", C, H, W) if cls.CHAIN_STEPS else 0
 
     CHAIN_STEPS = True               # False: every flow step its own launch at every batch size (A/B, tests)
 
-    _level_cache = {}
-
     def _level_min(self, C, H, W):
         """smallest batch at which cf_flow_step_fwd_level runs this shape's level in one launch (0: never)"""
-        if (C, H, W) not in self.LEVEL_STEPS:
-            return 0
-        v = self._level_cache.get((C, H, W))
-        if v is None:
-            v = self._level_cache[(C, H, W)] = int(_hip.lib().cf_flow_step_level_min_batch(C, H, W))
-        return v
+        return _shape_query("cf_flow_step_level_min_batch", C, H, W) if (C, H, W) in self.LEVEL_STEPS else 0
 
     # shapes whose resolution level runs as ONE launch at saturating batches, z in LDS from step to step (empty: every step its
     # own launch; A/B, tests).  A shape is listed where its level launch measured faster than its step launches by more than five
@@ -399,10 +321,7 @@ class FlowSequential(nn.Module):
         f, n = _hip.f32, len(steps)
         wsz = L.cf_flow_step_ws_bytes(C, H, W)
         ws = [torch.empty(wsz, device=dev, dtype=torch.uint8) for _ in range(n)]
-        cols = ([f(s[0].NN.detach()) for s in steps], [f(s[1].NN_t.detach()) for s in steps], [f(s[1].NN_logs.detach()) for s in steps],
-                [f(s[2].NN[0].weight.detach()) for s in steps], [f(s[2].NN[0].bias.detach()) for s in steps],
-                [f(s[2].NN[2].weight.detach()) for s in steps], [f(s[2].NN[2].bias.detach()) for s in steps],
-                [f(s[2].NN[4].weight.detach()) for s in steps], [f(s[2].NN[4].bias.detach()) for s in steps])
+        cols = list(zip(*[[f(t.detach()) for t in step_sources(*s)] for s in steps]))       # one column per source tensor
         A = _hip.ptr_array
         winv = [torch.empty(C, C, device=dev, dtype=torch.float32) for _ in range(n)] if train else None
         _hip.call("cf_flow_step_prepare_batch", n, *[A(c) for c in cols], A(ws), A(winv) if train else None, C, H, W, _hip.stream())
@@ -435,7 +354,7 @@ class FlowSequential(nn.Module):
         store_ok = cache_ok and not capturing
         for k, op in enumerate(plan):
             if op[0] == "step":
-                srcs = (op[1].NN, op[2].NN_t, op[2].NN_logs) + tuple(p for c in (op[3].NN[0], op[3].NN[2], op[3].NN[4]) for p in (c.weight, c.bias))
+                srcs = step_sources(op[1], op[2], op[3])
             elif op[0] == "vstep":
                 srcs = (op[1].NN, op[2].NN_t, op[2].NN_logs) + op[3].step_sources()
                 vkey[k] = op[3].step_variant(B)      # small / saturating batches: two kernels, two fragment layouts
@@ -564,36 +483,29 @@ class FlowSequential(nn.Module):
             if k in chained:
                 continue
             if kind == "pre":
-                _, deq, n1, n2, aug = op
+                _, g, aug = op
+                deq, n1, n2 = g.deq, g.n1, g.n2
                 xin = _hip.f32(x)
                 C, H, W = xin.shape[1:]
                 N = C * H * W
-                ca = aug.aug_size if aug is not None else 0
-                y = torch.empty(B, C + ca, H, W, device=dev, dtype=torch.float32)
-                if tape is not None:
-                    tape.append(_tape.Pre(y, N, n1._s, n2._s))
-                cst = -N * math.log(n1._s) - N * math.log(n2._s)      # normalize.py:42-49, twice
                 ldp = ld1 if k == 0 else torch.empty_like(ld1)         # the kernel assigns its per-sample ldj
-                if (deq.dist.fixed_noise is None and (aug is None or aug.distribution.fixed_noise is None)
-                        and N % 4 == 0 and (ca * H * W) % 4 == 0):
-                    # noise drawn inside the kernel (Philox, keyed by torch's seed): dequantisation uniforms and the
-                    # Augment channel's normals never travel through HBM as tensors of their own
-                    nonce = self._noise_nonce(dev)
-                    _hip.call("cf_preprocess_rng_fwd", _hip.p(xin), _hip.p(y), _hip.p(ldp), _hip.p(nonce), self._rng_key, B, N,
-                              ca * H * W, (C + ca) * H * W, n1._t, n1._s, n2._t, n2._s, cst, 0, st)
-                    if ldp is not ld1:
-                        ld1 += ldp
-                    x = y
-                    continue
-                u = _hip.f32(deq.dist.sample(B, context=xin)[0])
-                _hip.call("cf_preprocess_fwd", _hip.p(xin), _hip.p(u), _hip.p(y), _hip.p(ldp), B, N, (C + ca) * H * W,
-                          n1._t, n1._s, n2._t, n2._s, cst, st)
+                y = preprocess_rng_fwd(xin, g, aug, ldp)         # noise drawn inside the kernel ...
+                rng = y is not None
+                if not rng:                                            # ... or injected / odd sizes: noise tensors from the layers
+                    ca = aug.aug_size if aug is not None else 0
+                    y = torch.empty(B, C + ca, H, W, device=dev, dtype=torch.float32)
+                    cst = -N * math.log(n1._s) - N * math.log(n2._s)      # normalize.py:42-49, twice
+                    u = _hip.f32(deq.dist.sample(B, context=xin)[0])
+                    _hip.call("cf_preprocess_fwd", _hip.p(xin), _hip.p(u), _hip.p(y), _hip.p(ldp), B, N, (C + ca) * H * W,
+                              n1._t, n1._s, n2._t, n2._s, cst, st)
                 if ldp is not ld1:
                     ld1 += ldp
-                if aug is not None:
+                if aug is not None and not rng:
                     eps, logq = aug.distribution.sample(B)
                     y[:, C:].copy_(eps)
                     ld1 -= logq.squeeze(-1)                            # Augment ldj = -log q(eps)
+                if tape is not None:
+                    tape.append(_tape.Pre(y, N, n1._s, n2._s))
                 x = y
             elif kind == "step":
                 _, conv, act, cpl, (C, H, W), sq = op
@@ -625,42 +537,30 @@ class FlowSequential(nn.Module):
                 x, xbs = _hip.bview(x)
                 z = torch.empty(B, C, H, W, device=dev, dtype=torch.float32)
                 events = self.step_events
-                if events is None and 0 < B <= self._chain_max(C, H, W):
-                    # small batch: this step and the following steps of the same shape (a resolution level) in ONE launch
-                    run, tabs = chain_run(k, ws, 4, lambda nxt: nxt[0] == "step" and tuple(nxt[4]) == (C, H, W) and not nxt[5])
-                    if len(run) > 1:
-                        _hip.call("cf_flow_step_fwd_chain", _hip.p(x), _hip.p(z), _hip.p(ld1), _hip.ptr_array(tabs), len(run), B, C, H, W, xbs,
-                                  int(sq), st)
-                        chained.update(run[1:])
-                        x = z
-                        continue
-                if 0 < self._level_min(C, H, W) <= B:
-                    # saturating batch: the level in ONE launch, z in LDS from step to step.  With step_events the launch still
-                    # leaves one record per step: the first carries the launch, the others are empty (its end event twice)
-                    run, tabs = chain_run(k, ws, 4, lambda nxt: nxt[0] == "step" and tuple(nxt[4]) == (C, H, W) and not nxt[5])
-                    if len(run) > 1:
-                        if events is not None:
-                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                            e0.record(main)
+                # this step and the following ones of its shape (a resolution level) in ONE launch: the chain kernel at small batches (never
+                # under step_events), the level kernel - z in LDS from step to step - at saturating ones; the run is formed only for those
+                chain = events is None and 0 < B <= self._chain_max(C, H, W)
+                level = not chain and 0 < self._level_min(C, H, W) <= B
+                same = lambda nxt: nxt[0] == "step" and tuple(nxt[4]) == (C, H, W) and not nxt[5]
+                run, tabs = chain_run(k, ws, 4, same) if chain or level else ([k], [ws])
+                if len(run) > 1 and chain:
+                    _hip.call("cf_flow_step_fwd_chain", _hip.p(x), _hip.p(z), _hip.p(ld1), _hip.ptr_array(tabs), len(run), B, C, H, W, xbs,
+                              int(sq), st)
+                elif len(run) > 1:
+                    with _hip.probe(events, main, B, C, H * W):
                         _hip.call("cf_flow_step_fwd_level", _hip.p(x), _hip.p(z), _hip.p(ld1), _hip.ptr_array(tabs), len(run), B, C, H, W, xbs,
                                   int(sq), 0, st)
-                        if events is not None:
-                            e1.record(main)
-                            events.append((e0, e1, B, C, H * W))
-                            events.extend((e1, e1, B, C, H * W) for _ in run[1:])
-                        chained.update(run[1:])
-                        x = z
-                        continue
-                if events is not None:       # HIP events on the launch stream, bracketing exactly this kernel
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(main)
-                _hip.call("cf_flow_step_fwd", _hip.p(x), _hip.p(z), _hip.p(ld1), _hip.p(ws), B, C, H, W, xbs, int(sq), st)
-                if events is not None:
-                    e1.record(main)
-                    events.append((e0, e1, B, C, H * W))
+                    if events is not None:   # one record per step all the same: the first carries the launch, the others are empty
+                        events.extend([(events[-1][1], events[-1][1], B, C, H * W)] * (len(run) - 1))
+                else:
+                    with _hip.probe(events, main, B, C, H * W):
+                        _hip.call("cf_flow_step_fwd", _hip.p(x), _hip.p(z), _hip.p(ld1), _hip.p(ws), B, C, H, W, xbs, int(sq), st)
+                chained.update(run[1:])
                 x = z
             elif kind == "vstep":
                 tables, ev = prepared[k]
+                if ev is not None:
+                    main.wait_event(ev)
                 if tape is not None:         # training: the same one-kernel forward; the backward re-runs the step from its input
                     #                          (and reuses the packed tables when they are the row-split ones)
                     # the residual stream at the layer boundaries goes to a tape (5.8 KB per sample and step) and the backward
@@ -670,12 +570,8 @@ class FlowSequential(nn.Module):
                         depth = len(op[3].NN[0].transformer.layers)
                         xt = torch.empty(_hip.lib().cf_vit_step_tape_floats(B, x.shape[1], depth), device=dev, dtype=torch.float32)
                     tape.append(_tape.VStep(op[1], op[2], op[3], x, tables, xt))
-                    if ev is not None:
-                        main.wait_event(ev)
                     x = op[3].step_forward(x, tables, ld1, xtape=xt)
                     continue
-                if ev is not None:
-                    main.wait_event(ev)
                 if self.CHAIN_STEPS and tables.form == "rs" and _cpl.VIT_EVENTS is None:
                     # small batch (row-split form): this step and the transformer steps that follow it in ONE launch
                     depth = len(op[3].NN[0].transformer.layers)
@@ -768,7 +664,7 @@ class FlowSequential(nn.Module):
                 return FlowLogProb.apply(self, input, *params)
         with torch.no_grad():
             if self._fusable():
-                g = self._auto_graph(input)
+                g = graphs._auto_graph(self, input)
                 if g is not None:
                     z, logp = g(input)
                     return z.clone(), logp.clone()       # the graph's static outputs are overwritten by the next replay
@@ -779,71 +675,8 @@ class FlowSequential(nn.Module):
                     return specialist.forward_eval(self, input, context)
             return self._forward_layers(input, context)
 
-    AUTO_GRAPH_AFTER = 2
-    AUTO_GRAPH_MAX_BATCH = 4096
-
-    def _auto_graph(self, x):
-        """Graph replay for small, repeated evaluation batches (the reference's operating point is B = 256, config.py:10:
-        ~20 launches of a few microseconds of work each).  Conditions: same shape / dtype / device as the previous calls,
-        parameters unchanged since (version counters), in-kernel noise (no injected test noise), no event probes, not
-        already capturing.  Anything else runs eagerly, and a parameter update drops the graph."""
-        from . import coupling as _cpl
-        if (not self.auto_graph or self.step_events is not None or _cpl.VIT_EVENTS is not None or x.dim() != 4 or x.shape[0] == 0
-                or x.shape[0] > self.AUTO_GRAPH_MAX_BATCH or torch.cuda.is_current_stream_capturing()):
-            return None
-        for m in self.sequence_modules:
-            d = getattr(m, "dist", None) or getattr(m, "distribution", None)
-            if d is not None and getattr(d, "fixed_noise", None) is not None:
-                return None
-        gkey = (tuple(x.shape), x.dtype, x.device)
-        ver = self._versions()
-        st = self._graphs.get(gkey)
-        if st is None or st[1] != ver:
-            if len(self._graphs) >= 8:                   # bounded: each graph owns its intermediates
-                self._graphs.clear()
-            self._graphs[gkey] = [1, ver, None]
-            return None
-        if st[2] is None:
-            if self._graph_policy.get(gkey) is False:    # measured before for this shape: eager launches are faster
-                return None
-            st[0] += 1
-            if st[0] <= self.AUTO_GRAPH_AFTER:
-                return None
-            st[2] = GraphedFlow(self, x, warmup=1)
-            if gkey not in self._graph_policy:
-                self._graph_policy[gkey] = self._replay_wins(st[2], x)
-                if not self._graph_policy[gkey]:
-                    st[2] = None
-                    return None
-        return st[2]
-
-    def _replay_wins(self, g, x, n=5, rounds=2, margin=0.97):
-        """A replayed node costs ~7-12 us whatever its kernel does, eager launches are queued ahead of the running kernel:
-        with kernels longer than that (the transformer steps: ~30 us each at a batch of 256) the eager forward can be the
-        faster one.  Measured once per input shape (the answer does not depend on parameter values; invalidate_caches()
-        forgets it): n eager forwards against n replays between HIP events on the launch stream, best of `rounds` each -
-        device time, so that a busy host core (bench.py's CPU-baseline threads) cannot pin the verdict - and the graph is
-        only rejected when eager is faster by more than 3 %.  The generator is handed back as it was, so the noise
-        sequence does not see the probe."""
-        dev = x.device
-        gen = torch.cuda.default_generators[dev.index]
-        gstate = gen.get_state()
-        stream = torch.cuda.current_stream(dev)
-        best = []
-        for run in (lambda: self._forward_fused(x, None), lambda: g(x)):
-            run()
-            t = []
-            for _ in range(rounds):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                for _ in range(n):
-                    run()
-                e1.record(stream)
-                e1.synchronize()
-                t.append(e0.elapsed_time(e1))
-            best.append(min(t))
-        gen.set_state(gstate)
-        return best[1] * margin < best[0]
+    AUTO_GRAPH_AFTER = graphs.AUTO_GRAPH_AFTER           # graphs._auto_graph reads both through the flow:
+    AUTO_GRAPH_MAX_BATCH = graphs.AUTO_GRAPH_MAX_BATCH   # settable on the class or on an instance
 
     def capture_train_step(self, example_input, loss_fn, optimizer, warmup=1, data_parallel=None):
         """One whole training step - forward, loss, hand-written backward, optimizer update - captured into ONE HIP graph
@@ -923,50 +756,6 @@ class FlowSequential(nn.Module):
         """Capture the fused forward for inputs of this exact shape into a HIP graph; returns a callable
         `g(x) -> (z, logp)` (static output buffers, overwritten by the next replay)."""
         return GraphedFlow(self, example_input)
-
-    @staticmethod
-    def _inverse_step_sources(conv, act, cpl):
-        return (conv.NN, act.NN_t, act.NN_logs, cpl.NN[0].weight, cpl.NN[0].bias, cpl.NN[2].weight, cpl.NN[2].bias, cpl.NN[4].weight,
-                cpl.NN[4].bias)
-
-    def _inverse_tables(self, conv, act, cpl, shape, dev):
-        """(ws, wsi) of a fused step for the inverse kernel."""
-        C, H, W = shape
-        f, pp, st = _hip.f32, _hip.p, _hip.stream()
-        # the packed tables of the step (forward fragments of the conditioner, W^-1 and the inverse ActNorm) are kept while the
-        # parameters they derive from are unchanged - version counter and storage of every source tensor, as the forward's tables
-        # (two factorisations + two packing launches per step and call before: 13 - 17 % of a `sample` call at 16 384 samples)
-        srcs = self._inverse_step_sources(conv, act, cpl)
-        def build():
-            ws = self._prepare_step(conv, act, cpl, (C, H, W), dev)
-            wsi = torch.empty(_hip.lib().cf_flow_step_inv_ws_bytes(C, H, W), device=dev, dtype=torch.uint8)
-            _hip.call("cf_flow_step_inv_prepare", pp(f(conv.NN.detach())), pp(f(act.NN_t.detach())), pp(f(act.NN_logs.detach())),
-                      pp(wsi), C, H, W, st)
-            return ws, wsi
-        return _derived.get(self, ("inv_ws", id(cpl)), _derived.key(srcs, C, H, W, str(dev)), build, dev)
-
-    def _inverse_step(self, z, conv, act, cpl, unsqueeze=False, ld=None):
-        """Conv1x1^-1 o ActNorm^-1 o Coupling^-1 in one MFMA kernel (cf_flow_step_inv); unsqueeze: the Squeeze((2,2)) in front of
-        the step is inverted by the kernel's stores.  ld (B,): the step's forward log-det at the recovered input is added to it
-        (cf_flow_step_inv_ld: the same kernel, the same x)."""
-        z, zbs = _hip.bview(z)
-        B, C, H, W = z.shape
-        dev = z.device
-        pp, st = _hip.p, _hip.stream()
-        ws, wsi = self._inverse_tables(conv, act, cpl, (C, H, W), dev)
-        x = torch.empty((B, C // 4, 2 * H, 2 * W) if unsqueeze else (B, C, H, W), device=dev, dtype=torch.float32)
-        events = self.inv_events
-        if events is not None:               # HIP events on the launch stream, bracketing exactly this kernel
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(torch.cuda.current_stream(dev))
-        if ld is None:
-            _hip.call("cf_flow_step_inv", pp(z), pp(x), pp(ws), pp(wsi), B, C, H, W, zbs, int(unsqueeze), st)
-        else:
-            _hip.call("cf_flow_step_inv_ld", pp(z), pp(x), pp(ld), pp(ws), pp(wsi), B, C, H, W, zbs, int(unsqueeze), st)
-        if events is not None:
-            e1.record(torch.cuda.current_stream(dev))
-            events.append((e0, e1, B, C, H * W))
-        return x
 
     # ------------------------------------------------------------------ the stochastic context encoders, pinned
     def _stochastic_encoders(self):
@@ -1067,140 +856,11 @@ class FlowSequential(nn.Module):
         self._refuse_logp(return_logp)
         self._need_context("inverse", context)
         with self._pinned(noise, context):
-            return self._inverse(z, context, None, return_logp=return_logp)
+            return _inv._inverse(self, z, context, None, return_logp=return_logp)
 
     def _refuse_logp(self, return_logp):
         if return_logp and self._has_context_nets():
             raise NotImplementedError("return_logp: a context-conditioned (specialist) flow - its inverse kernels have no log-det output")
-
-    def _pixel_range(self):
-        """(0, bins - 1) of the image flows - Dequantization followed by Normalization(0, bins) (model.py:97-98) - else None."""
-        mods = self.sequence_modules
-        if len(mods) >= 2 and isinstance(mods[0], Dequantization) and isinstance(mods[1], Normalization) and mods[1]._t == 0.0:
-            return 0.0, mods[1]._s - 1.0
-        return None
-
-    def _reverse_scored(self, m, z, wd):
-        """m.reverse(z) for a layer other than a SplitPrior, with the layer's forward log-det at the recovered input added to the
-        walk's running term wd.ld1.  NotImplementedError, naming the layer, where there is no rule."""
-        if isinstance(m, (Squeeze, PermuteAxes)):
-            return m.reverse(z)                                     # index maps: 0
-        if isinstance(m, Conv1x1) and not m.context_net:
-            wd.ld1 += m.logdet_const(z.shape[2] * z.shape[3] if z.dim() == 4 else 1, z.device)
-            return m.reverse(z)
-        if isinstance(m, ActNorm) and not m.context_net:
-            wd.ld1 += _hip.f32(m.NN_logs.detach()).sum()            # actnorm.py:58: + sum logs, without the H W factor (the quirk kept)
-            return m.reverse(z)
-        if type(m) in (Coupling, _cpl.CouplingFC, TransCoupling) and not m.context_net:
-            x, ldj = m.reverse_ldj(z)
-            wd.ld1 += ldj
-            return x
-        if isinstance(m, Augment) and m.split_dim == 1 and isinstance(m.distribution, StandardNormal):
-            keep = z.shape[1] - m.aug_size
-            wd.ld1 -= m.distribution.log_prob(z[:, keep:]).squeeze(-1)          # -log N(e) of the dropped channels, read by stride
-            return m.reverse(z)
-        if isinstance(m, Dequantization) and isinstance(m.dist, UniformDistribution):
-            return m.reverse(z)                                     # uniform noise on [0, 1): log q = 0
-        if isinstance(m, Normalization):
-            wd.ld1 += m.logdet(z)
-            return m.reverse(z)
-        if isinstance(m, LogitTransform):
-            x = m.reverse(z)
-            wd.ld1 += m.logdet(x)                                   # -log v - log(1 - v) at v = sigmoid(z)
-            return x
-        raise NotImplementedError("return_logp: no log-det rule for the reverse of %s" % type(m).__name__)
-
-    def _inverse(self, z, context, clamp, latents=None, labels=None, temperature=1.0, ctx_draw=False, return_logp=False):
-        """`inverse`; clamp = (lo, hi): the output of the leading Dequantization's reverse is projected into that range.
-        return_logp: (x, logp) - the walk also gathers the (B, M) log-density `forward` returns at the continuous point it
-        passes through (_WalkDensity); x and the random numbers drawn are those of the plain walk.
-        latents: the split-off halves in forward order, put back by the SplitPriors instead of fresh draws (`decode`);
-        labels / temperature: passed to every SplitPrior's draw (`sample`).  All at their defaults: the plain chain.
-        A specialist flow (context nets, a context given): every ActNorm(c) <- Conv1x1(c) pair - with the Squeeze((2,2)) in front of
-        it - is one cf_affine_ctx_inv launch, everything else its own reverse(z, context); ctx_draw: the SplitPriors draw from the
-        context-shifted mixtures (`sample` under a context)."""
-        if latents is not None:
-            latents = list(latents)
-        _hip.require_device(z)
-        mods = self.sequence_modules
-        i = len(mods) - 1
-        spec = context is not None and self._has_context_nets()
-        wd = None
-        if return_logp:
-            self._refuse_logp(True)
-            with torch.no_grad():
-                wd = _WalkDensity(z)
-                wd.score(self.dist, z)
-        ld = None if wd is None else wd.ld1
-        with torch.no_grad():
-            while i >= 0:
-                m = mods[i]
-                if (spec and isinstance(m, ActNorm) and m.context_net and i >= 1 and z.dim() == 4 and isinstance(mods[i - 1], Conv1x1)
-                        and mods[i - 1].context_net and mods[i - 1].D == z.shape[1]):
-                    sq = i >= 2 and isinstance(mods[i - 2], Squeeze) and tuple(mods[i - 2].p) == (2, 2) and z.shape[1] % 4 == 0
-                    z = affine_ctx_inverse(z, conv=mods[i - 1], act=m, context=context, unsqueeze=sq)
-                    i -= 3 if sq else 2
-                elif (not spec and self.fused and i >= 2 and z.dim() == 4 and isinstance(mods[i - 1], ActNorm)
-                        and mods[i - 1].is_initialized()
-                        and self._step_supported(mods[i - 2], mods[i - 1], m, tuple(z.shape[1:]))):
-                    sq = i >= 3 and isinstance(mods[i - 3], Squeeze) and tuple(mods[i - 3].p) == (2, 2)
-                    z = self._inverse_step(z, mods[i - 2], mods[i - 1], m, unsqueeze=sq, ld=ld)
-                    i -= 4 if sq else 3
-                elif self.fused and self._tail_fusable(i, z):
-                    z = self._inverse_tail(z, i, clamp, ld=ld)
-                    i = -1
-                else:
-                    if wd is not None and not isinstance(m, SplitPrior):
-                        z = self._reverse_scored(m, z, wd)
-                    elif isinstance(m, SplitPrior) and latents is not None:
-                        if not latents:
-                            raise ValueError("decode: no latent left for the SplitPrior at layer %d" % i)
-                        z = m.reverse(z, context, latent=latents.pop())
-                    elif isinstance(m, SplitPrior) and ctx_draw:
-                        z = m.reverse(z, context, labels=labels, temperature=temperature, ctx_draw=True)
-                    elif isinstance(m, SplitPrior) and (labels is not None or temperature != 1.0):
-                        z = m.reverse(z, context, labels=labels, temperature=temperature)
-                    else:
-                        z = m.reverse(z, context)
-                    if wd is not None and isinstance(m, SplitPrior):
-                        wd.score(m.dist, z[:, z.shape[1] // 2:])     # the half just put back - drawn, or `decode`'s - scored in place
-                    if i == 0 and clamp is not None and isinstance(m, Dequantization):
-                        _hip.call("cf_clamp", _hip.p(z), _hip.p(z), z.numel(), clamp[0], clamp[1], _hip.stream())
-                    i -= 1
-            if wd is not None:
-                return z, wd.finish(self.mixtures)
-        return z
-
-    def _tail_fusable(self, i, z):
-        """mods[:i + 1] is the pre-processing of the image flows - Dequantization, Normalization x 2, LogitTransform [, Augment over
-        the channels] - whose reverse chain cf_postprocess_inv runs in one pass."""
-        mods = self.sequence_modules
-        if z.dim() != 4 or i not in (3, 4) or not (isinstance(mods[0], Dequantization) and isinstance(mods[1], Normalization)
-                                                   and isinstance(mods[2], Normalization) and isinstance(mods[3], LogitTransform)):
-            return False
-        return i == 3 or (isinstance(mods[4], Augment) and mods[4].split_dim == 1 and 0 < mods[4].aug_size < z.shape[1])
-
-    def _inverse_tail(self, z, i, clamp=None, ld=None):
-        """ld (B,): the pre-processing's forward log-det at the continuous point behind z - and -log q of the Augment channels that
-        are dropped - is added to it (cf_postprocess_inv_ld: one pass, the same x)."""
-        mods = self.sequence_modules
-        z, zbs = _hip.bview(z)
-        B, C, H, W = z.shape
-        keep = C - (mods[4].aug_size if i == 4 else 0)
-        x = torch.empty(B, keep, H, W, device=z.device, dtype=torch.float32)
-        n1, n2 = mods[1], mods[2]
-        if ld is not None:
-            N = keep * H * W
-            cst = -N * math.log(n1._s) - N * math.log(n2._s)          # normalize.py:42-49, twice (as the forward's `pre`)
-            lo, hi = clamp if clamp is not None else (0.0, 0.0)
-            _hip.call("cf_postprocess_inv_ld", _hip.p(z), _hip.p(x), _hip.p(ld), B, N, (C - keep) * H * W, zbs, n2._t, n2._s, n1._t, n1._s,
-                      cst, int(clamp is not None), lo, hi, _hip.stream())
-        elif clamp is None:
-            _hip.call("cf_postprocess_inv", _hip.p(z), _hip.p(x), B, keep * H * W, zbs, n2._t, n2._s, n1._t, n1._s, _hip.stream())
-        else:
-            _hip.call("cf_postprocess_inv_clamped", _hip.p(z), _hip.p(x), B, keep * H * W, zbs, n2._t, n2._s, n1._t, n1._s,
-                      clamp[0], clamp[1], _hip.stream())
-        return x
 
     def sample(self, n_samples, context=None, labels=None, temperature=1.0, noise=None, return_logp=False):
         """flowsequential.py:32-39: a prior draw through the reverse chain.  By specification, for the image flows: the pixels
@@ -1231,16 +891,16 @@ class FlowSequential(nn.Module):
             with self._pinned(noise, context):
                 labels = self.dist._class_labels(labels, n_samples)
                 z = self.dist.draw(n_samples, labels, temperature, context=context)
-                return self._inverse(z, context, self._pixel_range(), labels=labels, temperature=temperature, ctx_draw=True)
+                return _inv._inverse(self, z, context, _inv._pixel_range(self), labels=labels, temperature=temperature, ctx_draw=True)
         if labels is not None or temperature != 1.0:
             if not isinstance(self.dist, GaussianMixtureDistribution):
                 raise ValueError("sample: labels / temperature need a mixture prior, not %s" % type(self.dist).__name__)
             labels = self.dist._class_labels(labels, n_samples)      # checked and moved to the device once, for every level
             z = self.dist.draw(n_samples, labels, temperature)
-            return self._inverse(z, context, self._pixel_range(), labels=labels, temperature=temperature, return_logp=return_logp)
-        z = self.dist.sample(n_samples, context, need_log_prob=False)[0] if isinstance(self.dist, GaussianMixtureDistribution) \
-            else self.dist.sample(n_samples, context)[0]           # (the reference's sample() also returns log p(z): the walk scores z itself)
-        return self._inverse(z, context, self._pixel_range(), return_logp=return_logp)
+        else:
+            z = self.dist.sample(n_samples, context, need_log_prob=False)[0] if isinstance(self.dist, GaussianMixtureDistribution) \
+                else self.dist.sample(n_samples, context)[0]       # (the reference's sample() also returns log p(z): the walk scores z itself)
+        return _inv._inverse(self, z, context, _inv._pixel_range(self), labels=labels, temperature=temperature, return_logp=return_logp)
 
     def _split_priors(self):
         return [m for m in self.sequence_modules if isinstance(m, SplitPrior)]
@@ -1292,132 +952,7 @@ class FlowSequential(nn.Module):
         if differentiable:
             return self._run_differentiable(z, latents[:-1], context, noise)
         with self._pinned(noise, context):
-            return self._inverse(z, context, self._pixel_range() if clamp else None, latents=latents[:-1], return_logp=return_logp)
-
-
-class GraphedFlow:
-    """A FlowSequential forward captured once into a HIP graph (launch-bound regime: small batches, where the ~45
-    kernel launches + side-stream hand-offs of a call cost more than the kernels).  Replays write into static
-    output buffers; the noise layers keep drawing fresh noise (graph-safe Philox offsets)."""
-
-    def __init__(self, flow, example, warmup=2):
-        _hip.require_device(example)
-        if not flow._fusable():
-            raise RuntimeError("capture needs initialised ActNorms (run one forward first) and the fused plan")
-        self.flow = flow
-        self.static_in = example.detach().clone()
-        with torch.no_grad():
-            s = torch.cuda.Stream(device=example.device)
-            s.wait_stream(torch.cuda.current_stream(example.device))
-            gen = torch.cuda.default_generators[example.device.index]
-            gstate = gen.get_state()                   # the warm-up passes draw noise positions nobody sees: hand the
-            with torch.cuda.stream(s):                 # generator back as it was, so that capturing is invisible in the
-                for _ in range(warmup):               # noise sequence (same seed => same noise, captured or not)
-                    flow._forward_fused(self.static_in, None)       # warm-up off the default stream: first-use attribute
-            torch.cuda.current_stream(example.device).wait_stream(s)   # calls, allocator pools, plan construction
-            gen.set_state(gstate)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self.static_z, self.static_logp = flow._forward_fused(self.static_in, None)
-
-    def __call__(self, x):
-        self.static_in.copy_(x)
-        self.graph.replay()
-        return self.static_z, self.static_logp
-
-
-class GraphedTrainStep:
-    """See FlowSequential.capture_train_step.
-
-    First call: `warmup` (default 1) EAGER training steps on the given batch - real optimizer updates, off the default
-    stream - then the capture of one more step (a capture records, it does not execute: no update).  It returns the loss
-    of the last eager step, so with the default warmup the first call is exactly one update, like every later call.
-    Later calls replay.  Before the capture and before every replay the optimizer's `push_hyperparameters()` is called if it
-    has one: `optim.FusedAdamW` keeps the learning rate in a device scalar that the captured update reads, so a loop that
-    assigns floats to `param_group['lr']` between calls (the reference's `warmup_lr`, `scheduler.step()` of `StepLR`) drives the
-    captured step unchanged, and `FusedAdamW(max_grad_norm=...)` puts the reference's `clip_grad_norm_` between backward and
-    update.  `torch.optim.AdamW(capturable=True)` with a float `lr` stays FROZEN at the rate of the capture - the float is
-    baked into its captured launches and later assignments are silently ignored.
-    A replay changes the parameters on the device without moving their version counters, which the evaluation caches of
-    the flow key on (packed step tables, mixture tables, auto-captured forward graphs): every call therefore ends with
-    `flow.invalidate_caches()`, and a `log_prob` between training steps sees the current parameters."""
-
-    def __init__(self, flow, example, loss_fn, optimizer, warmup=1, loss_args=()):
-        _hip.require_device(example)
-        if not flow._fusable() and not flow._specialist():
-            raise RuntimeError("capture_train_step needs initialised ActNorms: run one forward first")
-        if warmup < 1:
-            raise ValueError("capture_train_step: warmup must be >= 1 (the first call returns the loss of its last eager step)")
-        self.flow, self.loss_fn, self.opt = flow, loss_fn, optimizer
-        self.static_in = example.detach().clone()
-        self.static_args = None
-        self.graph = None
-        self.warmup = warmup
-        self.updates = 0             # optimizer updates performed through this object
-
-    @staticmethod
-    def _drain_collectives(dev):
-        """Before a capture that contains RCCL collectives: let the process group's watchdog thread retire the EAGER
-        collectives of the warm-up step.  It polls their completion events (hipEventQuery) every 100 ms; once the capture has
-        pulled RCCL's internal stream into capture mode, HIP answers such a query with hipErrorCapturedEvent ("event last
-        recorded in a capturing stream" - for an event recorded BEFORE the capture, on a stream that is capturing NOW), and
-        the watchdog aborts the process.  Seen once in four captures with a warm-up step right in front.  The device is idle
-        after the synchronize, so every pending work is complete and the next poll (or the one after) drops it."""
-        import time
-        import torch.distributed as tdist
-        if tdist.is_available() and tdist.is_initialized() and tdist.get_backend() == "nccl":
-            torch.cuda.synchronize(dev)
-            time.sleep(0.35)
-
-    def _push(self):
-        # an optimizer that keeps hyper-parameters on the device (optim.FusedAdamW: the learning rate) refreshes them from
-        # param_groups here, outside the graph: the captured launches read them from there
-        push = getattr(self.opt, "push_hyperparameters", None)
-        if push is not None:
-            push()
-
-    def _step(self):
-        # grads start as None: the autograd engine then TAKES the gradient buffers the backward returns (allocated from
-        # the graph's private pool during capture, so their addresses are the ones every replay writes and the
-        # optimizer's captured kernels read) instead of a fill + an accumulate launch per parameter
-        self.opt.zero_grad(set_to_none=True)
-        logp = self.flow.log_prob(self.static_in)
-        loss = self.loss_fn(logp, *self.static_args)
-        loss.backward()
-        self.opt.step()
-        return loss
-
-    def __call__(self, x, *loss_args):
-        if getattr(self.opt, "_in_ema_scope", False):
-            raise RuntimeError("GraphedTrainStep inside the optimizer's ema_scope(): the parameters hold the averages; leave the scope first")
-        if self.graph is None:
-            self.static_args = tuple(a.detach().clone() if torch.is_tensor(a) else a for a in loss_args)
-            self.static_in.copy_(x)
-            dev = self.static_in.device
-            self._push()
-            s = torch.cuda.Stream(device=dev)
-            s.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(s):                   # warm-up steps are real optimizer steps
-                for _ in range(self.warmup):
-                    first = self._step().detach().clone()
-            torch.cuda.current_stream(dev).wait_stream(s)
-            self.updates += self.warmup
-            if self.flow.data_parallel:
-                self._drain_collectives(dev)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self.static_loss = self._step()
-            self.flow.invalidate_caches()
-            return first
-        self.static_in.copy_(x)
-        for dst, src in zip(self.static_args, loss_args):
-            if torch.is_tensor(dst):
-                dst.copy_(src)
-        self._push()
-        self.graph.replay()
-        self.updates += 1
-        self.flow.invalidate_caches()
-        return self.static_loss
+            return _inv._inverse(self, z, context, _inv._pixel_range(self) if clamp else None, latents=latents[:-1], return_logp=return_logp)
 
 
 class FlowInvSequential(nn.Module):

@@ -13,22 +13,17 @@ layer list is grouped the way `FlowSequential._build_plan` groups the generalist
 and the per-sample log-dets accumulate in ONE (B,) buffer inside the kernels instead of a (B, M) add per layer.
 Evaluation only (no tape); `FlowSequential.forward` uses it under no_grad and falls back to the layer loop when a
 model does not have this shape."""
-import math
-
 import torch
 
 from . import _derived, _hip
 from .actnorm import ActNorm
 from .context import ContextCode, cn_chain, cn_linear
 from .conv1x1 import Conv1x1, slogdet_inverse
-from .coupling import Coupling, identity_front_step_tables
-from .dequantize import Dequantization
+from .coupling import Coupling, conditioner_sources, identity_front_step_tables
+from .dequantize import preprocess_rng_fwd, preprocessing_group
 from .distributions.gaussian import StandardNormal
 from .distributions.uniform import UniformDistribution
-from .augment import Augment
-from .normalize import Normalization
 from .squeeze import Squeeze
-from .transforms import LogitTransform
 
 
 def _const_logp(net):
@@ -74,7 +69,7 @@ def _affine_ok(conv, act, shape):
 
 def _coupling_ws(flow, cpl, C, H, W, dev):
     """Packed weights of the coupling step (identity 1x1 / ActNorm in front), kept while the conditioner is unchanged."""
-    srcs = tuple(p for c in (cpl.NN[0], cpl.NN[2], cpl.NN[4]) for p in (c.weight, c.bias))
+    srcs = conditioner_sources(cpl)
     return _derived.get(flow, ("spec_ws", id(cpl)), _derived.key(srcs, C, H, W, str(dev)),
                         lambda: identity_front_step_tables(cpl, _hip.f32(srcs[0].detach()), C, H, W, dev), dev)
 
@@ -259,22 +254,13 @@ def forward_eval(flow, x, context):
         m = mods[i]
         shape = tuple(x.shape[1:])
         # ---- pre-processing in one kernel, noise drawn inside it (as the generalist's plan does)
-        if (isinstance(m, Dequantization) and isinstance(m.dist, UniformDistribution) and i + 3 < n and len(shape) == 3
-                and isinstance(mods[i + 1], Normalization) and isinstance(mods[i + 2], Normalization)
-                and isinstance(mods[i + 3], LogitTransform) and m.dist.fixed_noise is None):
-            aug = mods[i + 4] if (i + 4 < n and isinstance(mods[i + 4], Augment) and isinstance(mods[i + 4].distribution, StandardNormal)
-                                  and mods[i + 4].split_dim == 1) else None
-            C, H, W = shape
-            N, ca = C * H * W, (aug.aug_size if aug is not None else 0)
-            if (aug is None or aug.distribution.fixed_noise is None) and N % 4 == 0 and (ca * H * W) % 4 == 0:
-                n1, n2 = mods[i + 1], mods[i + 2]
-                xin = f(x)
-                y = torch.empty(B, C + ca, H, W, device=dev, dtype=torch.float32)
-                cst = -N * math.log(n1._s) - N * math.log(n2._s)
-                ldp = torch.empty(B, device=dev, dtype=torch.float32)
-                nonce = flow._noise_nonce(dev)
-                _hip.call("cf_preprocess_rng_fwd", pp(xin), pp(y), pp(ldp), pp(nonce), flow._rng_key, B, N, ca * H * W,
-                          (C + ca) * H * W, n1._t, n1._s, n2._t, n2._s, cst, 0, st)
+        # (FlowSequential._build_plan's conditions; without in-kernel noise - injected noise, odd sizes - the layers run one by one, below)
+        g = preprocessing_group(mods, i) if len(shape) == 3 else None
+        if g is not None and isinstance(g.deq.dist, UniformDistribution):
+            aug = g.aug if g.aug is not None and isinstance(g.aug.distribution, StandardNormal) else None
+            ldp = torch.empty(B, device=dev, dtype=torch.float32)
+            y = preprocess_rng_fwd(x, g, aug, ldp)
+            if y is not None:
                 acc.add(ldp)
                 x = y
                 i += 5 if aug is not None else 4

@@ -1614,14 +1614,15 @@ def test_captured_train_step_matches_the_eager_loop(L, name):
     assert stale > 1e-3                           # four updates moved the model: a stale cache would reproduce the fixture
 
 
-def test_auto_graph_replay_and_cache_invalidation(L):
+def test_auto_graph_replay_and_cache_invalidation(L, monkeypatch):
     """Evaluation under no_grad: the packed parameter tables are cached, and after two identical-shape calls the forward is
     replayed from a captured HIP graph (FlowSequential.auto_graph).  Replays must keep drawing fresh noise, return tensors
     the next call does not overwrite, and a parameter update (version counters) must drop both the graph and the tables."""
     from tests.gpu_util import build_model
     ops, _, M, params, fx = load_e2e("mnist")
     model = build_model("mnist", params)
-    model._replay_wins = lambda graph, inp: True         # the mechanics under test; the timing probe has its own test below
+    from contextflow_amd.layers import graphs
+    monkeypatch.setattr(graphs, "_replay_wins", lambda flow, graph, inp: True)  # the mechanics under test; the timing probe has its own test below
     g = torch.Generator().manual_seed(3)
     x = torch.randint(0, 256, (48, 1, 32, 32), generator=g).float().to(DEV)
     outs = []
@@ -1813,17 +1814,19 @@ def test_parameter_derived_tables_are_built_once_per_parameter_version(L):
         undo()
 
 
-def test_auto_graph_keeps_eager_where_replay_loses(L):
+def test_auto_graph_keeps_eager_where_replay_loses(L, monkeypatch):
     """The replay-or-eager decision is measured once per input shape and kept across parameter updates; a shape whose probe
     said "eager" is never captured again, and the probe leaves torch's generator where it was (same noise either way)."""
     from tests.gpu_util import build_model
     ops, _, M, params, fx = load_e2e("mnist")
     x = torch.randint(0, 256, (32, 1, 32, 32), generator=torch.Generator().manual_seed(5)).float().to(DEV)
+    from contextflow_amd.layers import graphs
+    replay_wins = graphs._replay_wins
     res = {}
     for verdict in (True, False):
         model = build_model("mnist", params)
         probes = []
-        model._replay_wins = lambda graph, inp, v=verdict, p=probes: (p.append(1), type(model)._replay_wins(model, graph, inp), v)[2]
+        monkeypatch.setattr(graphs, "_replay_wins", lambda flow, graph, inp, v=verdict, p=probes: (p.append(1), replay_wins(flow, graph, inp), v)[2])
         torch.manual_seed(11)
         with torch.no_grad():
             outs = [model.log_prob(x).clone() for _ in range(5)]

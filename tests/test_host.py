@@ -651,6 +651,46 @@ def test_gradient_bucket_follows_the_backward(built, name):
     assert ag._bucket_for(flow, tape, params) is b          # kept: p.grad keeps viewing the same storage
 
 
+def _steps(shape, n):
+    """n fused steps of one resolution level: the first with its Squeeze folded in."""
+    return [("step", shape, True)] + [("step", shape, False)] * (n - 1)
+
+
+# The fused plan of every preset as FlowSequential._build_plan grouped it before layers/flowsequential.py was split into
+# flowsequential.py / inverse.py / graphs.py: kind per op, with (C, H, W) and the squeeze flag of a conv step, (C, H, W) of a
+# transformer step.  The last entry: modules in the pre-processing group at index 0 (None: no such group).
+FUSED_PLANS = {
+    "cifar10": ([("pre",)] + _steps((16, 16, 16), 4) + [("split",)] + _steps((32, 8, 8), 4) + [("split",)] + _steps((64, 4, 4), 4), 5),
+    "mnist": ([("pre",)] + _steps((8, 16, 16), 2) + _steps((32, 8, 8), 2), 5),         # (1 + 1) * 4 = 8 channels: an Augment, as cifar10
+    "smap": ([("layer",)] + [("vstep", (26, 8, 1))] * 8, None),
+    "msl": ([("layer",)] * 25, None),
+    "smd": ([("layer",)] * 24, None),
+    "atm": (([("squeeze",)] + [("layer",)] * 16 + [("split",)]) * 2 + [("squeeze",)] + [("layer",)] * 16, None),
+}
+
+
+@pytest.mark.parametrize("name", sorted(FUSED_PLANS))
+def test_fused_plan_of_every_preset(built, name):
+    """The plan of each preset is the recorded one, op for op, and `preprocessing_group` finds the image flows' group - with
+    their Augment - at index 0 and nothing in the time-series flows.  Host only: no kernel is launched."""
+    import contextflow_amd as cfa
+    from contextflow_amd.layers.dequantize import preprocessing_group
+    cfg, ds, M = cfa.preset_config(name)
+    flow = cfa.create_model(cfg, ds, M)
+    want, group = FUSED_PLANS[name]
+    got = []
+    for op in flow._build_plan(tuple(ds)):
+        got.append((op[0],) + ((tuple(op[4]), bool(op[5])) if op[0] == "step" else (tuple(op[4]),) if op[0] == "vstep" else ()))
+    assert got == want
+    g = preprocessing_group(flow.sequence_modules)
+    if group is None:
+        assert g is None
+    else:
+        mods = flow.sequence_modules
+        assert g.count == group and (g.deq, g.n1, g.n2, g.logit) == tuple(mods[:4]) and g.aug is mods[4]
+        assert preprocessing_group(mods, 1) is None and preprocessing_group(mods, len(mods) - 2) is None
+
+
 def test_calls_run_on_the_device_that_owns_the_tensors(built, monkeypatch):
     """`_hip.call` launches on the device the tensor arguments live on, on that device's current stream - the reference
     picks `cuda:N` without torch.cuda.set_device (model.py:170).  Host-side check of the selection logic with stand-in

@@ -112,11 +112,12 @@ def step_modules(L, C, H):
 
 def both_steps(flow, z, conv, act, cpl, unsq, pre):
     """(x of cf_flow_step_inv, x and ld of cf_flow_step_inv_ld on ld pre-filled with `pre`, ld of a second flagged launch)."""
-    x0 = flow._inverse_step(z, conv, act, cpl, unsqueeze=unsq)
+    from contextflow_amd.layers.inverse import _inverse_step
+    x0 = _inverse_step(flow, z, conv, act, cpl, unsqueeze=unsq)
     ld = pre.clone()
-    x1 = flow._inverse_step(z, conv, act, cpl, unsqueeze=unsq, ld=ld)
+    x1 = _inverse_step(flow, z, conv, act, cpl, unsqueeze=unsq, ld=ld)
     ld2 = pre.clone()
-    flow._inverse_step(z, conv, act, cpl, unsqueeze=unsq, ld=ld2)
+    _inverse_step(flow, z, conv, act, cpl, unsqueeze=unsq, ld=ld2)
     torch.cuda.synchronize()
     return x0, x1, ld, ld2
 

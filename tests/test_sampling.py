@@ -351,9 +351,10 @@ def test_every_fused_step_of_the_fixtures(L, name, tag):
         assert isinstance(conv, cfa.layers.Conv1x1) and isinstance(act, cfa.layers.ActNorm) and isinstance(cpl, cfa.layers.Coupling)
         C, H = inputs[i].shape[1:3]
         form = conditioner_form(C, H, B)
+        from contextflow_amd.layers.inverse import _inverse_step
         model.inv_events = []
         try:
-            got = model._inverse_step(tile_rows(inputs[i + 3].float(), B).to(DEV), conv, act, cpl, unsqueeze=sq)
+            got = _inverse_step(model, tile_rows(inputs[i + 3].float(), B).to(DEV), conv, act, cpl, unsqueeze=sq)
             torch.cuda.synchronize()
             assert [(e[2], e[3], e[4]) for e in model.inv_events] == [(B, C, H * H)]
         finally:

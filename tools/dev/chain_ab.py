@@ -5,6 +5,7 @@ import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 import bench
+from contextflow_amd.layers import graphs
 from contextflow_amd.layers.flowsequential import FlowSequential
 dev = torch.device("cuda", 0)
 for name, B in (("cifar10", 64), ("cifar10", 256), ("cifar10", 512), ("mnist", 64), ("mnist", 256), ("smap", 64), ("smap", 256), ("smap", 1024)):
@@ -18,7 +19,7 @@ for name, B in (("cifar10", 64), ("cifar10", 256), ("cifar10", 512), ("mnist", 6
             for mode in ("eager", "graph"):
                 model.auto_graph = mode == "graph"
                 if mode == "graph":
-                    model._replay_wins = lambda g, inp: True
+                    graphs._replay_wins = lambda flow, g, inp: True
                 for _ in range(20):
                     model.log_prob(x)
                 torch.cuda.synchronize(); t0 = time.perf_counter()
