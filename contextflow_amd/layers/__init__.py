@@ -20,7 +20,7 @@ from .activations import (FlowActivationLayer, Identity, LeakyRelu, LearnableLea
 from .actnorm import ActNorm, ActNormFC
 from .squeeze import Squeeze, UnSqueeze
 from .transforms import LogitTransform
-from .coupling import Coupling, CouplingFC, TransCoupling
+from .coupling import Coupling, CouplingFC, SplineCoupling, TransCoupling
 from .simple_vit import SimpleViT, posemb_sincos_2d
 from .ar import MaskedCoupling
 from .permute_axes import PermuteAxes

@@ -191,9 +191,11 @@ def conv_backward(x_in, conv, gy, grads, need_gx=True):
     return gx
 
 
-def coupling_conv_backward(m, x_in, gz, gld, params=True):
-    """Coupling with a conv conditioner of any shape (coupling.py:39-66; the fused step kernels cover only the image
-    shapes): the conditioner is re-run layer by layer with its activations kept, then the chain back."""
+def _conv_conditioner_backward(m, x_in, gz, gld, params, map_backward):
+    """A coupling whose conditioner is the conv net m.NN (1x1 -> ReLU -> k x k reflect -> ReLU -> 1x1) of any shape: the conditioner is
+    re-run layer by layer with its activations kept, map_backward(x, xbs, h, gz, gzbs, gld, gx, gh) launches the backward of the
+    elementwise map - x, gz by their batch strides; gx (B, C, H, W) and gh (the shape of h) dense, allocated here - then the chain
+    back through the three convolutions."""
     from .coupling import conv2d_reflect
     x, xbs = _hip.bview(x_in)
     gzv, gzbs = _hip.bview(gz)
@@ -204,14 +206,32 @@ def coupling_conv_backward(m, x_in, gz, gld, params=True):
     a1 = conv2d_reflect(x0, c1, True)
     a2 = conv2d_reflect(a1, c2, True)
     h = conv2d_reflect(a2, c3, False)
-    gx, gh = _new(B, C, H, W, like=x), _new(B, C, H, W, like=x)
-    _hip.call("cf_coupling_apply_bwd", _hip.p(x), _hip.p(h), _hip.p(gzv), _hip.p(_hip.f32(gld)), _hip.p(gx), _hip.p(gh),
-              B, C, H * W, xbs, gzbs, _hip.stream())
+    gx, gh = _new(B, C, H, W, like=x), torch.empty_like(h)
+    map_backward(x, xbs, h, gzv, gzbs, _hip.f32(gld), gx, gh)
     grads = {} if params else None
     g2 = _relu_mask(a2, conv_backward(a2, c3, gh, grads))
     g1 = _relu_mask(a1, conv_backward(a1, c2, g2, grads))
     gx[:, :half] += conv_backward(x0, c1, g1, grads)
     return gx, grads or {}
+
+
+def coupling_conv_backward(m, x_in, gz, gld, params=True):
+    """Coupling with a conv conditioner of any shape (coupling.py:39-66; the fused step kernels cover only the image
+    shapes): the affine map's backward between the conditioner's re-run and the chain back."""
+    def affine(x, xbs, h, g, gbs, gl, gx, gh):
+        _hip.call("cf_coupling_apply_bwd", _hip.p(x), _hip.p(h), _hip.p(g), _hip.p(gl), _hip.p(gx), _hip.p(gh),
+                  x.shape[0], x.shape[1], x.shape[2] * x.shape[3], xbs, gbs, _hip.stream())
+    return _conv_conditioner_backward(m, x_in, gz, gld, params, affine)
+
+
+def spline_coupling_backward(m, x_in, gz, gld, params=True):
+    """SplineCoupling: z = [x0 | RQS(x1; NN(x0))], ldj = the sum of the log-derivatives.  cf_spline_coupling_bwd stands where
+    cf_coupling_apply_bwd stands for the affine map: the gradient w.r.t. x and w.r.t. the raw knot parameters h, tables and bin
+    recomputed from h and x1."""
+    def spline(x, xbs, h, g, gbs, gl, gx, gh):
+        _hip.call("cf_spline_coupling_bwd", _hip.p(x), _hip.p(h), _hip.p(g), _hip.p(gl), _hip.p(gx), _hip.p(gh),
+                  x.shape[0], x.shape[1], x.shape[2] * x.shape[3], m.bins, m.tail_bound, xbs, gbs, _hip.stream())
+    return _conv_conditioner_backward(m, x_in, gz, gld, params, spline)
 
 
 def masked_coupling_backward(m, x_in, gz, gld, params=True):
@@ -295,8 +315,10 @@ def layer_backward(m, x_in, gz, gld, params=True):
     from .augment import Augment
     from .conv1x1 import Conv1x1
     from .ar import MaskedCoupling
-    from .coupling import Coupling, TransCoupling
+    from .coupling import Coupling, SplineCoupling, TransCoupling
     from .permute_axes import PermuteAxes
+    if type(m) is SplineCoupling:
+        return spline_coupling_backward(m, x_in, gz, gld, params)
     if isinstance(m, TransCoupling):
         return transcoupling_backward(m, x_in, gz, gld, params)
     if type(m) is Coupling and not m.context_net:

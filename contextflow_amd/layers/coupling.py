@@ -1,8 +1,9 @@
-"""Affine coupling layers (reference: contextflow/layers/coupling.py:14-159), context-free branch.
+"""Coupling layers: the affine ones (reference: contextflow/layers/coupling.py:14-159) and SplineCoupling.
 
 Coupling      — conditioner = Conv2d 1x1 -> ReLU -> Conv2d kxk (reflect) -> ReLU -> Conv2d 1x1
 TransCoupling — conditioner = SimpleViT
-Both transform the SECOND channel half given the first: t = h[:, :C/2], log_s = 2 tanh(h[:, C/2:]/2),
+SplineCoupling — conditioner as Coupling's, a monotone rational-quadratic spline per element in place of the affine map
+The affine ones transform the SECOND channel half given the first: t = h[:, :C/2], log_s = 2 tanh(h[:, C/2:]/2),
 z1 = x1*exp(log_s) + t, ldj = sum log_s (coupling.py:52-66).  The nn.Conv2d / nn.Linear objects are
 kept purely as parameter containers so that `state_dict` keys equal the reference's; the arithmetic
 runs in the HIP kernels."""
@@ -235,6 +236,65 @@ class Coupling(_AffineCoupling):
         _hip.require_device(z)
         h, _ = self._net_ctx(z[:, : z.shape[1] // 2], context)
         return coupling_apply(z, h, True)[0]
+
+
+def spline_coupling_apply(x, h, bins, tail_bound, inverse, inverse_ldj=False):
+    """[x0 | RQS(x1; h)] (inverse: RQS^-1) and the forward log-det (cf_spline_coupling).  x may be a batch-strided slice;
+    inverse_ldj: the inverse map also returns the forward log-det at the point it recovers (None otherwise)."""
+    x, xbs = _hip.bview(x)
+    h = _hip.f32(h)
+    B, C = x.shape[0], x.shape[1]
+    HW = x.numel() // max(B * C, 1) if B else 1
+    z = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    ldj = None if inverse and not inverse_ldj else torch.empty(B, device=x.device, dtype=torch.float32)
+    _hip.call("cf_spline_coupling", _hip.p(x), _hip.p(h), _hip.p(z), _hip.p(ldj), B, C, HW, bins, float(tail_bound), xbs,
+              int(inverse), _hip.stream())
+    return z, ldj
+
+
+class SplineCoupling(FlowLayer):
+    """Rational-quadratic spline coupling: z = [x0 | RQS(x1; NN(x0))], the monotone spline with linear tails of
+    `SplineActivation` (layers/splines/rational_quadratic.py:21-176) with the knots of every element read from the
+    conditioner output (the layout sketched at layers/activations.py:140): channel c (3 bins - 1) + j of NN(x0) belongs to
+    data channel c - `bins` unnormalised widths, `bins` heights, `bins - 1` interior derivatives.  The conditioner has the
+    shape and the state-dict keys of `Coupling.NN` with a wider last convolution; that one starts at zero, so a fresh layer
+    is the identity on [-tail_bound, tail_bound] (outside it always is).  No context variant."""
+
+    def __init__(self, data_channels, kernel_size=(1, 1), padding=(0, 0), bins=8, tail_bound=3.0):
+        super().__init__()
+        if data_channels < 2 or data_channels % 2:
+            raise ValueError("SplineCoupling: data_channels must be even and positive, got %r" % (data_channels,))
+        if not 2 <= bins <= 16:
+            raise ValueError("SplineCoupling: bins must be in 2..16, got %r" % (bins,))
+        if not tail_bound > 0:
+            raise ValueError("SplineCoupling: tail_bound must be positive, got %r" % (tail_bound,))
+        D, Hd = data_channels // 2, data_channels * 2
+        self.context_net = None
+        self.bins, self.tail_bound = int(bins), float(tail_bound)
+        self.NN = nn.Sequential(
+            nn.Conv2d(D, Hd, 1), nn.ReLU(),
+            nn.Conv2d(Hd, Hd, kernel_size, padding=padding, padding_mode="reflect"), nn.ReLU(),
+            nn.Conv2d(Hd, D * (3 * self.bins - 1), 1))
+        nn.init.zeros_(self.NN[4].weight)
+        nn.init.zeros_(self.NN[4].bias)
+
+    net = Coupling.net                      # the same three convolutions over self.NN
+
+    def forward(self, x, context=None):
+        _hip.require_device(x)
+        return spline_coupling_apply(x, self.net(x[:, : x.shape[1] // 2]), self.bins, self.tail_bound, False)
+
+    def reverse(self, z, context=None):
+        _hip.require_device(z)
+        return spline_coupling_apply(z, self.net(z[:, : z.shape[1] // 2]), self.bins, self.tail_bound, True)[0]
+
+    def reverse_ldj(self, z):
+        """(x, ldj): `reverse` and the forward log-det at x, from the same conditioner pass."""
+        _hip.require_device(z)
+        return spline_coupling_apply(z, self.net(z[:, : z.shape[1] // 2]), self.bins, self.tail_bound, True, inverse_ldj=True)
+
+    def logdet(self, input, context=None):
+        return self.forward(input, context)[1]
 
 
 class CouplingFC(Coupling):

@@ -9,7 +9,7 @@ from . import _derived, _hip
 from .actnorm import ActNorm
 from .augment import Augment
 from .conv1x1 import Conv1x1, affine_ctx_inverse
-from .coupling import Coupling, CouplingFC, TransCoupling, step_sources
+from .coupling import Coupling, CouplingFC, SplineCoupling, TransCoupling, step_sources
 from .dequantize import Dequantization, preprocessing_group
 from .distributions.gaussian import GaussianMixtureDistribution, StandardNormal, gmm_logprob, gmm_levels_ok, gmm_logprob_levels, GMM_LEVELS_MAX_BATCH
 from .distributions.uniform import UniformDistribution
@@ -127,7 +127,7 @@ def _reverse_scored(m, z, wd):
     if isinstance(m, ActNorm) and not m.context_net:
         wd.ld1 += _hip.f32(m.NN_logs.detach()).sum()            # actnorm.py:58: + sum logs, without the H W factor (the quirk kept)
         return m.reverse(z)
-    if type(m) in (Coupling, CouplingFC, TransCoupling) and not m.context_net:
+    if type(m) in (Coupling, CouplingFC, TransCoupling, SplineCoupling) and not m.context_net:
         x, ldj = m.reverse_ldj(z)
         wd.ld1 += ldj
         return x

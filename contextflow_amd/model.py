@@ -6,8 +6,8 @@ Appendix B).  Generalist (context-free) models, and specialist models (`generali
 Coupling gets its own ContextEncoder, the priors an embedding lookup — model.py:117-162) for the conv couplings with
 the eye | onehot + uniform context encoders."""
 from .layers import (ActNorm, Augment, ContextEncoder, Conv1x1, Coupling, Dequantization, FlowSequential,
-                     GaussianMixtureDistribution, LogitTransform, MaskedCoupling, Normalization, PermuteAxes, SplitPrior, Squeeze,
-                     StandardNormal, TransCoupling, UniformDistribution)
+                     GaussianMixtureDistribution, LogitTransform, MaskedCoupling, Normalization, PermuteAxes, SplineCoupling, SplitPrior,
+                     Squeeze, StandardNormal, TransCoupling, UniformDistribution)
 
 ALPHA = 1e-4
 COMPONENTS = 8
@@ -75,6 +75,8 @@ def create_model(config, data_size=(1, 1, 1), mixtures=1, contexts=(-1,)):
             elif config["coupling"] == "conv":
                 layers.append(Coupling(sz[0], kernel_size=krn, padding=pad, context_net=ctxnet((sz[0],)),
                                        contextflow=contextflow))
+            elif config["coupling"] == "spline":       # (generalist only: refused above for a specialist model)
+                layers.append(SplineCoupling(sz[0], kernel_size=krn, padding=pad))
             elif config["coupling"] == "maf":
                 layers.append(MaskedCoupling(sz[0], kernel_size=krn, padding=pad, context_net=ctxnet((sz[0],)),
                                              contextflow=contextflow))

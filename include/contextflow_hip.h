@@ -586,6 +586,25 @@ int cf_spline_prepare(const float* uw, const float* uh, const float* ud, float* 
 int cf_spline(const float* x, const float* table, float* y, float* ldj, int B, int N, int P, int K, float tail_bound,
               int inverse, cf_stream_t stream);
 
+/* ---- SplineCoupling: the same spline with the knots of every element taken from a conditioner (layers/activations.py:140:
+ * h = NN(x0) as (B, D, 3K-1, H, W), D = C/2) ------------------------------------------------------------------------ */
+/* x (B,C,HW) by batch stride, h (B, D (3K-1), HW) dense: channel c (3K-1) + j of h belongs to data channel c - j < K
+ * unnormalised widths, K <= j < 2K heights, 2K <= j < 3K-1 interior derivatives (minimum width, height, derivative 1e-3,
+ * boundary derivatives 1, identity outside [-tail_bound, tail_bound]).  z (B,C,HW) dense.
+ * inverse=0: z = [x0 | RQS(x1; h)], ldj[b] = sum of the log-derivatives ;  inverse=1: z = [x0 | RQS^-1(x1; h)] (bin search on
+ * the cumulative heights, the quadratic's discriminant clamped at 0) and, where ldj is not NULL, ldj[b] = the forward log-det
+ * at the recovered input (NULL: nothing is stored).  B == 0: no-op.  K outside 2..16: CF_ERR_UNSUPPORTED.  Any alignment:
+ * dwordx4 accesses where HW % 4 == 0, x_bstride % 4 == 0 and the pointers are 16-byte aligned, dwords otherwise - same bits.
+ * No atomics: two launches give the same bits.  (Adds symbols only: CF_ABI_VERSION stays.)                              */
+int cf_spline_coupling(const float* x, const float* h, float* z, float* ldj, int B, int C, int HW, int K, float tail_bound,
+                       int64_t x_bstride, int inverse, cf_stream_t stream);
+/* backward of the forward map: x, gz (B,C,HW) by their batch strides, gld (B) = d/d ldj -> gx (B,C,HW) dense =
+ * [gz0 | gz1 dz1/dx1 + gld d(log-derivative)/dx1] (the conditioner's part of gx0 is the caller's), gh (B, D (3K-1), HW) dense =
+ * the gradient w.r.t. the raw conditioner outputs.  Outside the tails gx1 = gz1 and gh = 0.  Tables and bin are recomputed
+ * from h and x1; every entry of gh is written once, no atomics.                                                          */
+int cf_spline_coupling_bwd(const float* x, const float* h, const float* gz, const float* gld, float* gx, float* gh, int B, int C,
+                           int HW, int K, float tail_bound, int64_t x_bstride, int64_t gz_bstride, cf_stream_t stream);
+
 /* ---- backward of the layer-by-layer path (training step, experiment_ad.py:207-213: loss.backward()) ---------
  * SimpleViT conditioner of TransCoupling (simple_vit.py:30-127) and the generic ActNorm / affine coupling map.
  * The Linear layers' backward GEMMs (gX = gY W, gW = gY^T X) are plain library GEMMs on the host side.        */
