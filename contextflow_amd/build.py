@@ -23,7 +23,7 @@ def sources():
 
 
 def deps():
-    return sources() + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(os.path.dirname(PKG), "include", "contextflow_hip.h")]
+    return sources() + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + [os.path.join(os.path.dirname(PKG), "include", "contextflow_hip.h")]
 
 
 def up_to_date():

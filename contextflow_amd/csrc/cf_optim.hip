@@ -29,13 +29,14 @@ struct AdamBatch {
 
 // w1 = 1 - beta1, w2 = 1 - beta2, decay = 1 - lr weight_decay are formed by the host in double, as torch forms them; the bias
 // corrections 1 - beta^t in double on the device (t is only known there), from ln(beta): one exp per thread and moment.
-// The body lives in cf_adamw_body.h: k_adamw and k_adamw_dev below are compiled from the same text, and k_adamw's code is
-// the one it had before k_adamw_dev existed (compared in the assembly; the header says how, and why it is no function).
+// The body lives in cf_adamw_body.inc (a fragment included once per kernel, hence no header): k_adamw and k_adamw_dev below are
+// compiled from the same text, and k_adamw's code is the one it had before k_adamw_dev existed (compared in the assembly; the
+// fragment says how, and why it is no function).
 __global__ __launch_bounds__(256) void k_adamw(const AdamBatch tb, const float* __restrict__ step, double lr, double lnb1, double lnb2,
                                                float beta2, float w1, float w2, float eps, float decay, int maximize) {
 #define CF_ADAMW_GRAD(ge)
 #define CF_ADAMW_EMA(...)
-#include "cf_adamw_body.h"
+#include "cf_adamw_body.inc"
 #undef CF_ADAMW_EMA
 #undef CF_ADAMW_GRAD
 }
@@ -55,7 +56,7 @@ __global__ __launch_bounds__(256) void k_adamw_dev(const AdamBatch tb, const flo
     // into the first moment's subtraction)
 #define CF_ADAMW_GRAD(ge) if (SCALE) ge = __fmul_rn(ge, coef)
 #define CF_ADAMW_EMA(...)
-#include "cf_adamw_body.h"
+#include "cf_adamw_body.inc"
 #undef CF_ADAMW_EMA
 #undef CF_ADAMW_GRAD
 }
@@ -85,7 +86,7 @@ __global__ __launch_bounds__(256) void k_adamw_ema(const AdamEmaBatch tb, const 
                                                    int ema_warmup) {
 #define CF_ADAMW_GRAD(ge)
 #define CF_ADAMW_EMA(...) __VA_ARGS__
-#include "cf_adamw_body.h"
+#include "cf_adamw_body.inc"
 #undef CF_ADAMW_EMA
 #undef CF_ADAMW_GRAD
 }
@@ -99,7 +100,7 @@ __global__ __launch_bounds__(256) void k_adamw_dev_ema(const AdamEmaBatch tb, co
     const float coef = SCALE ? rec[1] : 1.f;
 #define CF_ADAMW_GRAD(ge) if (SCALE) ge = __fmul_rn(ge, coef)
 #define CF_ADAMW_EMA(...) __VA_ARGS__
-#include "cf_adamw_body.h"
+#include "cf_adamw_body.inc"
 #undef CF_ADAMW_EMA
 #undef CF_ADAMW_GRAD
 }

@@ -1,6 +1,7 @@
 // Shared device code of the fused flow-step kernels (forward, inverse, backward): compile-time geometry,
-// MFMA operand pipeline, wave-local staging, the conditioner (phases 1-3).  Included by cf_step.hip and
-// cf_step_bwd.hip; everything lives in an anonymous namespace of the including translation unit.
+// MFMA operand pipeline, wave-local staging, the conditioner (phases 1-3).  Included by cf_step.hip,
+// cf_step_inv.h, cf_step_dispatch.h and cf_step_bwd.h; everything lives in an anonymous namespace of
+// the including translation unit.
 #pragma once
 #include <type_traits>
 #include "cf_common.h"

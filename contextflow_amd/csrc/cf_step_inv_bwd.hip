@@ -1,10 +1,9 @@
-// The vector-Jacobian product of the inverse flow step: the INV form of k_flow_step_bwd (cf_step_bwd.hip), instantiated in a
+// The vector-Jacobian product of the inverse flow step: the INV form of k_flow_step_bwd (cf_step_bwd.h), instantiated in a
 // translation unit of its own.  Built next to the training and score forms it moves the register allocation of one of THEM
 // (k_flow_step_bwd<B64, taped>: 190 -> 189 VGPRs; profiles/decode_grad.md) although no line of their bodies changes - here they
 // compile to what they were.  The argument record, the check and the dispatch (StepBwdArgs, check_step_bwd, launch_bwd) are the
-// family's, from that text: this unit holds the entry point alone.
-#define CF_STEP_BWD_KERNELS_ONLY 1
-#include "cf_step_bwd.hip"
+// family's, from that header: this unit holds the entry point alone.
+#include "cf_step_bwd.h"
 
 extern "C" {
 

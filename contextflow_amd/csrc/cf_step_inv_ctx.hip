@@ -1,9 +1,9 @@
-// The specialist coupling backwards in one launch: the CTX form of k_flow_step_inv (cf_step.hip), instantiated in a translation
+// The specialist coupling backwards in one launch: the CTX form of k_flow_step_inv (cf_step_inv.h), instantiated in a translation
 // unit of its own so that every kernel of cf_step.hip compiles to what it was (cf_step_inv_bwd.hip has the precedent).  The
-// kernel is select()'s choice for Pass::InverseCtx and the launch is launch_step_inv with a StepInvArgs, both from that text:
+// kernel is select()'s choice for Pass::InverseCtx (cf_step_dispatch.h) and the launch is launch_step_inv with a StepInvArgs:
 // this unit holds the launch list of its four instantiations and the entry point.
-#define CF_STEP_KERNELS_ONLY 1
-#include "cf_step.hip"
+#include "cf_step_inv.h"
+#include "cf_step_dispatch.h"
 
 template <int CTX>
 static int launch_inv_ctx(Kernel k, const StepInvArgs& a) {

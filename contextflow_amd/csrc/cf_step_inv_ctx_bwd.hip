@@ -1,9 +1,8 @@
 // The vector-Jacobian product of the specialist coupling's inverse (cf_flow_step_inv_ctx): the INV form of k_flow_step_bwd
-// (cf_step_bwd.hip) with the per-sample bias in its recompute (IB), in a translation unit of its own for the reason
+// (cf_step_bwd.h) with the per-sample bias in its recompute (IB), in a translation unit of its own for the reason
 // cf_step_inv_bwd.hip gives - the kernels of the other units compile to what they were.  Record, check and dispatch are the
 // family's (StepBwdArgs, check_step_bwd, launch_bwd): this unit holds the entry point alone.
-#define CF_STEP_BWD_KERNELS_ONLY 1
-#include "cf_step_bwd.hip"
+#include "cf_step_bwd.h"
 
 namespace {
 // the eight instantiations of this unit, in the order their kernels have in its code object (the two modes of a geometry side by side)

@@ -1,5 +1,5 @@
 // Shared by the sources of the transformer coupling (cf_vit_fused.hip) and of the one-kernel transformer flow steps
-// (cf_vit_step.hip: the cf_vit_step_* entry points and the wave form, cf_vit_rs.hip: the row-split form, cf_vit_rs_bwd.hip: the
+// (cf_vit_step.hip: the cf_vit_step_* entry points and the wave form, cf_vit_rs.hip: the row-split form, cf_vit_rs_bwd.h: the
 // backward): the flat parameter layout, the limits and sizes every form agrees on, the device helpers they have in common, the
 // fused attention matrices, and the per-form host functions behind the entry points.
 #pragma once

@@ -1,5 +1,5 @@
 // Shared device code of the row-split transformer-coupling step kernels (cf_vit_rs.hip: forward for small batches,
-// cf_vit_rs_bwd.hip: the training backward): geometry, workspace layout, packing helpers, 16x16x4 product helpers, token
+// cf_vit_rs_bwd.h: the backward's kernels): geometry, workspace layout, packing helpers, 16x16x4 product helpers, token
 // statistics.  What they share with the wave form is in cf_vit_common.h.  Everything lives in an anonymous namespace of the
 // including translation unit.
 #pragma once

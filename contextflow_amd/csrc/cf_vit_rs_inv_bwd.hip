@@ -1,9 +1,8 @@
 // The vector-Jacobian product of the inverse transformer flow step: the DATA + INV form of k_vit_step_bwd_rs
-// (cf_vit_rs_bwd.hip), instantiated in a translation unit of its own so that the training forms keep compiling to what they
+// (cf_vit_rs_bwd.h), instantiated in a translation unit of its own so that the training forms keep compiling to what they
 // were (profiles/vit_decode_grad.md), as cf_step_inv_bwd.hip does for the conv steps.  This unit holds the pack kernel of the
 // front product's fragments and the entry points.
-#define CF_VIT_RS_BWD_KERNELS_ONLY 1
-#include "cf_vit_rs_bwd.hip"
+#include "cf_vit_rs_bwd.h"
 
 namespace {
 

@@ -104,6 +104,22 @@ def test_vit_step_family_sizes_and_symbols(built):
     assert sum(s.startswith("cf_vit_step") for s in syms) == 14
 
 
+def test_csrc_units_include_headers_only():
+    """A kernel family that more than one translation unit instantiates is a header: no file under csrc/ includes a .hip or is
+    cut down by a ..._KERNELS_ONLY macro, and every header's first line of code is `#pragma once` (a fragment that is meant to
+    be included more than once is no .h)."""
+    csrc = os.path.join(ROOT, "contextflow_amd", "csrc")
+    names = sorted(os.listdir(csrc))
+    assert sum(n.endswith(".hip") for n in names) >= 23 and sum(n.endswith(".h") for n in names) >= 8
+    for n in names:
+        text = open(os.path.join(csrc, n)).read()
+        assert not re.search(r'#\s*include\s*["<][^">]*\.hip[">]', text), n
+        assert "KERNELS_ONLY" not in text, n
+        if n.endswith(".h"):
+            code = [l.strip() for l in text.split("\n") if l.strip() and not l.strip().startswith("//")]
+            assert code[0] == "#pragma once", n
+
+
 # ---- the step dispatch as the flop accounting sees it -----------------------------------------------------------------
 # (first B, multiply-adds in units of C^2 HW) of cf_flow_step_macs for B in 0..8192, per shape and pass 0..3, and the largest
 # chained batch.  Recorded from the library as it was BEFORE the dispatch became one function (commit 76e3db3), per switch

@@ -1,10 +1,14 @@
 #!/usr/bin/env python3
 """Developer tool: builds contextflow_amd/build/abl/libcf_ticks.so = the product library with s_memtime probes at the
-phase boundaries of k_flow_step_bwd (patched copy of the source, the product source is untouched).  Workgroup 0 writes
+phase boundaries of k_flow_step_bwd (patched copy of the kernels' header cf_step_bwd.h and a copy of cf_step_bwd.hip that
+includes it; the product source is untouched, and the INV units keep the product header).  Workgroup 0 writes
 its per-phase cycle sums over gx[0..] (results of that launch are garbage).  Read with tools/dev/bwd_ticks.py on the GPU."""
 import glob, os, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-src = open(os.path.join(root, "contextflow_amd/csrc/cf_step_bwd.hip")).read()
+src = open(os.path.join(root, "contextflow_amd/csrc/cf_step_bwd.h")).read()
+unit = open(os.path.join(root, "contextflow_amd/csrc/cf_step_bwd.hip")).read()
+inc = '#include "cf_step_bwd.h"\n'
+assert unit.count(inc) == 1
 marks = [
     ("    // ---------------------------------------------------------------- what the data-gradient chain needs of the forward\n", None),
     ("    // ---------------------------------------------------------------- backward\n", "tape"),
@@ -25,14 +29,15 @@ for k, (m, name) in enumerate(marks):
     else:
         out = out.replace(m, "    TICK(%d);\n" % len(names) + m)
         names.append(name)
-tail = "        rows_store_t<G, C, C>(gx, GX, b0, B, wave, lane);\n    }\n}"
-assert tail in out
+tail = "        else rows_store_t<G, C, C>(gx, GX, b0, B, wave, lane);\n    }\n}"
+assert out.count(tail) == 1
 names.append("a0t")
-out = out.replace(tail, "        rows_store_t<G, C, C>(gx, GX, b0, B, wave, lane);\n    }\n    TICK(%d);\n    __syncthreads();\n"
+out = out.replace(tail, "        else rows_store_t<G, C, C>(gx, GX, b0, B, wave, lane);\n    }\n    TICK(%d);\n    __syncthreads();\n"
                   "    if (blockIdx.x == 0 && lane == 0) for (int k = 0; k < 12; ++k) gx[wave * 12 + k] = (float)tacc[k];\n}" % (len(names) - 1))
 tmp = os.path.join(root, "contextflow_amd/build/abl")
 os.makedirs(tmp, exist_ok=True)
-open(os.path.join(tmp, "cf_step_bwd_ticks.hip"), "w").write(out)
+open(os.path.join(tmp, "cf_step_bwd_ticks.h"), "w").write(out)
+open(os.path.join(tmp, "cf_step_bwd_ticks.hip"), "w").write(unit.replace(inc, '#include "cf_step_bwd_ticks.h"\n'))
 open(os.path.join(tmp, "ticks_names.txt"), "w").write(" ".join(names))
 srcs = [s for s in glob.glob(os.path.join(root, "contextflow_amd/csrc/*.hip")) if not s.endswith("cf_step_bwd.hip")]
 cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-comment", "-I" + os.path.join(root, "include"),
