@@ -244,7 +244,11 @@ __device__ __forceinline__ void flow_step_phases(float* __restrict__ z, float* _
     float* Y0 = lds;                    // [HALF][PIX]   y0 (phase 0 -> 1), later the z1 staging plane
     float* H1 = lds + HALF * PIX;       // [HID][PIX]    x plane (rows < C), then h1, then h2 in place
 
-    const int tid_ = LEVEL ? wave_u * 64 + cf_lane_fresh() : (int)threadIdx.x;      // (LEVEL: per step, see cf_lane_fresh)
+    // FRESH: the lane's indices are formed again behind the 3x3, from the wave's index in a scalar register, instead of living
+    // across it.  The zero-skipping geometry needs that as the level form does: carried, they cost it 15 spilled registers
+    constexpr bool FRESH = LEVEL || G::ZSKIP;
+    static_assert(!G::ZSKIP || (CTX == 0 && !DUMP && !DBG), "zero skip: the evaluation step");
+    const int tid_ = FRESH ? wave_u * 64 + cf_lane_fresh() : (int)threadIdx.x;      // (LEVEL: per step, see cf_lane_fresh)
     const int tid = tid_, wave = tid >> 6;
     int lane = tid & 63, li = lane & 31, lk = lane >> 5;
     const int ntiles = (B + G::SPW - 1) / G::SPW;
@@ -296,16 +300,17 @@ __device__ __forceinline__ void flow_step_phases(float* __restrict__ z, float* _
         if constexpr (DUMP) rows_store_t<G, HALF, HALF>(tp.y0, Y0, b0, B, wave, lane);
         if (dbg) {
             __syncthreads();
-            for (int e = tid; e < HALF * PIX; e += 256) dbg[(int64_t)(e / PIX) * dbg_cols + (int64_t)tile * PIX + (e % PIX)] = Y0[e];
+            for (int e = tid; e < HALF * PIX; e += G::NT) dbg[(int64_t)(e / PIX) * dbg_cols + (int64_t)tile * PIX + (e % PIX)] = Y0[e];
             __syncthreads();
         }
 
         f32x16 acc3[RT03][PTW];
-        if constexpr (LEVEL) {
+        if constexpr (FRESH) {
             // phases 1 and 2, then the lane's indices AGAIN and phase 3 with those: nothing but y1 is live across the 3x3, which fills
             // the register file (the 8x8 kernel sits at 256 registers; carried, the indices cost the level form 4 spilled ones)
             conditioner_net<G, 0, false, 2>(acc3, lds, wsl, pix, pin, lane, tid, nullptr, 0, tile, nullptr, nullptr, tp, B);
             lane = cf_lane_fresh(); li = lane & 31; lk = lane >> 5;
+            if constexpr (G::ZSKIP) lk &= 1;      // (says lk < 2: the `idx < HALF` tests of the epilogue below then fold away)
 #pragma unroll
             for (int q = 0; q < PTW; ++q) {
                 pix[q] = (wave_u * PTW + q) * 32 + li;
@@ -411,7 +416,7 @@ __device__ __forceinline__ void flow_step_phases(float* __restrict__ z, float* _
 }
 
 template <class G, bool SQ, int CTX = 0, bool DUMP = false, bool DBG = false>
-__global__ __launch_bounds__(256, G::MINW) void k_flow_step(const float* __restrict__ x, float* __restrict__ z,
+__global__ __launch_bounds__(G::NT, G::MINW) void k_flow_step(const float* __restrict__ x, float* __restrict__ z,
                                                    float* __restrict__ ldj_acc, const float* __restrict__ ws, int B,
                                                    int64_t xbs, float* __restrict__ dbg_arg, int flags,
                                                    const float* __restrict__ sb, StepTape tp) {
@@ -428,7 +433,8 @@ __global__ __launch_bounds__(256, G::MINW) void k_flow_step(const float* __restr
     const int tile = blockIdx.x;
     x_load<G, SQ>(xr, x, xbs, tile, B, wave, lane);
     x_to_lds<G, SQ>(xr, H1, wave, lane);
-    flow_step_phases<G, CTX, DUMP, DBG, false>(z, ldj_acc, ws, B, dbg_arg, sb, tp, tile);
+    if constexpr (G::ZSKIP) flow_step_phases<G, CTX, DUMP, DBG, false>(z, ldj_acc, ws, B, dbg_arg, sb, tp, tile, __builtin_amdgcn_readfirstlane(wave));
+    else flow_step_phases<G, CTX, DUMP, DBG, false>(z, ldj_acc, ws, B, dbg_arg, sb, tp, tile);
 }
 // Level form (cf_flow_step_fwd_level): the n <= kChain steps of one resolution level on this workgroup's samples in ONE launch, z in
 // LDS from step to step.  x is fetched once (squeeze-folded where the level begins behind a Squeeze), the loop has one body for
@@ -1332,7 +1338,7 @@ int launch_step_sq(const StepArgs& a) {
     }
     const int grid = (a.B + G::SPW - 1) / G::SPW;
     // (the kernel's `flags` argument is unused: 0)
-    k_flow_step<G, SQ, CTX, DUMP, DBG><<<dim3(grid), dim3(256), lds_bytes, a.s>>>(a.x, a.z, a.ldj, a.ws, a.B, a.xbs, a.dbg, 0, a.sb, a.tp);
+    k_flow_step<G, SQ, CTX, DUMP, DBG><<<dim3(grid), dim3(G::NT), lds_bytes, a.s>>>(a.x, a.z, a.ldj, a.ws, a.B, a.xbs, a.dbg, 0, a.sb, a.tp);
     return 0;
 }
 // the specialist coupling (CTX != 0) never sits behind a squeeze: only its SQ = false form is built
@@ -1381,6 +1387,7 @@ static int step_macs_c2hw(Kernel k) {
         case Kernel::Step_G64v2: return step_macs_c2hw<G64v2>();
         case Kernel::Step_G64w2: case Kernel::Inv_G64w2: return step_macs_c2hw<G64w2>();
         case Kernel::Step_G64w24: return step_macs_c2hw<G64w24>();
+        case Kernel::Step_G64z24: return step_macs_c2hw<G64z24>();      // (the count of the form: the skipped zero products are in it)
     }
     return 0;
 }
@@ -1403,6 +1410,7 @@ static int launch_fwd(Kernel k, const StepArgs& a) {         // evaluation forwa
         case Kernel::Step_G64v2: return launch_step<G64v2>(a);
         case Kernel::Step_G64w2: return launch_step<G64w2>(a);
         case Kernel::Step_G64w24: return launch_step<G64w24>(a);
+        case Kernel::Step_G64z24: return launch_step<G64z24>(a);
         case Kernel::Rs_G32: return launch_step_rs<G32, 2>(a);
         case Kernel::Rs16_G64: return launch_step_rs16<G64>(a);
         default: return not_built(__func__, k);
@@ -1506,8 +1514,9 @@ template int launch_inv<true>(Kernel, const StepInvArgs&);
 
 // test hook: (shape, variant = flags bits 16..19) -> kernel.  0: the default geometry of the shape in k_flow_step (the only one
 // with per-phase dumps besides 3), 2: half the samples per workgroup, 3: k_flow_step_small in the direct form, 4: Winograd
-// F(2x2, 3x3), 5: ... row-split at 128 pixels per workgroup, 6: Winograd F(2x4, 3x3) at 8x8 and 4x4.  (1 was an operand-pipeline
-// alternate of each shape, 6 at 16x16 and 7 two forms on the 16-bit matrix cores: gone with their geometries.)
+// F(2x2, 3x3), 5: ... row-split at 128 pixels per workgroup, 6: Winograd F(2x4, 3x3) at 8x8 and 4x4, 7 (4x4): ... with 16 samples
+// on 8 waves, skipping the zero products.  (1 was an operand-pipeline alternate of each shape, 6 at 16x16 and 7 at 16x16 two forms
+// on the 16-bit matrix cores: gone with their geometries.)
 template <class G>
 static int lane_table_copy(int* out, int cap) {      // host copy of kLaneTab<G> (cf_lane_table_debug): same constexpr initialiser
     static const LaneTab<G> tab = make_lane_tab<G>();
@@ -1522,7 +1531,7 @@ constexpr Kernel kDebugKernel[4][kDebugVariants] = {
     {Kernel::Step_G8, Kernel::None, Kernel::None, Kernel::Small_G8s, Kernel::Small_G8w, Kernel::None, Kernel::None, Kernel::None},
     {Kernel::Step_G16, Kernel::None, Kernel::None, Kernel::Small_G16s, Kernel::Small_G16w, Kernel::None, Kernel::None, Kernel::None},
     {Kernel::Step_G32, Kernel::None, Kernel::Step_G32v2, Kernel::None, Kernel::Step_G32w, Kernel::None, Kernel::Step_G32w24, Kernel::None},
-    {Kernel::Step_G64, Kernel::None, Kernel::Step_G64v2, Kernel::None, Kernel::None, Kernel::Step_G64w2, Kernel::Step_G64w24, Kernel::None},
+    {Kernel::Step_G64, Kernel::None, Kernel::Step_G64v2, Kernel::None, Kernel::None, Kernel::Step_G64w2, Kernel::Step_G64w24, Kernel::Step_G64z24},
 };
 
 extern "C" {
@@ -1684,6 +1693,13 @@ int cf_flow_step_fwd_debug(const float* x, float* z, float* ldj_acc, const void*
     CF_LAUNCH_CHECK();
     return 0;
 }
+// test hook (not part of the public header; host only): the smallest batch at which cf_flow_step_fwd runs this shape's step in the
+// zero-skipping F(2x4) kernel (G64z24) - 0 where it never does (other shapes, switched off, CONTEXTFLOW_DIRECT_CONV=1); and the
+// A/B switch of that dispatch (on by default; returns what it was).  The debug variants are not affected.
+int cf_flow_step_zero_skip_min_batch(int C, int H, int W) {
+    return select(Pass::Eval, shape_id(C, H, W), kZeroSkipMinB4x4) == Kernel::Step_G64z24 ? kZeroSkipMinB4x4 : 0;
+}
+int cf_flow_step_zero_skip_enable(int on) { return g_zero_skip.exchange(on != 0) ? 1 : 0; }
 // test hook (not part of the public header; host only): the per-lane address table the saturating-batch kernels of a shape read
 // (kLaneTab, cf_step_common.h) as 256 x n ints, thread-major.  Returns n, the ints per thread - 0 for a shape whose kernels derive
 // their addresses - and copies min(cap, 256 n) ints to `out`.
@@ -1733,7 +1749,7 @@ int cf_flow_step_fwd_level(const float* x, float* z, float* ldj_acc, const void*
         cf_set_error("cf_flow_step_fwd_level: shape (%d,%d,%d) at a batch of %d is not a level case", C, H, W, B);
         return CF_ERR_UNSUPPORTED;
     }
-    const Kernel k = select(Pass::Eval, sid, form == 1 && B < minb ? minb : B);
+    const Kernel k = select(Pass::Level, sid, form == 1 && B < minb ? minb : B);
     WsChain wc{};
     for (int i = 0; i < n; ++i) { CF_REQUIRE(ws[i]); wc.ws[i] = (const float*)ws[i]; }
     if (int rc = launch_fwd_level(k, StepArgs{x, z, ldj_acc, nullptr, B, x_bstride, in_squeeze != 0, cf_s(stream)}, wc, n)) return rc;

@@ -12,7 +12,7 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int kWaves = 4;
+constexpr int kWaves = 4;              // waves per workgroup of every geometry that does not say otherwise (Geo::WAVES)
 
 // ---- compile-time geometry of one supported shape ------------------------------------------------
 // PIPE_: form of phase 2, the 3x3 (0 = compiler-scheduled per-tap loop, 1 = explicit two-stage operand pipeline, 2 = all nine
@@ -23,12 +23,17 @@ constexpr int kWaves = 4;
 template <int C_, int H_, int W_, int SPW_, int PIPE_ = 1, int ABL_ = 0, int PATCH_ = 0>
 struct Geo {
     static constexpr int C = C_, H = H_, W = W_, SPW = SPW_, PIPE = PIPE_, ABL = ABL_, PATCH = PATCH_;
+    // PIPE == 6 at 4x4 with 16 samples: every column tile of 16 output tiles has ONE tile row, and a wave leaves out the vertical
+    // index whose two patch rows reflection makes the same row (winograd24_phase2, "zero skip"); on 8 waves
+    static constexpr bool ZSKIP = PIPE_ == 6 && H_ == 4 && SPW_ == 16;
+    // waves per workgroup (NT threads): a property of the geometry (not a template parameter: the kernels' names stay what they were)
+    static constexpr int WAVES = ZSKIP ? 8 : kWaves, NT = 64 * WAVES;
     static constexpr int HW = H * W;
     static constexpr int PIX = SPW * HW;              // pixels per workgroup
     static constexpr int HALF = C / 2;                // conditioner channels
     static constexpr int HID = 2 * C;                 // hidden width of the coupling net
     static constexpr int NPT = PIX / 32;              // 32-pixel tiles per workgroup
-    static constexpr int PTW = NPT / kWaves;          // pixel tiles per wave
+    static constexpr int PTW = NPT / WAVES;           // pixel tiles per wave
     static constexpr int HP = HALF <= 16 ? 16 : 32;   // packed rows per channel half
     static constexpr int R03 = 2 * HP;                // packed rows of the C-channel results (y, h)
     static constexpr int RT03 = R03 / 32;
@@ -92,9 +97,10 @@ struct Geo {
     static constexpr int LDS_FLOATS = (HALF + HID) * RS + LDS_W;
     // waves per SIMD the register allocator must leave room for = workgroups per CU the LDS footprint admits
     static constexpr int MINW = (160 * 1024) / (LDS_FLOATS * 4) >= 4 ? 4 : ((160 * 1024) / (LDS_FLOATS * 4) >= 2 ? 2 : 1);
-    static_assert(PIX % 128 == 0 && PTW >= 1, "workgroup must own a multiple of 128 pixels");
-    static_assert(!W24 || (H == 4 && W == 4 && SPW == 8) || (H == 8 && W == 8 && SPW == 4),
+    static_assert(PIX % 128 == 0 && PTW >= 1 && NPT % WAVES == 0, "workgroup must own a multiple of 128 pixels");
+    static_assert(!W24 || (H == 4 && W == 4 && SPW == 8) || (H == 8 && W == 8 && SPW == 4) || ZSKIP,
                   "F(2x4, 3x3): 4x4 images, 8 samples = one column tile of 16 output tiles; 8x8 images, 4 samples = two column tiles");
+    static_assert(!ZSKIP || (W == 4 && WAVES == 8 && C == 64), "zero skip: 16 samples of the 4x4 level on 8 waves, the whole LDS");
     static_assert(HID % 8 == 0 && C % 4 == 0, "channel counts must fill whole k-steps");
     static_assert((HW & (HW - 1)) == 0 && (W & (W - 1)) == 0, "power-of-two images");
 };
@@ -846,6 +852,18 @@ __device__ __forceinline__ void winograd_phase2(float* __restrict__ lds, const f
 // - the low five bits (the bank) are distinct for the 32 lanes of a group for every patch element (lanes whose reflected row
 // coincides read the same word), and the low six for all 64 lanes.  The word is a row part + a column part (w24_row / w24_col), so an operand address is one
 // addition.  (tests/test_winograd24_8x8.py checks the order exhaustively.)
+// 4x4, 16 samples per workgroup (Geo::ZSKIP): every output tile of a column tile has the same tile row, so a 32-lane group of a
+// patch read is (16 samples) x (2 channel parities) at ONE pixel (y, x).  With R = 2 y + (x >> 1), the word of pixel (s, y, x)
+// inside a row of parity k is
+//     32 R + 16 ((x ^ k) & 1) + (s ^ 2 R)
+// - a read group varies s and k at fixed (y, x): its banks 16 ((x ^ k) & 1) + (s ^ 2 R) are all 32;
+// - a 32-lane group of phase 1's stores is two samples (s >> 1 fixed) x their 16 pixels at one k: bank bits 3..1 are
+//   (s >> 1) ^ R, bit 0 is s & 1 and bit 4 is (x ^ k) & 1 - again all 32 (the order 16 (4 y + ((x + k) & 3)) + s puts those
+//   stores on four banks).  (tests/test_w24_zero_skip.py checks both, and that the order is a bijection, exhaustively.)
+__host__ __device__ constexpr int w24z_pix(int s, int y, int x, int kq) {
+    const int R = 2 * y + (x >> 1);
+    return 32 * R + 16 * ((x ^ kq) & 1) + ((s ^ (2 * R)) & 15);
+}
 template <class G> __host__ __device__ constexpr int w24_row(int s, int y, int kq) {
     return 128 * (s >> 1) + 32 * ((y ^ (kq >> 1)) & 1) + 8 * (y >> 1) + 4 * (s & 1);
 }
@@ -853,7 +871,8 @@ template <class G> __host__ __device__ constexpr int w24_col(int x, int kq) {
     return 64 * ((x >> 1) & 1) + 2 * (((x >> 2) ^ (x >> 1)) & 1) + ((x ^ kq) & 1);
 }
 template <class G> __host__ __device__ constexpr int w24_pix(int s, int y, int x, int kq) {      // kq = row & 3
-    if constexpr (G::H == 4) return 8 * (4 * y + ((x + y + kq) & 3)) + s;
+    if constexpr (G::ZSKIP) return w24z_pix(s, y, x, kq);
+    else if constexpr (G::H == 4) return 8 * (4 * y + ((x + y + kq) & 3)) + s;
     else return w24_row<G>(s, y, kq) + w24_col<G>(x, kq);
 }
 
@@ -912,6 +931,13 @@ template <class G> __host__ __device__ constexpr W22Lane<G> w22_lane(int wave, i
     e.dst = 4 * lg * PIX + smp * HW + 2 * ty * W + 2 * tx;
     return e;
 }
+// F(2, 3) down the rows: B2^T row xi = d[r1] + sigma d[r2] over the four patch rows, sigma = -1 but at xi = 1.  w24_xi_is_zero:
+// in an image of H rows, a tile of tile row ty gets +0 at xi from every patch: r1 and r2 are ONE image row under reflect padding
+constexpr int w24_r1(int xi) { return xi == 0 ? 0 : (xi == 2 ? 2 : 1); }
+constexpr int w24_r2(int xi) { return xi == 2 ? 1 : (xi == 3 ? 3 : 2); }
+constexpr bool w24_xi_is_zero(int xi, int ty, int H) {
+    return xi != 1 && cf_reflect(2 * ty - 1 + w24_r1(xi), H) == cf_reflect(2 * ty - 1 + w24_r2(xi), H);
+}
 template <class G> using LaneEntry = std::conditional_t<G::W24, W24Lane<G>, W22Lane<G>>;
 template <class G> struct LaneTab { LaneEntry<G> e[kWaves * 64]; };
 template <class G> constexpr LaneTab<G> make_lane_tab() {
@@ -939,8 +965,14 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
                                                   int wave, const int4 (&tw)[3]) {
     constexpr int W = G::W, H = G::H, HW = G::HW, PIX = G::PIX, HALF = G::HALF, RT16 = G::RT16, KG4 = G::KG4;
     constexpr int NCT = PIX / 128;                       // column tiles (16 output tiles of 2x4 pixels) of the workgroup
-    constexpr int RSP = kWaves / NCT;                    // waves that share a column tile and split the output rows
+    constexpr int RSP = G::WAVES / NCT;                  // waves that share a column tile and split the output rows
     static_assert(G::W24 && (NCT == 1 || NCT == 2) && RT16 % RSP == 0 && W % 4 == 0, "F(2x4, 3x3) geometry");
+    // Zero skip (4x4, 16 samples, 8 waves): column tile ct holds the tiles of tile row ty = ct of all 16 samples, and the wave leaves
+    // out the vertical index whose transform is d[r] - d[r] = +0 in every lane: xi = 0 at ty = 0, xi = 3 at ty = 1.  Its M would be
+    // +0 (+0 gains +-0 per product of finite weights), its Z +0, and Y[0] = +0 + 1 (+0) resp. Y[1] += (-1)(+0) = -0 change no bit.
+    constexpr bool ZS = G::ZSKIP;
+    static_assert(!ZS || (NCT == 2 && HW / 8 == 2 && w24_xi_is_zero(0, 0, H) && w24_xi_is_zero(3, 1, H)),
+                  "zero skip: the two patch rows of the skipped (xi, ty) must be ONE image row under the padding, and be subtracted");
     constexpr int RTW = RT16 / RSP;                      // 16-row tiles of this wave
     constexpr int NS = 6 * KG4;                         // (group, nu) steps per xi
     // nu order inside a group: 0 and 5 first, so that A0 / A5 die early and A1 .. A4 live on as P, Q, R, D
@@ -955,7 +987,8 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
     // 4x4 (derived: the table form measured slower there, profiles/lane_tables.md): this lane's output tile and its reflect-padded
     // patch rows; the patch columns are constants (one tile per image row).  The expressions are kept literally: hipcc's code for
     // that instantiation is then instruction for instruction what it was.
-    const int smp = l15 >> 1, ty = l15 & 1;
+    const int ct = ZS ? __builtin_amdgcn_readfirstlane(wave % NCT) : 0;      // zero skip: this wave's column tile = its tile row
+    const int smp = ZS ? l15 : l15 >> 1, ty = ZS ? ct : l15 & 1;
     int yrow[4];
     // 8x8: byte offsets of the patch rows and columns (the order is row part + column part) and the h2 offset, from the table
     int rpart[4], cpart[6], dsto = 0;
@@ -973,7 +1006,7 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
     }
     f32x4w Y[2][4][RTW];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < (ZS ? 1 : 2); ++i)          // (zero skip: Y[1] behind the xi = 0 that half the waves run - not live across it)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -984,6 +1017,8 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             if constexpr (H == 4) {
+                static_assert(w24_r1(0) == 0 && w24_r1(1) == 1 && w24_r1(2) == 2 && w24_r1(3) == 1 && w24_r2(0) == 2 && w24_r2(1) == 2 &&
+                              w24_r2(2) == 1 && w24_r2(3) == 3, "the rows below are w24_r1 / w24_r2, which the zero-skip check reads");
                 const int yy = h == 0 ? (xi == 0 ? yrow[0] : (xi == 2 ? yrow[2] : yrow[1]))
                                       : (xi == 2 ? yrow[1] : (xi == 3 ? yrow[3] : yrow[2]));
 #pragma unroll
@@ -1022,14 +1057,21 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
         for (int rt = 0; rt < RTW; ++rt) f.a[rt] = ws_frag(rs, lane, fr + rt * KG4 * 256);
     };
     int o[2][6];
-    addrs(0, o);
+    // zero skip: a row of the 256-pixel planes is 1 KB, and the k rows of the upper half of the k-groups lie beyond what the offset
+    // field of a ds_read2st64_b32 spans from the lane's address (255 x 256 B) - left to immediates, hipcc forms every such address
+    // with a v_add_u32 of its own (470 per step).  The addresses move up ONCE per xi instead, by a value the compiler cannot fold
+    int hoff = (KG4 / 2) * 16 * PIX * 4;
+    if constexpr (ZS) asm volatile("" : "+s"(hoff));
+    const int xi_first = ZS && ct == 0 ? 1 : 0;           // zero skip: the look-ahead chain starts at the wave's first xi
+    addrs(xi_first, o);
     Raw raw;
     WFrag wf[2];                                          // weight fragments requested one step ahead
     load_raw(o, 0, raw);
-    load_w(0, 0, wf[0]);
+    load_w(xi_first, 0, wf[0]);
     // A2^T[0][xi] = (1, 1, 1, 0), A2^T[1][xi] = (0, 1, -1, -1): xi = 0 and xi = 3 are peeled so that their zero half of the
     // output transform is not executed and, at xi = 0, Y[1] is not yet live (the loop keeps xi = 1, 2)
-    auto xi_body = [&](const int xi, auto has0, auto has1) {
+    // stop (zero skip only; wave-uniform): this xi is the wave's last, and nothing is requested for a next one
+    auto xi_body = [&](const int xi, auto has0, auto has1, const bool stop) {
         const int xn = xi < 3 ? xi + 1 : 3;               // (after the last xi the prefetches re-read xi = 3: harmless)
         const float sigma = xi == 1 ? 1.f : -1.f;
         const float c0 = xi < 3 ? 1.f : 0.f, c1 = xi == 0 ? 0.f : (xi == 1 ? 1.f : -1.f);      // A2^T[0][xi], A2^T[1][xi]
@@ -1050,7 +1092,15 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
             // the six steps, into the same registers (raw is dead once A is formed)
             if (kk + 1 == KG4) addrs(xn, o);              // first group of the next xi: its operand addresses replace this xi's
             const int kn = kk + 1 < KG4 ? kk + 1 : 0;
-            if constexpr (!SPREAD) load_raw(o, kn, raw);
+            if constexpr (ZS) {
+                if (kk + 1 == KG4 / 2) {                  // second half of the k-groups: the addresses move up by `hoff` (above)
+#pragma unroll
+                    for (int h = 0; h < 2; ++h)
+#pragma unroll
+                        for (int c = 0; c < 6; ++c) o[h][c] += hoff;
+                }
+                if (kk + 1 < KG4 || !stop) load_raw(o, kn % (KG4 / 2), raw);
+            } else if constexpr (!SPREAD) load_raw(o, kn, raw);
             // horizontal transform B4^T row nu:  nu 0: A0/4 - 5/4 A2 + A4;  1, 2: P +- Q (P = A4 - A2/4, Q = A3 - A1/4);
             // 3, 4: R +- (A3 - A1)/2 (R = A4 - A2);  5: A1/4 - 5/4 A3 + A5
             // (One lambda, called per step: written out inside the step loop, with the operand addresses of the next xi formed in
@@ -1072,7 +1122,7 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
             for (int t = 0; t < 6; ++t) {
                 const int s = kk * 6 + t, nu = NU[t];
                 if (s + 1 < NS) load_w(xi, s + 1, wf[(s + 1) & 1]);
-                else load_w(xn, 0, wf[0]);
+                else if (!ZS || !stop) load_w(xn, 0, wf[0]);
                 if constexpr (SPREAD) load_raw_cols(o, kn, raw, t, t + 1);
                 __builtin_amdgcn_sched_barrier(0);
                 f32x2w v[2];
@@ -1099,10 +1149,16 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
             }
         }
     };
-    xi_body(0, std::true_type{}, std::false_type{});
+    if (!ZS || ct == 1) xi_body(0, std::true_type{}, std::false_type{}, false);
+    if constexpr (ZS) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int rt = 0; rt < RTW; ++rt) Y[1][j][rt] = f32x4w{0.f, 0.f, 0.f, 0.f};
+    }
 #pragma unroll 1
-    for (int xi = 1; xi < 3; ++xi) xi_body(xi, std::true_type{}, std::true_type{});
-    xi_body(3, std::false_type{}, std::true_type{});
+    for (int xi = 1; xi < 3; ++xi) xi_body(xi, std::true_type{}, std::true_type{}, ZS && ct == 1 && xi == 2);
+    if (!ZS || ct == 0) xi_body(3, std::false_type{}, std::true_type{}, true);
     __syncthreads();                 // every wave has finished reading h1
 #pragma unroll
     for (int rt = 0; rt < RTW; ++rt) {
@@ -1227,7 +1283,7 @@ __device__ __forceinline__ void conditioner_net(f32x16 (&acc3)[G::RT03][G::PTW],
     __syncthreads();                 // h1 complete: the 3x3 taps read neighbouring waves' columns
     if (dbg) {
         float* d = dbg + (int64_t)C * dbg_cols;
-        for (int e = tid; e < HID * PIX; e += 256) d[(int64_t)(e / PIX) * dbg_cols + (int64_t)tile * PIX + (e % PIX)] = H1[e];
+        for (int e = tid; e < HID * PIX; e += G::NT) d[(int64_t)(e / PIX) * dbg_cols + (int64_t)tile * PIX + (e % PIX)] = H1[e];
     }
 
     // ================= phase 2: h2 = relu(NN.2 (*) h1 + b), 3x3, reflect padding   (coupling.py:27)
@@ -1409,7 +1465,7 @@ __device__ __forceinline__ void conditioner_net(f32x16 (&acc3)[G::RT03][G::PTW],
     if (dbg) {
         __syncthreads();
         float* d = dbg + (int64_t)(C + HID) * dbg_cols;
-        for (int e = tid; e < HID * PIX; e += 256) d[(int64_t)(e / PIX) * dbg_cols + (int64_t)tile * PIX + (e % PIX)] = H1[e];
+        for (int e = tid; e < HID * PIX; e += G::NT) d[(int64_t)(e / PIX) * dbg_cols + (int64_t)tile * PIX + (e % PIX)] = H1[e];
     }
 
     if constexpr (UPTO < 3) return;
@@ -1456,6 +1512,9 @@ using G32w = Geo<32, 8, 8, 4, 3>;
 using G64w2 = Geo<64, 4, 4, 8, 3>;       // 8 samples per workgroup, 2 workgroups / CU: two waves per column tile split the rows
 using G64w24 = Geo<64, 4, 4, 8, 6>;      // ... in the Winograd F(2x4, 3x3) form (winograd24_phase2): the four waves split the rows
 using G32w24 = Geo<32, 8, 8, 4, 6>;      // the 8x8 level in that form: two column tiles x two row halves
+// the 4x4 level's F(2x4) form with 16 samples on 8 waves (512 threads, 160 KB: one workgroup / CU, two waves / SIMD as G64w24's two
+// workgroups): a column tile holds ONE tile row, and its waves skip the vertical index that reflection zeroes (Geo::ZSKIP)
+using G64z24 = Geo<64, 4, 4, 16, 6>;
 
 
 int shape_id(int C, int H, int W) {

@@ -2,7 +2,7 @@
 """Micro-benchmark of the fused step kernel alone (GPU box).  usage: step_bench.py [B] [flags...] ; prints TFLOP/s per shape
 for the default geometry ("base") and for each `flags` value given: bits 16..19 = kernel variant of the test hook
 cf_flow_step_fwd_debug (e.g. 0x40000 = variant 4; its table is kDebugKernel in csrc/cf_step.hip: 2 half-size workgroups,
-3 k_flow_step_small direct, 4 Winograd F(2x2), 5 row-split 4x4, 6 Winograd F(2x4) at 8x8 and 4x4); the other bits are unused.  A shape without that variant prints "n/a"."""
+3 k_flow_step_small direct, 4 Winograd F(2x2), 5 row-split 4x4, 6 Winograd F(2x4) at 8x8 and 4x4, 7 the zero-skipping F(2x4) kernel of the 4x4 level); the other bits are unused.  A shape without that variant prints "n/a"."""
 import ctypes
 import sys
 import os
