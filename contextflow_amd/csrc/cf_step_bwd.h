@@ -699,7 +699,7 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
 
 
 // ---- the 4x4 level at small batches: ONE sample per workgroup on 16-column tiles ------------------------------------------------
-// The backward's analogue of k_flow_step_rs16 (cf_step.hip).  k_flow_step_bwd<B64> puts 8 samples into a workgroup: 32
+// The backward's analogue of k_flow_step_rs16 (cf_step_rs.h).  k_flow_step_bwd<B64> puts 8 samples into a workgroup: 32
 // workgroups at the reference's batch of 256, every wave running all four 32-row tiles of its two samples - 86 us per step,
 // 15 % of the captured training step.  Here a workgroup is one sample = the 16 columns of v_mfma_f32_16x16x4_f32 tiles, the
 // four waves split the OUTPUT rows (16-row tiles: 2 / 2 / 1 (half of K) / 1 per wave in the four products), planes
@@ -708,7 +708,6 @@ __global__ __launch_bounds__(256, (G::C <= 16 ? 3 : 2)) void k_flow_step_bwd(
 // one fold of a float4 per dx), after which a tap is a plain product.  TAPED form only (log-scale, y1 and the ReLU mask words
 // of the tape in the layout of the 32x32x2 kernels: one word holds the four rows of a lane's accumulator).
 // DATA = true: as in k_flow_step_bwd, the weight-gradient operand planes are not written (their pointers may be null).
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 template <class G, bool DATA = false>
 __global__ __launch_bounds__(256) void k_flow_step_bwd_rs16(const float* __restrict__ gz, const float* __restrict__ gld,
                                                             const float* __restrict__ wsb, float* __restrict__ gx,

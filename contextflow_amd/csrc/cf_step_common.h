@@ -1,5 +1,5 @@
 // Shared device code of the fused flow-step kernels (forward, inverse, backward): compile-time geometry,
-// MFMA operand pipeline, wave-local staging, the conditioner (phases 1-3).  Included by cf_step.hip,
+// MFMA operand pipeline, wave-local staging, the conditioner (phases 1-3).  Included by cf_step_fwd.h,
 // cf_step_inv.h, cf_step_dispatch.h and cf_step_bwd.h; everything lives in an anonymous namespace of
 // the including translation unit.
 #pragma once
@@ -11,6 +11,7 @@ namespace {
 
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kWaves = 4;              // waves per workgroup of every geometry that does not say otherwise (Geo::WAVES)
 
@@ -19,7 +20,7 @@ constexpr int kWaves = 4;              // waves per workgroup of every geometry 
 // taps unrolled with precomputed row / column offset parts, 3 = Winograd F(2x2,3x3): winograd_phase2)
 // ABL_: timing-only ablations for tools/step_bench.py (1 = phase-2 operands are constants: no LDS / L2 loads there)
 // PATCH_: (backward) every row of an LDS plane carries, behind its PIX pixel columns, the fold sums of the transposed
-// reflect-padded 3x3 (cf_step_bwd.hip): PP slots per sample + one zero slot; RS = row stride of all LDS planes.
+// reflect-padded 3x3 (cf_step_bwd.h): PP slots per sample + one zero slot; RS = row stride of all LDS planes.
 template <int C_, int H_, int W_, int SPW_, int PIPE_ = 1, int ABL_ = 0, int PATCH_ = 0>
 struct Geo {
     static constexpr int C = C_, H = H_, W = W_, SPW = SPW_, PIPE = PIPE_, ABL = ABL_, PATCH = PATCH_;
@@ -72,7 +73,7 @@ struct Geo {
     static constexpr bool WINO = (PIPE_ == 3 || W24);
     static constexpr int RT16 = HID / 16, KG4 = HID / 16;         // row tiles / k-step groups of the 16x16x4 products over HID
     static constexpr int OFF_AW = OFF_SA2 + (HID16 ? 9 * 256 : 0);
-    // one-sample-per-workgroup form of the 4x4 level for small batches (k_flow_step_rs16, cf_step.hip): 16x16x4 A fragments
+    // one-sample-per-workgroup form of the 4x4 level for small batches (k_flow_step_rs16, cf_step_rs.h): 16x16x4 A fragments
     // of all four products in NATURAL row order, [row tile][group of 4 k-steps][lane][4], + their biases
     static constexpr bool RS16 = (C == 64 && H == 4 && W == 4);
     static constexpr int OFF_RB0 = OFF_AW + 16 * HID * HID, OFF_RB1 = OFF_RB0 + C, OFF_RB2 = OFF_RB1 + HID, OFF_RB3 = OFF_RB2 + HID;
@@ -226,10 +227,9 @@ __device__ __forceinline__ void dense_phase(f32x16 (&acc)[RT][G::PTW], ws_rsrc_t
 #ifndef CF_STREAM_NT
 #define CF_STREAM_NT 1
 #endif
-typedef float cf_f32x4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 cf_ld_stream(const float4* p) {
 #if CF_STREAM_NT
-    const cf_f32x4v v = __builtin_nontemporal_load(reinterpret_cast<const cf_f32x4v*>(p));
+    const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
     return make_float4(v[0], v[1], v[2], v[3]);
 #else
     return *p;
@@ -244,7 +244,7 @@ __device__ __forceinline__ float cf_ldf_stream(const float* p) {
 }
 __device__ __forceinline__ void cf_st_stream(float4* p, const float4 v) {
 #if CF_STREAM_NT
-    __builtin_nontemporal_store(cf_f32x4v{v.x, v.y, v.z, v.w}, reinterpret_cast<cf_f32x4v*>(p));
+    __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4*>(p));
 #else
     *p = v;
 #endif
@@ -476,7 +476,6 @@ template <class G> __host__ __device__ constexpr int wino_pix(int sHW, int y, in
     return p;
 }
 
-typedef float f32x4w __attribute__((ext_vector_type(4)));
 #ifndef CF_WINO_PEEL
 #define CF_WINO_PEEL 1
 #endif
@@ -531,7 +530,7 @@ __device__ __forceinline__ void winograd_phase2(float* __restrict__ lds, const f
             cpart[ct][a] = 4 * ((((xx ^ lg) & 1) * (W / 2)) + (xx >> 1));
         }
     }
-    f32x4w Y[NT][2][2][RTW];
+    f32x4 Y[NT][2][2][RTW];
 #pragma unroll
     for (int ct = 0; ct < NT; ++ct)
 #pragma unroll
@@ -539,7 +538,7 @@ __device__ __forceinline__ void winograd_phase2(float* __restrict__ lds, const f
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
-                for (int rt = 0; rt < RTW; ++rt) Y[ct][i][j][rt] = f32x4w{0.f, 0.f, 0.f, 0.f};
+                for (int rt = 0; rt < RTW; ++rt) Y[ct][i][j][rt] = f32x4{0.f, 0.f, 0.f, 0.f};
     struct WFrag { float4 a[RTW]; };
     struct WPatch { f32x2w d[NT][2][4]; };
     constexpr int KGC = KG4 < 4 ? KG4 : 4, NCH = KG4 / KGC, NGX = 4 * KGC;       // groups per xi
@@ -624,11 +623,11 @@ __device__ __forceinline__ void winograd_phase2(float* __restrict__ lds, const f
             const float c0 = xi < 3 ? 1.f : 0.f, c1 = xi == 0 ? 0.f : (xi == 1 ? 1.f : -1.f);      // A^T[0][xi], A^T[1][xi]
 #pragma unroll
             for (int nu = 0; nu < 4; ++nu) {
-                f32x4w M[NT][RTW];
+                f32x4 M[NT][RTW];
 #pragma unroll
                 for (int ct = 0; ct < NT; ++ct)
 #pragma unroll
-                    for (int rt = 0; rt < RTW; ++rt) M[ct][rt] = f32x4w{0.f, 0.f, 0.f, 0.f};
+                    for (int rt = 0; rt < RTW; ++rt) M[ct][rt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int kk = 0; kk < KGC; ++kk) {
                     const int g = nu * KGC + kk;
@@ -740,11 +739,11 @@ __device__ __forceinline__ void winograd_phase2(float* __restrict__ lds, const f
             const float c0 = xi < 3 ? 1.f : 0.f, c1 = xi == 0 ? 0.f : (xi == 1 ? 1.f : -1.f);      // A^T[0][xi], A^T[1][xi]
 #pragma unroll
             for (int nu = 0; nu < 4; ++nu) {
-                f32x4w M[NT][RTW];
+                f32x4 M[NT][RTW];
 #pragma unroll
                 for (int ct = 0; ct < NT; ++ct)
 #pragma unroll
-                    for (int rt = 0; rt < RTW; ++rt) M[ct][rt] = f32x4w{0.f, 0.f, 0.f, 0.f};
+                    for (int rt = 0; rt < RTW; ++rt) M[ct][rt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int kk = 0; kk < KGC; ++kk) {
                     const int g = nu * KGC + kk;
@@ -1004,13 +1003,13 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
         cpart[0] = t1.x; cpart[1] = t1.y; cpart[2] = t1.z; cpart[3] = t1.w; cpart[4] = t2.x; cpart[5] = t2.y;
         dsto = t2.z;
     }
-    f32x4w Y[2][4][RTW];
+    f32x4 Y[2][4][RTW];
 #pragma unroll
     for (int i = 0; i < (ZS ? 1 : 2); ++i)          // (zero skip: Y[1] behind the xi = 0 that half the waves run - not live across it)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int rt = 0; rt < RTW; ++rt) Y[i][j][rt] = f32x4w{0.f, 0.f, 0.f, 0.f};
+            for (int rt = 0; rt < RTW; ++rt) Y[i][j][rt] = f32x4{0.f, 0.f, 0.f, 0.f};
     // operand addresses of one xi: patch rows r1 / r2 (B2^T row xi = d[r1] + sigma d[r2]) x the six patch columns
     // (BYTE offsets: an operand address is then this value + an immediate per k-step)
     auto addrs = [&](int xi, int (&o)[2][6]) {
@@ -1075,11 +1074,11 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
         const int xn = xi < 3 ? xi + 1 : 3;               // (after the last xi the prefetches re-read xi = 3: harmless)
         const float sigma = xi == 1 ? 1.f : -1.f;
         const float c0 = xi < 3 ? 1.f : 0.f, c1 = xi == 0 ? 0.f : (xi == 1 ? 1.f : -1.f);      // A2^T[0][xi], A2^T[1][xi]
-        f32x4w M[6][RTW];
+        f32x4 M[6][RTW];
 #pragma unroll
         for (int nu = 0; nu < 6; ++nu)
 #pragma unroll
-            for (int rt = 0; rt < RTW; ++rt) M[nu][rt] = f32x4w{0.f, 0.f, 0.f, 0.f};
+            for (int rt = 0; rt < RTW; ++rt) M[nu][rt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kk = 0; kk < KG4; ++kk) {
             f32x2w A[6][2];                               // vertical transform, once per patch column
@@ -1140,8 +1139,8 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
         // Y[i] += A2^T[i][xi] Z
 #pragma unroll
         for (int rt = 0; rt < RTW; ++rt) {
-            const f32x4w s12 = M[1][rt] + M[2][rt], d12 = M[1][rt] - M[2][rt], s34 = M[3][rt] + M[4][rt], d34 = M[3][rt] - M[4][rt];
-            const f32x4w Z[4] = {M[0][rt] + s12 + s34, d12 + 0.5f * d34, s12 + 0.25f * s34, d12 + 0.125f * d34 + M[5][rt]};
+            const f32x4 s12 = M[1][rt] + M[2][rt], d12 = M[1][rt] - M[2][rt], s34 = M[3][rt] + M[4][rt], d34 = M[3][rt] - M[4][rt];
+            const f32x4 Z[4] = {M[0][rt] + s12 + s34, d12 + 0.5f * d34, s12 + 0.25f * s34, d12 + 0.125f * d34 + M[5][rt]};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if constexpr (decltype(has0)::value) Y[0][j][rt] += c0 * Z[j];
@@ -1154,7 +1153,7 @@ __device__ __forceinline__ void winograd24_phase2(float* __restrict__ lds, const
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int rt = 0; rt < RTW; ++rt) Y[1][j][rt] = f32x4w{0.f, 0.f, 0.f, 0.f};
+            for (int rt = 0; rt < RTW; ++rt) Y[1][j][rt] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
 #pragma unroll 1
     for (int xi = 1; xi < 3; ++xi) xi_body(xi, std::true_type{}, std::true_type{}, ZS && ct == 1 && xi == 2);
@@ -1495,9 +1494,9 @@ __device__ __forceinline__ void conditioner_net(f32x16 (&acc3)[G::RT03][G::PTW],
 //   C16: 1 sample (256 px, 40 KB LDS, 3-4 workgroups/CU), compiler-scheduled tap loop    113 TFLOP/s
 //   C32: 4 samples (256 px, 80 KB, 2/CU), explicit operand pipeline                        130 TFLOP/s
 //   C64: 16 samples (256 px, 160 KB = the whole LDS, 1/CU), explicit pipeline, 4x2 tiles   136 TFLOP/s
-// Which of them runs a step - per pass, shape, batch size and switch - is decided in ONE function, select() in cf_step.hip;
+// Which of them runs a step - per pass, shape, batch size and switch - is decided in ONE function, select() in cf_step_dispatch.h;
 // the flop accounting (cf_flow_step_macs) reads the traits of the geometry that function names.  The backward has one geometry
-// per shape (cf_step_bwd.hip).
+// per shape (cf_step_bwd.h).
 using G8 = Geo<8, 16, 16, 1, 0>;
 using G16 = Geo<16, 16, 16, 1, 0>;
 using G32 = Geo<32, 8, 8, 4, 1>;

@@ -1,5 +1,6 @@
 // Which kernel runs a conv flow step (host only): Kernel, Pass, the batch thresholds and select().  Included by every unit that
-// launches a step kernel of the forward or inverse families - cf_step.hip and cf_step_inv_ctx.hip ask the same select().
+// launches a step kernel of the forward (cf_step_tile.h, cf_step_small.h, cf_step_rs.h) or inverse (cf_step_inv.h) families -
+// cf_step.hip and cf_step_inv_ctx.hip ask the same select().
 #pragma once
 #include "cf_step_common.h"
 #include <atomic>

@@ -1,6 +1,6 @@
 // The inverse flow step: table layout (GeoInv), the two inverse pack kernels, k_flow_step_inv (plain, LD and CTX forms), StepInvArgs
-// and the launch helpers.  Included by cf_step.hip (plain and LD forms) and cf_step_inv_ctx.hip (CTX forms); everything lives in an
-// anonymous namespace of the including translation unit.
+// and the launch helpers.  Included by cf_step.hip (plain and LD forms; beside the headers of the forward families) and
+// cf_step_inv_ctx.hip (CTX forms); everything lives in an anonymous namespace of the including translation unit.
 #pragma once
 #include "cf_step_common.h"
 #include <atomic>

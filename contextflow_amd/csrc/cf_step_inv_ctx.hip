@@ -1,5 +1,5 @@
 // The specialist coupling backwards in one launch: the CTX form of k_flow_step_inv (cf_step_inv.h), instantiated in a translation
-// unit of its own so that every kernel of cf_step.hip compiles to what it was (cf_step_inv_bwd.hip has the precedent).  The
+// unit of its own so that every kernel that cf_step.hip instantiates compiles to what it was (cf_step_inv_bwd.hip has the precedent).  The
 // kernel is select()'s choice for Pass::InverseCtx (cf_step_dispatch.h) and the launch is launch_step_inv with a StepInvArgs:
 // this unit holds the launch list of its four instantiations and the entry point.
 #include "cf_step_inv.h"

@@ -47,8 +47,8 @@ _SEED = {(64, 1, 0): 1}
 
 
 def _generalist():
-    # batch sizes: the smallest that reach each branch of the dispatch (cf_step.hip select(Pass::Taped, ...), cf_step_bwd.hip
-    # cf_flow_step_bwd_taped) with a ragged last workgroup, and both sides of every threshold
+    # batch sizes: the smallest that reach each branch of the dispatch (cf_step_dispatch.h select(Pass::Taped, ...), cf_step_bwd.h
+    # launch_bwd under cf_flow_step_bwd_taped) with a ragged last workgroup, and both sides of every threshold
     levels = [
         (8, 16, [3, 67]),                    # Small_G8s / B8 at every batch: one sample per workgroup, two sizes of grid
         (16, 16, [3, 67]),                   # Small_G16w (Winograd) / B16
